@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py -- throughput of the MaD hot path on MI355X.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload c3|c4|c2|c5|small]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload c3|c4|c2|c5|small] [--dump-outputs DIR] [--full]
 
 One "step" = one pass of the hot path over one batch of synthetic input already resident
 in HBM: orientation + description of the map and of every subunit (mad_set_build),
@@ -26,9 +26,16 @@ come from this library's own GPU density simulation, the scale space and the anc
 its device MapSpace / Detector (upstream of the hot path, untimed setup, times reported
 in config.setup_detail_s).
 
-The JSON line also carries `roofline` (dominant kernel, HIP-event timed on the library's
-stream inside the timed region) and `cpu_baseline` (the CPU oracle timed on a bounded
-sample of the same workload, rank 0, N = 1 only).
+A plain run sets up, warms up, times the K steps, writes the last step's outputs (--dump-outputs) and prints the headline line.
+Everything else the benchmark measures or checks takes runs of its own after the timed steps and is done only with --full:
+`roofline` (per-kernel times from a pass with the lanes serialised, HIP events around every launch, against spec peaks and
+against peaks measured in the same process), the single-step latency, the repeated-anchor-list steps, `cpu_baseline` (the CPU
+oracle on the same workload, rank 0, N = 1 only, with its top-k agreement), `refine_ccc`, the c3clean side line and, on N > 1,
+the sharded-map check and the one-GPU run of the same workload.  Without --full those keys are null.
+
+--dump-outputs DIR: after the timed steps, what the last one handed its caller, as float64 .npy files: every subunit's top-k
+pose rows after the exchange (topk_subunitNN.npy, k x 23, item order) and rank 0's per-match counts (match_stats.npy).  The
+inputs are seeded, so two builds run with the same arguments can be compared file for file.
 """
 import argparse
 import hashlib
@@ -342,6 +349,24 @@ def run_steps(lib, the_map, subs, cc, dist, k, set_groups, n_steps, after_step=N
     return out
 
 
+DUMP_LIMIT_BYTES = 64 << 20
+STAT_KEYS = ("n_pairs", "l_hi", "l_lo", "n_corr", "n_hi", "n_lo")
+
+
+def dump_outputs(out_dir, tops, stats):
+    """--dump-outputs: what the last timed step handed its caller.  topk_subunitNN.npy = subunit NN's top-k pose rows (k x 23, the
+    columns of mad_match_topk) after the step's exchange, i.e. every subunit on every rank; match_stats.npy = one row of STAT_KEYS per
+    match of this rank.  All float64; a few hundred KB on the workloads of bench/configs."""
+    arrays = {"topk_subunit%02d" % i: np.asarray(t, dtype=np.float64) for i, t in enumerate(tops)}
+    arrays["match_stats"] = np.array([[st[k_] for k_ in STAT_KEYS] for st in stats], dtype=np.float64).reshape(-1, len(STAT_KEYS))
+    total = sum(a.nbytes for a in arrays.values())
+    if total > DUMP_LIMIT_BYTES:
+        sys.exit("bench.py: --dump-outputs would write %d bytes, more than %d" % (total, DUMP_LIMIT_BYTES))
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+
+
 def refine_ccc_leg(lib, the_map, subs, tops, W, n_cand=8, reps=3):
     """refinement + CCC reported as their own line (candidates/s).  The n_cand best poses of
     every subunit are refined against the map (a13, all candidates in one launch), then each refined copy is turned
@@ -505,7 +530,12 @@ def main():
     ap.add_argument("--emulate-rank-of", type=int, default=0, metavar="N", help="REHEARSAL on one GPU: do the per-step work of rank 0 of an N-rank "
                     "job (its share of the map build, the import of all N shares, its subunits); the other ranks' map rows are built once, untimed.  "
                     "The line is labelled as an estimate and is not a multi-GPU measurement")
+    ap.add_argument("--full", action="store_true", help="after the timed steps also measure and check everything beside the headline "
+                    "(rooflines, latency, CPU baseline, refinement, side workloads, N > 1 checks); off: the headline line only")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write the last timed step's outputs to DIR/<name>.npy (float64)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         sys.exit(self_launch(args))
 
@@ -550,7 +580,7 @@ def main():
     lib.set_eqsp(1, e16.sphere_eqsp)
 
     # device peaks measured in this run (untimed): a streaming copy and the int8 MFMA issue rate
-    peak_copy_gbs, peak_i8_tops = lib.probe_peaks() if rank == 0 else (None, None)
+    peak_copy_gbs, peak_i8_tops = lib.probe_peaks() if rank == 0 and args.full else (None, None)
 
     emu = args.emulate_rank_of if (world == 1 and args.emulate_rank_of > 1) else 0
     wl = args.workload if args.workload != "auto" else ("c4" if (world > 1 or emu) else "c3")
@@ -679,10 +709,12 @@ def main():
             for k_, v in grp[0].host_s.items():
                 if k_ != "calls" and grp[0].host_s["calls"]:
                     host_overlapped["map_" + k_] = host_overlapped.get("map_" + k_, 0.0) + 1e3 * v / grp[0].host_s["calls"] / len(set_groups)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, gathered, stats)
 
     # The same steps with the anchor lists REPEATED (what rounds 1-3 timed): how much of a step is the upload of fresh lists.
     ms_repeat = None
-    if FRESH["on"]:
+    if args.full and FRESH["on"]:
         FRESH["on"] = False
         n_rep = max(args.steps // 2, 4)
         run_steps(lib, the_map, subs, cc, dist_thr, k, set_groups, len(set_groups) + 1)      # every group once with the list it keeps
@@ -695,7 +727,7 @@ def main():
 
     # One step at a time, lanes overlapped, nothing else in flight: what a caller who docks ONE batch waits for.
     lat = []
-    for _ in range(min(args.steps, 10)):
+    for _ in range(min(args.steps, 10) if args.full else 0):
         barrier()
         t1 = time.perf_counter()
         _, tops_l, _ = hot_path_step(lib, the_map, subs, cc, dist_thr, k, sets)
@@ -708,21 +740,22 @@ def main():
     # overlap on the device (one lane per structure), so a launch's elapsed time there depends on what ran beside it.  The same
     # steps are therefore repeated with the lanes serialised onto one stream, HIP events around every launch.
     n_serial = min(args.steps, 5)
-    lib.set_overlap(False)
-    lib.timing_enable(True)
-    lib.timing_reset()
-    HOST_T.clear()
-    t1 = time.perf_counter()
-    for _ in range(n_serial):
-        hot_path_step(lib, the_map, subs, cc, dist_thr, k, sets)
-    lib.synchronize()
-    dt_serial = time.perf_counter() - t1
-    lib.timing_enable(False)
-    lib.set_overlap(not args.serial)
+    if args.full:
+        lib.set_overlap(False)
+        lib.timing_enable(True)
+        lib.timing_reset()
+        HOST_T.clear()
+        t1 = time.perf_counter()
+        for _ in range(n_serial):
+            hot_path_step(lib, the_map, subs, cc, dist_thr, k, sets)
+        lib.synchronize()
+        dt_serial = time.perf_counter() - t1
+        lib.timing_enable(False)
+        lib.set_overlap(not args.serial)
 
     # how much of the pair list the pruned pose search had to search exactly, per subunit (untimed; one match at a time)
     pose_sel = []
-    if rank == 0 and not sharded:
+    if rank == 0 and not sharded and args.full:
         lo_x, his_x = enqueue_builds(lib, the_map, subs, sets)
         for hi_x in his_x:
             _, _, st_x = lib.match_topk(hi_x, lo_x, cc, dist_thr, k)
@@ -747,10 +780,10 @@ def main():
     # for bit; (b) rank 0 then runs the WHOLE workload alone (all subunits, unsharded map build), outside the timed region:
     # the one-GPU point of the strong-scaling curve measured in the same run, and the top-k every rank's result is held to.
     shard_check, one_gpu = None, None
-    if sharded:
+    if sharded and args.full:
         lo_sh = sets[0].enqueue()      # a collective: every rank takes part
         lib.synchronize()
-    if sharded and rank == 0:
+    if sharded and rank == 0 and args.full:
         a = lo_sh.download()
         ref_set = lib.set_build(the_map.slots, the_map.coords, the_map.octave, the_map.subv, the_map.index)
         b = ref_set.download()
@@ -788,113 +821,115 @@ def main():
         dist.barrier()
 
     if rank == 0:
-        groups = {}
-        for gname in ("orient", "describe", "correlate", "pairs", "pose", "topk"):
-            ms, n = lib.timing_get(gname)
-            groups[gname] = dict(ms_total=ms, launches=n)
         n_anchor_lo = len(the_map.coords) if not sharded else len(mdist.share_of(len(the_map.coords), 0, emu if emu else world))
         rows_lo = stats[0]["n_lo"] if stats else 0
         rows_lo_built = rows_lo if not sharded else sets[0].share.size()[0]
         rows_hi = sum(s["n_hi"] for s in stats)
         anchors_hi = sum(len(s.coords) for s in subs)
         pairs = sum(s["n_pairs"] for s in stats)
-        # one roofline entry per kernel group; counters (HBM traffic, VALU issue share) come from the committed PMC summary of THIS
-        # build, identified by the fingerprint of the kernel sources -- a summary of another build is named but not used
-        traffic, valu_util, counters_from = {}, {}, None
-        import glob
-        profs = sorted(glob.glob(os.path.join(ROOT, "profiles", "r*_bench_c3_serial_summary.json")))      # newest round last
-        pj = {}
-        if wl == "c3" and world == 1 and profs:      # PMC passes of this same command (profiles/README.md)
-            with open(profs[-1]) as fh:
-                pj = json.load(fh)
-            meta = pj.get("_meta", {})
-            fresh = meta.get("source_fingerprint") == source_fingerprint()
-            counters_from = dict(file=os.path.relpath(profs[-1], ROOT), git=meta.get("git"), source_fingerprint=meta.get("source_fingerprint"),
-                                 this_build=source_fingerprint(), stale=not fresh)
-            if not fresh:
-                pj = {}
-        def summary_of(prefix):      # template arguments are part of a kernel's name: the instance that took the most time
-            keys = [k_ for k_ in pj if k_ != "_meta" and (k_ == prefix or k_.startswith(prefix + "<") or (prefix == "k_corr_gemm" and k_.startswith(prefix)))]
-            return max(keys, key=lambda k_: pj[k_].get("total_us", 0.0)) if keys else None
+        roof = None      # --full: the per-kernel rooflines of the serialised pass
+        if args.full:
+            groups = {}
+            for gname in ("orient", "describe", "correlate", "pairs", "pose", "topk"):
+                ms, n = lib.timing_get(gname)
+                groups[gname] = dict(ms_total=ms, launches=n)
+            # one roofline entry per kernel group; counters (HBM traffic, VALU issue share) come from the committed PMC summary of THIS
+            # build, identified by the fingerprint of the kernel sources -- a summary of another build is named but not used
+            traffic, valu_util, counters_from = {}, {}, None
+            import glob
+            profs = sorted(glob.glob(os.path.join(ROOT, "profiles", "r*_bench_c3_serial_summary.json")))      # newest round last
+            pj = {}
+            if wl == "c3" and world == 1 and profs:      # PMC passes of this same command (profiles/README.md)
+                with open(profs[-1]) as fh:
+                    pj = json.load(fh)
+                meta = pj.get("_meta", {})
+                fresh = meta.get("source_fingerprint") == source_fingerprint()
+                counters_from = dict(file=os.path.relpath(profs[-1], ROOT), git=meta.get("git"), source_fingerprint=meta.get("source_fingerprint"),
+                                     this_build=source_fingerprint(), stale=not fresh)
+                if not fresh:
+                    pj = {}
+            def summary_of(prefix):      # template arguments are part of a kernel's name: the instance that took the most time
+                keys = [k_ for k_ in pj if k_ != "_meta" and (k_ == prefix or k_.startswith(prefix + "<") or (prefix == "k_corr_gemm" and k_.startswith(prefix)))]
+                return max(keys, key=lambda k_: pj[k_].get("total_us", 0.0)) if keys else None
 
-        for kn, gname in (("k_pose_bounds", "pose"), ("k_describe", "describe"), ("k_orient", "orient"), ("k_corr_gemm", "correlate"),
-                          ("k_pair_emit2", "pairs")):
-            kn = summary_of(kn)
-            if kn in pj and "fetch_size_bytes_avg" in pj[kn]:
-                traffic[gname] = pj[kn]["fetch_size_bytes_avg"] + pj[kn].get("write_size_bytes_avg", 0.0)
-            if kn in pj and "SQ_INSTS_VALU_avg" in pj[kn] and pj[kn].get("avg_us"):
-                # share of the SIMDs' issue cycles taken by vector ALU instructions (4 cycles each on a 16-lane SIMD, 1024 SIMDs, 2.4 GHz)
-                valu_util[gname] = 4.0 * pj[kn]["SQ_INSTS_VALU_avg"] / (pj[kn]["avg_us"] * 1e-6 * 2.4e9 * 1024)
-        per_step = {g: max(groups[g]["launches"], 1) / n_serial for g in groups}      # launches per step
-        alg = {
-            "describe": ("k_describe", "hbm", DESCRIBE_BYTES * (rows_lo_built + rows_hi), HBM_PEAK_GBS, "GB/s", 1e9),
-            "orient": ("k_orient", "hbm", ORIENT_BYTES * (n_anchor_lo + anchors_hi), HBM_PEAK_GBS, "GB/s", 1e9),
-            "correlate": ("k_corr_gemm2", "mfma", 2.0 * 1024 * corr, I8_PEAK_TOPS, "TOP/s", 1e12),
-            # pose scoring reads a pair (8 B) and writes a count (4 B); its real limit is float64 VALU + LDS latency
-            "pose": ("k_pose_bounds + k_pose_lds", "hbm", 12.0 * pairs, HBM_PEAK_GBS, "GB/s", 1e9),
-            "pairs": ("k_pair_count + k_pair_emit2", "hbm", 8.0 * corr + 16.0 * pairs, HBM_PEAK_GBS, "GB/s", 1e9),
-            "topk": ("top-k kernels", "hbm", 12.0 * pairs, HBM_PEAK_GBS, "GB/s", 1e9),
-        }
-        roofs = {}
-        for gname, (kname, bound, work_per_step, peak, unit, scale) in alg.items():
-            ms = groups[gname]["ms_total"] / max(groups[gname]["launches"], 1)
-            work = work_per_step / per_step[gname]
-            roofs[gname] = dict(kernel=kname, bound=bound, achieved=work / (ms * 1e-3) / scale if ms > 0 else 0.0, peak=peak, unit=unit,
-                                traffic=traffic.get(gname), avg_launch_ms=ms, ms_per_step=groups[gname]["ms_total"] / n_serial)
-            roofs[gname]["frac"] = roofs[gname]["achieved"] / peak
-            # against the peak MEASURED in this run on this device: a streaming copy for the HBM-bound kernels, the bare int8 MFMA loop for the GEMM
-            pk = peak_copy_gbs if bound == "hbm" else peak_i8_tops
-            roofs[gname]["peak_measured"] = pk
-            roofs[gname]["frac_of_measured"] = roofs[gname]["achieved"] / pk if pk else None
-            if gname in valu_util:
-                roofs[gname]["valu_issue_share"] = round(valu_util[gname], 3)      # from the SQ counters of the profiled run (profiles/)
-        # `roofline` = the HBM stage SURVEY.md 8(d) names as the binding roofline of the headline metric (the texel
-        # gathers of orient + describe), represented by its larger kernel, k_describe.  The pose search takes a comparable
-        # share of the device time but is bound by VALU issue and LDS latency, which an hbm | mfma roofline
-        # cannot express: it is listed under `others` with its own note.
-        dom_name = "describe"
-        roof = dict(roofs[dom_name])
-        roof["counters_from"] = counters_from
-        roof["kernel_ms_per_step"] = {g: groups[g]["ms_total"] / n_serial for g in groups}
-        roof["timing"] = ("HIP events around every launch over %d steps with the lanes serialised onto one stream (%.3f ms/step); "
-                          "the timed region overlaps the lanes (%.3f ms/step)" % (n_serial, 1e3 * dt_serial / n_serial, 1e3 * t_max / args.steps))
-        roof["host_ms_per_step"] = {k_: 1e3 * v / n_serial for k_, v in HOST_T.items()}
-        roof["host_ms_per_step_timed_region"] = host_overlapped
-        t_hbm = (groups["orient"]["ms_total"] + groups["describe"]["ms_total"]) / n_serial * 1e-3
-        b_hbm = ORIENT_BYTES * (n_anchor_lo + anchors_hi) + DESCRIBE_BYTES * (rows_lo_built + rows_hi)
-        roof["hbm_stage"] = dict(kernels="k_orient + k_describe", algorithmic_bytes_per_step=b_hbm, seconds_per_step=t_hbm,
-                                 achieved=b_hbm / t_hbm / 1e9 if t_hbm > 0 else 0.0, unit="GB/s", frac=(b_hbm / t_hbm / 1e9) / HBM_PEAK_GBS if t_hbm > 0 else 0.0)
-        roof["hbm_stage"]["peak_measured"] = peak_copy_gbs
-        roof["hbm_stage"]["frac_of_measured"] = roof["hbm_stage"]["achieved"] / peak_copy_gbs if peak_copy_gbs else None
-        roof["peaks"] = dict(hbm_spec_GBs=HBM_PEAK_GBS, hbm_copy_measured_GBs=peak_copy_gbs, i8_mfma_spec_TOPs=I8_PEAK_TOPS, i8_mfma_measured_TOPs=peak_i8_tops,
-                             how="mad_probe_peaks, untimed, same process and device: a 1 GiB -> 1 GiB streaming copy kernel (read + write bytes) and "
-                                 "v_mfma_i32_16x16x64_i8 from registers, 8 independent accumulators per wave, 4 waves per SIMD; spec figures from MI355X_MICROARCH.md")
-        roof["largest_share_of_device_time"] = max(groups, key=lambda g: groups[g]["ms_total"])
-        if roof.get("traffic") and roof.get("avg_launch_ms"):      # what the kernel really moved (FETCH_SIZE + WRITE_SIZE of the profiled run) over the same duration
-            roof["achieved_from_counters"] = roof["traffic"] / (roof["avg_launch_ms"] * 1e-3) / 1e9
-            roof["frac_from_counters"] = roof["achieved_from_counters"] / HBM_PEAK_GBS
-        roof["note"] = ("achieved = SURVEY 8(d)'s ALGORITHMIC 51 200 B per row (4 096 samples x 12 B gathered + 2 048 B written) over the launch time. "
-                        "Since round 3 the kernel gathers 4-byte texels (a quantised unit direction; 16 KB per row) and fetches the 16-byte texel "
-                        "only for the 3-4 % of samples its table classifier leaves open, so the bytes it really moves are about a third of the "
-                        "algorithmic figure; anchors are worked on in Morton order and neighbouring rows meet in the XCD's L2.  What it waits for is "
-                        "not HBM but the per-lane request path of fully divergent loads and the chain of phases of a row (DESIGN.md section 6c)")
-        l_hi_mean = float(np.mean([s["l_hi"] for s in stats])) if stats else 0.0
-        pts = pairs * l_hi_mean      # transformed hi-cloud points per step
-        t_pose = groups["pose"]["ms_total"] / n_serial * 1e-3
-        roofs["pose"]["note"] = ("not an HBM kernel (the HBM figure is its algorithmic 12 B/pair): every transformed hi point (%.3g per step, %.0f G/s) "
-                                 "goes through a float32 occupancy-bitmap test; vector-ALU issue is the binding resource (valu_issue_share, "
-                                 "SQ_INSTS_VALU of the profiled run)" % (pts, pts / t_pose / 1e9 if t_pose > 0 else 0.0))
-        roof["others"] = {g: roofs[g] for g in roofs if g != dom_name}
+            for kn, gname in (("k_pose_bounds", "pose"), ("k_describe", "describe"), ("k_orient", "orient"), ("k_corr_gemm", "correlate"),
+                              ("k_pair_emit2", "pairs")):
+                kn = summary_of(kn)
+                if kn in pj and "fetch_size_bytes_avg" in pj[kn]:
+                    traffic[gname] = pj[kn]["fetch_size_bytes_avg"] + pj[kn].get("write_size_bytes_avg", 0.0)
+                if kn in pj and "SQ_INSTS_VALU_avg" in pj[kn] and pj[kn].get("avg_us"):
+                    # share of the SIMDs' issue cycles taken by vector ALU instructions (4 cycles each on a 16-lane SIMD, 1024 SIMDs, 2.4 GHz)
+                    valu_util[gname] = 4.0 * pj[kn]["SQ_INSTS_VALU_avg"] / (pj[kn]["avg_us"] * 1e-6 * 2.4e9 * 1024)
+            per_step = {g: max(groups[g]["launches"], 1) / n_serial for g in groups}      # launches per step
+            alg = {
+                "describe": ("k_describe", "hbm", DESCRIBE_BYTES * (rows_lo_built + rows_hi), HBM_PEAK_GBS, "GB/s", 1e9),
+                "orient": ("k_orient", "hbm", ORIENT_BYTES * (n_anchor_lo + anchors_hi), HBM_PEAK_GBS, "GB/s", 1e9),
+                "correlate": ("k_corr_gemm2", "mfma", 2.0 * 1024 * corr, I8_PEAK_TOPS, "TOP/s", 1e12),
+                # pose scoring reads a pair (8 B) and writes a count (4 B); its real limit is float64 VALU + LDS latency
+                "pose": ("k_pose_bounds + k_pose_lds", "hbm", 12.0 * pairs, HBM_PEAK_GBS, "GB/s", 1e9),
+                "pairs": ("k_pair_count + k_pair_emit2", "hbm", 8.0 * corr + 16.0 * pairs, HBM_PEAK_GBS, "GB/s", 1e9),
+                "topk": ("top-k kernels", "hbm", 12.0 * pairs, HBM_PEAK_GBS, "GB/s", 1e9),
+            }
+            roofs = {}
+            for gname, (kname, bound, work_per_step, peak, unit, scale) in alg.items():
+                ms = groups[gname]["ms_total"] / max(groups[gname]["launches"], 1)
+                work = work_per_step / per_step[gname]
+                roofs[gname] = dict(kernel=kname, bound=bound, achieved=work / (ms * 1e-3) / scale if ms > 0 else 0.0, peak=peak, unit=unit,
+                                    traffic=traffic.get(gname), avg_launch_ms=ms, ms_per_step=groups[gname]["ms_total"] / n_serial)
+                roofs[gname]["frac"] = roofs[gname]["achieved"] / peak
+                # against the peak MEASURED in this run on this device: a streaming copy for the HBM-bound kernels, the bare int8 MFMA loop for the GEMM
+                pk = peak_copy_gbs if bound == "hbm" else peak_i8_tops
+                roofs[gname]["peak_measured"] = pk
+                roofs[gname]["frac_of_measured"] = roofs[gname]["achieved"] / pk if pk else None
+                if gname in valu_util:
+                    roofs[gname]["valu_issue_share"] = round(valu_util[gname], 3)      # from the SQ counters of the profiled run (profiles/)
+            # `roofline` = the HBM stage SURVEY.md 8(d) names as the binding roofline of the headline metric (the texel
+            # gathers of orient + describe), represented by its larger kernel, k_describe.  The pose search takes a comparable
+            # share of the device time but is bound by VALU issue and LDS latency, which an hbm | mfma roofline
+            # cannot express: it is listed under `others` with its own note.
+            dom_name = "describe"
+            roof = dict(roofs[dom_name])
+            roof["counters_from"] = counters_from
+            roof["kernel_ms_per_step"] = {g: groups[g]["ms_total"] / n_serial for g in groups}
+            roof["timing"] = ("HIP events around every launch over %d steps with the lanes serialised onto one stream (%.3f ms/step); "
+                              "the timed region overlaps the lanes (%.3f ms/step)" % (n_serial, 1e3 * dt_serial / n_serial, 1e3 * t_max / args.steps))
+            roof["host_ms_per_step"] = {k_: 1e3 * v / n_serial for k_, v in HOST_T.items()}
+            roof["host_ms_per_step_timed_region"] = host_overlapped
+            t_hbm = (groups["orient"]["ms_total"] + groups["describe"]["ms_total"]) / n_serial * 1e-3
+            b_hbm = ORIENT_BYTES * (n_anchor_lo + anchors_hi) + DESCRIBE_BYTES * (rows_lo_built + rows_hi)
+            roof["hbm_stage"] = dict(kernels="k_orient + k_describe", algorithmic_bytes_per_step=b_hbm, seconds_per_step=t_hbm,
+                                     achieved=b_hbm / t_hbm / 1e9 if t_hbm > 0 else 0.0, unit="GB/s", frac=(b_hbm / t_hbm / 1e9) / HBM_PEAK_GBS if t_hbm > 0 else 0.0)
+            roof["hbm_stage"]["peak_measured"] = peak_copy_gbs
+            roof["hbm_stage"]["frac_of_measured"] = roof["hbm_stage"]["achieved"] / peak_copy_gbs if peak_copy_gbs else None
+            roof["peaks"] = dict(hbm_spec_GBs=HBM_PEAK_GBS, hbm_copy_measured_GBs=peak_copy_gbs, i8_mfma_spec_TOPs=I8_PEAK_TOPS, i8_mfma_measured_TOPs=peak_i8_tops,
+                                 how="mad_probe_peaks, untimed, same process and device: a 1 GiB -> 1 GiB streaming copy kernel (read + write bytes) and "
+                                     "v_mfma_i32_16x16x64_i8 from registers, 8 independent accumulators per wave, 4 waves per SIMD; spec figures from AMD's published MI355X specifications")
+            roof["largest_share_of_device_time"] = max(groups, key=lambda g: groups[g]["ms_total"])
+            if roof.get("traffic") and roof.get("avg_launch_ms"):      # what the kernel really moved (FETCH_SIZE + WRITE_SIZE of the profiled run) over the same duration
+                roof["achieved_from_counters"] = roof["traffic"] / (roof["avg_launch_ms"] * 1e-3) / 1e9
+                roof["frac_from_counters"] = roof["achieved_from_counters"] / HBM_PEAK_GBS
+            roof["note"] = ("achieved = SURVEY 8(d)'s ALGORITHMIC 51 200 B per row (4 096 samples x 12 B gathered + 2 048 B written) over the launch time. "
+                            "Since round 3 the kernel gathers 4-byte texels (a quantised unit direction; 16 KB per row) and fetches the 16-byte texel "
+                            "only for the 3-4 % of samples its table classifier leaves open, so the bytes it really moves are about a third of the "
+                            "algorithmic figure; anchors are worked on in Morton order and neighbouring rows meet in the XCD's L2.  What it waits for is "
+                            "not HBM but the per-lane request path of fully divergent loads and the chain of phases of a row (DESIGN.md section 6c)")
+            l_hi_mean = float(np.mean([s["l_hi"] for s in stats])) if stats else 0.0
+            pts = pairs * l_hi_mean      # transformed hi-cloud points per step
+            t_pose = groups["pose"]["ms_total"] / n_serial * 1e-3
+            roofs["pose"]["note"] = ("not an HBM kernel (the HBM figure is its algorithmic 12 B/pair): every transformed hi point (%.3g per step, %.0f G/s) "
+                                     "goes through a float32 occupancy-bitmap test; vector-ALU issue is the binding resource (valu_issue_share, "
+                                     "SQ_INSTS_VALU of the profiled run)" % (pts, pts / t_pose / 1e9 if t_pose > 0 else 0.0))
+            roof["others"] = {g: roofs[g] for g in roofs if g != dom_name}
 
         cpu, agree, cpu_all, agree_whole = (None, None, None, None)
-        if world == 1 and not emu and not args.no_cpu_baseline:
+        if args.full and world == 1 and not emu and not args.no_cpu_baseline:
             cpu, agree = cpu_baseline(the_map, subs[:4], cc, dist_thr, k, lib)
             n_host = len(os.sched_getaffinity(0)) if hasattr(os, "sched_getaffinity") else (os.cpu_count() or 1)
             n_host = min(n_host, 16)      # a one-GPU box's CPU share
             if n_host > 1:      # the FULL step (every anchor, both octaves) on the host cores of this box's share: also the top-k check of the line
                 cpu_all, agree_whole = cpu_baseline(the_map, subs[:4], cc, dist_thr, k, lib, threads=n_host, whole=True)
         refine_line = None
-        if world == 1 and not emu:
+        if args.full and world == 1 and not emu:
             lib.timing_enable(True)
             refine_line = refine_ccc_leg(lib, the_map, subs[:4], tops[:4], W)
             lib.timing_enable(False)
@@ -903,7 +938,7 @@ def main():
         # The workload rounds 1-2 timed (C3 WITHOUT its noise: more than twice the pairs per match), a few steps of it beside the headline so
         # that this round's line can be held against theirs; not part of `value`.
         side_clean = None
-        if world == 1 and not emu and wl == "c3" and not args.no_cpu_baseline and "c3clean" in WORKLOADS:
+        if args.full and world == 1 and not emu and wl == "c3" and not args.no_cpu_baseline and "c3clean" in WORKLOADS:
             Wc = WORKLOADS["c3clean"]
             map_c, subs_c, _ = build_inputs(lib, Wc)
             groups_c = [[_lib.DeviceSet(lib) for _ in range(1 + len(subs_c))] for _ in range(args.in_flight)]
@@ -935,7 +970,7 @@ def main():
             "unit": "correlations/s",
             "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
             "ms_per_step": 1e3 * t_max / args.steps,
-            "latency_ms_single_step": 1e3 * float(lat_all.item()),
+            "latency_ms_single_step": 1e3 * float(lat_all.item()) if lat else None,
             "ms_per_step_repeated_anchor_lists": ms_repeat,
             "higher_is_better": True, "scaling": "strong", "vs_baseline": None,
             "dtype": "i8 (correlation, exact int32 accumulate) / f64 (binning, pose scoring)",
@@ -961,7 +996,7 @@ def main():
                        "pipelining": "%d steps in flight: the builds (and, with 3, the matches) of the next step are enqueued before the results of a step are awaited; every step does the full work" % args.in_flight,
                        "launches": ("batched: one launch per stage for all structures of a step, one GEMM grid for all its matches" if BATCHED["on"]
                                     else "one mad_set_build per structure and one GEMM per match, each on its own lane (batched alternative: --batched)"),
-                       "latency_note": "latency_ms_single_step = one step submitted alone (lanes overlapped, nothing else in flight, result exchange included), median of %d; ms_per_step = throughput of identical steps, %d in flight" % (len(lat), args.in_flight),
+                       "latency_note": "latency_ms_single_step = one step submitted alone (lanes overlapped, nothing else in flight, result exchange included), median of %d; ms_per_step = throughput of identical steps, %d in flight" % (len(lat), args.in_flight) if lat else None,
                        "topk_agrees_with_cpu_oracle": agree_whole if agree_whole is not None else agree,
                        "topk_agrees_with_cpu_oracle_on": None if agree is None else ("every anchor of both octaves, all subunits (the full step) and the base-octave sample" if agree_whole is not None else "the base-octave sample"),
                        "topk_agrees_on_sample": agree,

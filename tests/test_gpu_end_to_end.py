@@ -197,7 +197,7 @@ def test_bench_on_two_ranks_shares_the_map_build_and_gathers_the_topk(tmp_path, 
     env = dict(os.environ, MAD_DIST_BACKEND="gloo", MAD_DIST_TIMEOUT_S="240", MASTER_ADDR="127.0.0.1", HSA_ENABLE_IPC_MODE_LEGACY="0")
     for k in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_PORT"):
         env.pop(k, None)
-    p = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--workload", "c4", "--steps", "4", "--warmup", "1", "--no-cpu-baseline"] +
+    p = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--workload", "c4", "--steps", "4", "--warmup", "1", "--no-cpu-baseline", "--full"] +
                        (["--rehearse-resize", "64"] if overflow else []), cwd=str(tmp_path), env=env, capture_output=True, text=True, timeout=600)
     assert p.returncode == 0, (p.stdout[-2000:], p.stderr[-4000:])
     lines = [ln for ln in p.stdout.splitlines() if ln.startswith("{")]
@@ -209,3 +209,35 @@ def test_bench_on_two_ranks_shares_the_map_build_and_gathers_the_topk(tmp_path, 
     assert len(d["config"]["correlations_per_step_by_rank"]) == 2 and min(d["config"]["correlations_per_step_by_rank"]) > 0
     assert d["value"] > 0 and d["ms_per_step"] > 0
     assert d["config"]["map_image_resizes"] == (1 if overflow else 0)
+
+
+def test_bench_plain_run_times_its_steps_and_dumps_the_same_outputs_twice(tmp_path):
+    """`python bench.py --gpus 1 --steps K --warmup W --dump-outputs DIR` without --full, twice, in fresh child processes on the small
+    workload (C1): the line is the headline of K timed steps and carries none of what only --full measures; DIR holds the last step's
+    outputs (every subunit's top-k pose rows, float64), and with the same arguments the two runs write the same arrays bit for bit."""
+    import json
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    runs = []
+    for i in range(2):
+        out = tmp_path / ("outputs%d" % i)
+        p = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--workload", "small", "--steps", "3", "--warmup", "1",
+                            "--dump-outputs", str(out)], cwd=str(tmp_path), capture_output=True, text=True, timeout=600)
+        assert p.returncode == 0, (p.stdout[-2000:], p.stderr[-4000:])
+        lines = [ln for ln in p.stdout.splitlines() if ln.startswith("{")]
+        assert len(lines) == 1, p.stdout[-2000:]
+        d = json.loads(lines[0])
+        assert d["steps"] == 3 and d["warmup"] == 1 and d["n_gpus"] == 1
+        assert d["ms_per_step"] > 0 and d["value"] > 0 and d["unit"] == "correlations/s" and d["higher_is_better"] is True
+        assert d["roofline"] is None and d["cpu_baseline"] is None and d["refine_ccc"] is None and d["latency_ms_single_step"] is None
+        names = sorted(os.listdir(out))
+        assert names == ["match_stats.npy", "topk_subunit00.npy", "topk_subunit01.npy"], names
+        arrays = {n: np.load(out / n) for n in names}
+        assert all(a.dtype == np.float64 for a in arrays.values())
+        assert arrays["match_stats.npy"].shape == (2, 6) and np.all(arrays["match_stats.npy"][:, 0] > 0)      # pairs over cc in both matches
+        for n in ("topk_subunit00.npy", "topk_subunit01.npy"):
+            assert arrays[n].ndim == 2 and arrays[n].shape[1] == 23 and 0 < len(arrays[n]) <= d["config"]["top_k"]
+        runs.append(arrays)
+    for n in runs[0]:
+        np.testing.assert_array_equal(runs[0][n], runs[1][n], err_msg=n)
