@@ -350,8 +350,9 @@ int mad_match_shard_topk(mad_ctx *ctx, const mad_set *hi, const mad_set *lo, con
  *     from that number; the device checks it).  d_flags: hi->n_anchors + lo->n_anchors bytes, hi's flags first.
  *   mad_match_shard_score: the shard's pairs against the global clouds (d_flags_all: the OR over the shards, same layout); d_out:
  *     mad_match_shard_record_doubles(k) float64 = [rows m, flags, |hi cloud|, pairs][k x 23 result rows][k counts][k pair ranks].
- *     flags != 0 (1 score-matrix capacity, 2 pair capacity, 4 n_lo was wrong, 8 selection list): m = 0, repeat the shard through
- *     mad_match_shard_pairs / mad_match_shard_topk.
+ *     flags != 0 (1 score-matrix capacity, 2 pair capacity, 4 n_lo was wrong, 8 selection list, 16 the describe launch of hi or lo
+ *     fell short -- a set rebuilt in place with more rows than its previous build, not yet repaired by a host read of its size):
+ *     m = 0, repeat the shard through mad_match_shard_pairs / mad_match_shard_topk (which repair the sets).
  */
 int64_t mad_match_shard_record_doubles(int64_t k);
 int mad_match_shard_begin(mad_ctx *ctx, const mad_set *hi, const mad_set *lo, int64_t lo_begin, int64_t lo_end, int64_t n_lo,

@@ -3468,7 +3468,10 @@ static int match_finish(mad_ctx *ctx, int ri, const mad_set *hi, const mad_set *
     const int64_t *h_idx = (const int64_t *)(base + (size_t)P->k * MAD_RESULT_COLS * 8);
     const int32_t *hs = (const int32_t *)(h_idx + P->k);
     if (hs[ST_NHI + 3] || hs[ST_NLO + 3]) {
-        // a set's describe launch had been sized from a stale hint: repair the set(s), then match again
+        // a set's describe launch had been sized from a stale hint: repair the set(s), then match again.  Matches of the same
+        // bracket on other lanes may still read the lo set: they finish first (each then carries the flag it saw and is repeated
+        // in turn), so that the repair neither rewrites rows under them nor clears the flag before they have mirrored it.
+        MAD_TRY(mad_synchronize(ctx));
         int64_t dummy;
         const_cast<mad_set *>(hi)->n_rows_host = -1;
         const_cast<mad_set *>(lo)->n_rows_host = -1;
@@ -3899,20 +3902,27 @@ extern "C" int mad_match_shard_topk(mad_ctx *ctx, const mad_set *hi, const mad_s
 // ---------------------------------------------------------------------------
 
 #define ST_SHARD_NLO 17      // status word: the lo set has another number of rows than the caller assumed when it cut the blocks
+#define ST_SHARD_DSC 18      // status word: the describe launch of hi or lo fell short (sized from a stale rows_hint; dev_n[3])
 
-__global__ void k_shard_head(int32_t *st, int32_t nb, const int32_t *lo_n_rows, int32_t n_lo_assumed) {
+// hi_n / lo_n: the two sets' dev_n words {rows, range flag, border rejects, describe overflow}.  A set rebuilt in place sizes its
+// describe launch from the rows of its previous build; when the new anchors yield more, its rows are not those of this build, and
+// nothing in this form repairs them (the synchronous calls do, through set_rows): the shard is flagged instead.
+__global__ void k_shard_head(int32_t *st, int32_t nb, const int32_t *hi_n, const int32_t *lo_n, int32_t n_lo_assumed) {
     if (threadIdx.x == 0) {
         st[ST_NLO] = nb;
-        if (*lo_n_rows != n_lo_assumed) st[ST_SHARD_NLO] = 1;
+        if (lo_n[0] != n_lo_assumed) st[ST_SHARD_NLO] = 1;
+        if (hi_n[3] || lo_n[3]) st[ST_SHARD_DSC] = 1;
     }
 }
 
-// out: [0] rows m, [1] flags (1 score matrix capacity, 2 pair capacity, 4 lo row count, 8 selection list), [2] size of the global hi
-// cloud, [3] pairs of the shard, then k x 23 result rows, k match counts, k global pair ranks (hi_row * N_lo + lo_row), all float64
+// out: [0] rows m, [1] flags (1 score matrix capacity, 2 pair capacity, 4 lo row count, 8 selection list, 16 a set's describe launch
+// fell short), [2] size of the global hi cloud, [3] pairs of the shard, then k x 23 result rows, k match counts, k global pair ranks
+// (hi_row * N_lo + lo_row), all float64
 __global__ void k_shard_pack(const int64_t *__restrict__ sel, const int32_t *__restrict__ st, int64_t k, const int32_t *__restrict__ ph,
                              const int32_t *__restrict__ pl, const int32_t *__restrict__ cnt, const double *__restrict__ rows, int64_t n_lo,
                              int64_t begin, double *__restrict__ out) {
-    const int flags = (st[ST_FLAG_C] ? 1 : 0) | (st[ST_FLAG_PAIRS] ? 2 : 0) | (st[ST_SHARD_NLO] ? 4 : 0) | (st[ST_FLAG_SEL] ? 8 : 0);
+    const int flags = (st[ST_FLAG_C] ? 1 : 0) | (st[ST_FLAG_PAIRS] ? 2 : 0) | (st[ST_SHARD_NLO] ? 4 : 0) | (st[ST_FLAG_SEL] ? 8 : 0) |
+                      (st[ST_SHARD_DSC] ? 16 : 0);
     const int64_t m = (st[ST_NPAIRS] > 0 && !flags) ? min((int64_t)st[ST_NKEYS], k) : 0;
     if (blockIdx.x == 0 && threadIdx.x == 0) { out[0] = (double)m; out[1] = (double)flags; out[2] = (double)st[ST_LHI]; out[3] = (double)st[ST_NPAIRS]; }
     for (int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; t < k; t += (int64_t)gridDim.x * blockDim.x) {
@@ -3950,7 +3960,8 @@ extern "C" int mad_match_shard_begin(mad_ctx *ctx, const mad_set *hi, const mad_
     const int64_t cap_c = (mad_ceil_div(std::max<int64_t>(hi_rows, 1), 128) * 128) * (mad_ceil_div(std::max<int64_t>(nb, 1), 128) * 128);
     if (cap_c >= ((int64_t)1 << 31)) return mad_fail(ctx, MAD_EINVAL, "mad_match_shard_begin: score matrix of %lld entries", (long long)cap_c);
     mad_zero_words(ctx, st, zero_bytes(hi, lo));
-    hipLaunchKernelGGL(k_shard_head, dim3(1), dim3(64), 0, ctx->stream, st, (int32_t)nb, (const int32_t *)lo->dev_n.p, (int32_t)n_lo);
+    hipLaunchKernelGGL(k_shard_head, dim3(1), dim3(64), 0, ctx->stream, st, (int32_t)nb, (const int32_t *)hi->dev_n.p, (const int32_t *)lo->dev_n.p,
+                       (int32_t)n_lo);
     const Side H = side_of(hi), L = side_block(lo, lo_begin, st + ST_NLO, nb);
     MAD_TRY(correlate_device(ctx, H, L, hi->D, cc, st, cap_c, cap_pairs, d_used_hi, d_used_lo));
     if (hi->n_anchors > 0) MAD_HIP(hipMemcpyAsync(d_flags, d_used_hi, (size_t)hi->n_anchors, hipMemcpyDeviceToDevice, ctx->stream));

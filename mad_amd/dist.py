@@ -314,8 +314,9 @@ class ShardedMatchAsync(object):
     (`mad_match_shard_begin` / `mad_match_shard_score`), the flags and the shard's record stay in device tensors, and the two
     exchanges of SURVEY.md 8(e) -- OR all-reduce, all-gather -- are issued on that lane's stream between and behind them (the
     ExternalStream pattern of ShardedSetBuild).  `finish()` waits for ONE device-to-host copy and merges, or returns None when some
-    shard of the group raised a flag (a capacity hint too small, a map set with another row count than `n_lo`): every rank of
-    the group sees the same records, so all of them then repeat the match through the synchronous `sharded_match`.
+    shard of the group raised a flag (a capacity hint too small, a map set with another row count than `n_lo`, flag 16: a set
+    rebuilt in place whose describe launch, sized from its previous build, fell short): every rank of the group sees the same
+    records, so all of them then repeat the match through the synchronous `sharded_match`, which repairs the sets.
 
     group: the torch.distributed group of the shards (RCCL); `local=True`: no collective at all -- the rehearsal of one rank, or a
     group of one."""
