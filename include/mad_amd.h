@@ -453,8 +453,8 @@ int mad_overlap_matrix(mad_ctx *ctx, const double *atoms, const double *mass, co
                        int n_struct, double resolution, double voxsp, double density_isovalue,
                        double overlap_isovalue, double *overlap);
 
-/* ---- next to the path, upstream: MapSpace.build_space (MapSpace.py:116-189) and the
- *      dense half of Detector.find_anchors (Detector.py:28-29) ------------------------ */
+/* ---- next to the path, upstream: MapSpace.build_space (MapSpace.py:116-189) and
+ *      Detector.find_anchors (Detector.py:28-123) --------------------------------------- */
 
 typedef struct mad_space mad_space;
 
@@ -504,8 +504,34 @@ int mad_space_peaks(mad_ctx *ctx, const mad_space *s, int entry, double threshol
                     double *value, int64_t cap, int64_t *n_out);
 
 /* (2r+1)^3 LoG neighbourhoods of n voxels (zero outside), storage type of the entry: the input of
- * Detector.check_localize (Detector.py:53-123), which stays on the host. */
+ * Detector.check_localize (Detector.py:53-123) on the host, for the candidates mad_space_localize
+ * leaves undecided. */
 int mad_space_patches(mad_ctx *ctx, const mad_space *s, int entry, const int32_t *coords, int n, int r, void *out);
+
+/*
+ * Detector.check_localize (Detector.py:53-123) for n candidate voxels of map_space[entry], on the
+ * device and in place: the walk of at most 5 quadratic fits, the moves with the border limits
+ * x - 1 > 0 and x + 1 < shape - 1 per axis (:87-99), the stop when every |offset| < 0.6 (:84), and
+ * the rejection of a fit whose Hessian has a positive eigenvalue (:104-108).
+ *   cand      [n][3] starting voxels, each inside [1, shape - 2] on every axis (else MAD_EDOM)
+ *   status    [n]: 0 rejected, 1 accepted, 2 undecided
+ *   coord     [n][3]: the voxel the walk ended on (the anchor's voxel when status = 1)
+ *   H, G      [n][9] and [n][3] in the storage type of the entry: Hessian and gradient of the last
+ *             fit, built from the same voxel reads in the same operation order as the reference
+ *   n_undecided   number of status-2 candidates (may be NULL)
+ * H and G are exact; the decisions are taken from a float64 solve only outside a guard band that
+ * covers the rounding of numpy's -dot(inv(H), G) in the storage type and of geev (DESIGN.md section
+ * 4b).  Status 1: the caller finishes offset = -dot(inv(H), G) itself.  Status 2 (inside the band, or
+ * H near-singular, where numpy may or may not raise): the caller runs check_localize on that
+ * candidate.  Status 0 is final.  n = 0 is a no-op.  Results come back in one copy.
+ */
+int mad_space_localize(mad_ctx *ctx, const mad_space *s, int entry, const int32_t *cand, int n, int32_t *status,
+                       int32_t *coord, void *H, void *G, int64_t *n_undecided);
+
+/* The same kernel on a host volume [nx][ny][nz] (z fastest), float32 (is_f64 = 0) or float64 (1),
+ * uploaded for the call: for volumes that are not a mad_space, such as test fixtures. */
+int mad_localize_volume(mad_ctx *ctx, const void *vol, int is_f64, int nx, int ny, int nz, const int32_t *cand, int n,
+                        int32_t *status, int32_t *coord, void *H, void *G, int64_t *n_undecided);
 
 #ifdef __cplusplus
 }

@@ -28,7 +28,7 @@ SYMBOLS = [
     "mad_set_wire_bytes", "mad_set_export", "mad_set_import", "mad_set_lane", "mad_set_stream", "mad_set_bind_lane",
     "mad_upload_density", "mad_refine", "mad_structure_to_density", "mad_ccc", "mad_density_ccc", "mad_dock_refine_score", "mad_grid_overlap", "mad_overlap_matrix",
     "mad_space_create", "mad_space_destroy", "mad_space_build", "mad_space_info", "mad_space_download",
-    "mad_space_peaks", "mad_space_patches",
+    "mad_space_peaks", "mad_space_patches", "mad_space_localize", "mad_localize_volume",
 ]
 
 
@@ -202,6 +202,24 @@ class DeviceSet(object):
             pass
 
 
+def _localize(lib, dtype, coords, call):
+    """Shared body of DeviceSpace.localize and Lib.localize_volume: output arrays, one C call, the project's error codes."""
+    coords = np.asarray(coords)
+    if coords.size == 0:
+        coords = coords.reshape(0, 3)
+    if coords.ndim != 2 or coords.shape[1] != 3 or not np.issubdtype(coords.dtype, np.integer):
+        raise ValueError("localize: coords must be an integer (n, 3) array, got %s %s" % (coords.dtype, coords.shape))
+    if len(coords) and (coords.min() < np.iinfo(np.int32).min or coords.max() > np.iinfo(np.int32).max):
+        raise ValueError("localize: coordinates outside int32")
+    c = _c(coords, np.int32)
+    n = len(c)
+    status, coord = np.zeros(n, np.int32), np.zeros((n, 3), np.int32)
+    H, G = np.zeros((n, 3, 3), dtype), np.zeros((n, 3), dtype)
+    nu = C.c_int64(0)
+    lib._chk(call(_p(c), C.c_int(n), _p(status), _p(coord), _p(H), _p(G), C.byref(nu)))
+    return status, coord, H, G, int(nu.value)
+
+
 class DeviceSpace(object):
     """Device-resident scale space of one structure (mad_space): the volumes of MapSpace.build_space."""
 
@@ -281,6 +299,16 @@ class DeviceSpace(object):
         out = np.zeros((len(coords), side, side, side), self.dtypes[entry])
         self.lib._chk(self.lib.dll.mad_space_patches(self.lib.ctx, self.h, C.c_int(entry), _p(coords), C.c_int(len(coords)), C.c_int(r), _p(out)))
         return out
+
+    def localize(self, entry, coords):
+        """Detector.check_localize of every voxel in `coords` (n, 3) on map_space[entry], on the device (mad_space_localize).
+        -> (status int32 (n,): 0 rejected / 1 accepted / 2 undecided, coord int32 (n, 3), H (n, 3, 3), G (n, 3), n_undecided);
+        H and G in the storage type of the entry."""
+        entry = int(entry)
+        dtype = self.dtypes[entry] if 0 <= entry < len(self.dtypes) else np.float32      # a bad entry: MAD_EINVAL from the library
+        return _localize(self.lib, dtype, coords,
+                         lambda c, n, st, co, H, G, nu: self.lib.dll.mad_space_localize(self.lib.ctx, self.h, C.c_int(entry), c, n,
+                                                                                       st, co, H, G, nu))
 
     def close(self):
         if self.h and self.lib.ctx:
@@ -382,6 +410,18 @@ class Lib(object):
         if s >= 64:
             raise MadBackendError("MaD> out of gradient-field slots; free some with free_field()")
         return s
+
+    def localize_volume(self, vol, coords):
+        """Detector.check_localize of every voxel in `coords` on a host LoG volume (float32 or float64, (X, Y, Z)), on the device
+        (mad_localize_volume).  Same result tuple as DeviceSpace.localize."""
+        v = np.asarray(vol)
+        if v.ndim != 3 or v.dtype not in (np.float32, np.float64):
+            raise ValueError("localize_volume: volume must be a 3-D float32 or float64 array, got %s %s" % (v.dtype, v.shape))
+        v = np.ascontiguousarray(v)
+        return _localize(self, v.dtype.type, coords,
+                         lambda c, n, st, co, H, G, nu: self.dll.mad_localize_volume(
+                             self.ctx, _p(v), C.c_int(1 if v.dtype == np.float64 else 0), C.c_int(v.shape[0]), C.c_int(v.shape[1]),
+                             C.c_int(v.shape[2]), c, n, st, co, H, G, nu))
 
     def upload_field(self, slot, grad):
         """grad: the reference's grad_list entry, shape (X, Y, Z, 3), any strides; or a (3, X, Y, Z) array."""

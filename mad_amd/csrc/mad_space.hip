@@ -4,7 +4,7 @@
 // upsampling by successive 1-D not-a-knot cubic splines (scipy interp1d(kind="cubic"), :206-214), the light
 // pre-smoothing (:144), the scale-normalised LoG volumes (:169-173), the Gaussian-smoothed volumes and
 // their gradients (:178-189) -- and the dense part of Detector.find_anchors (mad/Detector.py:28-29): the
-// 3x3x3 local-maximum mask.  The gradients are written straight into a field slot as the 16-byte texels the
+// 3x3x3 local-maximum mask -- and its sub-voxel fit (check_localize, mad/Detector.py:53-123; k_localize, tiered).  The gradients are written straight into a field slot as the 16-byte texels the
 // orientation / descriptor kernels sample, so a structure never leaves the device between its density grid
 // and its descriptors.
 //
@@ -235,6 +235,154 @@ __global__ __launch_bounds__(256) void k_patches(const T *__restrict__ v, Dims d
         if (x >= 0 && x < d.n[0] && y >= 0 && y < d.n[1] && z >= 0 && z < d.n[2]) o = v[((size_t)x * d.n[1] + y) * d.n[2] + z];
         out[i] = o;
     }
+}
+
+// ---------------------------------------------------------------------------
+// k_localize: Detector.check_localize (mad/Detector.py:53-123) on the device, tiered
+// ---------------------------------------------------------------------------
+// H and G are built from the same voxel reads, in the same operation order and in the storage type T, as the
+// reference's numpy scalars.  Every decision numpy takes on them -- stop / move per axis of each iteration
+// (float32 or float64 offset against float32(0.6) or 0.6) and "no positive eigenvalue" at the end -- is taken
+// from an exact-input float64 solve (adjugate) only when it lies outside a band that covers the rounding of the
+// float64 solve here and of numpy's expression -(float32(inv64(H)) . G); otherwise the candidate is undecided
+// (status 2) and the host runs check_localize on it.  The band constants are mirrored by
+// tools/check_localize_tier.py (a CPU test checks both against numpy).
+#define MAD_LOC_U64 1.1102230246251565e-16      // 2^-53
+#define MAD_LOC_U32 5.9604644775390625e-08      // 2^-24
+#define MAD_LOC_KAPPA_MAX 16777216.0            // 2^24: ||H||inf ||H^-1||inf beyond this counts as near-singular
+#define MAD_LOC_INV_C 64.0                      // LAPACK inverse: |X - H^-1|_ij <= C u64 kappa ||H^-1||inf
+#define MAD_LOC_DOT_C32 5.0                     // float32 path: X rounded to float32 (1 u32) + 3-term float32 dot (gamma_3)
+#define MAD_LOC_DOT_C64 4.0                     // float64 path: 3-term float64 dot
+#define MAD_LOC_SAFETY 4.0                      // the band is SAFETY x (bound of this solve + bound of numpy's)
+#define MAD_LOC_EIG_SHIFT 1.4551915228366852e-11      // 2^-36: eigenvalue margin delta = shift x 3 max|h_ij| (>> geev's error)
+#define MAD_LOC_HMIN 1e-20                      // max|h_ij| below this: no eigenvalue decision
+#define MAD_LOC_ITERS 5
+#define MAD_LOC_BLOCK 64
+
+// float64 adjugate solve of the stop / move decision.  cls[i] = -1 (o_i < -t), 0 (|o_i| < t), 1 (o_i > t) as numpy will
+// find them; false = some component inside the band, or H near-singular.
+__device__ __forceinline__ bool loc_decide_offset(const double h[6], const double g[3], double t, bool f32, int cls[3]) {
+#pragma clang fp contract(off)
+    const double u = MAD_LOC_U64;
+    const double h00 = h[0], h01 = h[1], h02 = h[2], h11 = h[3], h12 = h[4], h22 = h[5];
+    double A[3][3], E[3][3];
+    A[0][0] = h11 * h22 - h12 * h12; E[0][0] = 2 * u * (fabs(h11 * h22) + h12 * h12);
+    A[0][1] = h02 * h12 - h01 * h22; E[0][1] = 2 * u * (fabs(h02 * h12) + fabs(h01 * h22));
+    A[0][2] = h01 * h12 - h02 * h11; E[0][2] = 2 * u * (fabs(h01 * h12) + fabs(h02 * h11));
+    A[1][1] = h00 * h22 - h02 * h02; E[1][1] = 2 * u * (fabs(h00 * h22) + h02 * h02);
+    A[1][2] = h01 * h02 - h00 * h12; E[1][2] = 2 * u * (fabs(h01 * h02) + fabs(h00 * h12));
+    A[2][2] = h00 * h11 - h01 * h01; E[2][2] = 2 * u * (fabs(h00 * h11) + h01 * h01);
+    A[1][0] = A[0][1]; A[2][0] = A[0][2]; A[2][1] = A[1][2];
+    E[1][0] = E[0][1]; E[2][0] = E[0][2]; E[2][1] = E[1][2];
+    const double det = (h00 * A[0][0] + h01 * A[0][1]) + h02 * A[0][2];
+    const double det_err = (fabs(h00) * E[0][0] + fabs(h01) * E[0][1] + fabs(h02) * E[0][2]) +
+                           3 * u * (fabs(h00 * A[0][0]) + fabs(h01 * A[0][1]) + fabs(h02 * A[0][2]));
+    const double ad = fabs(det);
+    if (!(ad > 4 * det_err) || !isfinite(ad)) return false;
+    const double norm_h = fmax(fabs(h00) + fabs(h01) + fabs(h02), fmax(fabs(h01) + fabs(h11) + fabs(h12), fabs(h02) + fabs(h12) + fabs(h22)));
+    double norm_inv = 0.0;
+    for (int i = 0; i < 3; i++) norm_inv = fmax(norm_inv, (fabs(A[i][0]) + fabs(A[i][1]) + fabs(A[i][2])) / ad);
+    const double kappa = norm_h * norm_inv;
+    if (!(kappa <= MAD_LOC_KAPPA_MAX)) return false;
+    const double g1 = fabs(g[0]) + fabs(g[1]) + fabs(g[2]);
+    const double inv_term = MAD_LOC_INV_C * u * kappa * norm_inv * g1;
+    const double dot_c = f32 ? MAD_LOC_DOT_C32 * MAD_LOC_U32 : MAD_LOC_DOT_C64 * u;
+    for (int i = 0; i < 3; i++) {
+        const double N = (A[i][0] * g[0] + A[i][1] * g[1]) + A[i][2] * g[2];
+        const double sabs = fabs(A[i][0] * g[0]) + fabs(A[i][1] * g[1]) + fabs(A[i][2] * g[2]);
+        const double n_err = (E[i][0] * fabs(g[0]) + E[i][1] * fabs(g[1]) + E[i][2] * fabs(g[2])) + 3 * u * sabs;
+        const double o = -N / det;
+        const double dev_err = (n_err + fabs(o) * det_err) / (ad - det_err) + 2 * u * fabs(o);
+        const double band = MAD_LOC_SAFETY * (dev_err + inv_term + dot_c * (sabs / ad));
+        if (!isfinite(o) || !isfinite(band)) return false;
+        if (o - band > t) cls[i] = 1;
+        else if (o + band < -t) cls[i] = -1;
+        else if (o + band < t && o - band > -t) cls[i] = 0;
+        else return false;
+    }
+    return true;
+}
+
+// "no eigenvalue of H is > 0" (np.linalg.eigvals, Detector.py:104-108), by Sylvester's criterion with a margin delta:
+// 1 = every eigenvalue < -delta (leading minors of -H - delta I positive beyond their rounding), 0 = some eigenvalue > delta
+// (a principal minor of delta I - H negative beyond its rounding), 2 = neither.
+__device__ __forceinline__ int loc_decide_eigen(const double h[6]) {
+#pragma clang fp contract(off)
+    const double u = MAD_LOC_U64;
+    double hmax = 0.0;
+    for (int k = 0; k < 6; k++) hmax = fmax(hmax, fabs(h[k]));
+    if (!(hmax >= MAD_LOC_HMIN) || !isfinite(hmax)) return 2;
+    const double delta = MAD_LOC_EIG_SHIFT * 3.0 * hmax;
+    for (int pass = 0; pass < 2; pass++) {
+        // pass 0: B = -H - delta I (accept if B is positive definite); pass 1: B = delta I - H (reject if B is not PSD)
+        const double s = pass == 0 ? -delta : delta;
+        const double b00 = s - h[0], b11 = s - h[3], b22 = s - h[5], b01 = -h[1], b02 = -h[2], b12 = -h[4];
+        const double m01 = b00 * b11 - b01 * b01, e01 = 4 * u * (fabs(b00 * b11) + b01 * b01);
+        const double m02 = b00 * b22 - b02 * b02, e02 = 4 * u * (fabs(b00 * b22) + b02 * b02);
+        const double m12 = b11 * b22 - b12 * b12, e12 = 4 * u * (fabs(b11 * b22) + b12 * b12);
+        const double c0 = b11 * b22 - b12 * b12, c1 = b01 * b22 - b12 * b02, c2 = b01 * b12 - b11 * b02;
+        const double m3 = (b00 * c0 - b01 * c1) + b02 * c2;
+        const double p3 = fabs(b00) * (fabs(b11 * b22) + b12 * b12) + fabs(b01) * (fabs(b01 * b22) + fabs(b12 * b02)) +
+                          fabs(b02) * (fabs(b01 * b12) + fabs(b11 * b02));
+        const double e3 = 16 * u * p3;
+        if (pass == 0) {
+            if (b00 > 0 && m01 > e01 && m3 > e3) return 1;
+        } else {
+            if (b00 < 0 || b11 < 0 || b22 < 0 || m01 < -e01 || m02 < -e02 || m12 < -e12 || m3 < -e3) return 0;
+        }
+    }
+    return 2;
+}
+
+// One lane per candidate: the walk of up to five steps of check_localize, in place on the LoG volume.  A latency kernel
+// (<= 5 x 19 gathers per lane, a few thousand lanes): one wavefront per block so that the lanes spread over the CUs.
+// Output per candidate: status (0 rejected, 1 accepted, 2 undecided), the voxel it ended on, H (9) and G (3) of the last
+// iteration in T.  cand holds starting voxels inside [1, n-2] on every axis (the host checks), and the moves keep them there.
+template <typename T>
+__global__ __launch_bounds__(MAD_LOC_BLOCK) void k_localize(const T *__restrict__ v, Dims d, const int32_t *__restrict__ cand, int n, double t,
+                                                            int32_t *__restrict__ status, int32_t *__restrict__ coord, T *__restrict__ Hout,
+                                                            T *__restrict__ Gout) {
+#pragma clang fp contract(off)
+    const int i = blockIdx.x * MAD_LOC_BLOCK + threadIdx.x;
+    if (i >= n) return;
+    const size_t sx = (size_t)d.n[1] * d.n[2], sy = (size_t)d.n[2];
+    int x = cand[3 * i], y = cand[3 * i + 1], z = cand[3 * i + 2];
+    int st = 0;
+    T xx = 0, yy = 0, zz = 0, xy = 0, xz = 0, yz = 0, gx = 0, gy = 0, gz = 0;
+    for (int it = 0; it < MAD_LOC_ITERS; it++) {
+        const T *p = v + (size_t)x * sx + (size_t)y * sy + z;
+        const T c = p[0];
+        const T xm = p[-(ptrdiff_t)sx], xp = p[sx], ym = p[-(ptrdiff_t)sy], yp = p[sy], zm = p[-1], zp = p[1];
+        // Detector.py:66-80, term by term as numpy evaluates them in T
+        xx = (xm + xp) - (T)2 * c;
+        yy = (ym + yp) - (T)2 * c;
+        zz = (zm + zp) - (T)2 * c;
+        xy = (T)0.25 * ((p[sx + sy] - p[sx - sy]) - (p[-(ptrdiff_t)sx + (ptrdiff_t)sy] - p[-(ptrdiff_t)sx - (ptrdiff_t)sy]));
+        xz = (T)0.25 * ((p[sx + 1] - p[sx - 1]) - (p[-(ptrdiff_t)sx + 1] - p[-(ptrdiff_t)sx - 1]));
+        yz = (T)0.25 * ((p[sy + 1] - p[sy - 1]) - (p[-(ptrdiff_t)sy + 1] - p[-(ptrdiff_t)sy - 1]));
+        gx = (T)0.5 * (xp - xm);
+        gy = (T)0.5 * (yp - ym);
+        gz = (T)0.5 * (zp - zm);
+        const double h[6] = {(double)xx, (double)xy, (double)xz, (double)yy, (double)yz, (double)zz};
+        const double g[3] = {(double)gx, (double)gy, (double)gz};
+        int cls[3];
+        if (!loc_decide_offset(h, g, t, sizeof(T) == 4, cls)) { st = 2; break; }
+        if (cls[0] == 0 && cls[1] == 0 && cls[2] == 0) {
+            st = loc_decide_eigen(h);
+            break;
+        }
+        if (cls[0] < 0 && x - 1 > 0) x -= 1;
+        else if (cls[0] > 0 && x + 1 < d.n[0] - 1) x += 1;
+        if (cls[1] < 0 && y - 1 > 0) y -= 1;
+        else if (cls[1] > 0 && y + 1 < d.n[1] - 1) y += 1;
+        if (cls[2] < 0 && z - 1 > 0) z -= 1;
+        else if (cls[2] > 0 && z + 1 < d.n[2] - 1) z += 1;
+    }
+    status[i] = st;
+    coord[3 * i] = x; coord[3 * i + 1] = y; coord[3 * i + 2] = z;
+    T *H = Hout + 9 * (size_t)i;
+    H[0] = xx; H[1] = xy; H[2] = xz; H[3] = xy; H[4] = yy; H[5] = yz; H[6] = xz; H[7] = yz; H[8] = zz;
+    Gout[3 * i] = gx; Gout[3 * i + 1] = gy; Gout[3 * i + 2] = gz;
 }
 
 struct Octave {
@@ -487,4 +635,77 @@ extern "C" int mad_space_patches(mad_ctx *ctx, const mad_space *s, int entry, co
     MAD_HIP(hipMemcpyAsync(out, mad_sb(ctx, S_TMP_B).p, total * esz, hipMemcpyDeviceToHost, ctx->stream));
     MAD_HIP(hipStreamSynchronize(ctx->stream));
     return MAD_OK;
+}
+
+// Runs k_localize on a device volume and brings status, voxel, H and G back in one copy.
+static int localize_run(mad_ctx *ctx, const void *vol, bool f64, Dims d, const int32_t *cand, int n, int32_t *status,
+                        int32_t *coord, void *H, void *G, int64_t *n_undecided) {
+    const size_t esz = f64 ? 8 : 4;
+    const size_t b_status = (size_t)n * 4, b_coord = (size_t)n * 12, b_H = (size_t)n * 9 * esz, b_G = (size_t)n * 3 * esz;
+    const size_t total = b_status + b_coord + b_H + b_G;      // status + coord = 16 n bytes: H stays 8-byte aligned
+    MAD_TRY(mad_reserve(ctx, mad_sb(ctx, S_TMP_A), b_coord));
+    MAD_TRY(mad_reserve(ctx, mad_sb(ctx, S_TMP_B), total));
+    MAD_HIP(hipMemcpyAsync(mad_sb(ctx, S_TMP_A).p, cand, b_coord, hipMemcpyHostToDevice, ctx->stream));
+    char *out = scratch<char>(ctx, S_TMP_B);
+    int32_t *d_status = (int32_t *)out, *d_coord = (int32_t *)(out + b_status);
+    void *d_H = out + b_status + b_coord, *d_G = out + b_status + b_coord + b_H;
+    const unsigned nb = (unsigned)((n + MAD_LOC_BLOCK - 1) / MAD_LOC_BLOCK);
+    if (f64) hipLaunchKernelGGL((k_localize<double>), dim3(nb), dim3(MAD_LOC_BLOCK), 0, ctx->stream, (const double *)vol, d,
+                                scratch<int32_t>(ctx, S_TMP_A), n, 0.6, d_status, d_coord, (double *)d_H, (double *)d_G);
+    else hipLaunchKernelGGL((k_localize<float>), dim3(nb), dim3(MAD_LOC_BLOCK), 0, ctx->stream, (const float *)vol, d,
+                            scratch<int32_t>(ctx, S_TMP_A), n, (double)0.6f, d_status, d_coord, (float *)d_H, (float *)d_G);
+    MAD_HIP(hipGetLastError());
+    std::vector<char> host(total);
+    MAD_HIP(hipMemcpyAsync(host.data(), out, total, hipMemcpyDeviceToHost, ctx->stream));
+    MAD_HIP(hipStreamSynchronize(ctx->stream));
+    std::memcpy(status, host.data(), b_status);
+    std::memcpy(coord, host.data() + b_status, b_coord);
+    std::memcpy(H, host.data() + b_status + b_coord, b_H);
+    std::memcpy(G, host.data() + b_status + b_coord + b_H, b_G);
+    int64_t und = 0;
+    for (int i = 0; i < n; i++) und += status[i] == 2;
+    if (n_undecided) *n_undecided = und;
+    return MAD_OK;
+}
+
+// every starting voxel inside [1, n-2] on every axis: the walk then never reads outside the volume
+static int localize_check(mad_ctx *ctx, const char *who, Dims d, const int32_t *cand, int n) {
+    if (d.n[0] < 3 || d.n[1] < 3 || d.n[2] < 3) return mad_fail(ctx, MAD_EINVAL, "%s: volume %dx%dx%d", who, d.n[0], d.n[1], d.n[2]);
+    for (int i = 0; i < n; i++)
+        for (int a = 0; a < 3; a++)
+            if (cand[3 * i + a] < 1 || cand[3 * i + a] > d.n[a] - 2)
+                return mad_fail(ctx, MAD_EDOM, "%s: candidate %d at (%d, %d, %d) is not inside [1, n-2] of %dx%dx%d", who, i, cand[3 * i],
+                                cand[3 * i + 1], cand[3 * i + 2], d.n[0], d.n[1], d.n[2]);
+    return MAD_OK;
+}
+
+extern "C" int mad_space_localize(mad_ctx *ctx, const mad_space *s, int entry, const int32_t *cand, int n, int32_t *status, int32_t *coord,
+                                  void *H, void *G, int64_t *n_undecided) {
+    if (!ctx || !s) return MAD_EINVAL;
+    if (n_undecided) *n_undecided = 0;
+    if (n < 0) return mad_fail(ctx, MAD_EINVAL, "mad_space_localize: n = %d", n);
+    if (entry < 0 || entry >= s->n_oct) return mad_fail(ctx, MAD_EINVAL, "mad_space_localize: entry %d of %d", entry, s->n_oct);
+    if (n == 0) return MAD_OK;
+    if (!cand || !status || !coord || !H || !G) return MAD_EINVAL;
+    mad_use_lane(ctx, 0);
+    const Octave &O = s->oct[entry];
+    MAD_TRY(localize_check(ctx, "mad_space_localize", O.d, cand, n));
+    return localize_run(ctx, O.logv, O.f64, O.d, cand, n, status, coord, H, G, n_undecided);
+}
+
+extern "C" int mad_localize_volume(mad_ctx *ctx, const void *vol, int is_f64, int nx, int ny, int nz, const int32_t *cand, int n,
+                                   int32_t *status, int32_t *coord, void *H, void *G, int64_t *n_undecided) {
+    if (!ctx) return MAD_EINVAL;
+    if (n_undecided) *n_undecided = 0;
+    if (n < 0) return mad_fail(ctx, MAD_EINVAL, "mad_localize_volume: n = %d", n);
+    if (is_f64 != 0 && is_f64 != 1) return mad_fail(ctx, MAD_EINVAL, "mad_localize_volume: is_f64 = %d", is_f64);
+    if (n == 0) return MAD_OK;
+    if (!vol || !cand || !status || !coord || !H || !G) return MAD_EINVAL;
+    mad_use_lane(ctx, 0);
+    const Dims d{{nx, ny, nz}};
+    MAD_TRY(localize_check(ctx, "mad_localize_volume", d, cand, n));
+    const size_t bytes = d.count() * (is_f64 ? 8 : 4);
+    MAD_TRY(mad_reserve(ctx, mad_sb(ctx, S_TMP_C), bytes));
+    MAD_HIP(hipMemcpyAsync(mad_sb(ctx, S_TMP_C).p, vol, bytes, hipMemcpyHostToDevice, ctx->stream));
+    return localize_run(ctx, mad_sb(ctx, S_TMP_C).p, is_f64 == 1, d, cand, n, status, coord, H, G, n_undecided);
 }
