@@ -225,7 +225,7 @@ int mad_match_topk(mad_ctx *ctx, const mad_set *hi, const mad_set *lo, double cc
 /*
  * The same for n subunit sets against one map set, with up to 4 matches in flight before the host waits for
  * the oldest.  results: n x k x 23; pair_index (nullable): n x k; n_out: n; stats (nullable): n x 4.
- * mad_match_fetch / _results / _used afterwards refer to the LAST match of the batch.
+ * mad_match_fetch / _results / _used afterwards refer to the LAST match of the batch (every match's flags: mad_match_topk_many2).
  */
 int mad_match_topk_many(mad_ctx *ctx, int n, const mad_set *const *hi, const mad_set *lo, double cc, double dist,
                         int64_t k, double *results, int64_t *pair_index, int64_t *n_out, int64_t *stats);
@@ -241,6 +241,24 @@ int mad_match_topk_many(mad_ctx *ctx, int n, const mad_set *const *hi, const mad
 int mad_match_topk_many_begin(mad_ctx *ctx, int n, const mad_set *const *hi, const mad_set *lo, double cc, double dist,
                               int64_t k, double *results, int64_t *pair_index, int64_t *n_out, int64_t *stats);
 int mad_match_topk_many_finish(mad_ctx *ctx);
+/*
+ * The same two calls, and mad_match_topk_many, with every match's anchor-use flags -- what mad_match_used returns after a single
+ * mad_match_topk -- for MaD.run, whose filter and refinement need each match's clouds (MaD.py:427-428).  Both arrays are nullable and
+ * belong to the bracket until _finish returns, like the other outputs:
+ *   used_hi: one byte per anchor of hi[0], then of hi[1], ... (sum of the hi sets' anchor counts); match i at the sum of the counts
+ *            of hi[0 .. i-1];
+ *   used_lo: n x (anchors of lo); match i at i * (anchors of lo).
+ * 1 = the anchor is in at least one pair above cc.  Flags are per canonical anchor, as in mad_match_used: anchors with identical
+ * sub-voxel coordinates count once, on the first of them in the set's anchor list; the others stay 0.  A match that is not run (an
+ * empty set) leaves 0.  Each match's flags are copied on its own lane, in stream order, into pinned staging of the bracket before the
+ * lane can take another match: no host synchronisation inside the bracket, and no device allocation.
+ */
+int mad_match_topk_many_begin2(mad_ctx *ctx, int n, const mad_set *const *hi, const mad_set *lo, double cc, double dist,
+                               int64_t k, double *results, int64_t *pair_index, int64_t *n_out, int64_t *stats,
+                               uint8_t *used_hi, uint8_t *used_lo);
+int mad_match_topk_many2(mad_ctx *ctx, int n, const mad_set *const *hi, const mad_set *lo, double cc, double dist,
+                         int64_t k, double *results, int64_t *pair_index, int64_t *n_out, int64_t *stats,
+                         uint8_t *used_hi, uint8_t *used_lo);
 /* on != 0: mad_match_topk_many(_begin) computes the score tiles of all matches of a bracket (first match of every lane) in ONE
  * GEMM grid -- fewer, fuller launches (C3: 0.151 -> 0.106 ms of device time per step) at the price of every match waiting for
  * the slowest set; off (default): one GEMM per match, each on its own lane, which overlaps better when several lanes are busy

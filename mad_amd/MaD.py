@@ -15,6 +15,21 @@ solution files land in the one results folder rank 0 created, and the lists of s
 ends with the reference's `buildable_subunits`; `build_assembly` runs on rank 0.  The exchanges are a few python objects over a
 gloo group (names, file lists): control plane, nothing of the data path crosses ranks.
 
+Resident path (the default): `_describe_struct` runs MapSpace and Detector as above and then builds the structure's rows straight
+into a device set (`Lib.set_build`: orientation + description, one call); the rows stay on the device as a `DescriptorRows`
+(mad_amd/rows.py) and become host objects only when somebody reads them.  The cache is written from and read into arrays
+(`set_load`, no row objects).  `get_solutions` matches every subunit and ensemble frame of this rank against the resident map set in
+`match_topk_many_begin` / `_finish` brackets, each match handing back its own clouds (`mad_match_topk_many_begin2`), then filters,
+refines and writes subunit by subunit in the reference's order.  MAD_STAGE_PATH=1 keeps the stage-by-stage path (Orientator ->
+Descriptor -> _RowSet -> one match_topk per subunit / frame); both write the same files.
+
+`run()` options and the resident path: ori_eqsp_size, dsc_eqsp_size and dsc_subregions are accepted and ignored on both paths, as
+the reference ignores them (only patch_size reaches the stages), and run() has no gw_sig (Orientator's default, 0,
+is what both paths use).  patch_size gives r = patch_size // 2 (an odd size loses one, as Orientator / Descriptor print); the
+resident path covers r = 2, 4, 6, 8 (patch_size 4-5, 8-9, 12-13, 16-17), the radii the description kernel is built for.  Any other
+patch_size falls back to the stage path with a one-line message (the stage path then reports the kernel's own error).
+`mad.timings`: wall seconds per stage of the last run() (prep, mapspace, detector, build, cache_io, match, filter, refine_ccc, write).
+
 Kept from the reference: method names, argument order and defaults, the
 `results/<map>_<comps>_res..._iso...` folder layout, the `Solutions_refined_<k>.csv`
 header and the descriptor cache file name (MaD.py:118).  Replaced: the h5py cache
@@ -23,6 +38,7 @@ with the built-in MRC writer.  Assembly building (MaD.py:632-843) is out of scop
 the hot path; `build_assembly` is provided by mad_amd.assembly when present.
 """
 import os
+import time
 from copy import deepcopy
 from operator import itemgetter
 
@@ -37,6 +53,7 @@ from .MapSpace import MapSpace
 from .math_utils import get_rototrans_SVD
 from .Orientator import Orientator
 from .PDB import PDB
+from .rows import DescriptorRows
 from .structure_utils import dock_refine_score_many, move_copy_structure
 
 try:      # optional: the reference's cache format
@@ -48,6 +65,9 @@ except Exception:      # pragma: no cover - h5py is absent in the build image
 D_CC, REPEAT, LO_IDX, LO_OCT, LO_BIN, HI_IDX, HI_OCT, HI_BIN = range(8)
 HI_COORD, LO_COORD = slice(8, 11), slice(11, 14)
 R1, R2, R3 = slice(14, 17), slice(17, 20), slice(20, 23)
+
+TIMING_KEYS = ("prep", "mapspace", "detector", "build", "cache_io", "match", "filter", "refine_ccc", "write")
+BRACKET_MAX = 16      # matches per bracket: two per lane of the context (MAD_RES); a chunk's ensemble frames are closed behind it
 
 
 class _RowSet(object):
@@ -85,6 +105,26 @@ class MaD(object):
         self.out_folder = None
         self.dsc_dict = {}
         self._rowsets = {}
+        self.timings = dict.fromkeys(TIMING_KEYS, 0.0)
+        self.n_correlations = 0    # descriptor pairs correlated by the matches of the last run() (rows x rows per match)
+        self._fallback = None      # why the last run() took the stage path although MAD_STAGE_PATH is not set (None: it did not)
+        self._pending = []         # resident path: this rank's matches not yet run, [(key, n_copies, is_frame)]
+        self._matched = {}         # ... and their outcome, key -> (top rows, map cloud, structure cloud)
+
+    def _stage(self):
+        """True when this run takes the stage-by-stage path (MAD_STAGE_PATH=1, or options the resident path does not cover)."""
+        return os.environ.get("MAD_STAGE_PATH", "0") == "1" or self._fallback is not None
+
+    def _tick(self, key, t0):
+        self.timings[key] = self.timings.get(key, 0.0) + time.perf_counter() - t0
+
+    @staticmethod
+    def resident_unsupported(patch_size=16):
+        """Why mad_set_build cannot serve these run() options (None when it can); see the module docstring."""
+        r = int(patch_size) // 2
+        if r not in (2, 4, 6, 8):
+            return "patch_size %s (r = %d): the resident build describes r = 2, 4, 6, 8 only" % (patch_size, r)
+        return None
 
     # ------------------------------------------------------------------ inputs
     def add_subunit(self, sub_filename_folder, n_copies=1, identifier=""):
@@ -157,7 +197,17 @@ class MaD(object):
     def run(self, transform_subunits=False, detect_sigma=2.0, presmooth_sigma=1, ori_eqsp_size=112, dsc_eqsp_size=16,
             dsc_subregions=64, patch_size=16, cc_threshold=0.6, weight_threshold=4, n_samples=60):
         self.transform_subunits = transform_subunits
-        if not self.check_preprocess_data():
+        self.timings = dict.fromkeys(TIMING_KEYS, 0.0)
+        self.n_correlations = 0
+        self._fallback = None
+        if os.environ.get("MAD_STAGE_PATH", "0") != "1":
+            self._fallback = self.resident_unsupported(patch_size)
+            if self._fallback is not None:
+                print("MaD> %s; taking the stage path" % self._fallback)
+        t0 = time.perf_counter()
+        ok = self.check_preprocess_data()
+        self._tick("prep", t0)
+        if not ok:
             return
         self.get_descriptors(detect_sigma=detect_sigma, presmooth_sigma=presmooth_sigma, patch_size=patch_size,
                              ori_eqsp_size=ori_eqsp_size, dsc_eqsp_size=dsc_eqsp_size, dsc_subregions=dsc_subregions)
@@ -195,12 +245,16 @@ class MaD(object):
         def described(key, struct, what):
             name = self._cache_name(key, detect_sigma, presmooth_sigma, patch_size, ori_eqsp_size, dsc_eqsp_size)
             if self._cache_exists(name):
+                t0 = time.perf_counter()
                 rows = self._load_descriptors(name)
+                self._tick("cache_io", t0)
                 print("MaD> %i descriptors for %s found in database" % (len(rows), key))
                 return rows, name
             print("\nMaD> Processing %s %s" % (what, key))
             rows = self._describe_struct(struct, detect_sigma, presmooth_sigma, ori_eqsp_size, dsc_eqsp_size, dsc_subregions, patch_size)
+            t0 = time.perf_counter()
             self._save_descriptors(rows, name)
+            self._tick("cache_io", t0)
             return rows, name
 
         rank, world, dist = self._ranks()
@@ -215,7 +269,9 @@ class MaD(object):
                 names[key] = self._cache_name(key, detect_sigma, presmooth_sigma, patch_size, ori_eqsp_size, dsc_eqsp_size)
             self._all_ranks(dist, lambda: [described(key, struct, what) for i, (key, struct, what) in enumerate(jobs) if i % world == rank])
             dist.barrier()
+            t0 = time.perf_counter()
             self.map_dsc = self._load_descriptors(names[self.map_name])
+            self._tick("cache_io", t0)
             for k in self.processed_subunits:
                 self.dsc_dict[k] = names[k]
             for ek in self.processed_ensembles:
@@ -230,8 +286,10 @@ class MaD(object):
             self.dsc_dict[ek] = {}
             print("\nMaD> Describing ensemble %s" % ek)
             for fk in self.processed_ensembles[ek]:
-                _, name = described(fk, self.processed_ensembles[ek][fk][0], "frame")
-                self.dsc_dict[fk] = name      # frames are re-loaded when matched (MaD.py:158-162)
+                rows, name = described(fk, self.processed_ensembles[ek][fk][0], "frame")
+                # stage path: frames are re-loaded when matched (MaD.py:158-162); resident path: a frame's rows stay where they are
+                # (a built set on the device, or the cache's arrays, loaded into a set by its bracket) until its match has run
+                self.dsc_dict[fk] = name if self._stage() else rows
 
     def get_solutions(self, cc_threshold=0.6, weight_threshold=4, n_samples=120):
         rank, world, dist = self._ranks()
@@ -243,6 +301,8 @@ class MaD(object):
             for ek in self.processed_ensembles:
                 jobs += [("frame", ek, fk) for fk in self.processed_ensembles[ek]]
             mine = {}
+            self._plan_matches([(key, (self.processed_subunits[key] if kind == "sub" else self.processed_ensembles[owner_key][key])[1], kind == "frame")
+                                for kind, owner_key, key in shard_round_robin(jobs, rank, world)])
 
             def dock_mine():
                 for kind, owner_key, key in shard_round_robin(jobs, rank, world):
@@ -266,6 +326,8 @@ class MaD(object):
                         self.buildable_subunits[owner_key] = [ensemble[list(ensemble.keys())[0]][1], []]
                     self.buildable_subunits[owner_key][1].extend(files)
             return
+        self._plan_matches([(k, v[1], False) for k, v in self.processed_subunits.items()] +
+                           [(fk, v[1], True) for ek in self.processed_ensembles for fk, v in self.processed_ensembles[ek].items()])
         for k in self.processed_subunits:
             pdbfile, n_copies = self.processed_subunits[k]
             files = self._match_filter_refine(pdbfile, n_copies, k, cc_threshold, weight_threshold, n_samples)
@@ -370,17 +432,59 @@ class MaD(object):
 
     # ------------------------------------------------------------------ hot path
     def _describe_struct(self, struct, detect_sigma, presmooth_sigma, ori_eqsp_size, dsc_eqsp_size, dsc_subregions, patch_size):
-        """MaD.py:358-368.  As in the reference, only patch_size reaches the stages."""
+        """MaD.py:358-368.  As in the reference, only patch_size reaches the stages.  Resident path: a DescriptorRows
+        over a set built by Lib.set_build; stage path: the list of DensityFeature rows of Orientator + Descriptor."""
         ms = MapSpace(struct, resolution=self.resolution, voxelsp=self.voxsp, sig_init=detect_sigma, sig_presmooth=presmooth_sigma)
         det = Detector()
-        ori = Orientator(ori_radius=patch_size)
-        dsc = Descriptor(dsc_radius=patch_size)
+        t0 = time.perf_counter()
         ms.build_space()
+        self._tick("mapspace", t0)
+        t0 = time.perf_counter()
         anchors = det.find_anchors(ms)
-        oriented = ori.assign_orientations(ms, anchors)
-        rows = dsc.generate_descriptors(ms, oriented)
+        self._tick("detector", t0)
+        t0 = time.perf_counter()
+        if self._stage():
+            ori = Orientator(ori_radius=patch_size)
+            dsc = Descriptor(dsc_radius=patch_size)
+            oriented = ori.assign_orientations(ms, anchors)
+            rows = dsc.generate_descriptors(ms, oriented)
+        else:
+            rows = self._build_rows(ms, anchors, patch_size)
+        self._tick("build", t0)
         ms.release_device()
         return rows
+
+    @staticmethod
+    def _bind_tables(lib):
+        """The EQSP tables of Orientator() / Descriptor() (112 orientation zones with their matrices, 16 descriptor zones), loaded
+        the way their _bind does, and no orientation window."""
+        if lib._eq_loaded.get(0) != ("ori", 112):
+            Orientator()._bind(lib)
+        if lib._eq_loaded.get(1) != ("dsc", 16):
+            Descriptor()._bind(lib)
+        lib.set_orient_window(0.0)
+
+    def _build_rows(self, ms, anchors, patch_size):
+        """Orientation + description of the detector's anchors into one device set (mad_set_build): the rows of
+        Orientator(ori_radius=patch_size) + Descriptor(dsc_radius=patch_size), in their order, without a row object."""
+        lib = _lib.get_lib()
+        self._bind_tables(lib)
+        print("MaD> Orienting and describing %i anchors on the device..." % len(anchors))
+        slots = ms.device_slots(lib)
+        kinds = ms.space.kinds      # list entry -> 0 upsampled / 1 base: the octave the kernels sample with
+        slot_of_octave = [-1, -1]
+        for e, kd in enumerate(kinds):
+            slot_of_octave[kd] = slots[e]
+        n = len(anchors)
+        entry = np.array([df.oct_scale for df in anchors], np.int64)
+        coords = np.array([df.coords for df in anchors], np.int64).reshape(n, 3)
+        map_coords = np.array([df.map_coords for df in anchors], np.float64).reshape(n, 3)
+        subv = np.array([df.subv_map_coords for df in anchors], np.float64).reshape(n, 3)
+        index = np.array([df.index for df in anchors], np.int64)
+        octave = np.array(kinds, np.int32)[entry] if n else np.zeros(0, np.int32)
+        dev = lib.set_build(slot_of_octave, coords, octave, subv, index, r=int(patch_size) // 2, lim_main=6, lim_sec=6, gw_sig=0.0)
+        dev.size()      # waits for the build: it reads the MapSpace fields, which are freed next
+        return DescriptorRows.built(dev, index, entry, coords, map_coords, subv, eqsp_size=112, subeqsp_size=16, D=1024)
 
     def _rowset(self, lib, dsc_list):
         key = id(dsc_list)
@@ -394,6 +498,7 @@ class MaD(object):
         lib = _lib.get_lib()
         lo, hi = self._rowset(lib, lo_dsc_list), self._rowset(lib, hi_dsc_list)
         top, idx, stats = lib.match_topk(hi.dev, lo.dev, cc_threshold, anchor_dist_thresh, k)
+        self.n_correlations = getattr(self, "n_correlations", 0) + stats["n_corr"]
         if stats["n_pairs"]:
             uh, ul = lib.match_used(len(hi.anchors), len(lo.anchors))
             hi_cloud, lo_cloud = hi.anchors[uh], lo.anchors[ul]
@@ -413,24 +518,85 @@ class MaD(object):
         _, _, _, top, _, _, lo_cloud, hi_cloud = self._match_device(lo_dsc_list, hi_dsc_list, anchor_dist_thresh, cc_threshold, k)
         return top, lo_cloud, hi_cloud
 
+    def _plan_matches(self, jobs):
+        """Resident path: the matches this rank will ask _match_filter_refine for, [(key, n_copies, is_frame)] in that order.  The
+        first request runs them all, in brackets (_run_brackets)."""
+        self._pending = [] if self._stage() else list(jobs)
+        self._matched = {}
+
+    def _as_rows(self, x):
+        """DescriptorRows of a structure, whichever form dsc_dict / map_dsc hold it in (rows, a cache name, a list of rows)."""
+        if isinstance(x, DescriptorRows):
+            return x
+        if isinstance(x, str):
+            t0 = time.perf_counter()
+            rows = self._load_descriptors(x)
+            self._tick("cache_io", t0)
+            return rows if isinstance(rows, DescriptorRows) else DescriptorRows.from_arrays(self._list_arrays(rows))
+        return DescriptorRows.from_arrays(self._list_arrays(x))
+
+    def _run_brackets(self, cc_threshold, n_samples):
+        """Every planned match against the resident map set, up to BRACKET_MAX per match_topk_many bracket, all at
+        k = the largest n_samples * n_copies: a subunit keeps its first n_samples * n_copies rows, which are its own top-k because the
+        device order is a total order (repeatability descending, then row-major pair rank -- the stable sort of MaD.py:480).  Each
+        match's clouds come from its own anchor-use flags, in np.unique(..., axis=0) order (MaD.py:427-428).  A chunk's ensemble
+        frames are closed behind its bracket."""
+        lib = _lib.get_lib()
+        jobs, self._pending = self._pending, []
+        if not jobs:
+            return
+        lo = self._as_rows(self.map_dsc)
+        self.map_dsc = lo
+        K = max(int(n_samples * n) for _, n, _ in jobs)
+        for c0 in range(0, len(jobs), BRACKET_MAX):
+            chunk = jobs[c0:c0 + BRACKET_MAX]
+            rows = [self._as_rows(self.dsc_dict[key]) for key, _, _ in chunk]
+            t0 = time.perf_counter()
+            h = lib.match_topk_many_begin([r.dev for r in rows], lo.dev, cc_threshold, 4.0, K, want_used=True)
+            out = lib.match_topk_many_finish(h)
+            for (key, n_copies, frame), r, (top, _, st, uh, ul) in zip(chunk, rows, out):
+                self.n_correlations += st["n_corr"]
+                if st["n_pairs"]:
+                    hi_cloud, lo_cloud = np.unique(r.anchor_subv[uh], axis=0), np.unique(lo.anchor_subv[ul], axis=0)
+                else:
+                    hi_cloud, lo_cloud = np.zeros((0, 3)), np.zeros((0, 3))
+                self._matched[key] = (top[:int(n_samples * n_copies)], lo_cloud, hi_cloud)
+                if frame:      # one frame resident only until its match has run (MaD.py:158-162, 379-380)
+                    r.close()
+            self._tick("match", t0)
+
     def _match_filter_refine(self, pdbfile, n_copies, k, cc_threshold, weight_threshold, n_samples):
         n_samples_sub = int(n_samples * n_copies)
         print("MaD> Matching descriptors (%s vs. %s) (cc = %.2f)..." % (self.map_name, k, cc_threshold))
-        from_cache = isinstance(self.dsc_dict[k], str)
-        hi_list = self._load_descriptors(self.dsc_dict[k]) if from_cache else self.dsc_dict[k]
-        top, map_anchors, comp_anchors = self._match_dsc_topk(self.map_dsc, hi_list, n_samples_sub, cc_threshold=cc_threshold)
-        if from_cache:      # an ensemble frame re-loaded for this match (MaD.py:158-162, 379-380): one frame resident at a time
-            hit = self._rowsets.pop(id(hi_list), None)
-            if hit is not None:
-                hit[1].dev.close()
+        if not self._stage() and (k in self._matched or any(j[0] == k for j in self._pending)):
+            if k not in self._matched:
+                self._run_brackets(cc_threshold, n_samples)
+            top, map_anchors, comp_anchors = self._matched.pop(k)
+        else:
+            t0 = time.perf_counter()
+            from_cache = isinstance(self.dsc_dict[k], str)
+            hi_list = self._load_descriptors(self.dsc_dict[k]) if from_cache else self.dsc_dict[k]
+            top, map_anchors, comp_anchors = self._match_dsc_topk(self.map_dsc, hi_list, n_samples_sub, cc_threshold=cc_threshold)
+            if from_cache:      # an ensemble frame re-loaded for this match (MaD.py:158-162, 379-380): one frame resident at a time
+                hit = self._rowsets.pop(id(hi_list), None)
+                if hit is not None:
+                    hit[1].dev.close()
+            self._tick("match", t0)
         if not len(top):
             print("MaD> No descriptor pair above the threshold for %s" % k)
             return []
         print("MaD> Filtering descriptor pairs (map %s vs. structure %s) (weight=%i, n_samples=%i*%i)..." % (self.map_name, k, weight_threshold, n_samples, n_copies))
+        t0 = time.perf_counter()
         filtered = self._filter_dsc_pairs(pdbfile, top, map_anchors, comp_anchors, wthresh=weight_threshold, n_samples=n_samples_sub, presorted=True)
+        self._tick("filter", t0)
         print("MaD> Refining %s in %s..." % (self.map_name, k))
+        t0 = time.perf_counter()
         refined = self._refine_filtered_solutions(pdbfile, filtered, map_anchors, comp_anchors)
-        return self._save_solutions_refined(refined, k)
+        self._tick("refine_ccc", t0)
+        t0 = time.perf_counter()
+        files = self._save_solutions_refined(refined, k)
+        self._tick("write", t0)
+        return files
 
     def _filter_dsc_pairs(self, pdbfile, match_data, lo_cloud, hi_cloud, wthresh=4, n_samples=200, presorted=False):
         """Greedy clustering of the best poses by cloud RMSD (MaD.py:456-553).  Host, float64."""
@@ -528,12 +694,18 @@ class MaD(object):
     def _cache_exists(self, name):
         return (h5py is not None and os.path.exists(name)) or os.path.exists(self._npz_name(name))
 
-    def _save_descriptors(self, df_list, outname):
-        data = dict(
+    @staticmethod
+    def _list_arrays(df_list):
+        """The four cache datasets of a list of DensityFeature rows."""
+        return dict(
             dsc=np.array([df.lin_ar_subeqsp for df in df_list], dtype=np.int16),
             info=np.array([[df.index, df.main_bin, df.sec_bin, df.oct_scale, df.eqsp_size, df.subeqsp_size] for df in df_list]).astype(np.uint16),
             coords=np.array([[df.coords, df.map_coords, df.subv_map_coords] for df in df_list], dtype=np.float64),
             rot=np.array([df.Rfinal for df in df_list], dtype=np.float64))
+
+    def _save_descriptors(self, df_list, outname):
+        """MaD.py:849-858.  A DescriptorRows is written from its arrays(), without row objects; the file is the same."""
+        data = df_list.arrays() if isinstance(df_list, DescriptorRows) else self._list_arrays(df_list)
         if h5py is not None:
             with h5py.File(outname, "w") as hf:
                 for k, v in data.items():
@@ -548,6 +720,8 @@ class MaD(object):
         else:
             with np.load(self._npz_name(input_name)) as z:
                 data = {k: z[k] for k in ("dsc", "info", "coords", "rot")}
+        if not self._stage():      # resident path: the arrays as they are; the set is loaded from them (set_load) when first matched
+            return DescriptorRows.from_arrays(data)
         rows = []
         for d, c, i, r in zip(data["dsc"], data["coords"], data["info"], data["rot"]):
             df = DensityFeature()

@@ -23,7 +23,7 @@ SYMBOLS = [
     "mad_set_eqsp", "mad_upload_field", "mad_upload_field_device", "mad_free_field",
     "mad_set_orient_window", "mad_orient", "mad_describe", "mad_describe_sized", "mad_correlate", "mad_pose_score", "mad_topk",
     "mad_set_create", "mad_set_destroy", "mad_set_build", "mad_set_build_many", "mad_set_load", "mad_set_size", "mad_set_download",
-    "mad_match_topk", "mad_match_topk_many", "mad_match_topk_many_begin", "mad_match_topk_many_finish", "mad_set_batching", "mad_set_option", "mad_last_pose_kernel", "mad_last_pose_selected", "mad_device_allocations", "mad_match_fetch", "mad_match_results", "mad_match_used",
+    "mad_match_topk", "mad_match_topk_many", "mad_match_topk_many_begin", "mad_match_topk_many_finish", "mad_match_topk_many_begin2", "mad_match_topk_many2", "mad_set_batching", "mad_set_option", "mad_last_pose_kernel", "mad_last_pose_selected", "mad_device_allocations", "mad_match_fetch", "mad_match_results", "mad_match_used",
     "mad_match_shard_pairs", "mad_match_shard_topk", "mad_match_shard_begin", "mad_match_shard_score", "mad_match_shard_record_doubles", "mad_match_shard_collect", "mad_match_shard_wait",
     "mad_set_wire_bytes", "mad_set_export", "mad_set_import", "mad_set_lane", "mad_set_stream", "mad_set_bind_lane",
     "mad_upload_density", "mad_refine", "mad_structure_to_density", "mad_ccc", "mad_density_ccc", "mad_dock_refine_score", "mad_grid_overlap", "mad_overlap_matrix",
@@ -568,22 +568,46 @@ class Lib(object):
         g = n_out.value
         return res[:g], idx[:g], dict(n_pairs=int(stats[0]), l_hi=int(stats[1]), l_lo=int(stats[2]), n_corr=int(stats[3]))
 
-    def match_topk_many(self, his, lo, cc, dist, k):
-        """[(rows, pair_index, stats)] for every subunit set of `his` against `lo`; see mad_match_topk_many."""
+    def match_topk_many(self, his, lo, cc, dist, k, want_used=False):
+        """[(rows, pair_index, stats)] for every subunit set of `his` against `lo`; see mad_match_topk_many.  want_used=True:
+        [(rows, pair_index, stats, used_hi, used_lo)], each match's anchor-use flags as bool arrays (mad_match_topk_many2)."""
+        h = self._many_args(his, lo, k, want_used)
+        n = h["n"]
+        if want_used:
+            self._chk(self.dll.mad_match_topk_many2(self.ctx, C.c_int(n), h["arr"], lo.h, C.c_double(cc), C.c_double(dist), C.c_int64(h["k"]),
+                                                    _p(h["res"]), _p(h["idx"]), _p(h["n_out"]), _p(h["stats"]), _p(h["used_hi"]),
+                                                    _p(h["used_lo"])))
+        else:
+            self._chk(self.dll.mad_match_topk_many(self.ctx, C.c_int(n), h["arr"], lo.h, C.c_double(cc), C.c_double(dist), C.c_int64(h["k"]),
+                                                   _p(h["res"]), _p(h["idx"]), _p(h["n_out"]), _p(h["stats"])))
+        return self._many_unpack(h)
+
+    @staticmethod
+    def _many_args(his, lo, k, want_used):
+        """Output arrays of one bracket (and, with want_used, its flag arrays: hi flags back to back, lo flags n x anchors of lo)."""
         k = int(k)
         n = len(his)
-        res = np.zeros((max(n, 1), max(k, 1), RESULT_COLS))
-        idx = np.zeros((max(n, 1), max(k, 1)), np.int64)
-        n_out = np.zeros(max(n, 1), np.int64)
-        stats = np.zeros((max(n, 1), 4), np.int64)
-        arr = (C.c_void_p * max(n, 1))(*[h.h.value for h in his])
-        self._chk(self.dll.mad_match_topk_many(self.ctx, C.c_int(n), arr, lo.h, C.c_double(cc), C.c_double(dist), C.c_int64(k),
-                                               _p(res), _p(idx), _p(n_out), _p(stats)))
+        h = dict(n=n, k=k, res=np.zeros((max(n, 1), max(k, 1), RESULT_COLS)), idx=np.zeros((max(n, 1), max(k, 1)), np.int64),
+                 n_out=np.zeros(max(n, 1), np.int64), stats=np.zeros((max(n, 1), 4), np.int64), sets=(list(his), lo),
+                 arr=(C.c_void_p * max(n, 1))(*[x.h.value for x in his]), want_used=bool(want_used))
+        if want_used:
+            h["hi_off"] = np.concatenate([[0], np.cumsum([x.n_anchors for x in his], dtype=np.int64)]).astype(np.int64)
+            h["used_hi"] = np.zeros(max(int(h["hi_off"][-1]), 1), np.uint8)
+            h["used_lo"] = np.zeros((max(n, 1), max(lo.n_anchors, 1)), np.uint8)
+        return h
+
+    @staticmethod
+    def _many_unpack(h):
         out = []
-        for i in range(n):
-            g = int(n_out[i])
-            out.append((res[i, :g], idx[i, :g], dict(n_pairs=int(stats[i, 0]), l_hi=int(stats[i, 1]), l_lo=int(stats[i, 2]),
-                                                     n_corr=int(stats[i, 3]))))
+        for i in range(h["n"]):
+            g = int(h["n_out"][i])
+            st = h["stats"][i]
+            row = (h["res"][i, :g], h["idx"][i, :g], dict(n_pairs=int(st[0]), l_hi=int(st[1]), l_lo=int(st[2]), n_corr=int(st[3])))
+            if h["want_used"]:
+                a, b = int(h["hi_off"][i]), int(h["hi_off"][i + 1])
+                n_lo = h["sets"][1].n_anchors
+                row += (h["used_hi"][a:b].astype(bool), h["used_lo"][i, :n_lo].astype(bool))
+            out.append(row)
         return out
 
     def last_pose_kernel(self):
@@ -598,16 +622,19 @@ class Lib(object):
         """Device buffers (re)allocated by this context so far (mad_device_allocations): 0 new ones across a steady-state region."""
         return int(self.dll.mad_device_allocations(self.ctx))
 
-    def match_topk_many_begin(self, his, lo, cc, dist, k):
+    def match_topk_many_begin(self, his, lo, cc, dist, k, want_used=False):
         """Enqueue every match and return a handle; `match_topk_many_finish(handle)` waits and unpacks.  In between
-        the caller may build the sets of its next batch (not the ones this bracket reads)."""
-        k = int(k)
-        n = len(his)
-        h = dict(n=n, k=k, res=np.zeros((max(n, 1), max(k, 1), RESULT_COLS)), idx=np.zeros((max(n, 1), max(k, 1)), np.int64),
-                 n_out=np.zeros(max(n, 1), np.int64), stats=np.zeros((max(n, 1), 4), np.int64), sets=(list(his), lo))
-        arr = (C.c_void_p * max(n, 1))(*[x.h.value for x in his])
-        self._chk(self.dll.mad_match_topk_many_begin(self.ctx, C.c_int(n), arr, lo.h, C.c_double(cc), C.c_double(dist), C.c_int64(k),
-                                                     _p(h["res"]), _p(h["idx"]), _p(h["n_out"]), _p(h["stats"])))
+        the caller may build the sets of its next batch (not the ones this bracket reads).  want_used=True: every match also
+        hands back its anchor-use flags (mad_match_topk_many_begin2), and finish returns 5-tuples."""
+        h = self._many_args(his, lo, k, want_used)
+        n = h["n"]
+        if want_used:
+            self._chk(self.dll.mad_match_topk_many_begin2(self.ctx, C.c_int(n), h["arr"], lo.h, C.c_double(cc), C.c_double(dist),
+                                                          C.c_int64(h["k"]), _p(h["res"]), _p(h["idx"]), _p(h["n_out"]), _p(h["stats"]),
+                                                          _p(h["used_hi"]), _p(h["used_lo"])))
+        else:
+            self._chk(self.dll.mad_match_topk_many_begin(self.ctx, C.c_int(n), h["arr"], lo.h, C.c_double(cc), C.c_double(dist),
+                                                         C.c_int64(h["k"]), _p(h["res"]), _p(h["idx"]), _p(h["n_out"]), _p(h["stats"])))
         self._open_brackets = getattr(self, "_open_brackets", []) + [h]      # at most three (MAD_BRACKETS); they finish in the order they began
         return h
 
@@ -617,12 +644,7 @@ class Lib(object):
             raise MadBackendError("MaD> match_topk_many_finish: brackets finish in the order they were begun")
         self._open_brackets = pending[1:]      # the library closes the bracket whether or not one of its matches failed
         self._chk(self.dll.mad_match_topk_many_finish(self.ctx))
-        out = []
-        for i in range(h["n"]):
-            g = int(h["n_out"][i])
-            st = h["stats"][i]
-            out.append((h["res"][i, :g], h["idx"][i, :g], dict(n_pairs=int(st[0]), l_hi=int(st[1]), l_lo=int(st[2]), n_corr=int(st[3]))))
-        return out
+        return self._many_unpack(h)
 
     def match_shard_pairs(self, hi, lo, lo_begin, lo_end, cc):
         """Stage B of a sharded match -> (used_hi flags, used_lo flags, n_pairs) of the lo-row block [lo_begin, lo_end)."""

@@ -223,6 +223,9 @@ struct mad_ctx {
     hipEvent_t gemm_done[MAD_BRACKETS];            // ... and that GEMM has been enqueued (per open bracket)
     void *host_res[MAD_BRACKETS][MAD_RES] = {};     // pinned staging of a match's results / indices / status
     size_t host_res_cap[MAD_BRACKETS][MAD_RES] = {};
+    // pinned staging of a bracket match's anchor-use flags (mad_match_topk_many_begin2): [hi flags, padded to 32][lo flags]
+    void *host_used[MAD_BRACKETS][MAD_RES] = {};
+    size_t host_used_cap[MAD_BRACKETS][MAD_RES] = {};
     int res_slot = 0, res_idx = 0;       // the (bracket, result index) the match calls below read and write
     // host pinned staging for small read-backs
     int64_t *pinned = nullptr;     // 1024 slots: [16 * lane ..] read-backs of the lane, [64..] two per mad_set

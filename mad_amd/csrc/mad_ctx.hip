@@ -131,6 +131,7 @@ extern "C" void mad_destroy(mad_ctx *ctx) {
         for (int r = 0; r < MAD_BRACKETS; r++) {
             (void)hipEventDestroy(ctx->lane_done[r][l]);
             if (ctx->host_res[r][l]) (void)hipHostFree(ctx->host_res[r][l]);
+            if (ctx->host_used[r][l]) (void)hipHostFree(ctx->host_used[r][l]);
         }
     for (int l = 0; l < MAD_LANES; l++)
         if (ctx->lane_stream[l]) (void)hipStreamDestroy(ctx->lane_stream[l]);

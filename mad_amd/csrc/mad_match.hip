@@ -3332,6 +3332,7 @@ struct MatchPlan {
     bool no_small;      // the one-workgroup top-k over the pruned selection overflowed: use the general selection
     bool pruned;        // this attempt's pose search was pruned by bounds (set when it is enqueued; per bracket and lane, not per lane)
     PosePlan pose;      // made by match_enqueue_head (which also zeroes the bitmaps), used by match_enqueue_tail
+    bool want_used;     // copy the anchor-use flags to ctx->host_used of this (bracket, result index) (mad_match_topk_many_begin2)
 };
 
 // enqueue a11 + a12 + top-k (+ the result rows) of one (hi, lo) pair in the CURRENT lane; no host round trip.
@@ -3346,6 +3347,16 @@ static size_t zero_bytes(const mad_set *hi, const mad_set *lo) {
     return ((size_t)(ST_COUNT + 2 * (hi->n_anchors + 17)) * 4 + (size_t)hi->n_anchors + lo->n_anchors + 64 + 15) / 16 * 16;
 }
 static size_t tail_bytes(int64_t k) { return (size_t)k * (MAD_RESULT_COLS * 8 + 8) + ST_COUNT * 4; }
+// the used flags as they lie in the zero region, [hi, padded to 32][lo], in whole words (inside zero_bytes: its 64 spare bytes cover the
+// padding)
+static int used_words(int n_hi, int n_lo) { return (((n_hi + 31) & ~31) + n_lo + 3) / 4; }
+
+// The anchor-use flags of one bracket match into the pinned staging of its (bracket, result index), in stream order behind the
+// pose search that last reads them and before the match's completion event: the lane's zero region is rewritten by its next match.
+// One word per thread, vector stores to host-visible memory (as k_results writes the rows).
+__global__ void k_used_out(const uint32_t *__restrict__ src, uint32_t *__restrict__ dst, int n_words) {
+    for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < n_words; i += gridDim.x * blockDim.x) dst[i] = src[i];
+}
 
 // A match is enqueued in two halves: what precedes the GEMM (waits, zeroed status, the GEMM's arguments) and what follows it.
 // Between them the caller launches the GEMM -- of this match alone, or of all matches of a bracket in one grid.
@@ -3404,6 +3415,11 @@ static int match_enqueue_tail(mad_ctx *ctx, const mad_set *hi, const mad_set *lo
                            scratch<int32_t>(ctx, S_PAIR_LO), scratch<double>(ctx, S_PAIR_SCORE), scratch<int32_t>(ctx, S_COUNTS),
                            st, H.p, H.R, H.meta, L.p, L.Rinv, L.meta, H.row_anchor, L.row_anchor, RA.out, 1);
     }
+    if (P.want_used) {
+        const int nw = used_words(hi->n_anchors, lo->n_anchors);
+        hipLaunchKernelGGL(k_used_out, dim3((unsigned)std::min<int64_t>(mad_ceil_div(nw, 256), 64)), dim3(256), 0, ctx->stream, (const uint32_t *)used_hi,
+                           (uint32_t *)ctx->host_used[ctx->res_slot][ctx->res_idx], nw);
+    }
     MAD_HIP(hipGetLastError());
     // rows, pair ranks and status words were written by the kernel straight into the pinned staging of this (bracket, lane): no copy
     // engine, no blit kernel; the host reads them once the event has passed
@@ -3425,6 +3441,7 @@ static int match_prepare(mad_ctx *ctx, const mad_set *hi, const mad_set *lo, dou
     P->dist = dist;
     P->no_small = false;
     P->pruned = false;
+    P->want_used = false;
     MAD_TRY(mad_reserve(ctx, mad_sb(ctx, S_ZERO), zero_bytes(hi, lo)));
     MAD_TRY(mad_reserve(ctx, mad_sb(ctx, S_HI_CLOUD), (size_t)hi->n_anchors * 24 + 24));
     MAD_TRY(mad_reserve(ctx, mad_sb(ctx, S_SEL_OUT), (size_t)(P->k + 8) * 8));
@@ -3554,6 +3571,8 @@ struct ManyState {
     int64_t k = 1;
     double *results = nullptr;
     int64_t *pair_index = nullptr, *n_out = nullptr, *stats = nullptr;
+    uint8_t *used_hi = nullptr, *used_lo = nullptr;      // (mad_match_topk_many_begin2) every match's anchor-use flags
+    std::vector<int64_t> hi_off;                          // match i's hi flags start at used_hi + hi_off[i]
     MatchPlan plans[MAD_RES];      // by result index: ri = the match's lane, or MAD_LANES + lane for the second match of a lane
     int pending[MAD_RES];
     int slot = 0;      // result slot (pinned staging + completion events) of this bracket
@@ -3578,11 +3597,37 @@ static int many_retire(mad_ctx *ctx, ManyState &M, int ri) {
         rc = match_finish(ctx, ri, M.hi[i], M.lo, &M.plans[ri], res_i, idx_i, &M.n_out[i], st_i);
     }
     if (rc == 1) return mad_fail(ctx, MAD_EHIP, "mad_match_topk_many: capacity negotiation did not converge");
+    if (rc == 0 && M.plans[ri].want_used) {      // the flags arrived with the completion event (k_used_out)
+        const uint8_t *f = (const uint8_t *)ctx->host_used[M.slot][ri];
+        const int n_hi = M.hi[i]->n_anchors, n_lo = M.lo->n_anchors;
+        if (M.used_hi && n_hi > 0) memcpy(M.used_hi + M.hi_off[i], f, (size_t)n_hi);
+        if (M.used_lo && n_lo > 0) memcpy(M.used_lo + (size_t)i * n_lo, f + ((n_hi + 31) & ~31), (size_t)n_lo);
+    }
     return rc;
 }
 
-extern "C" int mad_match_topk_many_begin(mad_ctx *ctx, int n, const mad_set *const *hi, const mad_set *lo, double cc, double dist, int64_t k,
-                                         double *results, int64_t *pair_index, int64_t *n_out, int64_t *stats) {
+// pinned staging of the flags of the current (bracket, result index), grown on demand (host memory: no device allocation)
+static int used_reserve(mad_ctx *ctx, const mad_set *hi, const mad_set *lo, MatchPlan *P) {
+    const size_t want = (size_t)used_words(hi->n_anchors, lo->n_anchors) * 4;
+    void *&buf = ctx->host_used[ctx->res_slot][ctx->res_idx];
+    size_t &cap = ctx->host_used_cap[ctx->res_slot][ctx->res_idx];
+    if (cap < want) {
+        if (buf) {      // an earlier match of this lane may still write into it
+            MAD_HIP(hipStreamSynchronize(ctx->stream));
+            (void)hipHostFree(buf);
+            buf = nullptr;
+            cap = 0;
+        }
+        if (hipHostMalloc(&buf, want * 2) != hipSuccess) return mad_fail(ctx, MAD_ENOMEM, "pinned flag staging of %zu bytes", want * 2);
+        cap = want * 2;
+    }
+    P->want_used = true;
+    return MAD_OK;
+}
+
+extern "C" int mad_match_topk_many_begin2(mad_ctx *ctx, int n, const mad_set *const *hi, const mad_set *lo, double cc, double dist, int64_t k,
+                                          double *results, int64_t *pair_index, int64_t *n_out, int64_t *stats, uint8_t *used_hi,
+                                          uint8_t *used_lo) {
     if (!ctx || !hi || !lo || !n_out || n < 0) return MAD_EINVAL;
     if (ctx->many_open >= MAD_BRACKETS) return mad_fail(ctx, MAD_EINVAL, "mad_match_topk_many_begin: %d brackets are open already", MAD_BRACKETS);
     if (k < 1) k = 1;
@@ -3593,6 +3638,14 @@ extern "C" int mad_match_topk_many_begin(mad_ctx *ctx, int n, const mad_set *con
     ctx->res_slot = M.slot;
     M.n = n; M.hi.assign(hi, hi + n); M.lo = lo; M.cc = cc; M.dist = dist; M.k = k;
     M.results = results; M.pair_index = pair_index; M.n_out = n_out; M.stats = stats;
+    M.used_hi = used_hi; M.used_lo = used_lo;
+    const bool want_used = used_hi || used_lo;
+    if (want_used) {      // a match that is not run (an empty set) leaves its flags at 0
+        M.hi_off.assign(n + 1, 0);
+        for (int i = 0; i < n; i++) M.hi_off[i + 1] = M.hi_off[i] + (hi[i] ? std::max(hi[i]->n_anchors, 0) : 0);
+        if (used_hi && M.hi_off[n] > 0) memset(used_hi, 0, (size_t)M.hi_off[n]);
+        if (used_lo && n > 0 && lo->n_anchors > 0) memset(used_lo, 0, (size_t)n * lo->n_anchors);
+    }
     for (int l = 0; l < MAD_RES; l++) M.pending[l] = -1;
     ctx->many[M.slot] = Mp;
     int rc_all = MAD_OK;
@@ -3617,6 +3670,7 @@ extern "C" int mad_match_topk_many_begin(mad_ctx *ctx, int n, const mad_set *con
         mad_use_lane(ctx, lane);
         ctx->res_idx = lane;
         rc_all = match_prepare(ctx, hi[i], lo, dist, k, &M.plans[lane]);
+        if (rc_all == MAD_OK && want_used) rc_all = used_reserve(ctx, hi[i], lo, &M.plans[lane]);
         if (rc_all != MAD_OK) break;
         GemmJob job;
         rc_all = match_enqueue_head(ctx, hi[i], lo, cc, M.plans[lane], &job);
@@ -3663,6 +3717,7 @@ extern "C" int mad_match_topk_many_begin(mad_ctx *ctx, int n, const mad_set *con
         ctx->res_slot = M.slot;
         ctx->res_idx = ri;
         rc_all = match_prepare(ctx, hi[i], lo, dist, k, &M.plans[ri]);
+        if (rc_all == MAD_OK && want_used) rc_all = used_reserve(ctx, hi[i], lo, &M.plans[ri]);
         if (rc_all != MAD_OK) break;
         rc_all = match_enqueue(ctx, hi[i], lo, cc, dist, M.plans[ri]);
         M.pending[ri] = i;
@@ -3679,6 +3734,11 @@ extern "C" int mad_match_topk_many_begin(mad_ctx *ctx, int n, const mad_set *con
     ctx->res_slot = 0;
     ctx->res_idx = 0;
     return rc_all;
+}
+
+extern "C" int mad_match_topk_many_begin(mad_ctx *ctx, int n, const mad_set *const *hi, const mad_set *lo, double cc, double dist, int64_t k,
+                                         double *results, int64_t *pair_index, int64_t *n_out, int64_t *stats) {
+    return mad_match_topk_many_begin2(ctx, n, hi, lo, cc, dist, k, results, pair_index, n_out, stats, nullptr, nullptr);
 }
 
 extern "C" int mad_set_option(mad_ctx *ctx, const char *name, double value) {
@@ -3747,6 +3807,12 @@ void mad_many_abandon(mad_ctx *ctx) {      // mad_destroy: a bracket left open
 extern "C" int mad_match_topk_many(mad_ctx *ctx, int n, const mad_set *const *hi, const mad_set *lo, double cc, double dist, int64_t k,
                                    double *results, int64_t *pair_index, int64_t *n_out, int64_t *stats) {
     MAD_TRY(mad_match_topk_many_begin(ctx, n, hi, lo, cc, dist, k, results, pair_index, n_out, stats));
+    return mad_match_topk_many_finish(ctx);
+}
+
+extern "C" int mad_match_topk_many2(mad_ctx *ctx, int n, const mad_set *const *hi, const mad_set *lo, double cc, double dist, int64_t k,
+                                    double *results, int64_t *pair_index, int64_t *n_out, int64_t *stats, uint8_t *used_hi, uint8_t *used_lo) {
+    MAD_TRY(mad_match_topk_many_begin2(ctx, n, hi, lo, cc, dist, k, results, pair_index, n_out, stats, used_hi, used_lo));
     return mad_match_topk_many_finish(ctx);
 }
 
