@@ -41,6 +41,7 @@ extern "C" {
 
 #define MAD_MAX_Z      128 /* zones per EQSP table */
 #define MAD_MAX_FIELDS 64  /* gradient-field slots per ctx */
+#define MAD_POSE_CLUSTER_MAX_N 4096 /* rows of one match in mad_pose_cluster_many (a d2 triangle of 64 MiB) */
 #define MAD_RESULT_COLS 23 /* row width of MaD._match_dsc results, MaD.py:451 */
 
 typedef struct mad_ctx mad_ctx;
@@ -550,6 +551,31 @@ int mad_space_localize(mad_ctx *ctx, const mad_space *s, int entry, const int32_
  * uploaded for the call: for volumes that are not a mad_space, such as test fixtures. */
 int mad_localize_volume(mad_ctx *ctx, const void *vol, int is_f64, int nx, int ny, int nz, const int32_t *cand, int n,
                         int32_t *status, int32_t *coord, void *H, void *G, int64_t *n_undecided);
+
+/* ---------------------------------------------------------------------------
+ * Pose filter: the greedy clustering of MaD._filter_dsc_pairs (mad/MaD.py:456-553) for n_match matches in one call.
+ *   rows[m]       float64 [>= n_rows[m]][23], the result rows sorted as _filter_dsc_pairs sorts them (repeatability
+ *                 descending, stable); the first n_rows[m] = min(len, n_samples) are read
+ *   cloud[m]      float64 [n_cloud[m]][3], the match's hi cloud
+ *   rmsd_thresh   the reference's rmsdcloud_thresh (10)
+ *   owner_out[m]  int32 [n_rows[m]]: the row index of the row's cluster leader (owner[i] == i: row i leads a new cluster)
+ *   d2min_out[m]  float64 [n_rows[m]]: the smallest sum((cloud(c) - cloud(i))**2) / N over the leaders c before row i (row 0: 0)
+ *   n_done_out[m] rows decided, from row 0;  status_out[m]  0 = all n rows decided, 1 = row n_done is undecided
+ * Row 0 leads cluster 0; row i leads a new one when sqrt(min d2) > rmsd_thresh and otherwise joins the leader with the
+ * smallest d2 (the earliest on a tie).  The device decides only outside a guard band around rmsd_thresh^2 and between
+ * the two nearest leaders that covers the rounding of numpy's expression and its own.  The first
+ * row inside the band ends the match: status 1, rows from n_done on have owner -1 and d2min NaN (d2min[n_done] = the
+ * doubtful minimum), and the caller runs the host loop for that match -- later rows depend on the undecided one.
+ * n = 0 does nothing (n_done 0, status 0), n = 1 leads trivially; N = 0 with n > 1 (the reference divides by zero) and
+ * non-finite input are undecided at row 1.  MAD_EINVAL: null pointers, negative sizes, a negative or non-finite
+ * threshold; MAD_EDOM: n_rows[m] > MAD_POSE_CLUSTER_MAX_N.  Host pointers, synchronous, on lane 0 (mad_stream); the d2
+ * triangles (n (n - 1) / 2 doubles per match) live in grow-only scratch of the context: a call is split into launches of at
+ * most 16 matches and 256 MiB of triangles, so the scratch never grows beyond that.
+ * Two calls on the same input return the same bits (fixed reduction trees, no atomics).
+ */
+int mad_pose_cluster_many(mad_ctx *ctx, int n_match, const double *const *rows, const int32_t *n_rows,
+                          const double *const *cloud, const int32_t *n_cloud, double rmsd_thresh, int32_t *const *owner_out,
+                          double *const *d2min_out, int32_t *n_done_out, int32_t *status_out);
 
 #ifdef __cplusplus
 }

@@ -5,8 +5,12 @@
 On the hot path: `_describe_struct` (orientation + description on
 the GPU), `_match_dsc` (int8-MFMA correlation, pose scoring, top-k on the GPU) and
 `_refine_filtered_solutions` (batched persistent refinement, density simulation and CCC
-on the GPU).  `_filter_dsc_pairs` (the greedy cloud clustering that picks which poses
-get refined, MaD.py:456-553) is the "next" row and runs on the host in float64 numpy.
+on the GPU).  The greedy cloud clustering that picks which poses get refined
+(`_filter_dsc_pairs`, MaD.py:456-553) is decided on the device (`Lib.pose_cluster_many`: one call
+per bracket chunk, float64 with a guard band) and turned into the candidate list by
+`_filter_from_owner`; a match with a decision inside the band, or with more than 4 096 rows
+(n_samples * n_copies beyond what the entry takes), goes through the host loop of
+`_filter_dsc_pairs`, and MAD_FILTER_HOST=1 sends every match there.  Both give the same list.
 
 Several GPUs (round 3): started under a launcher (`torchrun --nproc-per-node N run_MaD.py ...`: WORLD_SIZE / RANK / LOCAL_RANK in
 the environment), `run()` deals the structures to describe and then the subunits / ensemble frames to dock round-robin over the
@@ -29,6 +33,9 @@ is what both paths use).  patch_size gives r = patch_size // 2 (an odd size lose
 resident path covers r = 2, 4, 6, 8 (patch_size 4-5, 8-9, 12-13, 16-17), the radii the description kernel is built for.  Any other
 patch_size falls back to the stage path with a one-line message (the stage path then reports the kernel's own error).
 `mad.timings`: wall seconds per stage of the last run() (prep, mapspace, detector, build, cache_io, match, filter, refine_ccc, write).
+`mad.timings_detail`: the filter stage split into filter_cluster (the clustering: device call or host loop) and filter_place (the
+candidate list: reading the PDB, placing and copying the chain where a caller wants it), summed over the subunits;
+`mad.filter_undecided`: matches of the last run() the device left to the host loop.
 
 Kept from the reference: method names, argument order and defaults, the
 `results/<map>_<comps>_res..._iso...` folder layout, the `Solutions_refined_<k>.csv`
@@ -67,6 +74,8 @@ HI_COORD, LO_COORD = slice(8, 11), slice(11, 14)
 R1, R2, R3 = slice(14, 17), slice(17, 20), slice(20, 23)
 
 TIMING_KEYS = ("prep", "mapspace", "detector", "build", "cache_io", "match", "filter", "refine_ccc", "write")
+DETAIL_KEYS = ("filter_cluster", "filter_place")
+RMSDCLOUD_THRESH = 10      # MaD.py:476
 BRACKET_MAX = 16      # matches per bracket: two per lane of the context (MAD_RES); a chunk's ensemble frames are closed behind it
 
 
@@ -106,10 +115,12 @@ class MaD(object):
         self.dsc_dict = {}
         self._rowsets = {}
         self.timings = dict.fromkeys(TIMING_KEYS, 0.0)
+        self.timings_detail = dict.fromkeys(DETAIL_KEYS, 0.0)
+        self.filter_undecided = 0  # matches of the last run() whose clustering the device left to the host loop
         self.n_correlations = 0    # descriptor pairs correlated by the matches of the last run() (rows x rows per match)
         self._fallback = None      # why the last run() took the stage path although MAD_STAGE_PATH is not set (None: it did not)
         self._pending = []         # resident path: this rank's matches not yet run, [(key, n_copies, is_frame)]
-        self._matched = {}         # ... and their outcome, key -> (top rows, map cloud, structure cloud)
+        self._matched = {}         # ... and their outcome, key -> (top rows, map cloud, structure cloud, clustering or None)
 
     def _stage(self):
         """True when this run takes the stage-by-stage path (MAD_STAGE_PATH=1, or options the resident path does not cover)."""
@@ -117,6 +128,15 @@ class MaD(object):
 
     def _tick(self, key, t0):
         self.timings[key] = self.timings.get(key, 0.0) + time.perf_counter() - t0
+
+    def _tick_detail(self, key, seconds):
+        self.timings_detail[key] = self.timings_detail.get(key, 0.0) + seconds
+
+    @staticmethod
+    def _cluster_on_device(n_rows):
+        """Whether a match with n_rows rows to cluster goes to Lib.pose_cluster_many: not under MAD_FILTER_HOST=1, not when it is
+        empty, and not beyond the rows the entry takes (POSE_CLUSTER_MAX_N; the host loop has no limit)."""
+        return os.environ.get("MAD_FILTER_HOST", "0") != "1" and 0 < n_rows <= _lib.POSE_CLUSTER_MAX_N
 
     @staticmethod
     def resident_unsupported(patch_size=16):
@@ -198,6 +218,8 @@ class MaD(object):
             dsc_subregions=64, patch_size=16, cc_threshold=0.6, weight_threshold=4, n_samples=60):
         self.transform_subunits = transform_subunits
         self.timings = dict.fromkeys(TIMING_KEYS, 0.0)
+        self.timings_detail = dict.fromkeys(DETAIL_KEYS, 0.0)
+        self.filter_undecided = 0
         self.n_correlations = 0
         self._fallback = None
         if os.environ.get("MAD_STAGE_PATH", "0") != "1":
@@ -554,16 +576,32 @@ class MaD(object):
             t0 = time.perf_counter()
             h = lib.match_topk_many_begin([r.dev for r in rows], lo.dev, cc_threshold, 4.0, K, want_used=True)
             out = lib.match_topk_many_finish(h)
+            done = []
             for (key, n_copies, frame), r, (top, _, st, uh, ul) in zip(chunk, rows, out):
                 self.n_correlations += st["n_corr"]
                 if st["n_pairs"]:
                     hi_cloud, lo_cloud = np.unique(r.anchor_subv[uh], axis=0), np.unique(lo.anchor_subv[ul], axis=0)
                 else:
                     hi_cloud, lo_cloud = np.zeros((0, 3)), np.zeros((0, 3))
-                self._matched[key] = (top[:int(n_samples * n_copies)], lo_cloud, hi_cloud)
+                done.append((key, top[:int(n_samples * n_copies)], lo_cloud, hi_cloud))
                 if frame:      # one frame resident only until its match has run (MaD.py:158-162, 379-380)
                     r.close()
             self._tick("match", t0)
+            # the chunk's pose clustering in one call: the clouds exist only now
+            t0 = time.perf_counter()
+            todo = [d for d in done if self._cluster_on_device(len(d[1]))]
+            clusters = self._cluster_matches(lib, [d[1] for d in todo], [d[3] for d in todo]) if todo else []
+            by_key = {d[0]: c for d, c in zip(todo, clusters)}
+            for key, top, lo_cloud, hi_cloud in done:
+                self._matched[key] = (top, lo_cloud, hi_cloud, by_key.get(key))
+            self._tick("filter", t0)
+            self._tick_detail("filter_cluster", time.perf_counter() - t0)
+
+    @staticmethod
+    def _cluster_matches(lib, tops, hi_clouds):
+        """Lib.pose_cluster_many on the rows of several matches (each already cut to its n_samples * n_copies rows, in the order
+        _filter_dsc_pairs gives them) -> per match (owner, d2min, n_done, status)."""
+        return lib.pose_cluster_many([np.asarray(t, np.float64) for t in tops], hi_clouds, [len(t) for t in tops], rmsd_thresh=float(RMSDCLOUD_THRESH))
 
     def _match_filter_refine(self, pdbfile, n_copies, k, cc_threshold, weight_threshold, n_samples):
         n_samples_sub = int(n_samples * n_copies)
@@ -571,7 +609,7 @@ class MaD(object):
         if not self._stage() and (k in self._matched or any(j[0] == k for j in self._pending)):
             if k not in self._matched:
                 self._run_brackets(cc_threshold, n_samples)
-            top, map_anchors, comp_anchors = self._matched.pop(k)
+            top, map_anchors, comp_anchors, cluster = self._matched.pop(k)
         else:
             t0 = time.perf_counter()
             from_cache = isinstance(self.dsc_dict[k], str)
@@ -582,12 +620,18 @@ class MaD(object):
                 if hit is not None:
                     hit[1].dev.close()
             self._tick("match", t0)
+            cluster = None
+            if self._cluster_on_device(min(len(top), n_samples_sub)):      # the same entry as the resident path, with one match
+                t0 = time.perf_counter()
+                cluster = self._cluster_matches(_lib.get_lib(), [top[:n_samples_sub]], [comp_anchors])[0]
+                self._tick("filter", t0)
+                self._tick_detail("filter_cluster", time.perf_counter() - t0)
         if not len(top):
             print("MaD> No descriptor pair above the threshold for %s" % k)
             return []
         print("MaD> Filtering descriptor pairs (map %s vs. structure %s) (weight=%i, n_samples=%i*%i)..." % (self.map_name, k, weight_threshold, n_samples, n_copies))
         t0 = time.perf_counter()
-        filtered = self._filter_dsc_pairs(pdbfile, top, map_anchors, comp_anchors, wthresh=weight_threshold, n_samples=n_samples_sub, presorted=True)
+        filtered = self._filter_match(pdbfile, top, map_anchors, comp_anchors, cluster, weight_threshold, n_samples_sub)
         self._tick("filter", t0)
         print("MaD> Refining %s in %s..." % (self.map_name, k))
         t0 = time.perf_counter()
@@ -598,9 +642,29 @@ class MaD(object):
         self._tick("write", t0)
         return files
 
-    def _filter_dsc_pairs(self, pdbfile, match_data, lo_cloud, hi_cloud, wthresh=4, n_samples=200, presorted=False):
-        """Greedy clustering of the best poses by cloud RMSD (MaD.py:456-553).  Host, float64."""
-        rmsdcloud_thresh = 10
+    def _filter_match(self, pdbfile, top, map_anchors, comp_anchors, cluster, weight_threshold, n_samples_sub):
+        """The candidate list of one match for the run: from the device's clustering `cluster` = (owner, d2min, n_done, status) when it
+        decided every row, else (None: MAD_FILTER_HOST=1 or more rows than the entry takes; status 1: a decision inside the guard band)
+        from the host loop.  The run
+        reads poses, weights and members of a candidate, never its placed chain (_refine_filtered_solutions reads elements 0, 1, 2, 4
+        and 8), so the device path does not read the PDB, place or copy it."""
+        t0 = time.perf_counter()
+        if cluster is not None and cluster[3] == 0:
+            filtered = self._filter_from_owner(pdbfile, top, cluster[0], weight_threshold, place=False)
+            self._tick_detail("filter_place", time.perf_counter() - t0)
+            return filtered
+        self.filter_undecided += cluster is not None
+        detail = {}
+        filtered = self._filter_dsc_pairs(pdbfile, top, map_anchors, comp_anchors, wthresh=weight_threshold, n_samples=n_samples_sub,
+                                          presorted=True, _detail=detail)
+        self._tick_detail("filter_cluster", detail["cluster"])
+        self._tick_detail("filter_place", time.perf_counter() - t0 - detail["cluster"])
+        return filtered
+
+    def _filter_dsc_pairs(self, pdbfile, match_data, lo_cloud, hi_cloud, wthresh=4, n_samples=200, presorted=False, _detail=None):
+        """Greedy clustering of the best poses by cloud RMSD (MaD.py:456-553).  Host, float64.  _detail: a dict that receives the
+        seconds of the clustering loop under "cluster"."""
+        rmsdcloud_thresh = RMSDCLOUD_THRESH
         data = np.array(match_data if presorted else sorted(match_data, key=itemgetter(REPEAT), reverse=True))
         chain = PDB(pdbfile)
         chain_init = chain.get_coords().copy()
@@ -615,6 +679,7 @@ class MaD(object):
         weights = {0: 1}
         members = {0: [[best[HI_COORD], best[LO_COORD], best[HI_BIN], best[LO_BIN]]]}
         counter = 1
+        t_loop = time.perf_counter()
         for s in data[1:n_samples]:
             cur = moved_cloud(s)
             rmsd = np.sqrt(np.sum(np.square(cand_clouds - cur), axis=(1, 2)) / len(cur))
@@ -628,6 +693,8 @@ class MaD(object):
                 weights[owner] += 1
                 members[owner].append([s[HI_COORD], s[LO_COORD], s[HI_BIN], s[LO_BIN]])
             counter += 1
+        if _detail is not None:
+            _detail["cluster"] = time.perf_counter() - t_loop
         rep_thresh = max(5, best[REPEAT] * 0.3)
         out = []
         for cand in cand_ids:
@@ -641,6 +708,41 @@ class MaD(object):
             chain.rotate_atoms(Rt)
             chain.translate_atoms(s[LO_COORD])
             out.append([s[HI_COORD], s[LO_COORD], Rt, s[D_CC], w, s[REPEAT], s[REPEAT] * w, deepcopy(chain), members[cand]])
+        return sorted(out, key=itemgetter(6), reverse=True)
+
+    def _filter_from_owner(self, pdbfile, data, owner, wthresh, place=True):
+        """The list _filter_dsc_pairs returns, from its sorted rows `data` and the clustering `owner` (owner[i] = the row that leads
+        row i's cluster, owner[i] == i for a leader; len(owner) rows took part): weights = rows per leader, members in row order,
+        the weight and repeatability thresholds, the chain placed per kept candidate, and the stable sort by repeat * weight with
+        the leaders going in in row order.  place=False leaves the chain (element 7) None and does not read the PDB."""
+        data = np.array(data)
+        owner = np.asarray(owner)
+        n = len(owner)
+        best = data[0]
+        weights = np.bincount(owner, minlength=n)
+        members = {}
+        for i in range(n):
+            s = data[i]
+            members.setdefault(int(owner[i]), []).append([s[HI_COORD], s[LO_COORD], s[HI_BIN], s[LO_BIN]])
+        if place:
+            chain = PDB(pdbfile)
+            chain_init = chain.get_coords().copy()
+        rep_thresh = max(5, best[REPEAT] * 0.3)
+        out = []
+        for cand in np.flatnonzero(owner == np.arange(n)):
+            s = data[cand]
+            w = int(weights[cand])
+            if w < wthresh or s[REPEAT] < rep_thresh:
+                continue
+            Rt = np.array([s[R1], s[R2], s[R3]]).T
+            placed = None
+            if place:
+                chain.set_coords(chain_init)
+                chain.translate_atoms(-s[HI_COORD])
+                chain.rotate_atoms(Rt)
+                chain.translate_atoms(s[LO_COORD])
+                placed = deepcopy(chain)
+            out.append([s[HI_COORD], s[LO_COORD], Rt, s[D_CC], w, s[REPEAT], s[REPEAT] * w, placed, members[int(cand)]])
         return sorted(out, key=itemgetter(6), reverse=True)
 
     def _refine_filtered_solutions(self, pdbfile, filtered_candidate_list, lo_cloud, hi_cloud):

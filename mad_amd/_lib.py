@@ -13,6 +13,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 # MAD_LIB_PATH: another build of the same library (diagnostic builds with other compiler flags; tools/build_variant.sh)
 LIB_PATH = os.environ.get("MAD_LIB_PATH") or os.path.join(_HERE, "libmad_amd.so")
 RESULT_COLS = 23
+POSE_CLUSTER_MAX_N = 4096      # MAD_POSE_CLUSTER_MAX_N of include/mad_amd.h: rows of one match in pose_cluster_many
 
 ERRORS = {-22: "EINVAL", -12: "ENOMEM", -28: "ENOSPC", -19: "ENODEV", -33: "EDOM", -5: "EHIP"}
 
@@ -29,6 +30,7 @@ SYMBOLS = [
     "mad_upload_density", "mad_refine", "mad_structure_to_density", "mad_ccc", "mad_density_ccc", "mad_dock_refine_score", "mad_grid_overlap", "mad_overlap_matrix",
     "mad_space_create", "mad_space_destroy", "mad_space_build", "mad_space_info", "mad_space_download",
     "mad_space_peaks", "mad_space_patches", "mad_space_localize", "mad_localize_volume",
+    "mad_pose_cluster_many",
 ]
 
 
@@ -749,6 +751,33 @@ class Lib(object):
         uh, ul = np.zeros(max(n_hi_anchors, 1), np.uint8), np.zeros(max(n_lo_anchors, 1), np.uint8)
         self._chk(self.dll.mad_match_used(self.ctx, _p(uh), C.c_int32(n_hi_anchors), _p(ul), C.c_int32(n_lo_anchors)))
         return uh[:n_hi_anchors].astype(bool), ul[:n_lo_anchors].astype(bool)
+
+    def pose_cluster_many(self, rows_list, clouds, n_samples_list, rmsd_thresh=10.0):
+        """The greedy cloud-RMSD clustering of MaD._filter_dsc_pairs for several matches in one call (mad_pose_cluster_many).
+        rows_list[m]: the match's result rows, float64 (len, 23), sorted as _filter_dsc_pairs sorts them; clouds[m]: its hi cloud
+        (N, 3); n_samples_list[m]: rows that take part (min(len, n_samples) do).  Per match (owner int32 [n], d2min float64 [n],
+        n_done, status): owner[i] = the row that leads row i's cluster; status 1 = row n_done lies inside the guard band, run the
+        host loop for this match (owner is -1 from there on).  More than POSE_CLUSTER_MAX_N rows in a match: MadBackendError (EDOM)."""
+        nm = len(rows_list)
+        if not (len(clouds) == len(n_samples_list) == nm):
+            raise ValueError("pose_cluster_many: %d row lists, %d clouds, %d sample counts" % (nm, len(clouds), len(n_samples_list)))
+        rows, cl, ns = [], [], []
+        for r, c, k in zip(rows_list, clouds, n_samples_list):
+            r = _c(r, np.float64).reshape(-1, RESULT_COLS)
+            if int(k) < 0:
+                raise ValueError("pose_cluster_many: n_samples = %d" % int(k))
+            rows.append(r)
+            cl.append(_c(c, np.float64).reshape(-1, 3))
+            ns.append(min(len(r), int(k)))
+        owner = [np.zeros(n, np.int32) for n in ns]
+        d2min = [np.zeros(n, np.float64) for n in ns]
+        n_rows, n_cloud = np.array(ns, np.int32), np.array([len(c) for c in cl], np.int32)
+        n_done, status = np.zeros(max(nm, 1), np.int32), np.zeros(max(nm, 1), np.int32)
+        PP = C.c_void_p * max(nm, 1)
+        ptrs = [PP(*[a.ctypes.data if a.size else None for a in arrs]) for arrs in (rows, cl, owner, d2min)]
+        self._chk(self.dll.mad_pose_cluster_many(self.ctx, C.c_int(nm), ptrs[0], _p(n_rows), ptrs[1], _p(n_cloud), C.c_double(float(rmsd_thresh)),
+                                                 ptrs[2], ptrs[3], _p(n_done), _p(status)))
+        return [(owner[m], d2min[m], int(n_done[m]), int(status[m])) for m in range(nm)]
 
     # -- refinement / density / ccc --------------------------------------------------------
     def upload_density(self, grid, origin, voxsp):

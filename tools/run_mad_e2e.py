@@ -5,8 +5,10 @@
 The workload (bench/configs/<name>.json) is written into a temporary folder the way bench.py builds it -- the subunits with
 mad_amd.synth, the map = their placed copies simulated on the device, padded to N^3, plus the workload's noise -- as an MRC map and
 one PDB per subunit.  Then, for each path in its own folder, MaD.run() twice: cold (no descriptor cache) and warm (the cache of
-the cold run).  One JSON line on stdout: wall seconds, mad.timings, correlations / wall, and the seconds outside MapSpace,
-Detector, file preparation, cache I/O and solution writing.  MaD's own messages go to stderr.
+the cold run).  One JSON line on stdout: wall seconds, mad.timings, mad.timings_detail (the filter stage split into clustering and
+candidate list) with the matches whose clustering fell back to the host loop, correlations / wall, and the seconds outside MapSpace,
+Detector, file preparation, cache I/O and solution writing.  MaD's own messages go to stderr.  MAD_FILTER_HOST=1 in the
+environment keeps the filter's host loop (the stage as it was before the device clustering).
 """
 import argparse
 import contextlib
@@ -69,7 +71,8 @@ def run_once(folder, inputs, subs, W):
         os.chdir(cwd)
     t = {k: round(v, 4) for k, v in mad.timings.items()}
     outside = wall - sum(mad.timings[k] for k in ("prep", "mapspace", "detector", "cache_io", "write"))
-    return dict(wall_s=round(wall, 4), timings_s=t, correlations=int(mad.n_correlations),
+    detail = {k: round(v, 4) for k, v in mad.timings_detail.items()}
+    return dict(wall_s=round(wall, 4), timings_s=t, timings_detail_s=detail, filter_undecided=int(mad.filter_undecided), correlations=int(mad.n_correlations),
                 correlations_per_s=mad.n_correlations / wall if wall > 0 else None,
                 outside_mapspace_detector_io_s=round(outside, 4), solutions=sum(len(v[1]) for v in mad.buildable_subunits.values()))
 
