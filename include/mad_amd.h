@@ -125,6 +125,7 @@ int mad_free_field(mad_ctx *ctx, int slot);
  * sum), so a zone count can differ from the reference's only where its weight sum lies that close to an integer.
  */
 int mad_set_orient_window(mad_ctx *ctx, double gw_sig);
+/* r = box_side 1 .. 12 (Orientator(ori_radius = 2 .. 25)); with a window (gw_sig != 0) 1 .. 10.  Beyond: MAD_EINVAL. */
 int mad_orient(mad_ctx *ctx, int slot, int octave, const int32_t *coords, int n, int r,
                int lim_main, int lim_sec,
                int32_t *row_anchor, int32_t *row_main, int32_t *row_sec, double *row_R,
@@ -136,13 +137,16 @@ int mad_orient(mad_ctx *ctx, int slot, int octave, const int32_t *coords, int n,
  * coords: n_rows x 3 anchor voxel positions, R: n_rows x 9 Rfinal.  dsc: n_rows x
  * (64 * Zd) int16, sub-cube major (id j*16+i*4+k, Descriptor.py:44-64), zone minor.
  * A row whose sample cube leaves the grid is all zero (Descriptor.py:140-149).
+ * r = dsc_radius / 2: 2, 4, 6, 8, 10 or 12 (odd radii and larger ones: MAD_EINVAL).  At r = 12 a sub-region holds
+ * 6^3 = 216 samples, so a count may exceed 127: see "wide" sets below for what that means for a match.
  */
 int mad_describe(mad_ctx *ctx, int slot, int octave, const int32_t *coords, const double *R,
                  int64_t n_rows, int r, int16_t *dsc);
 /*
  * The same with another partition of the sample cube, Descriptor(dsc_size = 64 | 27 | 8 | 1) (Descriptor.py:44-93):
  * dsc is n_rows x (dsc_size * Zd), sub-regions in the order of the reference's sub_slices lists.  MaD.run never selects
- * them (it constructs Descriptor(dsc_radius=patch_size) only, MaD.py:362); 27, 8 and 1 exist for r = 8.
+ * them (it constructs Descriptor(dsc_radius=patch_size) only, MaD.py:362); 27, 8 and 1 exist for r = 8, and r = 10, 12
+ * for 64 regions of 16 zones only.
  */
 int mad_describe_sized(mad_ctx *ctx, int slot, int octave, const int32_t *coords, const double *R,
                        int64_t n_rows, int r, int dsc_size, int16_t *dsc);
@@ -191,6 +195,13 @@ int mad_topk(mad_ctx *ctx, const int32_t *counts, int64_t n, int64_t k, int64_t 
  *   anc_coords n x 3 int32, anc_octave n int32, anc_subv n x 3 double (Angstrom),
  *   anc_index n int32 (DensityFeature.index).
  * Row order = anchor order (as given) x main x sec, exactly the reference's list.
+ * r = 2, 4, 6, 8, 10 or 12 (what mad_orient and mad_describe both take).
+ *
+ * Wide sets.  A set built at r >= 11 (i.e. 12) is WIDE: its counts reach 216, beyond an int8, so its int8 rows hold
+ * count - 108 and every row carries c * sum(counts) - (D / 2) c^2 as int32; the correlation adds the two rows' terms to
+ * the int8 dot product and so hands the exact int32 dot product of the counts to everything behind it.  Results are those
+ * of the counts themselves.  A wide set matches wide sets only (against a narrow one: MAD_EINVAL), is matched whole on one
+ * device (mad_set_export and the mad_match_shard_* calls refuse it with MAD_EINVAL), and takes counts 0 .. 235.
  */
 int mad_set_create(mad_ctx *ctx, mad_set **out);
 void mad_set_destroy(mad_ctx *ctx, mad_set *set);
@@ -206,7 +217,12 @@ int mad_set_build_many(mad_ctx *ctx, int n_sets, mad_set *const *sets, const int
                        const int32_t *const *anc_coords, const int32_t *const *anc_octave,
                        const double *const *anc_subv, const int32_t *const *anc_index, const int *n_anchors,
                        int r, int lim_main, int lim_sec);
-/* Load rows computed earlier (descriptor cache, MaD.py:861-875): anchor = row -> anchor id. */
+/* Load rows computed earlier (descriptor cache, MaD.py:861-875): anchor = row -> anchor id.
+ * The rows are taken for narrow ones (counts -128 .. 127, else MAD_EDOM) unless the set has been marked with
+ * mad_set_mark_wide(set, 1) before: then for those of a wide set (counts 0 .. 235, else MAD_EDOM).  The mark stays until it
+ * is changed; mad_set_build does not look at it (it goes by r).  mad_set_is_wide: what the set holds now (1 / 0). */
+int mad_set_mark_wide(mad_ctx *ctx, mad_set *set, int wide);
+int mad_set_is_wide(mad_ctx *ctx, const mad_set *set);
 int mad_set_load(mad_ctx *ctx, mad_set *set, int64_t n_rows, const int32_t *row_anchor,
                  const int32_t *row_main, const double *row_R, const int16_t *dsc, int D,
                  const double *anc_subv, const int32_t *anc_index, const int32_t *anc_octave, int n_anchors);

@@ -8,9 +8,10 @@ Descriptor.py:123-202) runs in the HIP kernel `k_describe` through `mad_describe
 
 MaD.run only ever constructs `Descriptor(dsc_radius=patch_size)` (MaD.py:362): 64 sub-cubes x 16 zones.  The constructor's other
 options run on the device too and are pinned by goldens from the reference: `dsc_size` 27 / 8 / 1 (g17; built for the default
-dsc_radius), `dsc_radius` 8 / 16 / 24 with 64 sub-cubes, and `subeqsp_size=112` -- the reference's other EQSP table, rows of
-64 x 112 = 7 168 counts (g18; default layout).  Rows whose counts exceed 127 (`dsc_size` 8 and 1 can) are described but refused
-by the int8 correlation (MAD_EDOM) rather than wrapped.
+dsc_radius), `dsc_radius` 4 / 8 / 12 / 16 / 20 / 24 with 64 sub-cubes (g19 pins 20 and 24), and `subeqsp_size=112` -- the
+reference's other EQSP table, rows of 64 x 112 = 7 168 counts (g18; default layout).  Rows whose counts exceed 127 (`dsc_size` 8
+and 1 can) are described but refused by the int8 correlation (MAD_EDOM) rather than wrapped; at `dsc_radius` 24 (a sub-cube of
+6^3 = 216 samples) they are matched exactly, as the rows of a wide set (include/mad_amd.h).
 """
 import sys
 

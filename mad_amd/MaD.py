@@ -30,8 +30,11 @@ Descriptor -> _RowSet -> one match_topk per subunit / frame); both write the sam
 `run()` options and the resident path: ori_eqsp_size, dsc_eqsp_size and dsc_subregions are accepted and ignored on both paths, as
 the reference ignores them (only patch_size reaches the stages), and run() has no gw_sig (Orientator's default, 0,
 is what both paths use).  patch_size gives r = patch_size // 2 (an odd size loses one, as Orientator / Descriptor print); the
-resident path covers r = 2, 4, 6, 8 (patch_size 4-5, 8-9, 12-13, 16-17), the radii the description kernel is built for.  Any other
-patch_size falls back to the stage path with a one-line message (the stage path then reports the kernel's own error).
+resident path covers r = 2, 4, 6, 8, 10, 12 (patch_size 4-5, 8-9, 12-13, 16-17, 20-21, 24-25), the radii the description kernel is
+built for.  Any other patch_size falls back to the stage path with a one-line message (the stage path then reports the kernel's
+own error).  At r = 12 (patch_size 24, 25: the reference's low-resolution example) a count can pass 127 and the sets are "wide"
+(include/mad_amd.h): built sets know it by their radius, sets loaded from the descriptor cache or from stage rows are told by
+`get_descriptors`, which has the patch size; results are the same, the match runs on one device per subunit as always.
 `mad.timings`: wall seconds per stage of the last run() (prep, mapspace, detector, build, cache_io, match, filter, refine_ccc, write).
 `mad.timings_detail`: the filter stage split into filter_cluster (the clustering: device call or host loop) and filter_place (the
 candidate list: reading the PDB, placing and copying the chain where a caller wants it), summed over the subunits;
@@ -82,7 +85,7 @@ BRACKET_MAX = 16      # matches per bracket: two per lane of the context (MAD_RE
 class _RowSet(object):
     """Host view of a descriptor list + its device-resident twin (mad_set)."""
 
-    def __init__(self, lib, dsc_list):
+    def __init__(self, lib, dsc_list, wide=False):
         n = len(dsc_list)
         self.n_rows = n
         subv = np.array([df.subv_map_coords for df in dsc_list], dtype=np.float64).reshape(-1, 3)
@@ -99,7 +102,8 @@ class _RowSet(object):
         main = np.array([df.main_bin for df in dsc_list], dtype=np.int32)
         R = np.array([df.Rfinal for df in dsc_list], dtype=np.float64).reshape(-1, 9)
         dsc = np.array([df.lin_ar_subeqsp for df in dsc_list], dtype=np.int16).reshape(n, -1)
-        self.dev = lib.set_load(self.row_anchor, main, R, dsc, self.anchors, idx[first] if n else idx, octv[first] if n else octv)
+        self.dev = lib.set_load(self.row_anchor, main, R, dsc, self.anchors, idx[first] if n else idx, octv[first] if n else octv,
+                                wide=wide)
 
 
 class MaD(object):
@@ -142,8 +146,8 @@ class MaD(object):
     def resident_unsupported(patch_size=16):
         """Why mad_set_build cannot serve these run() options (None when it can); see the module docstring."""
         r = int(patch_size) // 2
-        if r not in (2, 4, 6, 8):
-            return "patch_size %s (r = %d): the resident build describes r = 2, 4, 6, 8 only" % (patch_size, r)
+        if r not in (2, 4, 6, 8, 10, 12):
+            return "patch_size %s (radius %d): the resident build describes r = 2, 4, 6, 8, 10, 12 only" % (patch_size, r)
         return None
 
     # ------------------------------------------------------------------ inputs
@@ -264,6 +268,7 @@ class MaD(object):
                 f"_patch{patch_size}_orieqsp{ori_eqsp_size}_dsceqsp{dsc_eqsp_size}_subregions{64}.h5")
 
     def get_descriptors(self, detect_sigma=2.0, presmooth_sigma=1, ori_eqsp_size=112, dsc_eqsp_size=16, dsc_subregions=64, patch_size=16):
+        self._wide = int(patch_size) // 2 >= 11      # what sets loaded from rows of this patch size are marked as (Lib.set_load)
         def described(key, struct, what):
             name = self._cache_name(key, detect_sigma, presmooth_sigma, patch_size, ori_eqsp_size, dsc_eqsp_size)
             if self._cache_exists(name):
@@ -512,7 +517,7 @@ class MaD(object):
         key = id(dsc_list)
         hit = self._rowsets.get(key)
         if hit is None or hit[0] is not dsc_list or hit[1].dev.lib is not lib:
-            hit = (dsc_list, _RowSet(lib, dsc_list))
+            hit = (dsc_list, _RowSet(lib, dsc_list, wide=getattr(self, "_wide", False)))
             self._rowsets[key] = hit
         return hit[1]
 
@@ -554,8 +559,8 @@ class MaD(object):
             t0 = time.perf_counter()
             rows = self._load_descriptors(x)
             self._tick("cache_io", t0)
-            return rows if isinstance(rows, DescriptorRows) else DescriptorRows.from_arrays(self._list_arrays(rows))
-        return DescriptorRows.from_arrays(self._list_arrays(x))
+            return rows if isinstance(rows, DescriptorRows) else DescriptorRows.from_arrays(self._list_arrays(rows), wide=getattr(self, "_wide", False))
+        return DescriptorRows.from_arrays(self._list_arrays(x), wide=getattr(self, "_wide", False))
 
     def _run_brackets(self, cc_threshold, n_samples):
         """Every planned match against the resident map set, up to BRACKET_MAX per match_topk_many bracket, all at
@@ -823,7 +828,7 @@ class MaD(object):
             with np.load(self._npz_name(input_name)) as z:
                 data = {k: z[k] for k in ("dsc", "info", "coords", "rot")}
         if not self._stage():      # resident path: the arrays as they are; the set is loaded from them (set_load) when first matched
-            return DescriptorRows.from_arrays(data)
+            return DescriptorRows.from_arrays(data, wide=getattr(self, "_wide", False))
         rows = []
         for d, c, i, r in zip(data["dsc"], data["coords"], data["info"], data["rot"]):
             df = DensityFeature()

@@ -14,6 +14,10 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("MAD_LIB_PATH") or os.path.join(_HERE, "libmad_amd.so")
 RESULT_COLS = 23
 POSE_CLUSTER_MAX_N = 4096      # MAD_POSE_CLUSTER_MAX_N of include/mad_amd.h: rows of one match in pose_cluster_many
+# wide sets (include/mad_amd.h; MAD_WIDE_* of csrc/mad_common.h): from this descriptor radius on a set's int8 rows hold count - WIDE_C
+WIDE_FROM_R = 11
+WIDE_C = 108
+WIDE_MAX = WIDE_C + 127
 
 ERRORS = {-22: "EINVAL", -12: "ENOMEM", -28: "ENOSPC", -19: "ENODEV", -33: "EDOM", -5: "EHIP"}
 
@@ -23,7 +27,7 @@ SYMBOLS = [
     "mad_timing_enable", "mad_timing_reset", "mad_timing_get", "mad_last_ms", "mad_probe_peaks",
     "mad_set_eqsp", "mad_upload_field", "mad_upload_field_device", "mad_free_field",
     "mad_set_orient_window", "mad_orient", "mad_describe", "mad_describe_sized", "mad_correlate", "mad_pose_score", "mad_topk",
-    "mad_set_create", "mad_set_destroy", "mad_set_build", "mad_set_build_many", "mad_set_load", "mad_set_size", "mad_set_download",
+    "mad_set_create", "mad_set_destroy", "mad_set_build", "mad_set_build_many", "mad_set_load", "mad_set_mark_wide", "mad_set_is_wide", "mad_set_size", "mad_set_download",
     "mad_match_topk", "mad_match_topk_many", "mad_match_topk_many_begin", "mad_match_topk_many_finish", "mad_match_topk_many_begin2", "mad_match_topk_many2", "mad_set_batching", "mad_set_option", "mad_last_pose_kernel", "mad_last_pose_selected", "mad_device_allocations", "mad_match_fetch", "mad_match_results", "mad_match_used",
     "mad_match_shard_pairs", "mad_match_shard_topk", "mad_match_shard_begin", "mad_match_shard_score", "mad_match_shard_record_doubles", "mad_match_shard_collect", "mad_match_shard_wait",
     "mad_set_wire_bytes", "mad_set_export", "mad_set_import", "mad_set_lane", "mad_set_stream", "mad_set_bind_lane",
@@ -169,6 +173,10 @@ class DeviceSet(object):
 
     def lane(self):
         return int(self.lib.dll.mad_set_lane(self.lib.ctx, self.h))
+
+    def is_wide(self):
+        """True when the set holds the centred int8 rows of a wide set (built at r >= 11, or loaded with wide=True)."""
+        return int(self.lib.dll.mad_set_is_wide(self.lib.ctx, self.h)) == 1
 
     def bind_lane(self, lane):
         """Put the set on lane `lane` (0..7): sets of one lane run in order on one stream.  Synchronises the context."""
@@ -543,8 +551,12 @@ class Lib(object):
     def set_build_many(self, jobs, r=8, lim_main=6, lim_sec=6, gw_sig=0.0):
         return self.prepare_build_many(jobs, r, lim_main, lim_sec, gw_sig).run()
 
-    def set_load(self, row_anchor, row_main, row_R, dsc, anc_subv, anc_index, anc_octave):
+    def set_load(self, row_anchor, row_main, row_R, dsc, anc_subv, anc_index, anc_octave, wide=False):
+        """wide: the rows were described at a radius of 11 or more (patch sizes 22 .. 25) and hold counts up to 216: the set is
+        marked wide before the load (include/mad_amd.h, "Wide sets") and matches wide sets only."""
         s = DeviceSet(self)
+        if wide:
+            self._chk(self.dll.mad_set_mark_wide(self.ctx, s.h, C.c_int(1)))
         row_anchor, row_main = _c(row_anchor, np.int32), _c(row_main, np.int32)
         row_R = _c(row_R, np.float64).reshape(-1, 9)
         dsc = _c(dsc, np.int16)

@@ -248,6 +248,19 @@ struct mad_ctx {
     int n_cu = 256;
 };
 
+// Wide rows (descriptor radius >= MAD_WIDE_FROM_R: a sub-region holds 6^3 = 216 samples, more than an int8 count).  The int8
+// operand of the correlation holds count - MAD_WIDE_C (counts 0 .. 235 -> -108 .. 127), and every row carries
+// MAD_WIDE_BIAS = c sum(v) - (D / 2) c^2 as int32, so that the GEMM's epilogue restores the true dot product with two adds:
+//     dot(h, l) = dot(h - c, l - c) + bias(h) + bias(l)          (c sum(h) + c sum(l) - D c^2, split evenly over the two rows)
+// Every term fits int32 (D = 1 024: |dot(h - c, l - c)| <= 1.7e7, |bias| <= 2.0e7).  A row that pads a set to a multiple of 128,
+// or a dead row, is all -c with bias(0): its true dot product with anything is 0, as a zero row's in a narrow set.
+#define MAD_WIDE_FROM_R 11
+#define MAD_WIDE_C 108
+#define MAD_WIDE_MAX (MAD_WIDE_C + 127)
+#define MAD_WIDE_ZERO4 ((int32_t)0x94949494)      // four int8 of -MAD_WIDE_C
+#define MAD_WIDE_BIAS(sum, D) (MAD_WIDE_C * (int)(sum) - ((int)(D) / 2) * (MAD_WIDE_C * MAD_WIDE_C))
+static_assert((uint8_t)(int8_t)-MAD_WIDE_C == 0x94, "MAD_WIDE_ZERO4");
+
 struct mad_set {
     int32_t n_anchors = 0;
     uint64_t gen = 0;            // counts the builds / loads / imports of this set: results that refer to an earlier one are stale
@@ -268,6 +281,9 @@ struct mad_set {
     hipEvent_t built = nullptr;         // recorded behind the last kernel of a build / load: consumers on other lanes wait for it
     // per row
     DevBuf row_anchor, row_main, row_sec, row_R, row_Rinv, row_meta, dsc, dsc8, norm;
+    DevBuf rsum;                 // wide sets only: MAD_WIDE_BIAS per row (int32), padded like norm
+    bool wide = false;           // the int8 rows are centred (built at r >= MAD_WIDE_FROM_R, or loaded under the mark)
+    bool wide_mark = false;      // mad_set_mark_wide: what the next mad_set_load takes the rows for
     DevBuf row_perm;             // k-th row in working order (rows of spatially neighbouring anchors next to each other)
     DevBuf row_rec;              // DscRowRec of the k-th row in working order
     DevBuf anc_rows;             // per anchor IN WORKING ORDER: MAD_ANCROW_WORDS ints {position of its first row in working order, rows, voxel coordinates} (k_orient_rows* write it)
@@ -408,6 +424,7 @@ struct DescribeJob {
     int16_t *d_dsc;
     int8_t *d_dsc8;
     double *d_norm;
+    int32_t *d_rsum = nullptr;                // with d_dsc8 at r >= MAD_WIDE_FROM_R: the rows' MAD_WIDE_BIAS (wide sets)
 };
 int mad_orient_device_many(mad_ctx *ctx, int n_jobs, const OrientJob *jobs, int r, int lim_main, int lim_sec);
 int mad_describe_device_many(mad_ctx *ctx, int n_jobs, const DescribeJob *jobs, int r, int dsc_size = 64);

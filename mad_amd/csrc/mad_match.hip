@@ -119,12 +119,14 @@ __device__ __forceinline__ unsigned s_pack_hh(unsigned a, unsigned b) { unsigned
 #define G2_NSTAGE 3
 #define G2_STAGE ((G2_BM + G2_BN) * G2_BK)
 #define G2_LDS (G2_NSTAGE * G2_STAGE + 2 * (G2_BM + G2_BN) * 4)      // three stages + two norm buffers (the tile in its K loop, the next one)
+#define G2_LDS_WIDE (G2_LDS + 2 * (G2_BM + G2_BN) * 4)               // ... and, behind them, two buffers of the rows' int32 biases (wide sets)
+static_assert(2 * G2_LDS_WIDE <= 160 * 1024, "two workgroups of k_corr_gemm2 per CU");
 static_assert(G2_BM == 256 && G2_BN == 128, "the tile arithmetic of k_corr_gemm2 shifts by these");
 
 // row pitch (bytes) of the candidate flags: one byte per mask word (32 columns) of the padded matrix, rows aligned for 4-byte reads
 __host__ __device__ __forceinline__ int64_t mad_cflag_pitch(int64_t ldc) { return (ldc / 32 + 3) & ~(int64_t)3; }
 
-struct GemmJob {
+struct GemmJobNarrow {
     const int8_t *A, *B;           // hi rows, lo rows (int8, K bytes each, zero-padded to multiples of 128 rows)
     int32_t *C;
     const int32_t *n_hi, *n_lo;    // device: row counts
@@ -134,13 +136,19 @@ struct GemmJob {
     uint32_t *mask;
     uint8_t *cflag;                // zeroed by the caller: one byte per mask word, set where the word has a bit (the pair kernels look nowhere else)
 };
-struct GemmBatch {
+// what the host passes around; the kernel's default instance takes the narrow part only
+struct GemmJob : GemmJobNarrow {
+    const int32_t *hb, *lb;        // wide sets (both or neither): MAD_WIDE_BIAS per hi / lo row, A and B hold count - MAD_WIDE_C
+};
+template <bool WIDE>
+struct GemmBatchT {
     int n_jobs;
     int K;
     int split_tail;                // the tiles of a last, short round as 128 x 128 halves (MAD_GEMM_NO_SPLIT: whole tiles, as in round 3)
     double cc;
-    GemmJob job[MAD_BATCH_MAX];
+    typename std::conditional<WIDE, GemmJob, GemmJobNarrow>::type job[MAD_BATCH_MAX];
 };
+typedef GemmBatchT<false> GemmBatch;
 
 __device__ __forceinline__ void glds16(const int8_t *g, int8_t *l) {
     __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void *)g, (__attribute__((address_space(3))) void *)l, 16, 0, 0);
@@ -156,9 +164,13 @@ extern "C" int mad_debug_g2_stamps(long long *out, int n) {
 #define G2_STAMP(k) do { } while (0)
 #endif
 
-__global__ __launch_bounds__(GEMM_THREADS, 2) void k_corr_gemm2(GemmBatch G) {
+// WIDE: the instance for wide sets (mad_common.h, MAD_WIDE_C): the same contraction on the centred int8 rows; the epilogue adds the
+// two rows' biases to an accumulator entry before anything looks at it, so the candidate test and C see the true dot product.
+template <bool WIDE>
+__global__ __launch_bounds__(GEMM_THREADS, 2) void k_corr_gemm2(GemmBatchT<WIDE> G) {
     extern __shared__ __align__(16) int8_t g2_smem[];      // the stages and, behind them, the norms of the tile: ONE object
     float *sT = (float *)(g2_smem + G2_NSTAGE * G2_STAGE);
+    int *const sBias = (int *)(g2_smem + G2_LDS);           // WIDE only
     const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6, wm = w >> 1, wn = w & 1;
     const int K = G.K, n_k = K / G2_BK;
     const int xcd = blockIdx.x & 7;
@@ -173,7 +185,7 @@ __global__ __launch_bounds__(GEMM_THREADS, 2) void k_corr_gemm2(GemmBatch G) {
     const bool g2_split = G.split_tail != 0;
     int nbuf = 0;      // which of the two norm buffers the tile in its K loop uses
     for (int j = 0; j < G.n_jobs; j++) {
-        const GemmJob &J = G.job[j];
+        const auto &J = G.job[j];
         const int64_t hp = (((int64_t)*J.n_hi + 127) >> 7) << 7, lp = (((int64_t)*J.n_lo + 127) >> 7) << 7;
         if (hp * lp > J.cap_c) {
             if (blockIdx.x == 0 && tid == 0) J.status[ST_FLAG_C] = 1;
@@ -203,9 +215,11 @@ __global__ __launch_bounds__(GEMM_THREADS, 2) void k_corr_gemm2(GemmBatch G) {
                 const int64_t r = row0 + tid < hp ? row0 + tid : hp - 1;
                 const double v = J.hn[r];
                 sN[tid] = (float)(v > 0 ? v : 1.0);
+                if constexpr (WIDE) sBias[buf * (G2_BM + G2_BN) + tid] = J.hb[r];
                 if (tid < G2_BN) {
                     const double u = J.ln[col0 + tid];
                     sN[G2_BM + tid] = (float)(G.cc * (u > 0 ? u : 1.0));
+                    if constexpr (WIDE) sBias[buf * (G2_BM + G2_BN) + G2_BM + tid] = J.lb[col0 + tid];
                 }
             };
             if (!decltype(norms_last)::value) norms();
@@ -316,10 +330,23 @@ __global__ __launch_bounds__(GEMM_THREADS, 2) void k_corr_gemm2(GemmBatch G) {
                     const float v = sN[G2_BM + wn * 64 + n * 16 + (lane & 15)];
                     tl[n] = v - fabsf(v) * 4e-6f;
                 }
+                [[maybe_unused]] const int *const sB = sBias + buf * (G2_BM + G2_BN);
+                [[maybe_unused]] int bl[4] = {0, 0, 0, 0};
+                if constexpr (WIDE) {
+#pragma unroll
+                    for (int n = 0; n < 4; n++) bl[n] = sB[G2_BM + wn * 64 + n * 16 + (lane & 15)];
+                }
 #pragma unroll
                 for (int m = 0; m < MT; m++) {
                     const float4 th4 = *(const float4 *)&sN[wm * (MT * 16) + m * 16 + (lane >> 4) * 4];
                     const float thv[4] = {th4.x, th4.y, th4.z, th4.w};
+                    if constexpr (WIDE) {      // the true dot products of this fragment row: dot(h - c, l - c) + bias(h) + bias(l)
+                        const v4i bh = *(const v4i *)&sB[wm * (MT * 16) + m * 16 + (lane >> 4) * 4];
+#pragma unroll
+                        for (int n = 0; n < 4; n++)
+#pragma unroll
+                            for (int jj = 0; jj < 4; jj++) acc[m][n][jj] += bh[jj] + bl[n];
+                    }
 #pragma unroll
                     for (int jj = 0; jj < 4; jj++) {
                         unsigned long long bal[4];
@@ -402,6 +429,8 @@ __global__ __launch_bounds__(GEMM_THREADS, 2) void k_corr_gemm2(GemmBatch G) {
         base += units;
     }
 }
+// (instantiated here, where the kernel stood before it was a template: it keeps its place in the code object)
+template __global__ void k_corr_gemm2<false>(GemmBatchT<false> G);
 
 // ---------------------------------------------------------------------------
 // threshold + ordered compaction (np.where(preds > cc), MaD.py:423)
@@ -2293,17 +2322,23 @@ struct Side {      // one side of a match, all device pointers
     const double *p;            // sub-voxel coordinates (per anchor, or per row when row_anchor == nullptr)
     const int32_t *n_rows;      // device
     int64_t cap_rows;           // upper bound of *n_rows
+    const int32_t *bias = nullptr;      // per row, wide sets only (MAD_WIDE_BIAS): dsc8 is centred
 };
 
 // correlate + compact: fills S_PAIR_*; status[ST_NPAIRS]; used flags (nullable)
-static int gemm2_launch(mad_ctx *ctx, const GemmBatch &G) {
+// the instance for wide sets (instantiated here, behind the kernels of the match: those keep their places in the code object)
+template __global__ void k_corr_gemm2<true>(GemmBatchT<true> G);
+
+template <bool WIDE>
+static int gemm2_launch(mad_ctx *ctx, const GemmBatchT<WIDE> &G) {
+    constexpr int lds = WIDE ? G2_LDS_WIDE : G2_LDS;
     static bool attr = false;
     if (!attr) {
-        MAD_HIP(hipFuncSetAttribute((const void *)k_corr_gemm2, hipFuncAttributeMaxDynamicSharedMemorySize, G2_LDS));
+        MAD_HIP(hipFuncSetAttribute((const void *)k_corr_gemm2<WIDE>, hipFuncAttributeMaxDynamicSharedMemorySize, lds));
         attr = true;
     }
     static const int per_cu = getenv("MAD_GEMM_WG_PER_CU") ? std::max(1, std::min(2, atoi(getenv("MAD_GEMM_WG_PER_CU")))) : 2;      // probe: 1 leaves half of every CU to the kernels of other lanes
-    hipLaunchKernelGGL(k_corr_gemm2, dim3(ctx->n_cu * per_cu), dim3(GEMM_THREADS), G2_LDS, ctx->stream, G);      // persistent: two per CU
+    hipLaunchKernelGGL(k_corr_gemm2<WIDE>, dim3(ctx->n_cu * per_cu), dim3(GEMM_THREADS), lds, ctx->stream, G);      // persistent: two per CU
     return MAD_OK;
 }
 
@@ -2324,17 +2359,30 @@ static int correlate_reserve(mad_ctx *ctx, const Side &hi, const Side &lo, int D
     MAD_TRY(mad_reserve(ctx, mad_sb(ctx, S_PAIR_SCORE), (size_t)cap_pairs * 8));
     MAD_TRY(mad_reserve(ctx, mad_sb(ctx, S_CMASK), (size_t)cap_c / 8 + 64));
     MAD_TRY(mad_reserve(ctx, mad_sb(ctx, S_CFLAG), cflag_bytes(cap_c)));
-    *job = GemmJob{hi.dsc8, lo.dsc8, scratch<int32_t>(ctx, S_CMAT), hi.n_rows, lo.n_rows, cap_c, d_status, hi.norm, lo.norm,
-                   scratch<uint32_t>(ctx, S_CMASK), scratch<uint8_t>(ctx, S_CFLAG)};
+    if ((hi.bias != nullptr) != (lo.bias != nullptr))
+        return mad_fail(ctx, MAD_EINVAL, "correlate: a wide set (descriptor radius >= %d) against a narrow one", MAD_WIDE_FROM_R);
+    *job = GemmJob{{hi.dsc8, lo.dsc8, scratch<int32_t>(ctx, S_CMAT), hi.n_rows, lo.n_rows, cap_c, d_status, hi.norm, lo.norm,
+                    scratch<uint32_t>(ctx, S_CMASK), scratch<uint8_t>(ctx, S_CFLAG)}, hi.bias, lo.bias};
     return MAD_OK;
 }
 
 static int correlate_gemm(mad_ctx *ctx, int n_jobs, const GemmJob *jobs, int D, double cc) {
     mad_timer_begin(ctx, MAD_T_CORRELATE);
+    static const bool no_split = getenv("MAD_GEMM_NO_SPLIT") != nullptr;      // diagnostic switch: whole tiles only, as in round 3
+    const bool wide = n_jobs > 0 && jobs[0].hb != nullptr;
+    for (int j = 1; j < n_jobs; j++)
+        if ((jobs[j].hb != nullptr) != wide) return mad_fail(ctx, MAD_EINVAL, "correlate: wide and narrow sets in one batch of matches");
     for (int j0 = 0; j0 < n_jobs; j0 += MAD_BATCH_MAX) {
-        GemmBatch G;
+        if (!wide) {
+            GemmBatch G;
+            G.n_jobs = std::min(n_jobs - j0, MAD_BATCH_MAX); G.K = D; G.cc = cc;
+            G.split_tail = no_split ? 0 : 1;
+            for (int j = 0; j < G.n_jobs; j++) G.job[j] = jobs[j0 + j];
+            MAD_TRY(gemm2_launch(ctx, G));
+            continue;
+        }
+        GemmBatchT<true> G;
         G.n_jobs = std::min(n_jobs - j0, MAD_BATCH_MAX); G.K = D; G.cc = cc;
-        static const bool no_split = getenv("MAD_GEMM_NO_SPLIT") != nullptr;      // diagnostic switch: whole tiles only, as in round 3
         G.split_tail = no_split ? 0 : 1;
         for (int j = 0; j < G.n_jobs; j++) G.job[j] = jobs[j0 + j];
         MAD_TRY(gemm2_launch(ctx, G));
@@ -2932,7 +2980,7 @@ extern "C" void mad_set_destroy(mad_ctx *ctx, mad_set *s) {
         if (ctx->match.shard_lo == s) ctx->match.shard_lo = nullptr;
     }
     DevBuf *bufs[] = {&s->anc_blob, &s->row_anchor, &s->row_main, &s->row_sec, &s->row_R, &s->row_Rinv, &s->row_meta, &s->dsc,
-                      &s->dsc8, &s->norm, &s->row_perm, &s->row_rec, &s->anc_rows, &s->cell_start, &s->cell_pts, &s->cell_ids};      // anc_* and dev_n are views
+                      &s->dsc8, &s->norm, &s->rsum, &s->row_perm, &s->row_rec, &s->anc_rows, &s->cell_start, &s->cell_pts, &s->cell_ids};      // anc_* and dev_n are views
     for (DevBuf *b : bufs) mad_release(*b);
     if (s->host_stage) (void)hipHostFree(s->host_stage);
     if (s->ready) (void)hipEventDestroy(s->ready);
@@ -2967,6 +3015,7 @@ static int set_rows(mad_ctx *ctx, const mad_set *cs, int64_t *n_rows) {
             }
             J.d_n_rows = (const int32_t *)s->dev_n.p; J.grid_rows = s->cap_rows; J.d_overflow = (int32_t *)s->dev_n.p + 3;
             J.d_dsc = (int16_t *)s->dsc.p; J.d_dsc8 = (int8_t *)s->dsc8.p; J.d_norm = (double *)s->norm.p;
+            J.d_rsum = s->wide ? (int32_t *)s->rsum.p : nullptr;
             MAD_TRY(mad_describe_device_many(ctx, 1, &J, s->last_r));
             MAD_HIP(hipEventRecord(s->built, ctx->stream));
             MAD_HIP(hipMemcpyAsync(&ctx->pinned[s->pinned_slot], s->dev_n.p, 16, hipMemcpyDeviceToHost, ctx->stream));
@@ -3146,9 +3195,41 @@ static int set_reserve_rows(mad_ctx *ctx, mad_set *s, int64_t cap) {
     MAD_TRY(mad_reserve(ctx, s->dsc, (size_t)cap_pad * s->D * 2));
     MAD_TRY(mad_reserve(ctx, s->dsc8, (size_t)cap_pad * s->D));
     MAD_TRY(mad_reserve(ctx, s->norm, (size_t)cap_pad * 8));
+    if (s->wide) MAD_TRY(mad_reserve(ctx, s->rsum, (size_t)cap_pad * 4));
     MAD_TRY(mad_reserve(ctx, s->row_perm, (size_t)cap_pad * 4));
     MAD_TRY(mad_reserve(ctx, s->row_rec, (size_t)cap_pad * sizeof(DscRowRec)));
     return MAD_OK;
+}
+
+// k_pack_rows for the rows of a wide set (mad_common.h, MAD_WIDE_C): counts 0 .. MAD_WIDE_MAX stored as count - MAD_WIDE_C, the row's
+// MAD_WIDE_BIAS beside its norm (the norm is that of the counts themselves), padding rows all -MAD_WIDE_C with the bias of sum 0
+__global__ __launch_bounds__(256) void k_pack_rows_wide(const int16_t *__restrict__ src, const int32_t *__restrict__ n_ptr, int D,
+                                                        int8_t *__restrict__ dst, double *__restrict__ norm,
+                                                        int32_t *__restrict__ bad, int32_t *__restrict__ bias) {
+    const int64_t n = *n_ptr;
+    const int64_t n_pad = (n + 127) / 128 * 128;
+    const int lane = lane_id();
+    const int64_t wave = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6), nw = (int64_t)gridDim.x * 4;
+    for (int64_t row = wave; row < n_pad; row += nw) {
+        if (row >= n) {
+            for (int k = lane; k < D; k += MAD_WAVE) dst[row * D + k] = (int8_t)-MAD_WIDE_C;
+            if (lane == 0) { norm[row] = 0.0; bias[row] = MAD_WIDE_BIAS(0, D); }
+            continue;
+        }
+        long long ss = 0;
+        int oob = 0, sv = 0;
+        for (int k = lane; k < D; k += MAD_WAVE) {
+            int v = src[row * D + k];
+            if (v > MAD_WIDE_MAX || v < 0) { oob = 1; v = 0; }      // (the set is refused on the host: the sums only have to stay in range)
+            dst[row * D + k] = (int8_t)(v - MAD_WIDE_C);
+            ss += (long long)v * v;
+            sv += v;
+        }
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) { ss += __shfl_xor(ss, o, MAD_WAVE); sv += __shfl_xor(sv, o, MAD_WAVE); }
+        if (bad && __any(oob) && lane == 0) atomicExch(bad, 1);
+        if (lane == 0) { norm[row] = sqrt((double)ss); bias[row] = MAD_WIDE_BIAS(sv, D); }
+    }
 }
 
 // for rows that came from the host (mad_set_load): int8 rows + norms with the range check, inverse rotations,
@@ -3157,8 +3238,12 @@ static int set_finish_rows(mad_ctx *ctx, mad_set *s) {
     int32_t *d_n = (int32_t *)s->dev_n.p;
     int32_t *bad = d_n + 1;      // zeroed with the other counters by the anchor upload
     const int64_t cap_pad = mad_ceil_div(s->cap_rows > 0 ? s->cap_rows : 1, GEMM_BM) * GEMM_BM;
-    hipLaunchKernelGGL(k_pack_rows, dim3((unsigned)std::min<int64_t>(mad_ceil_div(cap_pad, 4), (int64_t)ctx->n_cu * 8)), dim3(256), 0,
-                       ctx->stream, (const int16_t *)s->dsc.p, d_n, s->D, (int8_t *)s->dsc8.p, (double *)s->norm.p, bad);
+    if (s->wide)
+        hipLaunchKernelGGL(k_pack_rows_wide, dim3((unsigned)std::min<int64_t>(mad_ceil_div(cap_pad, 4), (int64_t)ctx->n_cu * 8)), dim3(256), 0,
+                           ctx->stream, (const int16_t *)s->dsc.p, d_n, s->D, (int8_t *)s->dsc8.p, (double *)s->norm.p, bad, (int32_t *)s->rsum.p);
+    else
+        hipLaunchKernelGGL(k_pack_rows, dim3((unsigned)std::min<int64_t>(mad_ceil_div(cap_pad, 4), (int64_t)ctx->n_cu * 8)), dim3(256), 0,
+                           ctx->stream, (const int16_t *)s->dsc.p, d_n, s->D, (int8_t *)s->dsc8.p, (double *)s->norm.p, bad);
     hipLaunchKernelGGL(k_row_aux, dim3((unsigned)std::min<int64_t>(mad_ceil_div(cap_pad, 256), 1024)), dim3(256), 0, ctx->stream,
                        (const double *)s->row_R.p, d_n, (double *)s->row_Rinv.p, (const int32_t *)s->row_anchor.p,
                        (const int32_t *)s->row_main.p, (const int32_t *)s->anc_index.p, (const int32_t *)s->anc_octave.p,
@@ -3213,6 +3298,7 @@ extern "C" int mad_set_build_many(mad_ctx *ctx, int n_sets, mad_set *const *sets
         const bool sort_ball = ctx->dsc_ball && r == 8 && oj[i].f[1].tex4 != nullptr && ctx->spatial_order;
         MAD_TRY(set_upload_anchors(ctx, s, anc_coords[i], anc_octave[i], anc_subv[i], anc_index[i], n, 0, sort_ball ? bdims : nullptr));
         s->D = 64 * ctx->eq_host[1].Z;
+        s->wide = r >= MAD_WIDE_FROM_R;      // a sub-region holds more samples than an int8 count: centred rows (mad_common.h)
         MAD_TRY(set_reserve_rows(ctx, s, (int64_t)n * lim_main * lim_sec));
         MAD_TRY(mad_reserve(ctx, s->anc_rows, (size_t)(n > 0 ? n : 1) * MAD_ANCROW_WORDS * 4));
         s->last_fan = lim_main * lim_sec;
@@ -3244,6 +3330,7 @@ extern "C" int mad_set_build_many(mad_ctx *ctx, int n_sets, mad_set *const *sets
         Q.grid_rows = n <= 0 ? 0 : (s->rows_hint > 0 ? std::min<int64_t>(s->cap_rows, s->rows_hint + s->rows_hint / 8 + 64) : s->cap_rows);
         Q.d_overflow = (int32_t *)s->dev_n.p + 3;
         Q.d_dsc = (int16_t *)s->dsc.p; Q.d_dsc8 = (int8_t *)s->dsc8.p; Q.d_norm = (double *)s->norm.p;      // int8 copy + norms included: counts are <= 64 by construction
+        Q.d_rsum = s->wide ? (int32_t *)s->rsum.p : nullptr;                                                // (wide: <= 216, centred, with the rows' biases)
         s->last_f[0] = J.f[0]; s->last_f[1] = J.f[1]; s->last_r = r;
         s->n_rows_host = -1;
     }
@@ -3273,6 +3360,7 @@ extern "C" int mad_set_load(mad_ctx *ctx, mad_set *s, int64_t n_rows, const int3
         if (row_anchor[i] < 0 || row_anchor[i] >= n_anchors) return mad_fail(ctx, MAD_EINVAL, "mad_set_load: row %lld -> anchor %d", (long long)i, row_anchor[i]);
     MAD_TRY(set_upload_anchors(ctx, s, nullptr, anc_octave, anc_subv, anc_index, n_anchors, (int32_t)n_rows));
     s->D = D;
+    s->wide = s->wide_mark;
     MAD_TRY(set_reserve_rows(ctx, s, n_rows));
     if (n_rows > 0) {
         MAD_HIP(hipMemcpyAsync(s->row_anchor.p, row_anchor, n_rows * 4, hipMemcpyHostToDevice, ctx->stream));
@@ -3285,9 +3373,20 @@ extern "C" int mad_set_load(mad_ctx *ctx, mad_set *s, int64_t n_rows, const int3
     MAD_HIP(hipEventRecord(s->built, ctx->stream));
     int64_t n_dev = 0;
     MAD_TRY(set_rows(ctx, s, &n_dev));      // synchronises (the host arrays may go away) and fetches the range check
+    if (s->range_bad && s->wide) return mad_fail(ctx, MAD_EDOM, "descriptor count outside 0..%d, the range of a wide set's centred int8 rows", MAD_WIDE_MAX);
     if (s->range_bad) return mad_fail(ctx, MAD_EDOM, "descriptor count outside the int8 range");
     return MAD_OK;
 }
+
+// Marks a set as wide (or narrow again) for the loads that follow: its rows were described at a radius >= MAD_WIDE_FROM_R and
+// hold counts up to MAD_WIDE_MAX.  mad_set_build decides by its radius and does not look at the mark.
+extern "C" int mad_set_mark_wide(mad_ctx *ctx, mad_set *s, int wide) {
+    if (!ctx || !s) return MAD_EINVAL;
+    s->wide_mark = wide != 0;
+    return MAD_OK;
+}
+
+extern "C" int mad_set_is_wide(mad_ctx *ctx, const mad_set *s) { return (ctx && s) ? (s->wide ? 1 : 0) : -1; }
 
 extern "C" int mad_set_size(mad_ctx *ctx, const mad_set *s, int64_t *n_rows, int32_t *n_anchors) {
     if (!ctx || !s) return MAD_EINVAL;
@@ -3320,6 +3419,7 @@ static Side side_of(const mad_set *s) {
     x.Rinv = (const double *)s->row_Rinv.p; x.meta = (const int32_t *)s->row_meta.p; x.row_anchor = (const int32_t *)s->row_anchor.p;
     x.p = (const double *)s->anc_subv.p; x.n_rows = (const int32_t *)s->dev_n.p; x.cap_rows = s->cap_rows;
     x.anc_canon = (const int32_t *)s->anc_canon.p;
+    x.bias = s->wide ? (const int32_t *)s->rsum.p : nullptr;
     return x;
 }
 
@@ -3834,6 +3934,7 @@ static Side side_block(const mad_set *s, int64_t begin, const int32_t *d_n_rows,
 extern "C" int mad_match_shard_pairs(mad_ctx *ctx, const mad_set *hi, const mad_set *lo, int64_t lo_begin, int64_t lo_end, double cc,
                                      uint8_t *used_hi, uint8_t *used_lo, int64_t *n_pairs) {
     if (!ctx || !hi || !lo || !used_hi || !used_lo || !n_pairs) return MAD_EINVAL;
+    if (hi->wide || lo->wide) return mad_fail(ctx, MAD_EINVAL, "%s: wide sets (descriptor radius >= %d) are matched whole, on one device", "mad_match_shard_pairs", MAD_WIDE_FROM_R);
     mad_use_lane(ctx, 0);
     *n_pairs = 0;
     ctx->match.shard_hi = nullptr;
@@ -4007,6 +4108,7 @@ extern "C" int64_t mad_match_shard_record_doubles(int64_t k) { return 4 + (k < 1
 extern "C" int mad_match_shard_begin(mad_ctx *ctx, const mad_set *hi, const mad_set *lo, int64_t lo_begin, int64_t lo_end, int64_t n_lo,
                                      double cc, uint8_t *d_flags) {
     if (!ctx || !hi || !lo || !d_flags) return MAD_EINVAL;
+    if (hi->wide || lo->wide) return mad_fail(ctx, MAD_EINVAL, "%s: wide sets (descriptor radius >= %d) are matched whole, on one device", "mad_match_shard_begin", MAD_WIDE_FROM_R);
     if (hi->D != lo->D) return mad_fail(ctx, MAD_EINVAL, "mad_match_shard_begin: descriptor lengths %d vs %d", hi->D, lo->D);
     if (lo_begin < 0 || lo_end < lo_begin || lo_end > n_lo || n_lo > lo->cap_rows)
         return mad_fail(ctx, MAD_EINVAL, "mad_match_shard_begin: lo rows [%lld, %lld) of %lld (capacity %lld)", (long long)lo_begin, (long long)lo_end, (long long)n_lo, (long long)lo->cap_rows);
@@ -4286,6 +4388,7 @@ __global__ __launch_bounds__(256) void k_set_export(const int32_t *__restrict__ 
 // synchronous.  A share with more than cap_rows rows travels as an empty image whose header says how many it had.
 extern "C" int mad_set_export(mad_ctx *ctx, const mad_set *s, void *wire, int wire_on_device, int64_t cap_rows) {
     if (!ctx || !s || !wire || cap_rows < 1) return MAD_EINVAL;
+    if (s->wide) return mad_fail(ctx, MAD_EINVAL, "mad_set_export: the wire image has no room for the row sums of a wide set (descriptor radius >= %d)", MAD_WIDE_FROM_R);
     if (!s->dev_n.p || s->D <= 0 || (s->D % 16)) return mad_fail(ctx, MAD_EINVAL, "mad_set_export: the set has not been built");
     mad_use_lane(ctx, s->lane);
     MAD_HIP(hipStreamWaitEvent(ctx->stream, s->built, 0));      // the build may have run on another lane (mad_set_build_many)
@@ -4404,6 +4507,7 @@ extern "C" int mad_set_import(mad_ctx *ctx, mad_set *s, const void *wires, int w
                               const int32_t *anc_coords, const int32_t *anc_octave, const double *anc_subv, const int32_t *anc_index,
                               int n_anchors) {
     if (!ctx || !s || !wires || n_shares < 1 || cap_rows < 1) return MAD_EINVAL;
+    if (s->wide_mark) return mad_fail(ctx, MAD_EINVAL, "mad_set_import: the set is marked wide (mad_set_mark_wide); wire images hold narrow rows only");
     if (n_anchors > 0 && (!anc_octave || !anc_subv || !anc_index)) return mad_fail(ctx, MAD_EINVAL, "mad_set_import: NULL anchors");
     if (n_anchors > 65536) return mad_fail(ctx, MAD_EINVAL, "mad_set_import: %d anchors exceed the single-launch scan", n_anchors);
     if (!ctx->eq_set[0] || !ctx->eq_set[1]) return mad_fail(ctx, MAD_EINVAL, "mad_set_import: EQSP tables not set");
@@ -4436,6 +4540,7 @@ extern "C" int mad_set_import(mad_ctx *ctx, mad_set *s, const void *wires, int w
                        (int32_t *)s->row_meta.p, (int16_t *)s->dsc.p, (int8_t *)s->dsc8.p, (double *)s->norm.p);
     MAD_HIP(hipGetLastError());
     s->last_r = 0;      // nothing to repeat locally: an incomplete import is the caller's to redo with larger images
+    s->wide = false;
     s->n_rows_host = -1;
     MAD_HIP(hipEventRecord(s->built, ctx->stream));
     if (!wires_on_device) MAD_HIP(hipStreamSynchronize(ctx->stream));      // the host images may go away

@@ -715,13 +715,15 @@ static int orient_batch(mad_ctx *ctx, int n_jobs, const OrientJob *jobs, int r, 
 
 int mad_orient_device_many(mad_ctx *ctx, int n_jobs, const OrientJob *jobs, int r, int lim_main, int lim_sec) {
     if (!ctx->eq_set[0]) return mad_fail(ctx, MAD_EINVAL, "mad_orient: orientation EQSP table not set");
-    if (r < 1 || r > 10) return mad_fail(ctx, MAD_EINVAL, "mad_orient: box_side %d outside 1..10", r);
+    if (r < 1 || r > 12) return mad_fail(ctx, MAD_EINVAL, "mad_orient: box_side %d outside 1..12", r);
+    // (with a window a voxel takes 14 bytes of LDS instead of 12 and the histograms are 64-bit: not sized, nor tested, beyond 10)
+    if (r > 10 && ctx->gw_sig != 0.0) return mad_fail(ctx, MAD_EINVAL, "mad_orient: box_side %d with a Gaussian window (gw_sig != 0) is outside 1..10", r);
     if (lim_main < 1 || lim_main > ORI_MAX_MAIN || lim_sec < 1 || lim_main * lim_sec > ORI_MAX_FAN)
         return mad_fail(ctx, MAD_EINVAL, "mad_orient: lim_main=%d lim_sec=%d unsupported", lim_main, lim_sec);
     MAD_TRY(ensure_mask(ctx, r));
     if (ctx->gw_sig != 0.0 && (ctx->gw_r != r || ctx->gw_built != ctx->gw_sig)) {
         // Orientator(gw_sig): the window's weights for this box size, as 2^-50 fixed point
-        unsigned long long tab[3 * 10 * 10 + 1];
+        unsigned long long tab[3 * 12 * 12 + 1];
         for (int d2 = 0; d2 <= 3 * r * r; d2++)
             tab[d2] = (unsigned long long)llround(ldexp(exp(-1.0 * ((double)d2 / (2.0 * (ctx->gw_sig * ctx->gw_sig)))), ORI_WFIX_BITS));
         if (!ctx->gw_tab && hipMalloc((void **)&ctx->gw_tab, sizeof(tab)) != hipSuccess) return mad_fail(ctx, MAD_ENOMEM, "orientation window table");
@@ -833,6 +835,7 @@ struct DescribeArgs {
     int16_t *dsc;                  // n_rows x 64*Z
     int8_t *dsc8;                  // nullable: the same rows as int8, zero-padded to a multiple of 128 rows (GEMM operand)
     double *norm;                  // with dsc8: |row|_2 (MaD.py:416)
+    int32_t *rsum;                 // with dsc8 at S = 24 (wide rows, counts up to 216): dsc8 holds count - MAD_WIDE_C, this the row's MAD_WIDE_BIAS
 };
 
 // The reference's arithmetic for one sample (Descriptor.py:153-187): float32 normalisation, float64
@@ -926,14 +929,19 @@ extern "C" int mad_debug_dsc_stamps(long long *out, int n) {
 #ifndef DSC_OCC_TAB
 #define DSC_OCC_TAB 4     // ... of the TAB form (5: 96 registers, 32 of them spilled, 88 -> 102 us per launch)
 #endif
+// threads of a row's workgroup: one per (j, k) lattice column -- 256 up to S = 16, whole waves over S * S beyond (448 at S = 20, 576 at 24)
+#define DSC_NT(S) ((S) <= 16 ? DSC_THREADS : ((S) * (S) + MAD_WAVE - 1) / MAD_WAVE * MAD_WAVE)
 template <int S, int NSUB = 64, int ZMAX = 16, bool TAB = false>
-__global__ __launch_bounds__(DSC_THREADS, TAB ? DSC_OCC_TAB : DSC_OCC) void k_describe(Batch<DescribeArgs> B) {
+__global__ __launch_bounds__(DSC_NT(S), TAB ? DSC_OCC_TAB : DSC_OCC) void k_describe(Batch<DescribeArgs> B) {
+    constexpr int NT = DSC_NT(S);
+    constexpr bool WIDE = S >= 2 * MAD_WIDE_FROM_R;      // S = 24 (r >= 11): a region holds 216 samples, the int8 operand is centred (mad_common.h)
     const int job = batch_job(B, (int)blockIdx.x);
     const DescribeArgs &A = B.job[job];
     const int bid = (int)blockIdx.x - B.first[job], gdim = B.first[job + 1] - B.first[job];      // this job's part of the grid (multiples of 8)
     __shared__ int hist[NSUB * ZMAX];
     __shared__ int s_oob, s_nq;
-    __shared__ int s_part[DSC_THREADS / MAD_WAVE];
+    __shared__ int s_part[NT / MAD_WAVE];
+    __shared__ int s_sum[WIDE ? NT / MAD_WAVE : 1];
     __shared__ __align__(16) int s_rec[32];      // the row's DscRowRec
     // TAB: the float32 / float64 tiers see 3-4 % of the samples, at the end, in full lanes: they read their tables from global
     // memory (cache-resident, shared by every workgroup) and the 12 KB image is not staged per row
@@ -964,8 +972,9 @@ __global__ __launch_bounds__(DSC_THREADS, TAB ? DSC_OCC_TAB : DSC_OCC) void k_de
         const int64_t n_pad = (n_rows + 127) / 128 * 128;
         const int Dp = NSUB * A.eq->Z;
         for (int64_t r = n_rows + bid; r < n_pad; r += gdim) {
-            for (int i = tid; i < Dp / 4; i += DSC_THREADS) ((int32_t *)(A.dsc8 + r * Dp))[i] = 0;
+            for (int i = tid; i < Dp / 4; i += NT) ((int32_t *)(A.dsc8 + r * Dp))[i] = WIDE ? MAD_WIDE_ZERO4 : 0;
             if (tid == 0) A.norm[r] = 0.0;
+            if (WIDE && tid == 0) A.rsum[r] = MAD_WIDE_BIAS(0, Dp);
         }
     }
     const int64_t work = (int64_t)(bid & 7) * chunk + (bid >> 3);
@@ -976,7 +985,7 @@ __global__ __launch_bounds__(DSC_THREADS, TAB ? DSC_OCC_TAB : DSC_OCC) void k_de
     const FieldDev F0 = A.f[0], F1 = A.f[1];
     const int Z = A.eq->Z;
     const int D = NSUB * Z;            // S = 2 r samples per axis (16), NSUB sub-regions of Z zones each
-    for (int i = tid; i < D; i += DSC_THREADS) hist[i] = 0;
+    for (int i = tid; i < D; i += NT) hist[i] = 0;
     // What a row starts from -- its index, its anchor's coordinates and octave, inv(Rfinal) -- is one 128-byte record (DscRowRec,
     // written with the rows by k_orient_rows* in WORKING order) that 32 lanes fetch with one vector load and park in LDS, next
     // to the staging of the tables.  Before (round 2) it was a chain of dependent scalar loads, row_perm -> row_anchor -> octave,
@@ -1032,7 +1041,7 @@ __global__ __launch_bounds__(DSC_THREADS, TAB ? DSC_OCC_TAB : DSC_OCC) void k_de
               ic2 = __builtin_amdgcn_readfirstlane(s_rec[3]);
     const float h0 = (float)sInv[0], h1 = (float)sInv[1], h2 = (float)sInv[2], h3 = (float)sInv[3], h4 = (float)sInv[4], h5 = (float)sInv[5],
                 h6 = (float)sInv[6], h7 = (float)sInv[7], h8 = (float)sInv[8];
-    // this thread's (j, k) column of the S^3 lattice; threads beyond S*S idle (S <= 16)
+    // this thread's (j, k) column of the S^3 lattice; threads beyond S*S idle (NT >= S * S)
     const int j = tid / S, k = tid % S;
     const bool active = tid < S * S;
     // lattice coordinate along an axis = lbase + lstep * index (Descriptor.py:34-35)
@@ -1052,8 +1061,11 @@ __global__ __launch_bounds__(DSC_THREADS, TAB ? DSC_OCC_TAB : DSC_OCC) void k_de
                           ic2 - reach >= 1 && ic2 + reach <= F.nz - 2;      // uniform over the workgroup
     // The S samples of a thread go through in DSC_PASSES passes: the texel requests of a pass all go out before its first texel is
     // looked at, then the pass is classified.  DSC_PASSES = 1 keeps all S texels (64 registers at S = 16) in flight at once.
-    constexpr int NP = (S % (DSC_CHUNK * DSC_PASSES) == 0) ? DSC_PASSES : 1;
+    // (S > 16: passes of at most 12 samples -- 3 x 8 at S = 24, 2 x 10 at S = 20 -- so that the texels in flight stay within the
+    // registers of four workgroups per CU: 24 float4 at once would be 96 of 128)
+    constexpr int NP = S > 16 ? (S % DSC_CHUNK == 0 ? S / DSC_CHUNK : 2) : ((S % (DSC_CHUNK * DSC_PASSES) == 0) ? DSC_PASSES : 1);
     constexpr int PS = S / NP;
+    static_assert(S % NP == 0 && PS <= 32, "a pass's samples are one bit each of `unsure` / `undecided`");
     bool oob = false;
     if (active) {
         // float32 guess of the offset from the anchor voxel, |error| < 1e-5 voxel: the nearest voxel is known unless the
@@ -1191,15 +1203,16 @@ __global__ __launch_bounds__(DSC_THREADS, TAB ? DSC_OCC_TAB : DSC_OCC) void k_de
     DSC_STAMP(5);
     const bool dead = s_oob != 0;      // Descriptor.py:142-149: a sample left the grid -> the whole descriptor is zero
     if (dead) {
-        for (int i = tid; i < D; i += DSC_THREADS) A.dsc[row * D + i] = 0;
+        for (int i = tid; i < D; i += NT) A.dsc[row * D + i] = 0;
         if (A.dsc8) {
-            for (int i = tid; i < D; i += DSC_THREADS) A.dsc8[row * D + i] = 0;
+            for (int i = tid; i < D; i += NT) A.dsc8[row * D + i] = WIDE ? (int8_t)-MAD_WIDE_C : 0;
             if (tid == 0) A.norm[row] = 0.0;
+            if (WIDE && tid == 0) A.rsum[row] = MAD_WIDE_BIAS(0, D);
         }
     } else if (s_nq > QCAP) {
         // more undecided points than the queue holds (not seen in practice): redo the whole row with the exact arithmetic
         __syncthreads();
-        for (int i = tid; i < D; i += DSC_THREADS) hist[i] = 0;
+        for (int i = tid; i < D; i += NT) hist[i] = 0;
         __syncthreads();
         if (active)
             for (int i = 0; i < S; i++) {      // not unrolled: indices again from the float64 expression
@@ -1213,7 +1226,7 @@ __global__ __launch_bounds__(DSC_THREADS, TAB ? DSC_OCC_TAB : DSC_OCC) void k_de
         const int nq = s_nq;
         const float f0 = (float)Rrow[0], f1 = (float)Rrow[1], f2 = (float)Rrow[2], f3 = (float)Rrow[3], f4 = (float)Rrow[4], f5 = (float)Rrow[5],
                     f6 = (float)Rrow[6], f7 = (float)Rrow[7], f8 = (float)Rrow[8];
-        for (int e = tid; e < nq; e += DSC_THREADS) {
+        for (int e = tid; e < nq; e += NT) {
             const float4 tx = F.tex[qidx[e]];
             if (tx.w < 1e-5f) continue;      // (cannot happen for a queued sample: such texels carry flag 3; kept for symmetry with the slow path)
             const float inv = __builtin_amdgcn_rcpf(fmaxf(tx.w, 1e-30f));
@@ -1224,26 +1237,37 @@ __global__ __launch_bounds__(DSC_THREADS, TAB ? DSC_OCC_TAB : DSC_OCC) void k_de
         }
     } else {
         const int nq = s_nq;
-        for (int qi = tid; qi < nq; qi += DSC_THREADS) atomicAdd(&hist[qsub[qi] * Z + describe_exact(exactp, qv[qi], Rrow)], 1);
+        for (int qi = tid; qi < nq; qi += NT) atomicAdd(&hist[qsub[qi] * Z + describe_exact(exactp, qv[qi], Rrow)], 1);
     }
     __syncthreads();
     DSC_STAMP(6);
-    int ss = 0;      // counts <= 64, 1024 of them: the sum of squares is exact in int32
-    for (int i = tid; i < D; i += DSC_THREADS) {
+    int ss = 0;      // counts <= 64 (S = 24: <= 216), 1024 of them: the sum of squares is exact in int32
+    int sv = 0;      // WIDE: the sum of the counts (not a constant: samples below the magnitude cut are not counted)
+    for (int i = tid; i < D; i += NT) {
         const int v = hist[i];
         if (dead) continue;
         A.dsc[row * D + i] = (int16_t)v;
-        if (A.dsc8) A.dsc8[row * D + i] = (int8_t)v;
+        if (A.dsc8) A.dsc8[row * D + i] = (int8_t)(WIDE ? v - MAD_WIDE_C : v);
         ss += v * v;
+        if (WIDE) sv += v;
     }
     if (A.dsc8 && !dead) {
         ss = wave_sum_i32(ss);
         if (lane_id() == 0) s_part[tid >> 6] = ss;
+        if (WIDE) {
+            sv = wave_sum_i32(sv);
+            if (lane_id() == 0) s_sum[tid >> 6] = sv;
+        }
         __syncthreads();
         if (tid == 0) {
             int tot = 0;
-            for (int w = 0; w < DSC_THREADS / MAD_WAVE; w++) tot += s_part[w];
+            for (int w = 0; w < NT / MAD_WAVE; w++) tot += s_part[w];
             A.norm[row] = sqrt((double)tot);
+            if (WIDE) {
+                int sum = 0;
+                for (int w = 0; w < NT / MAD_WAVE; w++) sum += s_sum[w];
+                A.rsum[row] = MAD_WIDE_BIAS(sum, D);
+            }
         }
     }
     DSC_STAMP(7);
@@ -1670,7 +1694,9 @@ int mad_describe_device_many(mad_ctx *ctx, int n_jobs, const DescribeJob *jobs, 
     const int Zd = ctx->eq_host[1].Z;
     if (Zd != 16 && !(Zd <= 128 && dsc_size == 64 && 2 * r == 16))
         return mad_fail(ctx, MAD_EINVAL, "mad_describe: %d descriptor zones: 16 for every layout, up to 128 (the 112-zone table) for the default 64 regions and dsc_radius 16", Zd);
-    if (r < 2 || r > 8 || (r % 2)) return mad_fail(ctx, MAD_EINVAL, "mad_describe: dsc radius %d must be 2, 4, 6 or 8", r);
+    if (r < 2 || r > 12 || (r % 2)) return mad_fail(ctx, MAD_EINVAL, "mad_describe: dsc radius %d must be 2, 4, 6, 8, 10 or 12", r);
+    if (r > 8 && (dsc_size != 64 || Zd != 16))
+        return mad_fail(ctx, MAD_EINVAL, "mad_describe: dsc radius %d is built for 64 regions of 16 zones only (dsc_size %d, %d zones)", r, dsc_size, Zd);
     const bool tab = Zd == 16 && ctx->eq_host[1].tab_ok && dsc_size == 64 && 2 * r == 16;
     const bool ball_ok = tab && ctx->dsc_ball;      // (mad_set_option "dsc_ball", MAD_BALL=1: off by default)
     if (ball_ok) MAD_TRY(ensure_ball(ctx));
@@ -1698,6 +1724,8 @@ int mad_describe_device_many(mad_ctx *ctx, int n_jobs, const DescribeJob *jobs, 
             A.anc_coords = J.d_anc_coords; A.anc_octave = J.d_anc_octave; A.uniform_octave = J.uniform_octave;
             A.row_anchor = J.d_row_anchor; A.row_R = J.d_row_R; A.row_Rinv = J.d_row_Rinv; A.row_perm = J.d_row_perm; A.n_rows = J.d_n_rows; A.overflow = J.d_overflow;
             A.r = r; A.eq = ctx->eq[1]; A.dsc = J.d_dsc; A.dsc8 = J.d_dsc8; A.norm = J.d_norm; A.row_rec = J.d_row_rec;
+            A.rsum = J.d_rsum;
+            if (J.d_dsc8 && r >= MAD_WIDE_FROM_R && !J.d_rsum) return mad_fail(ctx, MAD_EINVAL, "mad_describe: int8 rows at dsc radius %d need the row sums of a wide set", r);
             A.queue_cap = std::max(ctx->dsc_queue_cap, 0);
             A.row_limit = ball ? J.d_anc_rows + MAD_ANCROW_WORDS * (int64_t)J.n_rowwise : nullptr;      // first row position of the first base-octave anchor
             B.first[B.n_jobs++] = (int)blk;
@@ -1734,6 +1762,9 @@ int mad_describe_device_many(mad_ctx *ctx, int n_jobs, const DescribeJob *jobs, 
                 else if (tab) hipLaunchKernelGGL((k_describe<16, 64, 16, true>), dim3(nblk), dim3(DSC_THREADS), dsc_pad, ctx->stream, B);
                 else hipLaunchKernelGGL(k_describe<16>, dim3(nblk), dim3(DSC_THREADS), 0, ctx->stream, B);
                 break;
+            // (instantiated last: the instances above keep their places in the code object)
+            case 20: hipLaunchKernelGGL(k_describe<20>, dim3(nblk), dim3(DSC_NT(20)), 0, ctx->stream, B); break;
+            case 24: hipLaunchKernelGGL(k_describe<24>, dim3(nblk), dim3(DSC_NT(24)), 0, ctx->stream, B); break;
         }
         if (BB.n_jobs > 0) {
             // every job's grid: `chunks` runs of DSCB_RPB rows x its base-octave anchors rounded up to 8 (an anchor has at most fan rows;

@@ -25,6 +25,7 @@ class DescriptorRows(object):
         self._data = None      # the four cache arrays
         self._rows = None
         self._n = None
+        self._wide = False     # from_arrays: the set is loaded as a wide one
         self.anc = None        # per anchor of the set: index, octave, coords, map_coords, subv
 
     # ------------------------------------------------------------------ construction
@@ -40,9 +41,11 @@ class DescriptorRows(object):
         return self
 
     @classmethod
-    def from_arrays(cls, data, lib=None):
-        """Rows of a cache file: data = dict(dsc, info, coords, rot) as `arrays()` returns them."""
+    def from_arrays(cls, data, lib=None, wide=False):
+        """Rows of a cache file: data = dict(dsc, info, coords, rot) as `arrays()` returns them.
+        wide: they were described at a radius of 11 or more (the cache file does not say; its name carries the patch size)."""
         self = cls()
+        self._wide = bool(wide)
         self._data = {k: np.asarray(data[k]) for k in ("dsc", "info", "coords", "rot")}
         n = len(self._data["info"])
         self._n = n
@@ -72,7 +75,8 @@ class DescriptorRows(object):
             lib = self._lib if self._lib is not None else _lib.get_lib()
             d, n = self._data, self._n
             self._dev = lib.set_load(self._row_anchor, d["info"].reshape(n, 6)[:, 1].astype(np.int32), d["rot"].reshape(n, 9), d["dsc"].reshape(n, self.D),
-                                     self.anc["subv"], self.anc["index"].astype(np.int32), self.anc["octave"].astype(np.int32))
+                                     self.anc["subv"], self.anc["index"].astype(np.int32), self.anc["octave"].astype(np.int32),
+                                     wide=self._wide)
         return self._dev
 
     @property
