@@ -327,12 +327,23 @@ int mad_match_used(mad_ctx *ctx, uint8_t *hi_anchor_used, int32_t n_hi_anchors,
 int mad_upload_density(mad_ctx *ctx, const float *grid, int nx, int ny, int nz,
                        double ox, double oy, double oz, double voxsp);
 /*
- * Refine n_cand rigid placements of the same n_atoms-atom structure at once
- * (one persistent workgroup per candidate).  coords: n_cand x n_atoms x 3, updated
- * in place.  converged / last_step: per candidate, the reference's return values.
+ * Refine n_cand rigid placements of the same n_atoms-atom structure at once.  Each candidate
+ * runs in G persistent workgroups that share its atoms and meet at every reduction (G from 1 to 8,
+ * sized so that all n_cand x G workgroups are resident together); the atoms stay in registers when
+ * a thread holds at most 8 of them, otherwise the kernel walks them in global memory.
+ * coords: n_cand x n_atoms x 3, updated in place.  converged / last_step: per candidate, the
+ * reference's return values.
  */
 int mad_refine(mad_ctx *ctx, double *coords, int n_cand, int64_t n_atoms, int n_steps,
                double max_step, double min_step, int32_t *converged, int32_t *last_step);
+/*
+ * What the most recent refinement (mad_refine or mad_dock_refine_score) chose: *G = workgroups per candidate, *in_registers = 1 for
+ * the register-resident kernel form, 0 for the one over global memory; both -1 before the first.  For tests and diagnostics: the
+ * results of the plans agree to the last bits only, so only this tells when a sizing change has moved a workload to another plan.
+ */
+int mad_last_refine_plan(mad_ctx *ctx, int *G, int *in_registers);
+/* Into how many chunks (of at most 512 Mi float64 voxels) the most recent density simulation cut its batch; -1 before the first. */
+int mad_last_density_chunks(mad_ctx *ctx);
 
 /* ---- a14-a15: PDB.structure_to_density (PDB.py:131-292) ------------------------ */
 

@@ -31,7 +31,7 @@ SYMBOLS = [
     "mad_match_topk", "mad_match_topk_many", "mad_match_topk_many_begin", "mad_match_topk_many_finish", "mad_match_topk_many_begin2", "mad_match_topk_many2", "mad_set_batching", "mad_set_option", "mad_last_pose_kernel", "mad_last_pose_selected", "mad_device_allocations", "mad_match_fetch", "mad_match_results", "mad_match_used",
     "mad_match_shard_pairs", "mad_match_shard_topk", "mad_match_shard_begin", "mad_match_shard_score", "mad_match_shard_record_doubles", "mad_match_shard_collect", "mad_match_shard_wait",
     "mad_set_wire_bytes", "mad_set_export", "mad_set_import", "mad_set_lane", "mad_set_stream", "mad_set_bind_lane",
-    "mad_upload_density", "mad_refine", "mad_structure_to_density", "mad_ccc", "mad_density_ccc", "mad_dock_refine_score", "mad_grid_overlap", "mad_overlap_matrix",
+    "mad_upload_density", "mad_refine", "mad_last_refine_plan", "mad_last_density_chunks", "mad_structure_to_density", "mad_ccc", "mad_density_ccc", "mad_dock_refine_score", "mad_grid_overlap", "mad_overlap_matrix",
     "mad_space_create", "mad_space_destroy", "mad_space_build", "mad_space_info", "mad_space_download",
     "mad_space_peaks", "mad_space_patches", "mad_space_localize", "mad_localize_volume",
     "mad_pose_cluster_many",
@@ -811,6 +811,17 @@ class Lib(object):
         if single:
             return c[0], bool(conv[0]), int(last[0])
         return c, conv.astype(bool), last
+
+    def last_refine_plan(self):
+        """(G, in_registers) of the most recent refinement (mad_last_refine_plan): workgroups per candidate, and whether the atoms
+        stayed in registers (k_refine<8>) or were walked in global memory (k_refine<0>); (-1, -1) before the first."""
+        g, reg = C.c_int(-1), C.c_int(-1)
+        self._chk(self.dll.mad_last_refine_plan(self.ctx, C.byref(g), C.byref(reg)))
+        return g.value, reg.value
+
+    def last_density_chunks(self):
+        """Chunks the most recent density simulation cut its batch into (mad_last_density_chunks); -1 before the first."""
+        return int(self.dll.mad_last_density_chunks(self.ctx))
 
     def structure_to_density(self, atoms, mass, resolution, voxsp, isovalue=0.0, pad=0):
         atoms, mass = _c(atoms, np.float64), _c(mass, np.float64)

@@ -240,6 +240,8 @@ struct mad_ctx {
     bool shard_busy[MAD_LANES][MAD_SHARD_RING] = {};
     int shard_next[MAD_LANES] = {};
     int last_pose_kernel = -1;               // 0 k_pose_lds, 1 k_pose_lds32, 2 k_pose (mad_last_pose_kernel)
+    int last_refine_G = -1, last_refine_reg = -1;      // workgroups per candidate and kernel form (1 k_refine<8>, 0 k_refine<0>) of the last refine_device (mad_last_refine_plan)
+    int last_density_chunks = -1;            // chunks the last density_batch cut its jobs into (mad_last_density_chunks)
     int64_t lane_sel_hint[MAD_LANES] = {};   // pairs the last pruned match of a lane sent to the exact search (sizes the next launch)
     void *many[MAD_BRACKETS] = {};           // open mad_match_topk_many_begin brackets (ManyState, mad_match.hip), by result slot: a ring
     int many_oldest = 0, many_open = 0;      // the slot _finish collects next, and how many are open

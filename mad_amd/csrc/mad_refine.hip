@@ -2,11 +2,11 @@
 // cross-correlation (a16) for gfx950.  Reference: mad/structure_utils.py:58-161,
 // mad/PDB.py:131-292, mad/Dmap.py:153-258.
 //
-//  refine  : the <= 500 steps are sequentially dependent, so each candidate runs in ONE
-//            persistent 1024-thread workgroup that keeps the rigid transform in LDS and
-//            walks the steps without returning to the host; parallelism is over atoms
-//            (trilinear gather of the np.gradient texels) and over candidates (one
-//            workgroup each).  Reductions use a fixed tree, so results are reproducible.
+//  refine  : the <= 500 steps are sequentially dependent, so each candidate runs in G
+//            persistent workgroups (1 to 8, refine_device) that keep the rigid transform in
+//            LDS and walk the steps without returning to the host; parallelism is over atoms
+//            (trilinear gather of the np.gradient texels) and over candidates.  Reductions
+//            use a fixed tree, so results are reproducible for a given G.
 //  density : float64 atomic splat, three separable float64 blur passes (the reference's
 //            Gaussian is a product of 1-D Gaussians), float32 normalise + threshold.
 //  ccc     : three float64 dot products over the overlap box.
@@ -386,6 +386,7 @@ static int refine_device(mad_ctx *ctx, int n_cand, int64_t n_atoms, int n_steps,
     // global memory, with their two scratch copies
     static const bool no_reg = getenv("MAD_REFINE_NO_REG") != nullptr;      // diagnostic switch
     const bool reg = !no_reg && mad_ceil_div(n_atoms, (int64_t)G * RF_THREADS_REG) <= RF_MAXA;
+    ctx->last_refine_G = G; ctx->last_refine_reg = reg ? 1 : 0;
     if (!reg) {
         MAD_TRY(mad_reserve(ctx, mad_sb(ctx, S_TMP_F), bytes));
         MAD_TRY(mad_reserve(ctx, mad_sb(ctx, S_TMP_H), bytes));
@@ -421,6 +422,13 @@ extern "C" int mad_refine(mad_ctx *ctx, double *coords, int n_cand, int64_t n_at
     MAD_HIP(hipMemcpyAsync(converged, d_conv, (size_t)n_cand * 4, hipMemcpyDeviceToHost, ctx->stream));
     MAD_HIP(hipMemcpyAsync(last_step, d_last, (size_t)n_cand * 4, hipMemcpyDeviceToHost, ctx->stream));
     MAD_HIP(hipStreamSynchronize(ctx->stream));
+    return MAD_OK;
+}
+
+extern "C" int mad_last_refine_plan(mad_ctx *ctx, int *G, int *in_registers) {
+    if (!ctx) return MAD_EINVAL;
+    if (G) *G = ctx->last_refine_G;
+    if (in_registers) *in_registers = ctx->last_refine_reg;
     return MAD_OK;
 }
 
@@ -695,7 +703,9 @@ static int density_batch(mad_ctx *ctx, const std::vector<DensityPlan> &plans, co
     const size_t chunk_cap = (size_t)512 << 20;
     if (empty) empty->assign(n_jobs, 0);
     std::vector<DJob> jobs(n_jobs);
+    ctx->last_density_chunks = 0;
     for (int j0 = 0; j0 < n_jobs;) {
+        ctx->last_density_chunks++;
         size_t tot = 0, n_max = 0, np_max = 0, no_max = 0;
         int j1 = j0;
         while (j1 < n_jobs) {
@@ -773,6 +783,8 @@ static int density_batch(mad_ctx *ctx, const std::vector<DensityPlan> &plans, co
     }
     return MAD_OK;
 }
+
+extern "C" int mad_last_density_chunks(mad_ctx *ctx) { return ctx ? ctx->last_density_chunks : -1; }
 
 extern "C" int mad_structure_to_density(mad_ctx *ctx, const double *atoms, const double *mass, int64_t n, double resolution,
                                         double voxsp, double isovalue, int pad, int32_t dims[3], double origin[3], float *grid) {

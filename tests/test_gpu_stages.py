@@ -406,6 +406,7 @@ def test_refine_split_over_workgroups(lib):
     lib.upload_density(grid, origin, 1.5)
     for n_steps in (3, 500):
         got, conv, last = lib.refine(starts, n_steps=n_steps, max_step=1.0, min_step=0.1)
+        assert lib.last_refine_plan() == (4, 1)      # four workgroups per candidate, atoms in registers: the plan this case is meant for
         for i in range(len(starts)):
             ref, rconv, rlast, _ = O.refine(grid, origin, 1.5, starts[i], n_steps=n_steps, max_step=1.0, min_step=0.1)
             assert (bool(conv[i]), int(last[i])) == (rconv, rlast)
