@@ -42,6 +42,12 @@ extern "C" {
 #define MAD_MAX_Z      128 /* zones per EQSP table */
 #define MAD_MAX_FIELDS 64  /* gradient-field slots per ctx */
 #define MAD_POSE_CLUSTER_MAX_N 4096 /* rows of one match in mad_pose_cluster_many (a d2 triangle of 64 MiB) */
+#define MAD_RANK_MAX_N 96    /* rows of the overlap table in mad_rank_copies / mad_rank_models (LDS: DESIGN.md section 4f) */
+#define MAD_RANK_MAX_K 16    /* copies of a subunit / groups of a model, at most */
+#define MAD_RANK_MAX_TOP 512 /* entries a MAD_RANK_TOP call may ask for (the workgroups' lists in LDS) */
+#define MAD_RANK_MAX_OUT 4096 /* entries a MAD_RANK_BELOW call, or the band of mad_rank_models, may return */
+#define MAD_RANK_TOP 0
+#define MAD_RANK_BELOW 1
 #define MAD_RESULT_COLS 23 /* row width of MaD._match_dsc results, MaD.py:451 */
 
 typedef struct mad_ctx mad_ctx;
@@ -603,6 +609,46 @@ int mad_localize_volume(mad_ctx *ctx, const void *vol, int is_f64, int nx, int n
 int mad_pose_cluster_many(mad_ctx *ctx, int n_match, const double *const *rows, const int32_t *n_rows,
                           const double *const *cloud, const int32_t *n_cloud, double rmsd_thresh, int32_t *const *owner_out,
                           double *const *d2min_out, int32_t *n_done_out, int32_t *status_out);
+
+/* ---------------------------------------------------------------------------
+ * Assembly ranking: the HEAD of the two sorted lists MaD.build_assembly searches, by ordered enumeration with prefix
+ * pruning on the device.  overlap is the n x n float64 table of mad_overlap_matrix (host).
+ *
+ * mad_rank_copies serves mad/MaD.py:684-694: every n_copies-subset of the n solutions of one subunit, keyed by the
+ * maximum of overlap[a, b] over its pairs a < b, in the order of the reference's stable sort (maximum ascending, then
+ * itertools.combinations order).  A maximum is exact, so the result is that order bit for bit.
+ *   mode MAD_RANK_TOP    the first min(cap, C(n, n_copies)) entries (at most MAD_RANK_MAX_TOP, else MAD_EDOM)
+ *   mode MAD_RANK_BELOW  every entry with maximum <= max_overlap, *n_total of them; more than min(cap, MAD_RANK_MAX_OUT):
+ *                        MAD_ENOSPC with *n_total = the count
+ *   idx_out  int32 [cap][n_copies]   key_out  float64 [cap]: the maximum   rank_out  int64 [cap]: position in combinations order
+ *   (key_out is +0 for a maximum of -0: the table is read as overlap + 0.0, which changes no comparison)
+ *
+ * mad_rank_models serves mad/MaD.py:797-807: one row out of each of n_groups contiguous groups (group l = rows
+ * group_first[l] .. group_first[l + 1] - 1, group_first[0] = 0, group_first[n_groups] = n), keyed by the sum of the FULL
+ * k x k block overlap[pick][:, pick] (no triangular table assumed), in itertools.product order on ties.  The sum is a rounded
+ * one, so the device returns a SUPERSET: with T the cap-th smallest device sum by (sum, rank), every pick whose device sum is
+ * <= T (1 + 8 k^2 2^-53), in (device sum, rank) order; the reference's first cap entries are among them (derivation: DESIGN.md
+ * section 4f) and the caller decides with numpy's own sum.  T = 0 returns exactly cap entries (a sum of 0 has only zero terms).
+ *   cap <= MAD_RANK_MAX_TOP (after min with the size of the product), cap <= out_cap; more than min(out_cap, MAD_RANK_MAX_OUT)
+ *   candidates: MAD_ENOSPC with *n_total = the count
+ *   idx_out  int32 [out_cap][n_groups]: rows   key_out  float64 [out_cap]: device sums   rank_out  int64 [out_cap]
+ *
+ * Both: launch_items = ranks covered by one kernel launch (<= 0: the default), budget = items a call may evaluate (<= 0: the
+ * default); past it, with ranks still to visit, *status = 1, *n_out = 0 and the call returns MAD_OK (no partial result); *status = 0 otherwise.
+ * MAD_EDOM (the caller runs the host loop): an entry that is negative or not finite, a NaN max_overlap, n > MAD_RANK_MAX_N,
+ * n_copies outside 2 .. min(n, MAD_RANK_MAX_K), n_groups outside 1 .. MAD_RANK_MAX_K, groups that do not tile 0 .. n, a
+ * space beyond int64.  MAD_RANK_NO_PRUNE=1 in the environment (read per call) turns the prefix jumps off; the result does not
+ * depend on it.  Host pointers, synchronous, lane 0; two calls return the same bits.
+ */
+int mad_rank_copies(mad_ctx *ctx, const double *overlap, int n, int n_copies, int mode, double max_overlap, int64_t cap,
+                    int64_t launch_items, int64_t budget, int32_t *idx_out, double *key_out, int64_t *rank_out,
+                    int64_t *n_out, int64_t *n_total, int32_t *status);
+int mad_rank_models(mad_ctx *ctx, const double *overlap, int n, const int32_t *group_first, int n_groups, int64_t cap,
+                    int64_t out_cap, int64_t launch_items, int64_t budget, int32_t *idx_out, double *key_out,
+                    int64_t *rank_out, int64_t *n_out, int64_t *n_total, int32_t *status);
+/* The last mad_rank_* call: kernel launches over rank ranges, items whose key was evaluated, items jumped over by prefix
+ * pruning, and whether the band of mad_rank_models held more than cap candidates. */
+int mad_last_rank_plan(mad_ctx *ctx, int64_t *launches, int64_t *evaluated, int64_t *skipped, int32_t *band_extra);
 
 #ifdef __cplusplus
 }

@@ -13,6 +13,8 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 # MAD_LIB_PATH: another build of the same library (diagnostic builds with other compiler flags; tools/build_variant.sh)
 LIB_PATH = os.environ.get("MAD_LIB_PATH") or os.path.join(_HERE, "libmad_amd.so")
 RESULT_COLS = 23
+RANK_MAX_N, RANK_MAX_K, RANK_MAX_TOP, RANK_MAX_OUT = 96, 16, 512, 4096      # MAD_RANK_* of include/mad_amd.h
+RANK_TOP, RANK_BELOW = 0, 1
 POSE_CLUSTER_MAX_N = 4096      # MAD_POSE_CLUSTER_MAX_N of include/mad_amd.h: rows of one match in pose_cluster_many
 # wide sets (include/mad_amd.h; MAD_WIDE_* of csrc/mad_common.h): from this descriptor radius on a set's int8 rows hold count - WIDE_C
 WIDE_FROM_R = 11
@@ -35,6 +37,7 @@ SYMBOLS = [
     "mad_space_create", "mad_space_destroy", "mad_space_build", "mad_space_info", "mad_space_download",
     "mad_space_peaks", "mad_space_patches", "mad_space_localize", "mad_localize_volume",
     "mad_pose_cluster_many",
+    "mad_rank_copies", "mad_rank_models", "mad_last_rank_plan",
 ]
 
 
@@ -790,6 +793,75 @@ class Lib(object):
         self._chk(self.dll.mad_pose_cluster_many(self.ctx, C.c_int(nm), ptrs[0], _p(n_rows), ptrs[1], _p(n_cloud), C.c_double(float(rmsd_thresh)),
                                                  ptrs[2], ptrs[3], _p(n_done), _p(status)))
         return [(owner[m], d2min[m], int(n_done[m]), int(status[m])) for m in range(nm)]
+
+    # -- assembly ranking ------------------------------------------------------------------
+    def _rank_result(self, rc, width, idx, key, rank, n_out, n_total, status):
+        """(status, entries, n_total) of a mad_rank_* call: status "ok" with entries = (idx [m][width], key [m], rank [m]), or
+        "edom" / "enospc" / "budget" with entries None -- the three answers after which the caller runs the host loop."""
+        if rc == -33:
+            return "edom", None, 0
+        if rc == -28:
+            return "enospc", None, int(n_total.value)
+        self._chk(rc)
+        if status.value:
+            return "budget", None, 0
+        m = int(n_out.value)
+        return "ok", (idx[:m * width].reshape(m, width).copy(), key[:m].copy(), rank[:m].copy()), int(n_total.value)
+
+    def rank_copies(self, overlap, n_copies, cap, max_overlap=None, launch_items=0, budget=0):
+        """The head of assembly.rank_copies(overlap, n_copies) (mad_rank_copies).  max_overlap None: the first `cap` entries (TOP);
+        else every entry whose maximum is <= max_overlap, up to `cap` of them (BELOW).  launch_items: ranks per kernel launch
+        (0: the default), budget: items the call may evaluate (0: the default).  Returns (status, (idx, max, rank), n_total), see
+        _rank_result; last_error() has the reason of an "edom"."""
+        t = _c(overlap, np.float64)
+        if t.ndim != 2 or t.shape[0] != t.shape[1]:
+            raise ValueError("rank_copies: overlap has shape %s" % (t.shape,))
+        n, c, cap = len(t), int(n_copies), max(int(cap), 0)
+        room = max(min(cap, RANK_MAX_OUT), 1)
+        idx, key, rank = np.zeros(room * max(c, 1), np.int32), np.zeros(room, np.float64), np.zeros(room, np.int64)
+        n_out, n_total, status = C.c_int64(0), C.c_int64(0), C.c_int32(0)
+        mode = RANK_TOP if max_overlap is None else RANK_BELOW
+        rc = self.dll.mad_rank_copies(self.ctx, _p(t), C.c_int(n), C.c_int(c), C.c_int(mode), C.c_double(0.0 if max_overlap is None else float(max_overlap)),
+                                      C.c_int64(min(cap, room)), C.c_int64(int(launch_items)), C.c_int64(int(budget)), _p(idx), _p(key), _p(rank),
+                                      C.byref(n_out), C.byref(n_total), C.byref(status))
+        return self._rank_result(rc, c, idx, key, rank, n_out, n_total, status)
+
+    def rank_models(self, overlap, groups, cap, out_cap=None, launch_items=0, budget=0):
+        """Candidates for the head of assembly.rank_models(overlap, groups) (mad_rank_models): every pick whose device sum lies
+        within the band of the cap-th smallest, in (device sum, rank) order -- a superset of the reference's first `cap` entries.
+        groups: lists of consecutive rows, together 0 .. n - 1 (what build_models makes); anything else is an "edom".
+        Returns (status, (picks, device sums, ranks), n_total)."""
+        t = _c(overlap, np.float64)
+        if t.ndim != 2 or t.shape[0] != t.shape[1]:
+            raise ValueError("rank_models: overlap has shape %s" % (t.shape,))
+        n, g, cap = len(t), len(groups), max(int(cap), 0)
+        first, at = [0], 0
+        for grp in groups:
+            if list(grp) != list(range(at, at + len(grp))):
+                return "edom", None, 0
+            at += len(grp)
+            first.append(at)
+        out_cap = RANK_MAX_OUT if out_cap is None else max(int(out_cap), cap)
+        room = max(min(out_cap, RANK_MAX_OUT), 1)
+        idx, key, rank = np.zeros(room * max(g, 1), np.int32), np.zeros(room, np.float64), np.zeros(room, np.int64)
+        n_out, n_total, status = C.c_int64(0), C.c_int64(0), C.c_int32(0)
+        first = np.array(first, np.int32)
+        rc = self.dll.mad_rank_models(self.ctx, _p(t), C.c_int(n), _p(first), C.c_int(g), C.c_int64(min(cap, room)), C.c_int64(room),
+                                      C.c_int64(int(launch_items)), C.c_int64(int(budget)), _p(idx), _p(key), _p(rank),
+                                      C.byref(n_out), C.byref(n_total), C.byref(status))
+        return self._rank_result(rc, g, idx, key, rank, n_out, n_total, status)
+
+    def last_rank_plan(self):
+        """(launches, evaluated, skipped, band_extra) of the most recent rank_copies / rank_models (mad_last_rank_plan): kernel
+        launches over rank ranges, items whose key was formed, items jumped over by prefix pruning, and whether the band of
+        rank_models held more than `cap` candidates."""
+        a, b, c, d = C.c_int64(0), C.c_int64(0), C.c_int64(0), C.c_int32(0)
+        self._chk(self.dll.mad_last_rank_plan(self.ctx, C.byref(a), C.byref(b), C.byref(c), C.byref(d)))
+        return a.value, b.value, c.value, bool(d.value)
+
+    def last_error(self):
+        msg = self.dll.mad_last_error(self.ctx)
+        return msg.decode() if msg else ""
 
     # -- refinement / density / ccc --------------------------------------------------------
     def upload_density(self, grid, origin, voxsp):

@@ -6,8 +6,10 @@ each ranked by the pairwise occupancy overlap of low-resolution densities (resol
 MaD.py:669,760) and the final models scored by their CCC with the map.
 
 The numerical part -- n density simulations and the n x n overlap table -- is ONE device call (`mad_overlap_matrix`:
-the grids never leave HBM); the CCC of each model is `mad_density_ccc`.  The combinatorics are small host logic, kept
-here as pure functions of the overlap table so that they can be checked without a GPU.
+the grids never leave HBM); the CCC of each model is `mad_density_ccc`.  The combinatorics are DEFINED by the pure host
+functions `rank_copies` / `rank_models` below, which can be checked without a GPU; `build_assembly` reads only a short head
+of either list and gets it from the device (`rank_copies_head` / `rank_models_head`: `mad_rank_copies` / `mad_rank_models`,
+ordered enumeration with prefix pruning), rebuilt entry by entry with the numpy expressions of the definition.
 """
 import csv
 import os
@@ -61,6 +63,77 @@ def select_models(ranked, max_models, max_overlap):
             break
         keep.append(cand)
     return keep
+
+
+# ---------------------------------------------------------------------------- heads of the two lists, from the device
+RANK_U = 2.0 ** -53
+
+
+def rank_band(s, k):
+    """How far above the cap-th smallest DEVICE sum s a device sum may lie while its pick can still belong to the first `cap`
+    entries of rank_models: 8 k^2 u s.  Any two float64 sums of the same k x k block of non-negative
+    terms, in whatever order, differ by at most a quarter of it."""
+    return 8.0 * k * k * RANK_U * s
+
+
+def _host_reason(status, lib):
+    return {"edom": "outside the device's range: %s" % lib.last_error(), "enospc": "more candidates than the device returns",
+            "budget": "the device's work budget ran out"}[status]
+
+
+def _use_host():
+    return os.environ.get("MAD_ASSEMBLY_HOST", "0") == "1"
+
+
+def rank_copies_head(overlap, n_copies, cap=None, max_overlap=None, lib=None):
+    """A prefix of rank_copies(overlap, n_copies), element for element and bit for bit: its first `cap` entries
+    (max_overlap None), or every entry whose maximum is <= max_overlap.  The order comes from the device (mad_rank_copies:
+    maximum ascending, then combinations order -- a maximum is exact), the statistics of each returned subset from the
+    expressions of rank_copies.  One copy, empty inputs, MAD_ASSEMBLY_HOST=1 and whatever the device declines (a NaN or
+    negative overlap, more entries than it returns, an exhausted work budget: one printed line) take the host loop."""
+    overlap = np.asarray(overlap)
+    n_sol = len(overlap)
+    if not (n_copies == 1 or n_sol == 0 or n_copies > n_sol or _use_host() or (cap is None and max_overlap is None)):
+        lib = lib if lib is not None else _lib.get_lib()
+        room = _lib.RANK_MAX_OUT if cap is None else cap
+        status, got, _ = lib.rank_copies(overlap, n_copies, room, max_overlap)
+        if status == "ok":
+            out = []
+            for row in got[0]:
+                subset = tuple(int(x) for x in row)
+                vals = [overlap[a, b] for a, b in combinations(subset, 2)]
+                out.append([subset, np.sum(vals) / n_copies, np.std(vals), np.max(vals)])
+            return out
+        print("MaD> Ranking the sub-complexes on the host (%s)" % _host_reason(status, lib))
+    ranked = rank_copies(overlap, n_copies)
+    if max_overlap is not None:
+        keep = 0
+        for i, cand in enumerate(ranked):      # (a prefix unless an overlap is NaN: then up to the last entry the writer takes)
+            if not cand[3] > max_overlap:
+                keep = i + 1
+        ranked = ranked[:keep]
+    return ranked if cap is None else ranked[:max(cap, 0)]
+
+
+def rank_models_head(overlap, groups, cap, lib=None):
+    """The first `cap` entries of rank_models(overlap, groups), element for element and bit for bit.  The device returns a
+    conservative superset (mad_rank_models: every pick whose device sum lies within rank_band of the cap-th smallest); the
+    entries are rebuilt with the expressions of rank_models and ordered by (numpy sum, product order), which is its stable sort."""
+    overlap = np.asarray(overlap)
+    groups = [list(g) for g in groups]
+    if groups and all(groups) and not _use_host():
+        lib = lib if lib is not None else _lib.get_lib()
+        status, got, _ = lib.rank_models(overlap, groups, cap)
+        if status == "ok":
+            out = []
+            for row, rank in zip(got[0], got[2]):
+                pick = np.array(tuple(int(x) for x in row))
+                block = overlap[np.ix_(pick, pick)].T.ravel()
+                out.append((int(rank), [pick, np.sum(block), np.std(block), np.max(block)]))
+            out.sort(key=lambda e: (e[1][1], e[0]))
+            return [e[1] for e in out[:max(cap, 0)]]
+        print("MaD> Ranking the assembly models on the host (%s)" % _host_reason(status, lib))
+    return rank_models(overlap, groups)[:max(cap, 0)]
 
 
 def format_overlap_table(overlap, labels, wide=False):
@@ -165,10 +238,11 @@ def build_from_single(mad, sub_key, homomultimer=False):
             print(row)
         print()
         print("MaD> Assembling %i copies of chain %s from %i solutions..." % (n_copies, sub_key, len(solutions)))
-    ranked = rank_copies(overlap, n_copies)
     if homomultimer:
+        ranked = rank_copies_head(overlap, n_copies, cap=mad.max_models)      # select_models reads no further
         # the reference tests the literal 0.1 here, not max_overlap_complex (MaD.py:727)
         return _score_and_report(mad, ranked, solutions, out_dir, 0.1)
+    ranked = rank_copies_head(overlap, n_copies, max_overlap=mad.max_overlap_complex)      # a prefix: s_idx is the position in the full list
     written = []
     for s_idx, (idx, _, _, s_max) in enumerate(ranked):
         if s_max > mad.max_overlap_complex:
@@ -197,7 +271,7 @@ def build_models(mad, sub_sol_dict):
     for row in format_overlap_table(overlap, labels, wide=True):
         print(row)
     print()
-    ranked = rank_models(overlap, groups)
+    ranked = rank_models_head(overlap, groups, mad.max_models)
     out_dir = os.path.join(mad.out_folder, "assembly_models")
     os.makedirs(out_dir, exist_ok=True)
     return _score_and_report(mad, ranked, files, out_dir, mad.max_overlap_complex)

@@ -241,6 +241,8 @@ struct mad_ctx {
     int shard_next[MAD_LANES] = {};
     int last_pose_kernel = -1;               // 0 k_pose_lds, 1 k_pose_lds32, 2 k_pose (mad_last_pose_kernel)
     int last_refine_G = -1, last_refine_reg = -1;      // workgroups per candidate and kernel form (1 k_refine<8>, 0 k_refine<0>) of the last refine_device (mad_last_refine_plan)
+    int64_t last_rank_launches = 0, last_rank_evaluated = 0, last_rank_skipped = 0;      // the last mad_rank_* call (mad_last_rank_plan)
+    int last_rank_band_extra = 0;
     int last_density_chunks = -1;            // chunks the last density_batch cut its jobs into (mad_last_density_chunks)
     int64_t lane_sel_hint[MAD_LANES] = {};   // pairs the last pruned match of a lane sent to the exact search (sizes the next launch)
     void *many[MAD_BRACKETS] = {};           // open mad_match_topk_many_begin brackets (ManyState, mad_match.hip), by result slot: a ring
@@ -337,6 +339,7 @@ enum {
     S_TIE_FLAG, S_TIE_OFF, S_SEL_OUT, S_TMP_H, S_TMP_I, S_TMP_J,
     S_CELL_START, S_CELL_PTS, S_CELL_IDS, S_PG_START, S_PG_PTS, S_PG_PTSF, S_ZERO, S_CMASK, S_PG_BITS, S_PG_PAIRS, S_PERM_OFF, S_CFLAG,
     S_FILT_IN, S_FILT_D2, S_FILT_OUT,      // mad_pose_cluster_many: rows + clouds, the d2 triangles, owner / d2min / status
+    S_RANK,                                // mad_rank_copies / mad_rank_models: control words, tables, the workgroups' lists, the output
     S_N_SLOTS
 };
 static_assert(S_N_SLOTS <= 64, "grow mad_ctx::scratch");
