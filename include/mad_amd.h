@@ -372,8 +372,9 @@ int mad_ccc(mad_ctx *ctx, float *grid1, const int32_t dims1[3], const double ori
             float *grid2, const int32_t dims2[3], const double origin2[3],
             double voxsp, double isovalue, double *ccc);
 
-/* ---- one subunit's pair grid sharded over GPUs by blocks of map rows (the exchange steps are the caller's:
- *      OR of the flag vectors, all-gather of the per-shard top-k; mad_amd/dist.py::sharded_match) -------------- */
+/* ---- one subunit's pair grid sharded over GPUs by blocks of map rows (the exchange steps -- OR of the flag vectors,
+ *      all-gather of the per-shard top-k -- are the caller's, mad_amd/dist.py::sharded_match, or the library's own:
+ *      mad_dist_or_allreduce / mad_dist_allgather_topk below) ------------------------------------------------- */
 
 /*
  * Stage B of a sharded match: correlate hi against the lo rows [lo_begin, lo_end) (MaD.py:416-424 on that block of
@@ -418,6 +419,74 @@ int mad_match_shard_score(mad_ctx *ctx, const mad_set *hi, const mad_set *lo, co
  */
 int mad_match_shard_collect(mad_ctx *ctx, const mad_set *hi, const double *d_all, int64_t n, int *ticket);
 int mad_match_shard_wait(mad_ctx *ctx, int ticket, double *out, int64_t n);
+/*
+ * The merge of a group's records on the device (k_shard_merge; the order of mad_amd/dist.py::merge_topk): d_all holds nranks
+ * records of mad_match_shard_record_doubles(k) float64 back to back, d_merged (another buffer) receives ONE record of the same
+ * layout, enqueued on the lane of `hi`:
+ *   - its first m = min(k, sum of the shards' m) entries are the shards' entries in the stable order of MaD.py:480 -- count
+ *     descending, global pair rank ascending -- rows copied bit for bit, the rest of the record zero;
+ *   - flags = the OR of the shards' flags; m = 0 when that is non-zero (the whole group repeats the match synchronously);
+ *   - |hi cloud| is the first record's, pairs the sum of the shards'.
+ *   - flag 32 (beside 1 / 2 / 4 / 8 / 16 above): the records do not belong together or are malformed -- they disagree on
+ *     |hi cloud|, or an m lies outside 0 .. k, a count outside 0 .. 2^24 - 1, a pair rank outside 0 .. 2^40 - 1 (the sort key
+ *     is (max count - count) << 40 | pair rank; the ranks live in device memory, so it is the kernel that checks them).
+ * One workgroup sorts nranks x k keys in LDS: nranks x k > MAD_SHARD_MERGE_MAX is MAD_EDOM (merge on the host then).
+ */
+#define MAD_SHARD_MERGE_MAX 8192
+#define MAD_SHARD_FLAG_MISMATCH 32
+int mad_match_shard_merge(mad_ctx *ctx, const mad_set *hi, const double *d_all, int nranks, int64_t k, double *d_merged);
+
+/* ---- the exchanges between the GPUs of a sharded step, inside the library (mad_dist.hip) -------------------------------
+ *      One communicator per ctx.  RCCL is resolved at run time (dlopen of librccl.so.1, then librccl.so, and dlsym of the six
+ *      entry points used) by mad_dist_unique_id / mad_dist_init and by nothing else: libmad_amd.so does not depend on it, a
+ *      process that never calls these never loads it, and a process that has it mapped already (one that imported torch) keeps
+ *      that one copy.  When it cannot be loaded the call returns MAD_ENODEV and the message names what was tried; an RCCL error
+ *      is MAD_EHIP with ncclGetErrorString in mad_last_error.  Every collective is enqueue-only: none blocks the host.
+ *      The RCCL branch has run at world size 1 only; more than one rank on hardware is unmeasured. ------------------------ */
+
+#define MAD_DIST_ID_BYTES 128      /* sizeof(ncclUniqueId) */
+/* Rank 0 takes an id and hands it to the other ranks by whatever means the caller has (a file, MPI, a socket). */
+int mad_dist_unique_id(mad_ctx *ctx, void *id128);
+/*
+ * Creates the communicator of rank `rank` of `nranks` (collective over the ranks when id128 != NULL).  id128 == NULL: a
+ * REHEARSAL communicator -- one rank of nranks alone on its GPU, RCCL not loaded: the OR-reduce is the identity (or adds the
+ * peers' flags registered with mad_dist_rehearse_flags), the all-gathers copy this rank's block into slot `rank` of the
+ * receive buffer and leave every other slot as the caller filled it.  What a rehearsal reports is a per-rank cost without
+ * link traffic, never a multi-GPU measurement.  A second mad_dist_init without mad_dist_destroy in between: MAD_EINVAL.
+ */
+int mad_dist_init(mad_ctx *ctx, int nranks, int rank, const void *id128);
+int mad_dist_destroy(mad_ctx *ctx);      /* mad_destroy calls it; without a communicator it does nothing */
+int mad_dist_info(mad_ctx *ctx, int *nranks, int *rank, int *rehearsal);      /* MAD_EINVAL without a communicator */
+/* Rehearsal only: d_peer_or (n bytes 0 / 1 in device memory, NULL to forget them) is what the absent ranks would contribute
+ * to every later mad_dist_or_allreduce of n flags; the buffer stays the caller's and must outlive those calls. */
+int mad_dist_rehearse_flags(mad_ctx *ctx, const uint8_t *d_peer_or, int64_t n);
+/* In place on n bytes 0 / 1 in device memory, on `stream` (a stream of the library: mad_set_stream, mad_stream): ncclMax on
+ * uint8 -- RCCL has no bitwise-OR reduction. */
+int mad_dist_or_allreduce(mad_ctx *ctx, void *stream, uint8_t *d_flags, int64_t n);
+/* d_recv: nranks x bytes_per_rank, rank r's block at r * bytes_per_rank (the wire images of mad_set_export for mad_set_import). */
+int mad_dist_allgather(mad_ctx *ctx, void *stream, const void *d_send, void *d_recv, int64_t bytes_per_rank);
+/*
+ * Exchange 2 of a sharded match on the lane of `hi`: the all-gather of the shards' records (d_mine: this rank's, what
+ * mad_match_shard_score wrote; d_all: nranks records) and then mad_match_shard_merge into d_merged -- one record, ready for
+ * mad_match_shard_collect.  nranks x k > MAD_SHARD_MERGE_MAX: MAD_EDOM, nothing enqueued (gather with mad_dist_allgather and
+ * merge on the host).
+ */
+int mad_dist_allgather_topk(mad_ctx *ctx, const mad_set *hi, const double *d_mine, double *d_all, int64_t k, double *d_merged);
+/*
+ * Device memory for the buffers of these calls, for callers that have no allocator of their own on the device: buffer `which`
+ * of lane `lane`, at least `bytes` long, grow-only and counted by mad_device_allocations (a steady state shows none).  A
+ * buffer that grows is a NEW buffer: ask again for the address before every use, and not while work that uses it is in flight.
+ * mad_dist_copy moves bytes between host memory and such a buffer, synchronously (kind 0: host to device, 1: device to host);
+ * it waits for the device first.  For set-up, rehearsals and tests, not for the steady state.
+ */
+#define MAD_DIST_BUF_FLAGS  0
+#define MAD_DIST_BUF_MINE   1
+#define MAD_DIST_BUF_ALL    2
+#define MAD_DIST_BUF_MERGED 3
+#define MAD_DIST_BUF_WIRE   4
+#define MAD_DIST_BUF_GATHER 5
+int mad_dist_scratch(mad_ctx *ctx, int lane, int which, int64_t bytes, void **d_out);
+int mad_dist_copy(mad_ctx *ctx, void *dst, const void *src, int64_t bytes, int kind);
 
 /* ---- one structure's rows built in shares on several GPUs (stage A).  Orientation and description
  *      are independent per anchor (Orientator.py:80-108, Descriptor.py:106-116): anchor a of the structure's list goes

@@ -15,6 +15,10 @@ LIB_PATH = os.environ.get("MAD_LIB_PATH") or os.path.join(_HERE, "libmad_amd.so"
 RESULT_COLS = 23
 RANK_MAX_N, RANK_MAX_K, RANK_MAX_TOP, RANK_MAX_OUT = 96, 16, 512, 4096      # MAD_RANK_* of include/mad_amd.h
 RANK_TOP, RANK_BELOW = 0, 1
+SHARD_MERGE_MAX = 8192      # MAD_SHARD_MERGE_MAX: records x k one workgroup of k_shard_merge sorts
+SHARD_FLAG_MISMATCH = 32    # MAD_SHARD_FLAG_MISMATCH
+DIST_ID_BYTES = 128         # MAD_DIST_ID_BYTES
+DIST_BUF_FLAGS, DIST_BUF_MINE, DIST_BUF_ALL, DIST_BUF_MERGED, DIST_BUF_WIRE, DIST_BUF_GATHER = range(6)      # MAD_DIST_BUF_*
 POSE_CLUSTER_MAX_N = 4096      # MAD_POSE_CLUSTER_MAX_N of include/mad_amd.h: rows of one match in pose_cluster_many
 # wide sets (include/mad_amd.h; MAD_WIDE_* of csrc/mad_common.h): from this descriptor radius on a set's int8 rows hold count - WIDE_C
 WIDE_FROM_R = 11
@@ -31,7 +35,9 @@ SYMBOLS = [
     "mad_set_orient_window", "mad_orient", "mad_describe", "mad_describe_sized", "mad_correlate", "mad_pose_score", "mad_topk",
     "mad_set_create", "mad_set_destroy", "mad_set_build", "mad_set_build_many", "mad_set_load", "mad_set_mark_wide", "mad_set_is_wide", "mad_set_size", "mad_set_download",
     "mad_match_topk", "mad_match_topk_many", "mad_match_topk_many_begin", "mad_match_topk_many_finish", "mad_match_topk_many_begin2", "mad_match_topk_many2", "mad_set_batching", "mad_set_option", "mad_last_pose_kernel", "mad_last_pose_selected", "mad_device_allocations", "mad_match_fetch", "mad_match_results", "mad_match_used",
-    "mad_match_shard_pairs", "mad_match_shard_topk", "mad_match_shard_begin", "mad_match_shard_score", "mad_match_shard_record_doubles", "mad_match_shard_collect", "mad_match_shard_wait",
+    "mad_match_shard_pairs", "mad_match_shard_topk", "mad_match_shard_begin", "mad_match_shard_score", "mad_match_shard_record_doubles", "mad_match_shard_collect", "mad_match_shard_wait", "mad_match_shard_merge",
+    "mad_dist_unique_id", "mad_dist_init", "mad_dist_destroy", "mad_dist_info", "mad_dist_rehearse_flags", "mad_dist_or_allreduce", "mad_dist_allgather",
+    "mad_dist_allgather_topk", "mad_dist_scratch", "mad_dist_copy",
     "mad_set_wire_bytes", "mad_set_export", "mad_set_import", "mad_set_lane", "mad_set_stream", "mad_set_bind_lane",
     "mad_upload_density", "mad_refine", "mad_last_refine_plan", "mad_last_density_chunks", "mad_structure_to_density", "mad_ccc", "mad_density_ccc", "mad_dock_refine_score", "mad_grid_overlap", "mad_overlap_matrix",
     "mad_space_create", "mad_space_destroy", "mad_space_build", "mad_space_info", "mad_space_download",
@@ -707,7 +713,64 @@ class Lib(object):
         self._chk(self.dll.mad_match_shard_wait(self.ctx, C.c_int(int(ticket)), _p(out), C.c_int64(int(n))))
         return out
 
-    # -- a structure's rows built in shares (SURVEY.md 8(e) stage A; the all-gather itself is mad_amd/dist.py's) --------
+    def match_shard_merge(self, hi, all_ptr, nranks, k, merged_ptr):
+        """k_shard_merge on hi's lane: the `nranks` records at device address `all_ptr` -> one record at `merged_ptr` (the order of
+        dist.merge_topk).  nranks * k > SHARD_MERGE_MAX raises (EDOM)."""
+        self._chk(self.dll.mad_match_shard_merge(self.ctx, hi.h, C.c_void_p(int(all_ptr)), C.c_int(int(nranks)), C.c_int64(int(k)),
+                                                 C.c_void_p(int(merged_ptr))))
+
+    # -- the exchanges of a sharded step inside the library (mad_dist.hip; mad_amd/dist.py::LibComm drives them) ---------
+    def dist_unique_id(self):
+        """The 128 bytes rank 0 hands to every rank of the communicator (loads RCCL)."""
+        buf = C.create_string_buffer(DIST_ID_BYTES)
+        self._chk(self.dll.mad_dist_unique_id(self.ctx, buf))
+        return buf.raw
+
+    def dist_init(self, nranks, rank, unique_id=None):
+        """unique_id None: the rehearsal communicator (one rank of nranks alone on its GPU, RCCL not loaded)."""
+        if unique_id is not None and len(unique_id) != DIST_ID_BYTES:
+            raise ValueError("dist_init: a unique id has %d bytes" % DIST_ID_BYTES)
+        self._chk(self.dll.mad_dist_init(self.ctx, C.c_int(int(nranks)), C.c_int(int(rank)), C.c_char_p(unique_id) if unique_id is not None else None))
+
+    def dist_destroy(self):
+        self._chk(self.dll.mad_dist_destroy(self.ctx))
+
+    def dist_info(self):
+        """-> (nranks, rank, rehearsal)"""
+        n, r, e = C.c_int(0), C.c_int(0), C.c_int(0)
+        self._chk(self.dll.mad_dist_info(self.ctx, C.byref(n), C.byref(r), C.byref(e)))
+        return n.value, r.value, bool(e.value)
+
+    def dist_rehearse_flags(self, peer_ptr, n):
+        self._chk(self.dll.mad_dist_rehearse_flags(self.ctx, C.c_void_p(int(peer_ptr)) if peer_ptr else None, C.c_int64(int(n))))
+
+    def dist_or_allreduce(self, stream, flags_ptr, n):
+        self._chk(self.dll.mad_dist_or_allreduce(self.ctx, C.c_void_p(stream), C.c_void_p(int(flags_ptr)), C.c_int64(int(n))))
+
+    def dist_allgather(self, stream, send_ptr, recv_ptr, bytes_per_rank):
+        self._chk(self.dll.mad_dist_allgather(self.ctx, C.c_void_p(stream), C.c_void_p(int(send_ptr)), C.c_void_p(int(recv_ptr)), C.c_int64(int(bytes_per_rank))))
+
+    def dist_allgather_topk(self, hi, mine_ptr, all_ptr, k, merged_ptr):
+        self._chk(self.dll.mad_dist_allgather_topk(self.ctx, hi.h, C.c_void_p(int(mine_ptr)), C.c_void_p(int(all_ptr)), C.c_int64(int(k)),
+                                                   C.c_void_p(int(merged_ptr))))
+
+    def dist_scratch(self, lane, which, nbytes):
+        """Device address of the grow-only buffer `which` (DIST_BUF_*) of `lane`, at least nbytes long."""
+        p = C.c_void_p()
+        self._chk(self.dll.mad_dist_scratch(self.ctx, C.c_int(int(lane)), C.c_int(int(which)), C.c_int64(int(nbytes)), C.byref(p)))
+        return int(p.value)
+
+    def dist_upload(self, dev_ptr, array):
+        """Host array -> device memory at `dev_ptr`, synchronous (set-up, rehearsals, tests)."""
+        a = np.ascontiguousarray(array)
+        self._chk(self.dll.mad_dist_copy(self.ctx, C.c_void_p(int(dev_ptr)), _p(a), C.c_int64(a.nbytes), C.c_int(0)))
+
+    def dist_download(self, dev_ptr, n, dtype=np.float64):
+        out = np.zeros(int(n), dtype)
+        self._chk(self.dll.mad_dist_copy(self.ctx, _p(out), C.c_void_p(int(dev_ptr)), C.c_int64(out.nbytes), C.c_int(1)))
+        return out
+
+    # -- a structure's rows built in shares (SURVEY.md 8(e) stage A; the all-gather is mad_amd/dist.py's, or mad_dist_allgather) --------
     def set_wire_bytes(self, cap_rows, D=1024):
         n = int(self.dll.mad_set_wire_bytes(C.c_int(int(D)), C.c_int64(int(cap_rows))))
         if n < 0:

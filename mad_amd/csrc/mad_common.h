@@ -141,7 +141,8 @@ enum { MAD_T_ORIENT = 0, MAD_T_DESCRIBE, MAD_T_CORRELATE, MAD_T_PAIRS, MAD_T_POS
 #define MAD_LANES 8
 #define MAD_BRACKETS 3      // mad_match_topk_many_begin brackets that may be open at once (steps in flight - 1)
 #define MAD_SHARD_RING 8     // shard records of one lane that may be on their way to the host at once
-#define MAD_RES (2 * MAD_LANES)      // matches of one bracket that may be in flight: two per lane, the second queued behind the first on the lane's stream
+#define MAD_DIST_BUFS 6      // MAD_DIST_BUF_* of include/mad_amd.h
+#define MAD_RES (2 * MAD_LANES)     // matches of one bracket that may be in flight: two per lane, the second queued behind the first on the lane's stream
 
 struct TimerGroup {
     hipEvent_t start[MAD_T_RING];
@@ -250,6 +251,9 @@ struct mad_ctx {
     bool timing = false;
     TimerGroup timers[MAD_T_COUNT];
     int n_cu = 256;
+    // mad_dist_* (mad_dist.hip): the communicator, and the grow-only device buffers mad_dist_scratch hands out, per lane
+    void *dist = nullptr;
+    DevBuf dist_buf[MAD_LANES][MAD_DIST_BUFS];
 };
 
 // Wide rows (descriptor radius >= MAD_WIDE_FROM_R: a sub-region holds 6^3 = 216 samples, more than an int8 count).  The int8

@@ -107,7 +107,10 @@ extern "C" void mad_destroy(mad_ctx *ctx) {
     for (int l = 0; l < MAD_LANES; l++) (void)hipStreamSynchronize(ctx->lane_stream[l]);
     for (int i = 0; i < MAD_MAX_FIELDS; i++)
         if (ctx->field_mem[i]) (void)hipFree(ctx->field_mem[i]);
+    (void)mad_dist_destroy(ctx);
     for (auto &b : ctx->scratch) mad_release(b);
+    for (auto &lane : ctx->dist_buf)
+        for (auto &b : lane) mad_release(b);
     if (ctx->eq[0]) (void)hipFree(ctx->eq[0]);
     if (ctx->eq[1]) (void)hipFree(ctx->eq[1]);
     if (ctx->mask_off) (void)hipFree(ctx->mask_off);

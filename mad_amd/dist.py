@@ -19,9 +19,61 @@ of ONE subunit split into column blocks of map rows): it merges per-shard top-k 
 into the global top-k in the reference's order (count descending, row-major pair rank
 ascending, MaD.py:480).
 """
+import os
+
 import numpy as np
 
 RESULT_COLS = 23
+
+
+def lib_collectives():
+    """MAD_DIST_COLLECTIVES=lib: the exchanges of the sharded steps go through the library's own communicator (`LibComm`:
+    mad_dist_* of include/mad_amd.h, RCCL loaded by the library, the merge of the top-k records on the device) instead of
+    torch.distributed calls on a stream of the library.  Opt-in: that branch has run at world size 1 only."""
+    return os.environ.get("MAD_DIST_COLLECTIVES", "") == "lib"
+
+
+class LibComm(object):
+    """The communicator of a context (one per `lib`): rank `rank` of `world` -- the ranks of ONE group of shards.
+
+    Rank 0 of the group takes the unique id (mad_dist_unique_id) and it travels over the control plane -- `control_group`, a
+    torch.distributed group of exactly these ranks, or the default group -- with broadcast_object_list, as MaD._ranks does
+    for file names; world 1 needs no control plane.  rehearsal=True: one rank of `world` alone on its GPU (mad_dist_init
+    without an id: no RCCL; the all-gathers fill this rank's slot only, `set_peer_flags` stands for the peers' flags)."""
+
+    def __init__(self, lib, rank, world, control_group=None, rehearsal=False):
+        self.lib, self.rank, self.world, self.rehearsal = lib, int(rank), int(world), bool(rehearsal)
+        uid = None
+        if not self.rehearsal:
+            box = [lib.dist_unique_id() if self.rank == 0 else None]
+            if self.world > 1:
+                import torch.distributed as dist
+                src = dist.get_global_rank(control_group, 0) if control_group is not None else 0
+                dist.broadcast_object_list(box, src=src, group=control_group)
+            uid = box[0]
+        lib.dist_init(self.world, self.rank, uid)
+        self.open = True
+
+    def match_buffers(self, lane, n_flags, rec):
+        """Device addresses (flags, mine, all, merged) of the lane's grow-only buffers for a sharded match."""
+        from . import _lib
+        L = self.lib
+        return (L.dist_scratch(lane, _lib.DIST_BUF_FLAGS, n_flags), L.dist_scratch(lane, _lib.DIST_BUF_MINE, rec * 8),
+                L.dist_scratch(lane, _lib.DIST_BUF_ALL, self.world * rec * 8), L.dist_scratch(lane, _lib.DIST_BUF_MERGED, rec * 8))
+
+    def wire_buffers(self, lane, nbytes):
+        """Device addresses (wire, gathered) of the lane's buffers for the wire images of a sharded build."""
+        from . import _lib
+        return (self.lib.dist_scratch(lane, _lib.DIST_BUF_WIRE, nbytes), self.lib.dist_scratch(lane, _lib.DIST_BUF_GATHER, self.world * nbytes))
+
+    def set_peer_flags(self, peer_ptr, n):
+        """Rehearsal: the OR of the absent ranks' flags (n bytes in device memory) joins every later OR-reduce of n flags."""
+        self.lib.dist_rehearse_flags(peer_ptr, n)
+
+    def close(self):
+        if self.open and self.lib.ctx:
+            self.lib.dist_destroy()
+        self.open = False
 
 
 def shard_round_robin(items, rank, world):
@@ -191,8 +243,10 @@ class PartitionedMatch(object):
         corr, tops, stats = pm.finish(lib, st)          # tops: what this rank reports to the top-k exchange, in slot order
     """
 
-    def __init__(self, n_items, rank, world, make_group=None, stand_ins=None):
+    def __init__(self, n_items, rank, world, make_group=None, stand_ins=None, comm=None):
         self.n_items, self.rank, self.world = n_items, rank, world
+        # comm: a LibComm over the ranks of this rank's group of shards (MAD_DIST_COLLECTIVES=lib: made at the first begin, see _comm_for)
+        self.comm, self.use_lib = comm, lib_collectives()
         self.n_lo_seen = None      # rows of the map set at the last collected step: what the next steps cut their blocks from
         self.async_ok = False      # RCCL groups (or the rehearsal of one rank: stand_ins == "local"): ShardedMatchAsync
         self.units, self.groups = plan_partition(n_items, world)
@@ -219,6 +273,14 @@ class PartitionedMatch(object):
     def load(self):
         return partition_load(self.units)
 
+    def _comm_for(self, lib, j, part, parts):
+        """The LibComm of this rank's group (a rank belongs to one group, or every group is all ranks), when one was passed in or
+        MAD_DIST_COLLECTIVES=lib asks for it; else None.  Made once: collective over the group's ranks, which all get here at the
+        same block of the same step."""
+        if self.comm is None and self.use_lib:
+            self.comm = LibComm(lib, 0, 1, rehearsal=True) if self.local else LibComm(lib, part, parts, control_group=self.pg.get(j))
+        return self.comm
+
     def _block_sync(self, lib, hi, lo, cc, dist_thr, k, part, parts, j):
         kw = {}
         if self.stand_ins is not None:
@@ -234,7 +296,8 @@ class PartitionedMatch(object):
             d = dict(item=item, part=part, parts=parts, j=j, hi=hi, lo=lo, args=(cc, dist_thr, k), rows=None, pending=None)
             if self.async_ok and self.n_lo_seen is not None and self.stand_ins is None:
                 # no host round trip: both stages and both exchanges on the lane of the subunit's set, collected in finish()
-                d["pending"] = ShardedMatchAsync(lib, hi, lo, cc, dist_thr, k, part, parts, self.n_lo_seen, group=self.pg.get(j), local=self.local)
+                d["pending"] = ShardedMatchAsync(lib, hi, lo, cc, dist_thr, k, part, parts, self.n_lo_seen, group=self.pg.get(j), local=self.local,
+                                                 comm=self._comm_for(lib, j, part, parts))
             else:
                 d["rows"] = self._block_sync(lib, hi, lo, cc, dist_thr, k, part, parts, j)
             done.append(d)
@@ -319,11 +382,21 @@ class ShardedMatchAsync(object):
     records, so all of them then repeat the match through the synchronous `sharded_match`, which repairs the sets.
 
     group: the torch.distributed group of the shards (RCCL); `local=True`: no collective at all -- the rehearsal of one rank, or a
-    group of one."""
+    group of one.
+
+    comm: a `LibComm` over the shards' ranks.  Then no torch tensor and no ExternalStream is involved: the buffers are the
+    library's (mad_dist_scratch, one set per lane: steps in flight on a lane reuse them in stream order) and the chain on the lane
+    is mad_dist_or_allreduce -> mad_match_shard_score -> mad_dist_allgather_topk (all-gather + k_shard_merge) ->
+    mad_match_shard_collect, so ONE merged record travels to the host and `finish()` unpacks it without sorting.  More than
+    SHARD_MERGE_MAX entries (comm.world * k): all-gather only, the records are merged on the host as without a comm."""
 
     _pool = {}      # device / pinned buffers of finished handles, by size (released before the interpreter tears the runtime down)
 
-    def __init__(self, lib, hi, lo, cc, dist_thr, k, part, parts, n_lo, group=None, local=False):
+    def __init__(self, lib, hi, lo, cc, dist_thr, k, part, parts, n_lo, group=None, local=False, comm=None):
+        self.comm = comm
+        if comm is not None:
+            self._begin_lib(lib, hi, lo, cc, dist_thr, k, part, parts, n_lo)
+            return
         import torch
         if not ShardedMatchAsync._pool:
             import atexit
@@ -361,11 +434,40 @@ class ShardedMatchAsync(object):
         self.lib, self.n_out = lib, src.numel()
         self.ticket = lib.match_shard_collect(hi, src.data_ptr(), self.n_out)
 
+    def _begin_lib(self, lib, hi, lo, cc, dist_thr, k, part, parts, n_lo):
+        from . import _lib
+        comm = self.comm
+        self.lib, self.k, self.parts, self.part = lib, int(k), int(parts), int(part)
+        self.rec = rec = lib.match_shard_record_doubles(self.k)
+        n_fl = max(hi.n_anchors + lo.n_anchors, 1)
+        flags, mine, all_, merged = comm.match_buffers(hi.lane(), n_fl, rec)
+        b, e = lo_row_block(n_lo, part, parts)
+        stream = hi.stream()
+        lib.match_shard_begin(hi, lo, b, e, n_lo, cc, flags)
+        lib.dist_or_allreduce(stream, flags, hi.n_anchors + lo.n_anchors)      # behind the shard's pair kernels, in front of its pose kernels
+        lib.match_shard_score(hi, lo, flags, dist_thr, self.k, mine)
+        self.merged = comm.world * self.k <= _lib.SHARD_MERGE_MAX
+        if self.merged:
+            lib.dist_allgather_topk(hi, mine, all_, self.k, merged)
+            src, self.n_out = merged, rec
+        else:
+            lib.dist_allgather(stream, mine, all_, rec * 8)
+            src, self.n_out = all_, comm.world * rec
+        self.ticket = lib.match_shard_collect(hi, src, self.n_out)
+
     def finish(self):
         """-> (rows, counts, global pair ranks) merged over the shards, or None (some shard flagged: repeat synchronously)."""
-        B, k = self.buf, self.k
+        k = self.k
         out = self.lib.match_shard_wait(self.ticket, self.n_out).reshape(-1, self.rec)
-        ShardedMatchAsync._pool[self.key].append(B)
+        if self.comm is not None and self.merged:      # the device has merged: one record, already in order
+            r = out[0]
+            if r[1] != 0:
+                return None
+            m = int(r[0])
+            return (r[4:4 + m * RESULT_COLS].reshape(m, RESULT_COLS).copy(), r[4 + k * RESULT_COLS:4 + k * RESULT_COLS + m].astype(np.int64),
+                    r[4 + k * (RESULT_COLS + 1):4 + k * (RESULT_COLS + 1) + m].astype(np.int64))
+        if self.comm is None:
+            ShardedMatchAsync._pool[self.key].append(self.buf)
         if np.any(out[:, 1] != 0):
             return None
         rows, cnt, prank = [], [], []
@@ -441,9 +543,12 @@ class ShardedSetBuild(object):
     here once (untimed) and stay in the gather buffer; each call builds, exports and "receives" only this rank's share.
     Whatever it reports is a per-rank cost estimate without link traffic, never a multi-GPU measurement."""
 
-    def __init__(self, lib, slots, coords, octave, subv, index, rank, world, group=None, emulate=None, force=False, r=8, lim_main=6, lim_sec=6):
+    def __init__(self, lib, slots, coords, octave, subv, index, rank, world, group=None, emulate=None, force=False, r=8, lim_main=6, lim_sec=6, comm=None):
         from . import _lib
         self.lib, self.slots, self.group = lib, slots, group
+        # comm: a LibComm over the ranks (emulate: a rehearsal one) -- the wire images then live in buffers of the library and travel
+        # with mad_dist_allgather; the sizing exchange of resize() stays on the control plane (one integer, once)
+        self.comm = comm
         self.coords = np.ascontiguousarray(coords, np.int32).reshape(-1, 3)
         self.octave = np.ascontiguousarray(octave, np.int32)
         self.subv = np.ascontiguousarray(subv, np.float64).reshape(-1, 3)
@@ -461,11 +566,13 @@ class ShardedSetBuild(object):
         if self.sharded:
             self.mine = share_of(len(self.octave), rank, world)
             self.share = _lib.DeviceSet(lib, lane=self.full.lane())      # one lane: build -> export -> gather -> import in stream order
-            if emulate is None:
+            if emulate is not None:
+                self.backend = "emulate"
+            elif comm is not None:
+                self.backend = "lib"
+            else:
                 import torch.distributed as dist
                 self.backend = dist.get_backend(group)
-            else:
-                self.backend = "emulate"
 
     # -- pieces ---------------------------------------------------------------------------------
     def _build_share(self, rank=None, into=None):
@@ -490,26 +597,39 @@ class ShardedSetBuild(object):
             rows_max = max(counts)
         else:
             import torch.distributed as dist
-            dev = "cuda" if self.backend == "nccl" else "cpu"
-            t = torch.tensor([rows], dtype=torch.int64, device=dev)
-            dist.all_reduce(t, op=dist.ReduceOp.MAX, group=self.group)
-            rows_max = int(t.item())
+            if self.comm is not None and self.world == 1:
+                rows_max = int(rows)      # (a LibComm of one rank needs no process group: nobody to agree with)
+            else:
+                dev = "cuda" if dist.get_backend(self.group) == "nccl" else "cpu"
+                t = torch.tensor([rows], dtype=torch.int64, device=dev)
+                dist.all_reduce(t, op=dist.ReduceOp.MAX, group=self.group)
+                rows_max = int(t.item())
         self._allocate(rows_max + rows_max // 8 + 64)
-        nbytes = self.wire.numel()
+        nbytes = self.wire_bytes
         if self.backend == "emulate":      # the other ranks' images, once
             for rr in range(self.world):
                 self._build_share(rr, into=tmp)
-                self.lib.set_export(tmp, self.cap_rows, device_ptr=self.gathered.data_ptr() + rr * nbytes)
+                self.lib.set_export(tmp, self.cap_rows, device_ptr=self._ptrs()[1] + rr * nbytes)
             self.lib.synchronize()
             tmp.close()
 
     def _allocate(self, cap_rows):
-        import torch
         self.cap_rows = int(cap_rows)
-        nbytes = self.lib.set_wire_bytes(self.cap_rows)
+        nbytes = self.wire_bytes = self.lib.set_wire_bytes(self.cap_rows)
+        if self.comm is not None:      # buffers of the library, asked for again before every use (they only grow)
+            self.wire = self.gathered = None
+            self._ptrs()
+            return
+        import torch
         dev = "cpu" if self.backend == "gloo" else "cuda"
         self.wire = torch.zeros(nbytes, dtype=torch.uint8, device=dev)
         self.gathered = torch.zeros(self.world * nbytes, dtype=torch.uint8, device=dev)
+
+    def _ptrs(self):
+        """Device addresses (wire image of the share, gather buffer)."""
+        if self.comm is not None:
+            return self.comm.wire_buffers(self.share.lane(), self.wire_bytes)
+        return self.wire.data_ptr(), self.gathered.data_ptr()
 
     def shrink_for_rehearsal(self, cap_rows):
         """Rehearsal of an overflow (bench.py --rehearse-resize, tests): wire images of `cap_rows` rows, as if an earlier, smaller
@@ -543,10 +663,12 @@ class ShardedSetBuild(object):
 
     def finish(self):
         """What follows the build of the share: export, all-gather, import -> the full DeviceSet."""
-        import torch
         lib = self.lib
         if not self.sharded:
             return self.full
+        if self.comm is not None:
+            return self._finish_lib()
+        import torch
         nbytes = self.wire.numel()
         if self.backend == "gloo":
             import torch.distributed as dist
@@ -568,6 +690,21 @@ class ShardedSetBuild(object):
                 dist.all_gather_into_tensor(self.gathered, self.wire, group=self.group, async_op=True).wait()
         t2 = time.perf_counter()
         out = lib.set_import(self.world, self.cap_rows, self.coords, self.octave, self.subv, self.index, device_ptr=self.gathered.data_ptr(), into=self.full)
+        t3 = time.perf_counter()
+        T["export"] += t1 - t0; T["collective"] += t2 - t1; T["import"] += t3 - t2; T["calls"] += 1
+        return out
+
+    def _finish_lib(self):
+        """export -> mad_dist_allgather -> import on the share's lane, every buffer the library's."""
+        import time
+        lib, T = self.lib, self.host_s
+        wire, gathered = self._ptrs()
+        t0 = time.perf_counter()
+        lib.set_export(self.share, self.cap_rows, device_ptr=wire)
+        t1 = time.perf_counter()
+        lib.dist_allgather(self.share.stream(), wire, gathered, self.wire_bytes)      # (a rehearsal comm fills this rank's slot only)
+        t2 = time.perf_counter()
+        out = lib.set_import(self.world, self.cap_rows, self.coords, self.octave, self.subv, self.index, device_ptr=gathered, into=self.full)
         t3 = time.perf_counter()
         T["export"] += t1 - t0; T["collective"] += t2 - t1; T["import"] += t3 - t2; T["calls"] += 1
         return out
