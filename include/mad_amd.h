@@ -372,6 +372,33 @@ int mad_ccc(mad_ctx *ctx, float *grid1, const int32_t dims1[3], const double ori
             float *grid2, const int32_t dims2[3], const double origin2[3],
             double voxsp, double isovalue, double *ccc);
 
+/* ---- next to a16: a map against a map (mad_mapops.hip) ---------------------------- */
+
+/*
+ * Dmap.mask_with (Dmap.py:99-151).  Host pointers, synchronous.  grid1 (float32 [x][y][z]) is updated IN PLACE: a voxel outside
+ * the planes the reference's slices keep -- s = round(origin2 / voxsp - origin1 / voxsp) per axis (half to even), min = max(s, 0),
+ * max = min(n1, n2 + s), `grid[:min] = 0`, `grid[max:] = 0` with python's slice semantics: a negative max zeroes the last -max
+ * planes only -- or over a mask voxel < (float)1e-8 becomes 0; every other voxel keeps its bits.  The mask is read only.  Where
+ * the reference raises IndexError (the mask begins behind the map's last plane: it has zeroed the whole map by then) this returns
+ * MAD_OK with the map zeroed.  MAD_EINVAL: NULL, a dimension < 1, voxsp <= 0, a grid of 2^32 voxels or more.
+ */
+int mad_map_mask(mad_ctx *ctx, float *grid1, const int32_t dims1[3], const double origin1[3],
+                 const float *mask, const int32_t dims2[3], const double origin2[3], double voxsp);
+
+/*
+ * Dmap.get_CCC_with_dmap (Dmap.py:260-372) of grid 1 against n second maps: grids2[j] float32 [x][y][z] with dims2[3 j ..] and
+ * origins2[3 j ..].  Grid 1 is uploaded once and its voxels above the isovalue are counted once; the call with one map is the
+ * n = 1 case of the same path (same bits).  No grid is modified.  With n1 / n2 = voxels of the whole grids above the isovalue and,
+ * over the common box of mad_ccc (on a half-voxel tie the smaller extent, where the reference raises ValueError),
+ * common = voxels with m2 != 0, m2 > isovalue, m1 > isovalue, S1 = sum m1^2 where m2 > 0, S2 = sum m2^2 where m1 > 0, D = sum m1 m2
+ * (float32 comparisons, float64 sums in a fixed order):
+ *     out[j] = 0 if common = 0 or min(n1, n2) = 0, else D / (sqrt(S1) sqrt(S2)) common / min(n1, n2)      (inf / NaN if S1 S2 = 0)
+ * MAD_EINVAL: NULL, n < 1 or > 32767, a dimension < 1, voxsp <= 0, a grid of 2^32 voxels or more.
+ */
+int mad_map_ccc(mad_ctx *ctx, const float *grid1, const int32_t dims1[3], const double origin1[3], int n,
+                const float *const *grids2, const int32_t *dims2, const double *origins2,
+                double voxsp, double isovalue, double *out);
+
 /* ---- one subunit's pair grid sharded over GPUs by blocks of map rows (the exchange steps -- OR of the flag vectors,
  *      all-gather of the per-shard top-k -- are the caller's, mad_amd/dist.py::sharded_match, or the library's own:
  *      mad_dist_or_allreduce / mad_dist_allgather_topk below) ------------------------------------------------- */

@@ -2,9 +2,9 @@
 
 Field contract of the reference's `Dmap` (mad/Dmap.py:6-71): `grid3d` float32 [x,y,z],
 origin `xi, yi, zi` (Angstrom), box `xb, yb, zb`, `voxsp`, `map_name`, `name`.
-`get_CCC_with_grid` (Dmap.py:153-258) runs on the GPU through `mad_ccc`.
-`mask_with`, `get_CCC_with_dmap` and the per-voxel text writer are not used by
-`MaD.run` / `build_assembly` and are out of scope.
+`get_CCC_with_grid` (Dmap.py:153-258) runs on the GPU through `mad_ccc`, `mask_with` (Dmap.py:99-151) through `mad_map_mask`
+and `get_CCC_with_dmap` (Dmap.py:260-372) through `mad_map_ccc`: together the reference's support for docking into a segment of
+a map.  None of them has a CPU fallback.  The reference's per-voxel text writer is replaced by `mapio.write_situs`.
 """
 import os
 import sys
@@ -80,6 +80,31 @@ class Dmap(object):
             except Exception:
                 pass
         return ccc
+
+    def mask_with(self, mask_map):
+        """Zero every voxel of this map that lies outside `mask_map` or where `mask_map` is below 1e-8 (Dmap.py:99-151).
+        Changes `self.grid3d` and nothing else; the planes kept are those python's slices keep in the reference."""
+        if not np.isclose(self.voxsp, mask_map.voxsp):
+            print("ERROR: voxsp do not match! %f vs %f" % (self.voxsp, mask_map.voxsp))
+            sys.exit(1)
+        g1 = self.grid3d
+        if g1.dtype != np.float32 or not g1.flags.c_contiguous or not g1.flags.writeable:
+            g1 = np.ascontiguousarray(g1, dtype=np.float32)
+            if not g1.flags.writeable:
+                g1 = g1.copy()
+            self.grid3d = g1
+        mask = np.ascontiguousarray(mask_map.grid3d, dtype=np.float32)
+        _lib.get_lib().map_mask(g1, (self.xi, self.yi, self.zi), mask, (mask_map.xi, mask_map.yi, mask_map.zi), self.voxsp)
+
+    def get_CCC_with_dmap(self, m2, isovalue=0):
+        """Overlap-normalised score of two maps (Dmap.py:260-372): each map is normalised over the other's support inside the
+        common box, and the result is scaled by the share of the smaller map's voxels above `isovalue` that the box has in
+        common.  Neither map is modified."""
+        if self.voxsp != m2.voxsp:
+            print("ERROR: voxsp differ (%f vs %f)" % (self.voxsp, m2.voxsp))      # ... and goes on with self.voxsp (Dmap.py:265-267)
+        g1 = np.ascontiguousarray(self.grid3d, dtype=np.float32)
+        g2 = np.ascontiguousarray(m2.grid3d, dtype=np.float32)
+        return float(_lib.get_lib().map_ccc(g1, (self.xi, self.yi, self.zi), [(g2, (m2.xi, m2.yi, m2.zi))], self.voxsp, isovalue)[0])
 
     def write_to_mrc(self, outname):
         mapio.write_mrc(outname, self.grid3d, (self.xi, self.yi, self.zi), self.voxsp)

@@ -39,7 +39,7 @@ SYMBOLS = [
     "mad_dist_unique_id", "mad_dist_init", "mad_dist_destroy", "mad_dist_info", "mad_dist_rehearse_flags", "mad_dist_or_allreduce", "mad_dist_allgather",
     "mad_dist_allgather_topk", "mad_dist_scratch", "mad_dist_copy",
     "mad_set_wire_bytes", "mad_set_export", "mad_set_import", "mad_set_lane", "mad_set_stream", "mad_set_bind_lane",
-    "mad_upload_density", "mad_refine", "mad_last_refine_plan", "mad_last_density_chunks", "mad_structure_to_density", "mad_ccc", "mad_density_ccc", "mad_dock_refine_score", "mad_grid_overlap", "mad_overlap_matrix",
+    "mad_upload_density", "mad_refine", "mad_last_refine_plan", "mad_last_density_chunks", "mad_structure_to_density", "mad_ccc", "mad_map_mask", "mad_map_ccc", "mad_density_ccc", "mad_dock_refine_score", "mad_grid_overlap", "mad_overlap_matrix",
     "mad_space_create", "mad_space_destroy", "mad_space_build", "mad_space_info", "mad_space_download",
     "mad_space_peaks", "mad_space_patches", "mad_space_localize", "mad_localize_volume",
     "mad_pose_cluster_many",
@@ -1056,6 +1056,40 @@ class Lib(object):
         self._chk(self.dll.mad_ccc(self.ctx, _p(g1), _p(d1), _p(o1), _p(g2), _p(d2), _p(o2), C.c_double(voxsp),
                                    C.c_double(isovalue), C.byref(out)))
         return out.value
+
+    def map_mask(self, g1, o1, mask, o2, voxsp):
+        """Dmap.mask_with: g1 (writable C-contiguous float32) is zeroed in place outside `mask` and where `mask` is below 1e-8;
+        the mask (C-contiguous float32) is only read."""
+        if g1.dtype != np.float32 or not g1.flags.c_contiguous or not g1.flags.writeable:
+            raise ValueError("map_mask needs a writable C-contiguous float32 grid")
+        if mask.dtype != np.float32 or not mask.flags.c_contiguous:
+            raise ValueError("map_mask needs a C-contiguous float32 mask")
+        if g1.ndim != 3 or mask.ndim != 3:
+            raise ValueError("map_mask needs 3-D grids")
+        d1, d2 = np.array(g1.shape, np.int32), np.array(mask.shape, np.int32)
+        o1, o2 = _c(o1, np.float64), _c(o2, np.float64)
+        self._chk(self.dll.mad_map_mask(self.ctx, _p(g1), _p(d1), _p(o1), _p(mask), _p(d2), _p(o2), C.c_double(voxsp)))
+
+    def map_ccc(self, g1, o1, seconds, voxsp, isovalue=0.0):
+        """Dmap.get_CCC_with_dmap of g1 against every (grid, origin) of `seconds` in one call -> float64 array.
+        All grids C-contiguous float32; none is modified."""
+        seconds = list(seconds)
+        for g in [g1] + [g for g, _ in seconds]:
+            if g.dtype != np.float32 or not g.flags.c_contiguous:
+                raise ValueError("map_ccc needs C-contiguous float32 grids")
+            if g.ndim != 3:
+                raise ValueError("map_ccc needs 3-D grids")
+        n = len(seconds)
+        out = np.zeros(n, np.float64)
+        if n == 0:
+            return out
+        d1, o1 = np.array(g1.shape, np.int32), _c(o1, np.float64)
+        d2 = np.array([g.shape for g, _ in seconds], np.int32).reshape(n, 3)
+        o2 = _c(np.array([np.asarray(o, np.float64).reshape(3) for _, o in seconds]), np.float64)
+        ptrs = (C.c_void_p * n)(*[g.ctypes.data for g, _ in seconds])
+        self._chk(self.dll.mad_map_ccc(self.ctx, _p(g1), _p(d1), _p(o1), C.c_int(n), ptrs, _p(d2), _p(o2), C.c_double(voxsp),
+                                       C.c_double(isovalue), _p(out)))
+        return out
 
 
 _default = None

@@ -462,6 +462,13 @@ int mad_build_cells(mad_ctx *ctx, mad_set *set, double cell);
 
 static inline int64_t mad_ceil_div(int64_t a, int64_t b) { return (a + b - 1) / b; }
 
+// mad_refine.hip: python's round() (half to even), and the common box of two grids as Dmap.get_CCC_with_grid and
+// Dmap.get_CCC_with_dmap select it (Dmap.py:163-234 = :271-343): starts mn1 / mn2 in either grid and the extent e, python slice
+// semantics, the smaller extent on a half-voxel tie.  false: the boxes miss each other (the reference returns 0).
+long py_round(double v);
+bool ccc_overlap(const int32_t d1[3], const double o1[3], const int32_t d2[3], const double o2[3], double voxsp, long mn1[3], long mn2[3],
+                 long e[3]);
+
 // ---------------------------------------------------------------------------
 // device helpers
 // ---------------------------------------------------------------------------

@@ -432,11 +432,11 @@ extern "C" int mad_last_refine_plan(mad_ctx *ctx, int *G, int *in_registers) {
     return MAD_OK;
 }
 
-static long py_round(double v) { return (long)nearbyint(v); }      // python round(): half to even
+long py_round(double v) { return (long)nearbyint(v); }      // python round(): half to even (declared in mad_common.h)
 
 // Dmap.py:163-230: overlap box of two grids in voxel units.  Returns false when the boxes do not overlap
-// (Dmap.py:232-234); e[] may still hold a zero extent (0/0 -> NaN, as the reference).
-static bool ccc_overlap(const int32_t d1[3], const double o1[3], const int32_t d2[3], const double o2[3], double voxsp, long mn1[3],
+// (Dmap.py:232-234); e[] may still hold a zero extent (0/0 -> NaN, as the reference).  Shared with mad_mapops.hip (mad_common.h).
+bool ccc_overlap(const int32_t d1[3], const double o1[3], const int32_t d2[3], const double o2[3], double voxsp, long mn1[3],
                         long mn2[3], long e[3]) {
     long mx1[3], mx2[3];
     bool empty = false;
