@@ -138,11 +138,14 @@ __device__ __forceinline__ void classify_exact64(const EqspFastLds *eq, const Eq
 #ifdef MAD_PROBE_STAMPS      // diagnostic build: s_memtime at the phases of every anchor's workgroup (tools/probe_orient.py)
 __device__ long long ori_stamps[4096 * 12];
 #define ORI_STAMP(k) do { if (threadIdx.x == 0 && blockIdx.x < 4096) ori_stamps[blockIdx.x * 12 + (k)] = __builtin_amdgcn_s_memtime(); } while (0)
+// the twelfth word of an anchor's record: what its re-binning pass had to do (candidates | pole among them << 8 | voxels << 16)
+#define ORI_NOTE(v) do { if (threadIdx.x == 0 && blockIdx.x < 4096) ori_stamps[blockIdx.x * 12 + 11] = (v); } while (0)
 extern "C" int mad_debug_ori_stamps(long long *out, int n) {
     return hipMemcpyFromSymbol(out, HIP_SYMBOL(ori_stamps), (size_t)n * 8) == hipSuccess ? 0 : -1;
 }
 #else
 #define ORI_STAMP(k) do { } while (0)
+#define ORI_NOTE(v) do { } while (0)
 #endif
 
 template <bool GW>
@@ -345,27 +348,44 @@ __global__ __launch_bounds__(ORI_THREADS, GW ? 4 : ORI_WPE) void k_orient(Batch<
 
     // step03 for every main-bin candidate at once: rotate by to_dom (Orientator.py:303) and re-bin
     ORI_STAMP(6);
-    // (a voxel's candidates classified side by side, three at a time in straight-line code, so that their chains of dependent LDS
-    // reads overlap instead of following each other: this pass was 12 100 of an anchor's 45 600 cycles, two thirds of its
-    // instructions -- then the tallies.  A group's last candidates may repeat the anchor's last one: classified, not tallied)
-    constexpr int ORI_SIDE = 3;
-    for (int v = tid; v < nvox; v += ORI_THREADS) {
-        const float g0 = vx[v], g1 = vy[v], g2 = vz[v];
-        for (int c0 = 0; c0 < nmain; c0 += ORI_SIDE) {
-            int zn[ORI_SIDE];
+    ORI_NOTE(nmain | (main_list[0] == 0 ? 1 << 8 : 0) | nvox << 16);      // (main bins ascend: the pole, zone 0, can only be the first)
+    // Candidate-major: a thread keeps ORI_W of its voxels' directions in registers (at r = 8 all of them: the outer loop
+    // runs once) and takes the accepted candidates one after the other.  Only real candidates are classified: the pole is
+    // skipped before anything is computed, and nothing is padded (the voxel-major form classified candidates three at a
+    // time and filled a short group with repeats: +65 % classifications on the base octave's mix of one to six main bins).
+    // The candidate's float32 matrix is the same for the whole workgroup: read once from LDS into scalar registers, it
+    // enters the products as a scalar operand.  The ORI_W classifications stand side by side in straight-line code, so
+    // that their chains of dependent LDS reads overlap as in the first pass -- then the tallies.  Only a thread's last
+    // voxels may repeat the box's last one: classified, not tallied.
+    constexpr int ORI_W = ORI_TRIPS;
+    for (int v0 = tid; v0 < nvox; v0 += ORI_W * ORI_THREADS) {
+        float g0[ORI_W], g1[ORI_W], g2[ORI_W];
 #pragma unroll
-            for (int u = 0; u < ORI_SIDE; u++) {
-                const float *d = s_domf[min(c0 + u, nmain - 1)];
-                const float rx = g0 * d[0] + g1 * d[1] + g2 * d[2];
-                const float ry = g0 * d[3] + g1 * d[4] + g2 * d[5];
-                const float rz = g0 * d[6] + g1 * d[7] + g2 * d[8];
-                zn[u] = eqsp_fast32<true>(&fast, rx, ry, rz);
+        for (int k = 0; k < ORI_W; k++) {
+            const int v = min(v0 + k * ORI_THREADS, nvox - 1);
+            g0[k] = vx[v]; g1[k] = vy[v]; g2[k] = vz[v];
+        }
+        for (int c = 0; c < nmain; c++) {
+            if (__builtin_amdgcn_readfirstlane(main_list[c]) == 0) continue;      // Orientator.py:211: the pole keeps the first binning
+            float d[9];
+#pragma unroll
+            for (int i = 0; i < 9; i++) d[i] = __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(s_domf[c][i])));
+            int zn[ORI_W];
+#pragma unroll
+            for (int k = 0; k < ORI_W; k++) {
+                // Explicit fmaf although the file is built with -ffp-contract=off: these products decide nothing.  The float32
+                // direction is a guess that eqsp_fast32 accepts only when it lies a guard band inside a zone, a band that
+                // covers the rounding of either form; every other direction is redone below from the float64 products.
+                const float rx = fmaf(g2[k], d[2], fmaf(g1[k], d[1], g0[k] * d[0]));
+                const float ry = fmaf(g2[k], d[5], fmaf(g1[k], d[4], g0[k] * d[3]));
+                const float rz = fmaf(g2[k], d[8], fmaf(g1[k], d[7], g0[k] * d[6]));
+                zn[k] = eqsp_fast32<true>(&fast, rx, ry, rz);
             }
 #pragma unroll
-            for (int u = 0; u < ORI_SIDE; u++) {
-                const int c = c0 + u;
-                if (c >= nmain || main_list[c] == 0) continue;      // Orientator.py:211: the pole keeps the first binning
-                if (zn[u] >= 0) { tally(1 + c, zn[u], v); continue; }
+            for (int k = 0; k < ORI_W; k++) {
+                const int v = v0 + k * ORI_THREADS;
+                if (v >= nvox) continue;
+                if (zn[k] >= 0) { tally(1 + c, zn[k], v); continue; }
                 const int slot = atomicAdd(&s_nq, 1);
                 if (slot < A.queue_cap) queue[slot] = v | (c << 16);      // (a full queue: the whole pass again below)
             }
