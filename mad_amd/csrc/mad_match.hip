@@ -1629,215 +1629,6 @@ __global__ __launch_bounds__(PB_THREADS) void k_pose_bounds(const int32_t *__res
     }
 }
 
-// ---- the same bracket with the coarse map on the matrix cores ---------------------------------------------------------------
-//
-// The coarse phase of k_pose_bounds spends 9 of its ~26 vector instructions per 64 points on v = M c + t.  That map is a small
-// matrix product, and v_mfma_f32_16x16x4_f32 does 16 x 16 of them per instruction if the operands are laid out for it:
-//   A (16 x 4), row 4 q + i = row i of [M | t] of pair q of FOUR pairs (i = 3: zeros);  B (4 x 16), column n = (x, y, z, 1) of point n
-//   D (16 x 16): lane l holds D[4 (l / 16) + i][l % 16], i = 0..3 = the voxel coordinates of point l % 16 under pair l / 16
-// so a wave works on four pairs at once, one pair per group of 16 lanes, 16 points per instruction, and every lane ends up with one
-// whole mapped point -- the rest of the phase (voxel, LDS bitmap, ballot compaction) runs on full lanes as before, minus the nine
-// fused multiply-adds.  float32 with another summation order than the fmaf chain: the bitmaps' slack (0.02 A against < 1e-3 A,
-// PoseBits) covers any of them, and the bracket L <= count <= U is all the selection needs (a voxel of difference moves a bound by
-// one, never the top-k).  The wave's queue holds (point | pair << 10) of all four pairs; the fine phase reads each entry's map from
-// the four records in LDS.  A group of four pairs is worked in two halves of the point blocks, so that the queue (one half, all
-// passing: 2 NB sets) stays small and the lookups of one half fly under the coarse phase of the next.  SPLIT = false only (nothing
-// is abandoned); NB <= 8.
-typedef float v4f __attribute__((ext_vector_type(4)));
-
-template <int NB>
-__global__ __launch_bounds__(PB_THREADS) void k_pose_bounds_mx(const int32_t *__restrict__ status, int64_t cap_pairs, const PosePair *__restrict__ rec,
-                                                               const double *__restrict__ hi_cloud, PoseBits B, const unsigned *__restrict__ bits,
-                                                               PoseCoarse C, const unsigned *__restrict__ bits_c, int32_t *__restrict__ lower,
-                                                               unsigned short *__restrict__ upper, int32_t *__restrict__ hist, int nbins) {
-    extern __shared__ __align__(16) unsigned char smem[];
-    if (status[ST_FLAG_C] || status[ST_FLAG_PAIRS]) return;
-    constexpr int NBLK = NB * 4, HALF = NBLK / 2;      // blocks of 16 points; a half of them per coarse / fine turn
-    constexpr int QSETS = 2 * NB;                      // the queue: one half with every point passing
-    constexpr int NF = NB / 2;                         // sets of 64 queued entries whose lookups are in flight (more: looked up on the spot)
-    constexpr int NWV = PB_THREADS / MAD_WAVE;
-    unsigned *lb = (unsigned *)smem;                                           // coarse bitmap
-    float4 *clf = (float4 *)(smem + pad16((size_t)C.n_words * 4));             // hi cloud, float32
-    const int64_t n_pairs = min((int64_t)status[ST_NPAIRS], cap_pairs);
-    const int l_hi = status[ST_LHI];
-    unsigned char *after = smem + pad16((size_t)C.n_words * 4) + pad16((size_t)(l_hi + 4) * 16);
-    const int wv = threadIdx.x >> 6;
-    unsigned short *queue = (unsigned short *)after + wv * ((QSETS + 1) * MAD_WAVE);
-    unsigned short *dump = queue + QSETS * MAD_WAVE;      // 64 entries behind the wave's queue, never read
-    float *wrec = (float *)(after + (size_t)NWV * (QSETS + 1) * MAD_WAVE * 2) + wv * 48;      // the fine maps of the wave's four pairs
-    int *lh = (int *)(after + (size_t)NWV * (QSETS + 1) * MAD_WAVE * 2 + (size_t)NWV * 192);
-    for (int i = threadIdx.x; i < nbins; i += PB_THREADS) lh[i] = 0;
-    stage_lds(lb, bits_c, (size_t)C.n_words * 4);
-    for (int i = threadIdx.x; i < l_hi; i += PB_THREADS)
-        clf[i] = make_float4((float)hi_cloud[3 * i], (float)hi_cloud[3 * i + 1], (float)hi_cloud[3 * i + 2], 0.f);
-    __syncthreads();
-    const int lane = lane_id(), g = lane >> 4, c16 = lane & 15;
-    const int64_t wave = __builtin_amdgcn_readfirstlane((int)(blockIdx.x * NWV + wv));
-    const int64_t nwaves = (int64_t)gridDim.x * NWV;
-
-    // B operands: component g of point 16 j + c16 (g = 3: the 1 that takes the translation); a lane beyond the cloud holds a NaN,
-    // which maps to NaN and converts to voxel 0 -- on the bitmap's outermost layer, never marked
-    float bp[NBLK];
-#pragma unroll
-    for (int j = 0; j < NBLK; j++) {
-        const int a = 16 * j + c16;
-        const float4 c = clf[min(a, max(l_hi - 1, 0))];
-        const float v = g == 0 ? c.x : (g == 1 ? c.y : (g == 2 ? c.z : 1.0f));
-        bp[j] = a < l_hi ? v : __int_as_float(0x7fc00000);
-    }
-    // A operand of this lane: entry (i, k = g) of [M | t] of pair q_a, i = c16 % 4, q_a = c16 / 4 -- one float of PoseVox per lane
-    const int q_a = c16 >> 2, i_a = c16 & 3;
-    const int a_off = g < 3 ? i_a * 3 + g : 9 + i_a;      // PoseVox: m[9] (row-major), t[3]
-    auto pair_of = [&](int64_t grp, int q) -> int64_t { return wave + (4 * grp + q) * nwaves; };
-    // (both loads are unconditional, at a clamped pair: a load inside a branch makes the compiler lose count of what is in flight and
-    // wait for everything -- the lookups of the previous half included -- at the next use of any loaded value)
-    auto load_a = [&](int64_t grp) -> float {
-        const int64_t p = min(pair_of(grp, q_a), n_pairs - 1);
-        return ((const float *)&rec[p].vc)[i_a < 3 ? a_off : 0];
-    };
-    auto valid_a = [&](int64_t grp) -> bool { return pair_of(grp, q_a) < n_pairs && i_a < 3; };      // else 0: a pair past the end maps every point to voxel 0
-    auto load_f = [&](int64_t grp) -> float {      // lanes 0..47: float lane % 12 of the fine map of pair lane / 12
-        const int64_t p = min(pair_of(grp, min(lane / 12, 3)), n_pairs - 1);
-        return ((const float *)&rec[p].vf)[lane % 12];
-    };
-    const int dx1 = C.B.dim[0] - 1, dy1 = C.B.dim[1] - 1, dz1 = C.B.dim[2] - 1;
-    const int fx1 = B.dim[0] - 1, fy1 = B.dim[1] - 1, fz1 = B.dim[2] - 1;
-    const unsigned ent0 = (unsigned)c16 | ((unsigned)g << 10);
-    const v4f zero4 = {0.f, 0.f, 0.f, 0.f};
-
-    // coarse phase of one half of a group -> number of queued entries (wave-uniform)
-    auto coarse = [&](const float a_op, auto half_tag) -> int {
-        constexpr int half = decltype(half_tag)::value;      // (a constant: bp[] must be indexed with constants to stay in registers)
-        int nq = 0;
-        // four blocks (64 points x 4 pairs) at a time in straight-line code: the four matrix instructions first, then the four chains
-        // voxel -> LDS word -> bit side by side, then the queue writes
-#pragma unroll
-        for (int jb = 0; jb < HALF / 4; jb++) {
-            const int j0 = half * HALF + 4 * jb;
-            if (16 * j0 >= l_hi) break;           // wave-uniform; a block past the cloud inside a batch holds NaNs (voxel 0, never marked)
-            v4f d[4];
-#pragma unroll
-            for (int t = 0; t < 4; t++) d[t] = __builtin_amdgcn_mfma_f32_16x16x4f32(a_op, bp[half * HALF + 4 * jb + t], zero4, 0, 0, 0);
-            asm volatile("" : "+v"(d[0]), "+v"(d[1]), "+v"(d[2]), "+v"(d[3]));      // four results in four register quads: issued back to back (left alone the compiler reuses one quad and waits four times)
-            unsigned cw[4];
-            int jz[4];
-#pragma unroll
-            for (int t = 0; t < 4; t++) {
-                const int jx = clamp0(cvt_floor(d[t][0]), dx1), jy = clamp0(cvt_floor(d[t][1]), dy1);
-                jz[t] = clamp0(cvt_floor(d[t][2]), dz1);
-                cw[t] = lb[mad_u24s(mad_u24s((unsigned)jx, (unsigned)C.B.dim[1], (unsigned)jy), (unsigned)C.B.wz, (unsigned)(jz[t] >> 5))];
-            }
-            asm volatile("" : "+v"(cw[0]), "+v"(cw[1]), "+v"(cw[2]), "+v"(cw[3]));      // (likewise: the four LDS reads go out together)
-#pragma unroll
-            for (int t = 0; t < 4; t++) {
-                const bool pass = __builtin_amdgcn_ubfe(cw[t], (unsigned)jz[t], 1u) != 0u;
-                const unsigned long long bal = __ballot(pass);
-                const int below = __builtin_amdgcn_mbcnt_hi((unsigned)(bal >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)bal, 0u));
-                const int idx = pass ? nq + below : QSETS * MAD_WAVE + lane;      // a lane that does not pass writes to its dump slot
-                queue[idx] = (unsigned short)(ent0 + 16u * (unsigned)(j0 + t));
-                nq += __popcll(bal);
-            }
-        }
-        return nq;
-    };
-    // fine phase of the queue entries [64 s0, min(64 (s0 + NF), n)): the lookups go out ...
-    auto lookup = [&](const int s0, const int n, uint2 (&w)[NF], int (&bit)[NF]) {
-        __builtin_amdgcn_wave_barrier();      // the queue and the records were written by this wave's own lanes
-        // straight-line over all NF sets, no branch: a lane without an entry reads the queue's entry 0 (whatever it holds: a point id
-        // below 1 024, a pair below 4 -- LDS reads past the cloud return what lies there), looks up word 0 of the bitmap and tests its
-        // bit 0 -- voxel (0, 0, 0), on the outermost layer, never marked -- so it counts nothing.  (With a branch per set the compiler
-        // waits for ALL lookups in flight at the top of every set.)
-#pragma unroll
-        for (int u = 0; u < NF; u++) {
-            const int e = (s0 + u) * MAD_WAVE + lane;
-            const bool have = e < n;
-            const unsigned ent = queue[have ? e : 0];
-            const unsigned q = (ent >> 10) & 3u;
-            const float4 c = clf[ent & 1023u];
-            const float4 *mv = (const float4 *)(wrec + q * 12);
-            const float4 r0 = mv[0], r1 = mv[1], r2 = mv[2];      // m0..m3 | m4..m7 | m8 t0 t1 t2
-            const float vx = fmaf(c.z, r0.z, fmaf(c.y, r0.y, fmaf(c.x, r0.x, r2.y)));
-            const float vy = fmaf(c.z, r1.y, fmaf(c.y, r1.x, fmaf(c.x, r0.w, r2.z)));
-            const float vz = fmaf(c.z, r2.x, fmaf(c.y, r1.w, fmaf(c.x, r1.z, r2.w)));
-            const int ix = clamp0(cvt_floor(vx), fx1), iy = clamp0(cvt_floor(vy), fy1), iz = clamp0(cvt_floor(vz), fz1);
-            const unsigned fi = mad_u24s(mad_u24s((unsigned)ix, (unsigned)B.dim[1], (unsigned)iy), (unsigned)B.wz, (unsigned)(iz >> 5));
-            bit[u] = have ? (iz & 31) | (int)(q << 5) : 0;
-            w[u] = ((const uint2 *)bits)[have ? fi : 0u];
-        }
-    };
-    // ... and are counted: per lane, the inner / outer hits of pair q in bits 8 q .. 8 q + 7 of two words (a lane sees one entry per
-    // set, at most 2 x 2 NB sets per group: the fields cannot overflow)
-    unsigned acc_in = 0u, acc_out = 0u;
-    auto tally = [&](const uint2 (&w)[NF], const int (&bit)[NF]) {
-#pragma unroll
-        for (int u = 0; u < NF; u++) {
-            const unsigned in = __builtin_amdgcn_ubfe(w[u].y, (unsigned)bit[u], 1u), out = __builtin_amdgcn_ubfe(w[u].x | w[u].y, (unsigned)bit[u], 1u);
-            const unsigned sh = ((unsigned)bit[u] >> 2) & 0x18u;
-            acc_in += in << sh;
-            acc_out += out << sh;
-        }
-    };
-    auto put = [&](const int64_t grp) {      // the group's four brackets: lane q writes pair q
-        // 8-bit fields widened to 16 before the sum over the lanes: pairs 0 and 2 in one word, 1 and 3 in the other
-        const unsigned i_02 = (unsigned)wave_sum_i32((int)(acc_in & 0x00ff00ffu)), i_13 = (unsigned)wave_sum_i32((int)((acc_in >> 8) & 0x00ff00ffu));
-        const unsigned o_02 = (unsigned)wave_sum_i32((int)(acc_out & 0x00ff00ffu)), o_13 = (unsigned)wave_sum_i32((int)((acc_out >> 8) & 0x00ff00ffu));
-        acc_in = 0u; acc_out = 0u;
-        if (lane < 4) {
-            const int64_t p = pair_of(grp, lane);
-            const unsigned iw = (lane & 1) ? i_13 : i_02, ow = (lane & 1) ? o_13 : o_02;
-            const int L = (int)((iw >> (16 * (lane >> 1))) & 0xffffu), U = (int)((ow >> (16 * (lane >> 1))) & 0xffffu);
-            if (p < n_pairs) { lower[p] = L; upper[p] = (unsigned short)U; atomicAdd(&lh[min(L, nbins - 1)], 1); }
-        }
-    };
-
-    uint2 wA[NF], wB[NF];
-    int bitA[NF], bitB[NF];
-    // entries beyond the NF sets in flight (a half where more than ~3 points in 8 pass): looked up and counted on the spot, in the
-    // buffer that has just been counted
-    auto overflow = [&](const int n, uint2 (&w)[NF], int (&bit)[NF]) {
-        for (int s0 = NF; s0 * MAD_WAVE < n; s0 += NF) {
-            lookup(s0, n, w, bit);
-            tally(w, bit);
-        }
-    };
-    // Turns: (group, half) = (0, 0), (0, 1), (1, 0), ...  Per turn: the coarse phase of this half, the count of the previous turn's
-    // lookups, this half's lookups into the other buffer -- two turns per trip so that the buffers swap without copies.
-    if (wave < n_pairs) {
-#pragma unroll
-        for (int u = 0; u < NF; u++) { wB[u] = make_uint2(0u, 0u); bitB[u] = 0; }      // "the lookups of the group before the first": nothing
-        float a_op = valid_a(0) ? load_a(0) : 0.f, f_op = load_f(0);
-        for (int64_t grp = 0;; grp++) {
-            float a_next = load_a(grp + 1), f_next = load_f(grp + 1);      // (clamped: harmless past the end)
-            // half 0 of the group -> buffer A (the previous turn's lookups, half 1 of the group before, sit in buffer B)
-            const int n0 = coarse(a_op, std::integral_constant<int, 0>());
-            tally(wB, bitB);
-            if (grp > 0) put(grp - 1);
-            else { acc_in = 0u; acc_out = 0u; }
-            // the next group's operands have arrived by now (a coarse phase ago) and nothing else is in flight: taken here, before
-            // the overflow loop, whose loads the compiler cannot count
-            asm volatile("" : "+v"(a_next), "+v"(f_next));
-            if (lane < 48) wrec[lane] = f_op;      // this group's fine maps (the lookups of the group before are out)
-            overflow(n0, wB, bitB);
-            lookup(0, n0, wA, bitA);
-            // half 1 -> buffer B
-            const int n1 = coarse(a_op, std::integral_constant<int, 1>());
-            tally(wA, bitA);
-            overflow(n1, wA, bitA);
-            lookup(0, n1, wB, bitB);
-            if (pair_of(grp + 1, 0) >= n_pairs) {      // wave-uniform
-                tally(wB, bitB);
-                put(grp);
-                break;
-            }
-            a_op = valid_a(grp + 1) ? a_next : 0.f;
-            f_op = f_next;
-        }
-    }
-    __syncthreads();
-    for (int i = threadIdx.x; i < nbins; i += PB_THREADS)
-        if (lh[i]) atomicAdd(&hist[i], lh[i]);
-}
-
 // T = the k-th largest lower bound (from its histogram; 0 when there are fewer than k pairs), then the pairs whose upper bound
 // reaches it, in no particular order.  Every workgroup derives T for itself, as k_tie_chunks does.
 __global__ __launch_bounds__(256) void k_prune_select(const int32_t *__restrict__ status_in, int64_t cap_pairs, const int32_t *__restrict__ hist,
@@ -2496,7 +2287,8 @@ static void pose_plan(const mad_ctx *ctx, int l_hi_max, int n_cloud, const doubl
         PoseBits &Bc = P.PC.B;
         // beside the bitmap: the float32 hi cloud and one queue of 2-byte point ids per wave
         const int nb_sets = (l_hi_max + MAD_WAVE - 1) / MAD_WAVE;
-        // (clouds of up to 8 sets go through k_pose_bounds_mx: a queue of 2 nbv sets + the dump slots and four fine maps per wave)
+        // (clouds of up to 8 sets: room for a queue of 2 nbv sets + the dump slots and four fine maps per wave -- more than k_pose_bounds
+        // takes; it is the budget their coarse voxel was sized and measured with, and changing it would change that voxel)
         const size_t q_sets = nb_sets <= 8 ? (size_t)2 * ((nb_sets + 1) & ~1) + 1 : (size_t)((nb_sets + 1) & ~1) + 5;      // else: up to 4 sets of rounding (nbv) + the dump slots
         const size_t budget = (size_t)150 * 1024 - pad16((size_t)(l_hi_max + 4) * 16) - (size_t)(PB_THREADS / MAD_WAVE) * (q_sets * MAD_WAVE * 2 + 192) - pad16((size_t)(l_hi_max + 1) * 4) - 64;
         size_t n_words_c = 0;
@@ -2649,10 +2441,6 @@ static int pose_device(mad_ctx *ctx, const Side &hi, const Side &lo, int32_t *d_
                 MAD_HIP(hipFuncSetAttribute((const void *)k_pose_bounds<12, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 155 * 1024));
                 MAD_HIP(hipFuncSetAttribute((const void *)k_pose_bounds<16, false>, hipFuncAttributeMaxDynamicSharedMemorySize, 155 * 1024));
                 MAD_HIP(hipFuncSetAttribute((const void *)k_pose_bounds<16, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 155 * 1024));
-                MAD_HIP(hipFuncSetAttribute((const void *)k_pose_bounds_mx<2>, hipFuncAttributeMaxDynamicSharedMemorySize, 155 * 1024));
-                MAD_HIP(hipFuncSetAttribute((const void *)k_pose_bounds_mx<4>, hipFuncAttributeMaxDynamicSharedMemorySize, 155 * 1024));
-                MAD_HIP(hipFuncSetAttribute((const void *)k_pose_bounds_mx<6>, hipFuncAttributeMaxDynamicSharedMemorySize, 155 * 1024));
-                MAD_HIP(hipFuncSetAttribute((const void *)k_pose_bounds_mx<8>, hipFuncAttributeMaxDynamicSharedMemorySize, 155 * 1024));
                 attr_b = true;
             }
             // two launches of the bounds kernel, best-scoring pairs first: the second abandons pairs early (k_pose_bounds)
@@ -2675,25 +2463,7 @@ static int pose_device(mad_ctx *ctx, const Side &hi, const Side &lo, int32_t *d_
             // (T_stop and the ticket of phase 1, hist2[nbins + 1] and [nbins + 2], must lie inside the zero-filled region of the match)
             static_assert(3 <= 17, "hist2 has l_hi_max + 17 words (zr_hist2): bins 0 .. l_hi_max, then T_stop and the ticket");
             if (split && nbins + 3 > l_hi_max + 17) return mad_fail(ctx, MAD_EINVAL, "pose bounds: %d bins for %d hi anchors", nbins, l_hi_max);
-            // one phase, at most 8 sets: the coarse map on the matrix cores (k_pose_bounds_mx; MAD_POSE_MX=0: the vector form)
-            // Built for the round-3 review and measured slower on C3 (32.4 against 29.2 us per launch for clouds of 7-8 sets, 25.5 against 26.2
-            // for 6; DESIGN.md section 6d: the coarse phase loses 7 of its 26 vector instructions per 64 points, the fine phase -- whose map
-            // now is a per-lane operand read from LDS -- gains as many per 64 points again): OFF unless mad_set_option "pose_mx" (MAD_POSE_MX=1).
-            const bool mx = ctx->pose_mx != 0 && !split && nbv <= 8;
-            if (mx) {
-                const size_t lds_mx = pad16((size_t)PC.n_words * 4) + pad16((size_t)(l_hi_max + 4) * 16) +
-                                      (size_t)(PB_THREADS / MAD_WAVE) * ((size_t)(2 * nbv + 1) * MAD_WAVE * 2 + 192) + pad16((size_t)nbins * 4) + 16;
-                if (lds_mx > (size_t)155 * 1024) return mad_fail(ctx, MAD_EINVAL, "pose bounds: %zu bytes of LDS", lds_mx);
-#define MAD_PBX_LAUNCH(NBV)                                                                                                                        \
-    hipLaunchKernelGGL((k_pose_bounds_mx<NBV>), dim3(ctx->n_cu), dim3(PB_THREADS), lds_mx, ctx->stream, d_status, cap_pairs, d_rec, d_hi_cloud, B, \
-                       d_bits, PC, d_bits_c, scratch<int32_t>(ctx, S_COUNTS), scratch<unsigned short>(ctx, S_TMP_C), hist2, nbins)
-                if (nbv == 2) MAD_PBX_LAUNCH(2);
-                else if (nbv == 4) MAD_PBX_LAUNCH(4);
-                else if (nbv == 6) MAD_PBX_LAUNCH(6);
-                else MAD_PBX_LAUNCH(8);
-#undef MAD_PBX_LAUNCH
-            }
-            for (int pass = 0; pass < (mx ? 0 : (split ? 2 : 1)); pass++) {
+            for (int pass = 0; pass < (split ? 2 : 1); pass++) {
                 const int pb_phase = split ? pass + 1 : 0;
                 const int64_t pb_stop = split ? prune_k : 0;      // phase 1 leaves T_stop for phase 2 (hist2[nbins + 1]; [nbins + 2]: its workgroups' tickets)
                 if (split) {
@@ -2980,7 +2750,7 @@ extern "C" void mad_set_destroy(mad_ctx *ctx, mad_set *s) {
         if (ctx->match.shard_lo == s) ctx->match.shard_lo = nullptr;
     }
     DevBuf *bufs[] = {&s->anc_blob, &s->row_anchor, &s->row_main, &s->row_sec, &s->row_R, &s->row_Rinv, &s->row_meta, &s->dsc,
-                      &s->dsc8, &s->norm, &s->rsum, &s->row_perm, &s->row_rec, &s->anc_rows, &s->cell_start, &s->cell_pts, &s->cell_ids};      // anc_* and dev_n are views
+                      &s->dsc8, &s->norm, &s->rsum, &s->row_perm, &s->row_rec, &s->cell_start, &s->cell_pts, &s->cell_ids};      // anc_* and dev_n are views
     for (DevBuf *b : bufs) mad_release(*b);
     if (s->host_stage) (void)hipHostFree(s->host_stage);
     if (s->ready) (void)hipEventDestroy(s->ready);
@@ -3009,10 +2779,6 @@ static int set_rows(mad_ctx *ctx, const mad_set *cs, int64_t *n_rows) {
             J.d_row_anchor = (const int32_t *)s->row_anchor.p; J.d_row_R = (const double *)s->row_R.p; J.d_row_Rinv = (const double *)s->row_Rinv.p;
             J.d_row_perm = s->last_perm ? (const int32_t *)s->row_perm.p : nullptr;
             J.d_row_rec = s->last_rec ? (const DscRowRec *)s->row_rec.p : nullptr;
-            if (s->last_perm && s->last_rec && s->anc_rows.p && s->ball_dims[0] > 0 && s->ball_dims[0] == s->last_f[1].nx &&
-                s->ball_dims[1] == s->last_f[1].ny && s->ball_dims[2] == s->last_f[1].nz) {
-                J.d_anc_rows = (const int32_t *)s->anc_rows.p; J.n_anchors = s->n_anchors; J.n_rowwise = s->n_rowwise; J.fan = s->last_fan;
-            }
             J.d_n_rows = (const int32_t *)s->dev_n.p; J.grid_rows = s->cap_rows; J.d_overflow = (int32_t *)s->dev_n.p + 3;
             J.d_dsc = (int16_t *)s->dsc.p; J.d_dsc8 = (int8_t *)s->dsc8.p; J.d_norm = (double *)s->norm.p;
             J.d_rsum = s->wide ? (int32_t *)s->rsum.p : nullptr;
@@ -3034,12 +2800,9 @@ static int set_rows(mad_ctx *ctx, const mad_set *cs, int64_t *n_rows) {
     return MAD_OK;
 }
 
-// ball_dims (nullable): the base-octave grid; base-octave anchors whose sample ball lies inside it (mad_ball_interior) are sorted
-// behind all others in working order -- k_describe_ball takes them, s->n_rowwise anchors stay with k_describe
 static int set_upload_anchors(mad_ctx *ctx, mad_set *s, const int32_t *anc_coords, const int32_t *anc_octave,
-                              const double *anc_subv, const int32_t *anc_index, int n, int32_t rows0 = 0, const int *ball_dims = nullptr) {
+                              const double *anc_subv, const int32_t *anc_index, int n, int32_t rows0 = 0) {
     s->n_anchors = n;
-    const int bd[3] = {ball_dims && anc_coords ? ball_dims[0] : 0, ball_dims && anc_coords ? ball_dims[1] : 0, ball_dims && anc_coords ? ball_dims[2] : 0};
     s->gen++;
     const size_t m = (size_t)(n > 0 ? n : 1);
     const size_t o_subv = 64, o_coords = o_subv + m * 24, o_oct = o_coords + m * 12, o_idx = o_oct + m * 4, o_canon = o_idx + m * 4,
@@ -3067,7 +2830,6 @@ static int set_upload_anchors(mad_ctx *ctx, mad_set *s, const int32_t *anc_coord
     // The same anchors as last time (a set rebuilt in place, step after step): the staging buffer and the device copy already
     // hold them -- only the counters are reset.  Decided by comparing the bytes, not by trusting the caller.
     const bool same = n > 0 && s->staged_n == n && s->staged_coords == (anc_coords != nullptr) && blob_before == s->anc_blob.p &&
-                      bd[0] == s->ball_dims[0] && bd[1] == s->ball_dims[1] && bd[2] == s->ball_dims[2] &&
                       memcmp(h + o_subv, anc_subv, (size_t)n * 24) == 0 && (!anc_coords || memcmp(h + o_coords, anc_coords, (size_t)n * 12) == 0) &&
                       memcmp(h + o_oct, anc_octave, (size_t)n * 4) == 0 && memcmp(h + o_idx, anc_index, (size_t)n * 4) == 0;
     memset(h, 0, 64);      // the device counters start from zero
@@ -3080,8 +2842,6 @@ static int set_upload_anchors(mad_ctx *ctx, mad_set *s, const int32_t *anc_coord
         return MAD_OK;
     }
     s->staged_n = n; s->staged_coords = anc_coords != nullptr;
-    s->ball_dims[0] = bd[0]; s->ball_dims[1] = bd[1]; s->ball_dims[2] = bd[2];
-    s->n_rowwise = n;
     if (n > 0) {
         memcpy(h + o_subv, anc_subv, (size_t)n * 24);
         if (anc_coords) memcpy(h + o_coords, anc_coords, (size_t)n * 12);
@@ -3147,17 +2907,13 @@ static int set_upload_anchors(mad_ctx *ctx, mad_set *s, const int32_t *anc_coord
                 v = (v | v << 4) & 0x10c30c30c30c30c3ull; v = (v | v << 2) & 0x1249249249249249ull;
                 return v;
             };
-            bool small = packable;      // coordinates below 2^12 (after the octave's shift): class (2 bits) | Morton (36 bits) | number (24 bits) in one word
+            bool small = packable;      // coordinates below 2^12 (after the octave's shift): octave (the top 2 bits; bit 62) | Morton (36 bits) | number (24 bits) in one word
             for (int i = 0; i < n; i++) {
                 const int sh = anc_octave[i] == 0 ? 1 : 0;      // the same physical cell size in both octaves
                 const uint64_t x = (uint64_t)std::max(anc_coords[3 * i], 0) >> sh, y = (uint64_t)std::max(anc_coords[3 * i + 1], 0) >> sh,
                                z = (uint64_t)std::max(anc_coords[3 * i + 2], 0) >> sh;
-                // (bit 63: a base-octave anchor whose ball of samples lies inside the grid -- k_describe_ball's, behind all others)
-                const bool ball = bd[0] > 0 && anc_octave[i] == 1 &&
-                                  mad_ball_interior(anc_coords[3 * i], anc_coords[3 * i + 1], anc_coords[3 * i + 2], bd[0], bd[1], bd[2]);
-                if (ball) s->n_rowwise--;
                 small = small && (x | y | z) < 4096;
-                keys[i] = ((uint64_t)ball << 63) | ((uint64_t)(anc_octave[i] != 0) << 62) | ((spread(x) << 2 | spread(y) << 1 | spread(z)) & ~(3ull << 62));
+                keys[i] = ((uint64_t)(anc_octave[i] != 0) << 62) | ((spread(x) << 2 | spread(y) << 1 | spread(z)) & ~(3ull << 62));
             }
             if (small) {      // equal keys (anchors in one cell) keep their list order, as below: the number is the low end of the word
                 for (int i = 0; i < n; i++) keys[i] = (keys[i] & (3ull << 62)) | ((keys[i] & ((1ull << 36) - 1)) << 24) | (uint64_t)i;
@@ -3293,15 +3049,10 @@ extern "C" int mad_set_build_many(mad_ctx *ctx, int n_sets, mad_set *const *sets
     for (int i = 0; i < n_sets; i++) {
         mad_set *s = sets[i];
         const int n = n_anchors[i];
-        // (r = 8, the default patch: the only size k_describe_ball is built for)
-        const int bdims[3] = {oj[i].f[1].nx, oj[i].f[1].ny, oj[i].f[1].nz};
-        const bool sort_ball = ctx->dsc_ball && r == 8 && oj[i].f[1].tex4 != nullptr && ctx->spatial_order;
-        MAD_TRY(set_upload_anchors(ctx, s, anc_coords[i], anc_octave[i], anc_subv[i], anc_index[i], n, 0, sort_ball ? bdims : nullptr));
+        MAD_TRY(set_upload_anchors(ctx, s, anc_coords[i], anc_octave[i], anc_subv[i], anc_index[i], n));
         s->D = 64 * ctx->eq_host[1].Z;
         s->wide = r >= MAD_WIDE_FROM_R;      // a sub-region holds more samples than an int8 count: centred rows (mad_common.h)
         MAD_TRY(set_reserve_rows(ctx, s, (int64_t)n * lim_main * lim_sec));
-        MAD_TRY(mad_reserve(ctx, s->anc_rows, (size_t)(n > 0 ? n : 1) * MAD_ANCROW_WORDS * 4));
-        s->last_fan = lim_main * lim_sec;
         OrientJob &J = oj[i];
         J.d_coords = (const int32_t *)s->anc_coords.p; J.d_octave = (const int32_t *)s->anc_octave.p; J.uniform_octave = 0; J.n = n;
         OrientOut &out = J.out;
@@ -3313,17 +3064,12 @@ extern "C" int mad_set_build_many(mad_ctx *ctx, int n_sets, mad_set *const *sets
         out.anc_order = ctx->spatial_order ? (const int32_t *)s->anc_order.p : nullptr;
         out.row_perm = ctx->spatial_order ? (int32_t *)s->row_perm.p : nullptr;
         out.row_rec = (DscRowRec *)s->row_rec.p;
-        out.anc_rows = out.anc_order && sort_ball ? (int32_t *)s->anc_rows.p : nullptr;
         out.counters_zeroed = true;
         DescribeJob &Q = dj[i];
         Q.f[0] = J.f[0]; Q.f[1] = J.f[1];
         Q.d_anc_coords = J.d_coords; Q.d_anc_octave = J.d_octave; Q.uniform_octave = 0;
         Q.d_row_anchor = out.row_anchor; Q.d_row_R = out.row_R; Q.d_row_Rinv = out.row_Rinv; Q.d_row_perm = out.row_perm; Q.d_n_rows = out.d_n_rows;
         Q.d_row_rec = out.row_rec;
-        // the anchors sorted behind n_rowwise go through k_describe_ball (when the sort was made for this base-octave grid)
-        if (out.anc_rows && s->ball_dims[0] == bdims[0] && s->ball_dims[1] == bdims[1] && s->ball_dims[2] == bdims[2] && s->ball_dims[0] > 0) {
-            Q.d_anc_rows = out.anc_rows; Q.n_anchors = n; Q.n_rowwise = s->n_rowwise; Q.fan = lim_main * lim_sec;
-        }
         s->last_perm = out.row_perm != nullptr;
         s->last_rec = out.row_rec != nullptr;
         // the describe launch is sized from the row count of this set's previous build when there is one
@@ -3848,10 +3594,6 @@ extern "C" int mad_set_option(mad_ctx *ctx, const char *name, double value) {
         ctx->pose_split_min = (int64_t)value;
         return MAD_OK;
     }
-    if (!strcmp(name, "pose_mx")) {      // 1: the bounds pass of clouds of up to 512 points with its coarse map on the matrix cores (k_pose_bounds_mx)
-        ctx->pose_mx = value != 0 ? 1 : 0;
-        return MAD_OK;
-    }
     if (!strcmp(name, "pose_split")) {      // -1: on for hi clouds of more than 512 points (default), 0: off, 1: on
         ctx->pose_split = value < 0 ? -1 : (value != 0 ? 1 : 0);
         return MAD_OK;
@@ -3859,10 +3601,6 @@ extern "C" int mad_set_option(mad_ctx *ctx, const char *name, double value) {
     if (!strcmp(name, "ori_queue") || !strcmp(name, "dsc_queue")) {      // test hooks: a small cap drives the kernels' full-queue paths
         if (!(value >= 0) || !(value < 1e9)) return mad_fail(ctx, MAD_EINVAL, "mad_set_option: %s = %g", name, value);
         (name[0] == 'o' ? ctx->ori_queue_cap : ctx->dsc_queue_cap) = (int)value;
-        return MAD_OK;
-    }
-    if (!strcmp(name, "dsc_ball")) {      // 1: the base-octave anchors through k_describe_ball; 0 (default): every row through k_describe
-        ctx->dsc_ball = value != 0;
         return MAD_OK;
     }
     return mad_fail(ctx, MAD_EINVAL, "mad_set_option: unknown option '%s'", name);

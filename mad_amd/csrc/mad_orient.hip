@@ -481,23 +481,17 @@ struct RowsArgs {
     int32_t *perm_off;             // with order: n + 1 row offsets in working order
     int32_t *row_perm;             // with order: the rows in working order
     DscRowRec *row_rec;            // nullable: what k_describe starts a row from, in working order
-    int32_t *anc_rows;             // nullable: per anchor in working order MAD_ANCROW_WORDS ints {position of its first row in working order, rows, voxel coordinates}
     const int32_t *coords;         // with row_rec: the anchors' voxel coordinates
     int uniform_octave;            // ... and their octave when anc_octave is null
 };
 
 // the record of one row (k_describe reads it with one 128-byte load); inv = inv(Rfinal), still in the thread's registers
-__device__ __forceinline__ void put_row_rec(const RowsArgs &A, int64_t pos, int row, int a, const double *inv, const double *R) {
+__device__ __forceinline__ void put_row_rec(const RowsArgs &A, int64_t pos, int row, int a, const double *inv) {
     DscRowRec &q = A.row_rec[pos];
     q.row = row;
     q.c[0] = A.coords[3 * a]; q.c[1] = A.coords[3 * a + 1]; q.c[2] = A.coords[3 * a + 2];
     q.octave = A.anc_octave ? A.anc_octave[a] : A.uniform_octave;
     for (int i = 0; i < 9; i++) q.inv[i] = inv[i];
-    if (!A.anc_rows) return;      // (only k_describe_ball reads the rest)
-    // the float32 values k_describe's threads form for themselves, once per row
-    for (int i = 0; i < 9; i++) q.hf[i] = (float)inv[i];
-    for (int i = 0; i < 9; i++) q.rf[i] = i < 6 ? (float)R[i] : (float)R[i] * (1.0f / 511.0f);
-    for (int i = 0; i < 3; i++) q.ru[i] = (float)R[6 + i];
 }
 
 // row offsets of every job: exclusive scan of its anchors' row counts, one workgroup per job
@@ -548,10 +542,6 @@ __global__ __launch_bounds__(256) void k_orient_rows(Batch<RowsArgs> B, int fan,
     if (p >= A.n) return;
     const int a = A.order ? A.order[p] : p;
     const int c = A.slot_cnt[a];
-    if (s == 0 && A.anc_rows) {
-        int32_t *q = A.anc_rows + MAD_ANCROW_WORDS * (int64_t)p;
-        q[0] = A.order ? A.perm_off[p] : A.row_off[a]; q[1] = c; q[2] = A.coords[3 * a]; q[3] = A.coords[3 * a + 1]; q[4] = A.coords[3 * a + 2];
-    }
     if (s >= c) return;
     const int64_t row = (int64_t)A.row_off[a] + s;
     if (A.order) A.row_perm[A.perm_off[p] + s] = (int32_t)row;
@@ -571,7 +561,7 @@ __global__ __launch_bounds__(256) void k_orient_rows(Batch<RowsArgs> B, int fan,
     if (A.row_Rinv)
         for (int i = 0; i < 9; i++) A.row_Rinv[9 * row + i] = inv9[i];
     if (A.row_meta) { A.row_meta[3 * row] = A.anc_index[a]; A.row_meta[3 * row + 1] = A.anc_octave[a]; A.row_meta[3 * row + 2] = mb; }
-    if (A.row_rec) put_row_rec(A, A.order ? A.perm_off[p] + s : row, (int)row, a, inv9, R9);
+    if (A.row_rec) put_row_rec(A, A.order ? A.perm_off[p] + s : row, (int)row, a, inv9);
 }
 
 // k_orient_scan + k_orient_rows in ONE launch (round 3): every workgroup forms the exclusive scan of its job's
@@ -583,7 +573,9 @@ __global__ __launch_bounds__(256) void k_orient_rows(Batch<RowsArgs> B, int fan,
 // (256 threads since round 4: a 1 024-thread workgroup needs half a CU's wave slots at once, and beside the k_describe workgroups of
 // other lanes -- 24 of a CU's 32 waves -- it waited for them: 42 us per launch in the overlapped run against 10 alone)
 #define ORS_THREADS 256
-__global__ __launch_bounds__(ORS_THREADS) void k_orient_rows_scan(Batch<RowsArgs> B, int fan, int lim_main, const EqspDev *eq) {
+// (eight waves per SIMD asked for: without a target the scheduler lets the register count of this kernel drift between 70 and 74
+// from one build to the next -- seven waves or six -- over changes elsewhere in the file; with it, 55 and no scratch)
+__global__ __launch_bounds__(ORS_THREADS, 8) void k_orient_rows_scan(Batch<RowsArgs> B, int fan, int lim_main, const EqspDev *eq) {
     extern __shared__ __align__(16) int s_off[];
     __shared__ int wt[ORS_THREADS / MAD_WAVE + 1];
     __shared__ int s_perm[ORS_THREADS];
@@ -614,10 +606,6 @@ __global__ __launch_bounds__(ORS_THREADS) void k_orient_rows_scan(Batch<RowsArgs
     if (pl >= ppb || pp >= n) return;
     const int a = A.order ? A.order[pp] : pp;
     const int c = A.slot_cnt[a];
-    if (sl == 0 && A.anc_rows) {
-        int32_t *q = A.anc_rows + MAD_ANCROW_WORDS * (int64_t)pp;
-        q[0] = s_perm[pl]; q[1] = c; q[2] = A.coords[3 * a]; q[3] = A.coords[3 * a + 1]; q[4] = A.coords[3 * a + 2];
-    }
     if (sl >= c) return;
     const int64_t row = (int64_t)s_off[a] + sl;
     if (A.order) A.row_perm[s_perm[pl] + sl] = (int32_t)row;
@@ -637,7 +625,7 @@ __global__ __launch_bounds__(ORS_THREADS) void k_orient_rows_scan(Batch<RowsArgs
     if (A.row_Rinv)
         for (int i = 0; i < 9; i++) A.row_Rinv[9 * row + i] = inv9[i];
     if (A.row_meta) { A.row_meta[3 * row] = A.anc_index[a]; A.row_meta[3 * row + 1] = A.anc_octave[a]; A.row_meta[3 * row + 2] = mb; }
-    if (A.row_rec) put_row_rec(A, A.order ? s_perm[pl] + sl : row, (int)row, a, inv9, R9);
+    if (A.row_rec) put_row_rec(A, A.order ? s_perm[pl] + sl : row, (int)row, a, inv9);
 }
 
 // Runs a1-a8 for the anchor lists of n_jobs structures (coordinates and octaves already on the device) in one k_orient
@@ -692,7 +680,6 @@ static int orient_batch(mad_ctx *ctx, int n_jobs, const OrientJob *jobs, int r, 
         Q.n_rows = J.out.d_n_rows;
         Q.order = A.order; Q.perm_off = scratch<int32_t>(ctx, S_PERM_OFF) + a0 + j; Q.row_perm = J.out.row_perm;
         Q.row_rec = J.out.row_rec; Q.coords = J.d_coords; Q.uniform_octave = J.uniform_octave;
-        Q.anc_rows = J.out.anc_rows;
         if (!Q.anc_octave) Q.anc_octave = J.d_octave;
         R.first[j] = (int)blk;
         a0 += J.n;
@@ -848,7 +835,6 @@ struct DescribeArgs {
     const DscRowRec *row_rec;      // nullable: the k-th record = everything the k-th row in working order starts from
     int queue_cap;                 // entries of the undecided-sample queue in use (<= its size)
     const int32_t *n_rows;         // device: number of rows
-    const int32_t *row_limit;      // device, nullable: this launch takes the first *row_limit rows in working order only (the rest: k_describe_ball)
     int32_t *overflow;             // device: set when the launch was sized for fewer rows than *n_rows
     int r;
     const EqspDev *eq;
@@ -981,8 +967,7 @@ __global__ __launch_bounds__(DSC_NT(S), TAB ? DSC_OCC_TAB : DSC_OCC) void k_desc
     // neighbours in the anchor list and sample the same neighbourhood: running side by side on ONE XCD
     // they meet in its L2.  The row count lives on the device; the grid is an upper bound of it.
     const int64_t n_rows = *A.n_rows;
-    const int64_t n_work = A.row_limit ? (int64_t)*A.row_limit : n_rows;
-    const int64_t chunk = (n_work + 7) / 8;
+    const int64_t chunk = (n_rows + 7) / 8;
     const int tid = threadIdx.x;
     if (8 * chunk > (int64_t)gdim) {      // the launch was sized from a stale hint: tell the host
         if (bid == 0 && tid == 0) *A.overflow = 1;
@@ -998,7 +983,7 @@ __global__ __launch_bounds__(DSC_NT(S), TAB ? DSC_OCC_TAB : DSC_OCC) void k_desc
         }
     }
     const int64_t work = (int64_t)(bid & 7) * chunk + (bid >> 3);
-    if ((int64_t)(bid >> 3) >= chunk || work >= n_work) return;
+    if ((int64_t)(bid >> 3) >= chunk || work >= n_rows) return;
     DSC_STAMP(0);
     if (TAB) { stage_lds(&tab, &A.eq->tab, sizeof(EqspTabLds)); stage_lds(&fast_s, &A.eq->image, sizeof(fast_s)); }
     else eqsp_fast_stage(A.eq, (EqspFastLds *)&fast_s);
@@ -1293,420 +1278,6 @@ __global__ __launch_bounds__(DSC_NT(S), TAB ? DSC_OCC_TAB : DSC_OCC) void k_desc
     DSC_STAMP(7);
 }
 
-// ---------------------------------------------------------------------------
-// descriptor kernel of the base octave: the anchor's ball of 4-byte texels in LDS (round 4)
-// ---------------------------------------------------------------------------
-// k_describe runs at the rate its gathers are accepted: ~3.3 clocks per scattered lane-load per CU, whatever the lanes' addresses have
-// in common, 4 096 of them per row.  In the base octave (Descriptor.py:35: lattice -7.5 .. 7.5 voxels) every
-// sample of every row of an anchor lies within 7.5 sqrt(3) = 12.99 voxels of it, so its nearest voxel d satisfies
-// sum_i max(|d_i| - 0.5, 0)^2 <= 168.75: 11 027 texels = 43 KB as 4-byte texels.  One 1 024-thread workgroup per (anchor, run of
-// DSCB_RPB rows) fetches that ball ONCE with coalesced loads (z-runs of up to 27 consecutive texels) and samples the rows from LDS:
-// a thread owns four samples of a row -- one (j, k) column, a quarter of the i axis = one sub-region -- and the rows go through
-// one after the other, one barrier each: histogram of row r (packed, two 16-bit counters per word: a count is <= 64) | barrier |
-// the samples the table left open (their 16-byte texels from global memory, the float32 / float64 tiers, as in k_describe) and,
-// by one wave, the write-out of row r - 1.  Same arithmetic per sample as k_describe<16, 64, 16, true>: same descriptors, bit for bit.
-// (The upsampled octave's ball is 53^3 texels: it does not fit, and stays with k_describe.)
-#define DSCB_THREADS 1024
-#define DSCB_M 13
-#define DSCB_SIDE (2 * DSCB_M + 1)
-#define DSCB_COLS (DSCB_SIDE * DSCB_SIDE)
-#define DSCB_E2MAX 676                  // voxel d is in the ball iff sum_i max(2 |d_i| - 1, 0)^2 <= 4 (7.5 sqrt(3) + 0.01)^2 = 676.04
-#define DSCB_NBALL 11027
-#define DSCB_RPB 4                      // rows of an anchor one workgroup takes, four waves each (an anchor of n rows: ceil(n / 4) workgroups, each with its own ball)
-#define DSCB_FAST_BYTES ((offsetof(EqspFastLds, dir) + 15) / 16 * 16)
-#define DSCB_OFF_TAB ((DSCB_NBALL + 3) / 4 * 16)
-#define DSCB_OFF_FAST (DSCB_OFF_TAB + sizeof(EqspTabLds))
-#define DSCB_OFF_COL (DSCB_OFF_FAST + DSCB_FAST_BYTES)
-#define DSCB_COL_BYTES ((DSCB_COLS * 2 + 15) / 16 * 16)
-#define DSCB_OFF_HIST (DSCB_OFF_COL + DSCB_COL_BYTES)
-#define DSCB_OFF_Q (DSCB_OFF_HIST + DSCB_RPB * 512 * 4)
-#define DSCB_OFF_FLAGS (DSCB_OFF_Q + DSCB_RPB * 256 * 4)
-#define DSCB_ROWC 24                    // floats of a row's constants in LDS (21 used)
-#define DSCB_OFF_ROWC (DSCB_OFF_FLAGS + 64)      // (wtot: one int per wave)
-#define DSCB_OFF_ROWD (DSCB_OFF_ROWC + DSCB_RPB * DSCB_ROWC * 4 + 16)      // behind the constants: the rows' indices (4 ints)
-#define DSCB_LDS_BYTES (DSCB_OFF_ROWD + DSCB_RPB * 9 * 8)
-static_assert(DSCB_LDS_BYTES <= 80 * 1024, "two workgroups of k_describe_ball per CU");
-
-// half-length of the z-run of column (cx, cy) of the ball (its voxels: z = DSCB_M - h .. DSCB_M + h), or -1
-__host__ __device__ __forceinline__ int dscb_col_h(int cx, int cy) {
-    const int ax = cx > DSCB_M ? cx - DSCB_M : DSCB_M - cx, ay = cy > DSCB_M ? cy - DSCB_M : DSCB_M - cy;
-    const int ex = ax > 0 ? 2 * ax - 1 : 0, ey = ay > 0 ? 2 * ay - 1 : 0;
-    const int rem = DSCB_E2MAX - ex * ex - ey * ey;
-    if (rem < 0) return -1;
-    const int sq = (int)__builtin_sqrtf((float)rem + 0.5f);      // floor(sqrt(rem)): rem <= 676, the square root is correctly rounded
-    return (sq + 1) >> 1;                                         // max(2 |dz| - 1, 0) <= sq
-}
-
-
-// The float64 tier of k_describe_ball, out of line: inlined, its float64 temporaries (and the loop invariants the optimiser
-// hoists for them) would set the register count of a kernel that has 64 registers per thread.
-__device__ __noinline__ int dscb_describe_exact(const EqspFastLds *eq, float tx, float ty, float tz, float tw, const double *R) {
-    return describe_exact(eq, make_float4(tx, ty, tz, tw), R);
-}
-typedef const __attribute__((address_space(4))) DscRowRec *dscb_rec_t;      // records and rotations were written by earlier launches:
-typedef const __attribute__((address_space(4))) double *dscb_f64_t;         // constant for this kernel -> scalar loads
-
-struct DescribeBallArgs {
-    FieldDev f;                    // the base octave's field
-    const DscRowRec *row_rec;      // the rows' records in working order
-    const int32_t *anc_rows;       // per anchor in working order: {position of its first row, rows}
-    const double *row_R;           // n_rows x 9
-    int n_base, n_rowwise;         // anchors of this kernel, and the anchors before them in working order (k_describe's)
-    const EqspDev *eq;
-    int32_t *overflow;             // device: -2 when an anchor that is not interior arrives here
-    const unsigned *colinfo;       // mad_ctx::ball_colinfo
-    int16_t *dsc;                  // n_rows x 1024
-    int8_t *dsc8;                  // nullable
-    double *norm;
-};
-
-#ifdef MAD_PROBE_STAMPS      // diagnostic build: s_memtime at the phases of every workgroup (tools/probe_ball.py)
-__device__ long long dscb_stamps[16384 * 8];
-__device__ int dscb_stamp_rows[16384];
-__device__ int dscb_stamp_n;
-__device__ int dscb_dbg[16384 * 4];      // per workgroup: longest dscb_exact_voxel / dscb_describe_exact call of the drain (ticks), calls of each
-extern "C" int mad_debug_dscb_dbg(int *out, int n) { return hipMemcpyFromSymbol(out, HIP_SYMBOL(dscb_dbg), (size_t)n * 16) == hipSuccess ? 0 : -1; }
-__device__ long long dscb_real[16384 * 2];      // s_memrealtime (100 MHz, one clock for the whole device) at a workgroup's start and end
-extern "C" int mad_debug_dscb_real(long long *out, int n) { return hipMemcpyFromSymbol(out, HIP_SYMBOL(dscb_real), (size_t)n * 16) == hipSuccess ? 0 : -1; }
-#define DSCB_STAMP(k) do { __builtin_amdgcn_sched_barrier(0); if (threadIdx.x == 0 && st_slot < 16384) dscb_stamps[st_slot * 8 + (k)] = __builtin_amdgcn_s_memtime(); __builtin_amdgcn_sched_barrier(0); } while (0)
-extern "C" int mad_debug_dscb_stamps(long long *out, int *rows, int n) {
-    int used = 0;
-    if (hipMemcpyFromSymbol(&used, HIP_SYMBOL(dscb_stamp_n), 4) != hipSuccess) return -1;
-    if (hipMemcpyFromSymbol(out, HIP_SYMBOL(dscb_stamps), (size_t)n * 64) != hipSuccess) return -1;
-    if (hipMemcpyFromSymbol(rows, HIP_SYMBOL(dscb_stamp_rows), (size_t)n * 4) != hipSuccess) return -1;
-    const int zero = 0;
-    if (hipMemcpyToSymbol(HIP_SYMBOL(dscb_stamp_n), &zero, 4) != hipSuccess) return -1;
-    return used;
-}
-#else
-#define DSCB_STAMP(k) do { } while (0)
-#endif
-__global__ __launch_bounds__(DSCB_THREADS, 8) void k_describe_ball(Batch<DescribeBallArgs> B, int chunks) {
-    extern __shared__ __align__(16) unsigned char dscb_lds[];
-    const int job = batch_job(B, (int)blockIdx.x);
-    const DescribeBallArgs &A = B.job[job];
-    const int bid = (int)blockIdx.x - B.first[job];
-    // workgroup -> (run of rows, anchor): the FIRST runs of all anchors come first in the grid (most anchors have no second one), and
-    // within a run the anchors are dealt so that each XCD (workgroups b, b + 8, ...) gets a contiguous stretch of the Morton order
-    const int per = (A.n_base + 7) / 8, nbp = per * 8;
-    const int ch = bid / nbp, bi = bid - ch * nbp;
-    const int slot = (bi & 7) * per + (bi >> 3);
-    if (ch >= chunks || slot >= A.n_base) return;
-    // one scalar load: where the anchor's rows lie and where the anchor is (written by k_orient_rows* of this build: constant here)
-    typedef const __attribute__((address_space(4))) int32_t *ci32_t;
-    const ci32_t an = (ci32_t)(A.anc_rows + MAD_ANCROW_WORDS * (int64_t)(A.n_rowwise + slot));
-    const int pos0 = an[0], cnt = an[1], ic0 = an[2], ic1 = an[3], ic2 = an[4];
-    const int r_begin = ch * DSCB_RPB;
-    if (r_begin >= cnt) return;
-    const int n_here = min(cnt - r_begin, DSCB_RPB);      // rows of this workgroup: r_begin .. r_begin + n_here - 1 of the anchor
-#ifdef MAD_PROBE_STAMPS
-    __shared__ int st_slot_s;
-    if (threadIdx.x == 0) { st_slot_s = atomicAdd(&dscb_stamp_n, 1); if (st_slot_s < 16384) dscb_stamp_rows[st_slot_s] = n_here; }
-    __syncthreads();
-    const int st_slot = st_slot_s;
-    __shared__ int dbg_s[4];
-    if (threadIdx.x < 4) dbg_s[threadIdx.x] = 0;
-    if (threadIdx.x == 0 && st_slot < 16384) dscb_real[2 * st_slot] = __builtin_amdgcn_s_memrealtime();
-#endif
-    DSCB_STAMP(0);
-
-    unsigned *const ball = (unsigned *)dscb_lds;
-    const EqspTabLds *const tab = (const EqspTabLds *)(dscb_lds + DSCB_OFF_TAB);
-    const EqspFastLds *const fastp = (const EqspFastLds *)(dscb_lds + DSCB_OFF_FAST);      // float32 tier (the head of the image)
-    const EqspFastLds *const exactp = &A.eq->image;                                          // float64 tier: global memory, a few samples per row
-    short *const colb = (short *)(dscb_lds + DSCB_OFF_COL);
-    const short *const colc = colb + DSCB_M * (DSCB_SIDE + 1);      // indexed by r0 * 27 + r1 with the offsets r = -13 .. 13 from the anchor voxel
-    unsigned *const hist = (unsigned *)(dscb_lds + DSCB_OFF_HIST);      // per row of the run: 512 words of two 16-bit counters
-    // per row and column: which of its 16 samples are open (the table could not decide them, or their voxel is next to a tie), and
-    // the running count of open samples up to and including the column
-    unsigned short *const omask = (unsigned short *)(dscb_lds + DSCB_OFF_Q), *const ocum = omask + DSCB_RPB * 256;
-    int *const wtot = (int *)(dscb_lds + DSCB_OFF_FLAGS);                // per wave: its open samples
-    float *const rowc = (float *)(dscb_lds + DSCB_OFF_ROWC);            // per row: hf[9], rf[9], ru[3] of its record
-    int *const rowi = (int *)(rowc + DSCB_RPB * DSCB_ROWC);             // ... and its row index
-    double *const rowd = (double *)(dscb_lds + DSCB_OFF_ROWD);          // ... and inv(Rfinal) in float64 (the voxel of a sample next to a tie)
-    const int tid = (int)threadIdx.x;
-    const FieldDev F = A.f;
-    const DscRowRec *const grec = A.row_rec + pos0 + r_begin;           // the records of this run
-    // Only anchors whose ball lies inside the grid with a voxel to spare come here (no sample of theirs can leave the grid, as in
-    // k_describe's `interior`); the host sorts the others in front of `n_rowwise` with the same expression (mad_ball_interior).
-    if (!mad_ball_interior(ic0, ic1, ic2, F.nx, F.ny, F.nz)) {
-        if (tid == 0) *A.overflow = -2;      // refused, loudly: the set's describe stage reports the flag
-        return;
-    }
-
-    // ---- tables (one 16-byte piece per thread) and the ball's column list first; then half a wave per x-plane of the ball: the 27
-    // ---- columns' texels of a thread all requested before the first is stored (z-runs of up to 27 consecutive texels)
-    unsigned *const cinfo = (unsigned *)omask;      // (the open-sample lists are not in use yet) per column: LDS offset of its first texel | half-length << 16 (31: none)
-    {
-        constexpr int N_TAB = (int)sizeof(EqspTabLds) / 16, N_FAST = (int)DSCB_FAST_BYTES / 16;
-        static_assert(N_TAB + N_FAST <= DSCB_THREADS && DSCB_COLS <= DSCB_THREADS && DSCB_RPB * 256 * 4 >= DSCB_COLS * 4, "one table piece per thread");
-        const uint4 *src = (const uint4 *)&A.eq->tab;      // (a valid address for every thread; stored only where dst4 is set)
-        uint4 *dst4 = nullptr;
-        if (tid < N_TAB) { src = (const uint4 *)&A.eq->tab + tid; dst4 = (uint4 *)tab + tid; }
-        else if (tid < N_TAB + N_FAST) { src = (const uint4 *)&A.eq->image + (tid - N_TAB); dst4 = (uint4 *)fastp + (tid - N_TAB); }
-        const uint4 tv = *src;
-        const unsigned ci = A.colinfo[min(tid, DSCB_COLS - 1)];
-        const int rq = tid / DSCB_ROWC, ri = tid - rq * DSCB_ROWC;
-        const bool has_rc = rq < n_here && ri < 21;
-        const float rcv = ((const float *)grec[has_rc ? rq : 0].hf)[has_rc ? ri : 0];      // hf, rf, ru are contiguous
-        const int riv = grec[tid < n_here ? tid : 0].row;
-        const bool has_rd = tid < 9 * n_here;
-        const double rdv = grec[has_rd ? tid / 9 : 0].inv[has_rd ? tid % 9 : 0];
-        if (dst4) *dst4 = tv;
-        if (has_rd) rowd[tid] = rdv;
-        if (tid < DSCB_COLS) {
-            cinfo[tid] = ci;
-            colb[tid] = (short)((ci & 0xffffu) + (ci >> 16));      // the column's middle texel: what a sample's dz is added to
-        }
-        if (has_rc) rowc[tid] = rcv;
-        if (tid < n_here) rowi[tid] = riv;
-        for (int i = tid; i < DSCB_RPB * 512; i += DSCB_THREADS) hist[i] = 0;
-        __syncthreads();
-        const int hw = tid >> 5, zl = tid & 31;      // half-wave hw: the plane x = ic0 - 13 + hw; lane zl: the zl-th texel of a column's run
-        if (hw < DSCB_SIDE) {
-            unsigned v[DSCB_SIDE];
-            const unsigned plane = mad_u24((unsigned)(ic0 - DSCB_M + hw), (unsigned)F.ny, (unsigned)(ic1 - DSCB_M));
-#pragma unroll
-            for (int u = 0; u < DSCB_SIDE; u++) {
-                const int h = (int)(cinfo[hw * DSCB_SIDE + u] >> 16);
-                // (the ball lies inside the grid; the clamp keeps the lanes beyond a column's run, or of no column, inside the texture)
-                const int gz = min(max(ic2 - h + zl, 0), F.nz - 1);
-                v[u] = F.tex4[mad_u24(plane + (unsigned)u, (unsigned)F.nz, (unsigned)gz)];
-            }
-#pragma unroll
-            for (int u = 0; u < DSCB_SIDE; u++) {
-                const unsigned c2 = cinfo[hw * DSCB_SIDE + u];
-                const int h = (int)(c2 >> 16);
-                if (h != 31 && zl <= 2 * h) ball[(c2 & 0xffffu) + zl] = v[u];
-            }
-        }
-    }
-    __syncthreads();
-    DSCB_STAMP(1);
-
-    // Four waves per row, the rows of the run side by side: wave w belongs to row g = w / 4; its thread owns column (j, k) of that
-    // row's lattice and walks i = 0 .. 15 four samples at a time -- a sub-region (Descriptor.py:44-64) per trip.
-    const int g = tid >> 8, col = tid & 255, j = col >> 4, k = col & 15;
-    const bool live = g < n_here;      // (uniform per wave)
-    const int sub_jk = (j >> 2) * 16 + (k >> 2);
-    const float lbf = -7.5f;      // Descriptor.py:35, dsc_radius 16: the lattice -7.5 .. 7.5
-    const float m1 = lbf + (float)j, m2 = lbf + (float)k;
-    const float *const rcp = rowc + (live ? g : 0) * DSCB_ROWC;
-    auto rc = [&](int i) {      // constant i of this wave's row: the same value in every lane -> a scalar register
-        return __builtin_bit_cast(float, __builtin_amdgcn_readfirstlane(__builtin_bit_cast(int, rcp[i])));
-    };
-    unsigned *const H = hist + g * 512;
-
-    // ---- table tier.  The float32 guess of a sample's offset from the anchor voxel is formed exactly as in k_describe: the nearest
-    // ---- voxel is cvt_round(a) unless a fraction is within 2e-4 of the 0.5 tie -- such a sample is left open with the ones the
-    // ---- table cannot decide, and whoever takes it from the row's list lets the reference's float64 expression choose the voxel.
-    unsigned openmask = 0;      // bit i: sample i of this thread is open
-    int open_inc = 0;
-    if (live) {
-        const float h0 = rc(0), h1 = rc(1), h2 = rc(2), h3 = rc(3), h4 = rc(4), h5 = rc(5), h6 = rc(6), h7 = rc(7), h8 = rc(8);      // (float)inv(Rfinal)
-        // (float)Rfinal, the third row with the 1 / 511 of the texel's components: z on the unit scale, x and y on any common one
-        const float f0 = rc(9), f1 = rc(10), f2 = rc(11), f3 = rc(12), f4 = rc(13), f5 = rc(14), f6 = rc(15), f7 = rc(16), f8 = rc(17);
-        const float b0 = fmaf(m1, h1, m2 * h2), b1 = fmaf(m1, h4, m2 * h5), b2 = fmaf(m1, h7, m2 * h8);
-        // A row whose rotation keeps a grid axis (nearly) fixed has EVERY sample next to a tie along that axis: the lattice sits on
-        // half-integers (Descriptor.py:35), and the reference's float64 expression has to place each sample (scipy: a fraction <= 0.5
-        // takes the lower voxel).  These are the rows of main bin 0 / 111 -- the poles: Rfinal is a turn about z -- about one row in
-        // a hundred.  Such a row takes that expression for all its samples here, in line, instead of leaving 4 096 samples open.
-        // (Which rows take this path changes their cost, never their result: both paths place a sample with the float64 expression
-        // whenever float32 cannot.)
-        auto tiny = [](float x) { return fabsf(x) < 2e-5f ? 1 : 0; };
-        const bool tie_row = tiny(h0) + tiny(h1) + tiny(h2) >= 2 || tiny(h3) + tiny(h4) + tiny(h5) >= 2 || tiny(h6) + tiny(h7) + tiny(h8) >= 2;
-        const double *const dinv = rowd + 9 * g;
-#pragma unroll 1
-        for (int i0 = 0; i0 < 16; i0 += 4) {
-            unsigned q[4], open = 0;
-            if (tie_row) {      // (uniform per wave)
-#pragma unroll
-                for (int u = 0; u < 4; u++) {
-                    const double l0 = -7.5 + (double)(i0 + u), l1 = -7.5 + (double)j, l2 = -7.5 + (double)k;
-                    int r[3];
-#pragma unroll
-                    for (int ax = 0; ax < 3; ax++) {
-                        const int ic = ax == 0 ? ic0 : (ax == 1 ? ic1 : ic2), nmax = ax == 0 ? F.nx : (ax == 1 ? F.ny : F.nz);
-                        const double pp = (l0 * dinv[3 * ax] + l1 * dinv[3 * ax + 1] + l2 * dinv[3 * ax + 2]) + (double)ic;      // Descriptor.py:132-133
-                        const int lo = min((int)floor(pp), nmax - 2);
-                        r[ax] = ((pp - (double)lo <= 0.5) ? lo : lo + 1) - ic;
-                    }
-                    const int li = (int)colc[mad_i24(r[0], DSCB_SIDE, r[1])] + r[2];
-                    q[u] = ball[min(max(li, 0), DSCB_NBALL - 1)];
-                }
-            } else {
-#pragma unroll
-                for (int u = 0; u < 4; u++) {
-                    const float m0 = lbf + (float)(i0 + u);
-                    const float a0 = fmaf(m0, h0, b0), a1 = fmaf(m0, h3, b1), a2 = fmaf(m0, h6, b2);
-                    const float fr0 = __builtin_amdgcn_fractf(a0), fr1 = __builtin_amdgcn_fractf(a1), fr2 = __builtin_amdgcn_fractf(a2);
-                    const bool safe = fminf(fminf(fabsf(fr0 - 0.5f), fabsf(fr1 - 0.5f)), fabsf(fr2 - 0.5f)) > 2e-4f;
-                    // |a| <= 12.991, so the voxel lies in the ball; the clamp of the LDS index keeps a corrupt record from reading outside it
-                    const int cidx = mad_i24(cvt_round(a0), DSCB_SIDE, cvt_round(a1));
-                    const int li = (int)colc[cidx] + cvt_round(a2);
-                    q[u] = ball[min(max(li, 0), DSCB_NBALL - 1)];
-                    open |= safe ? 0u : (1u << u);
-                }
-            }
-            // zones of the four samples in straight-line code (4-byte texel -> float32 rotation -> table: k_describe's TAB tier)
-            int zone[4];
-            unsigned any_flag = 0;
-#pragma unroll
-            for (int u = 0; u < 4; u++) {
-                const unsigned t = q[u];
-                const float gx = (float)(int)__builtin_amdgcn_sbfe(t, 0, 10), gy = (float)(int)__builtin_amdgcn_sbfe(t, 10, 10),
-                            gz = (float)(int)__builtin_amdgcn_sbfe(t, 20, 10);
-                const float rx = fmaf(gz, f2, fmaf(gy, f1, gx * f0));
-                const float ry = fmaf(gz, f5, fmaf(gy, f4, gx * f3));
-                const float rz = fmaf(gz, f8, fmaf(gy, f7, gx * f6));
-                zone[u] = eqsp_tab32(tab, rx, ry, rz);
-                any_flag |= t;
-            }
-            if ((int)any_flag < 0) {      // rare: 2 = not finite -> the exact tiers, 3 = below the magnitude cut-off, not counted (Descriptor.py:190)
-#pragma unroll
-                for (int u = 0; u < 4; u++) {
-                    const unsigned fl = q[u] >> 30;
-                    zone[u] = fl == 3u ? -2 : (fl == 0u ? zone[u] : -1);
-                }
-            }
-            const int sub8 = (sub_jk + i0) * 8;      // sub-region of these four samples: i0 / 4 along i = + 4 (i0 / 4), x 8 words
-#pragma unroll
-            for (int u = 0; u < 4; u++) {
-                const bool op = (open >> u) & 1u;      // voxel not certain: whatever the guessed texel said does not count
-                if (zone[u] >= 0 && !op) atomicAdd(&H[sub8 + (zone[u] >> 1)], 1u << ((zone[u] & 1) << 4));
-                open |= zone[u] == -1 ? (1u << u) : 0u;
-            }
-            openmask |= open << i0;
-        }
-        // where this thread's open samples stand in the row's list: a scan over the wave now, the waves before it after the barrier
-        open_inc = wave_incl_scan_i32(__popc(openmask));
-        if (lane_id() == MAD_WAVE - 1) wtot[tid >> 6] = open_inc;
-    }
-    DSCB_STAMP(2);
-    __syncthreads();
-    DSCB_STAMP(3);
-
-    // ---- the open samples of each row (~4 % of a row; up to most of it where the directions hug a zone's edge), dealt evenly to
-    // ---- the row's 256 threads whatever their number: the columns' masks and running counts in LDS, the e-th open sample found by
-    // ---- a binary search.  Per sample: its voxel again (float64 next to a tie: Descriptor.py:132-133, scipy's rule), its 16-byte
-    // ---- texel, the float32 tier with its 1e-4 guard, the float64 tier behind it -- as k_describe's queue phase.
-    if (live) {
-        int before = 0;
-        for (int w = g * 4; w < (tid >> 6); w++) before += wtot[w];
-        ocum[g * 256 + col] = (unsigned short)(open_inc + before);
-        omask[g * 256 + col] = (unsigned short)openmask;
-    }
-    __syncthreads();
-    auto settle = [&](int ei, int ej, int ek) {
-        const float e1 = lbf + (float)ej, e2 = lbf + (float)ek, e0 = lbf + (float)ei;
-        const float a0 = fmaf(e0, rcp[0], fmaf(e1, rcp[1], e2 * rcp[2])), a1 = fmaf(e0, rcp[3], fmaf(e1, rcp[4], e2 * rcp[5])),
-                    a2 = fmaf(e0, rcp[6], fmaf(e1, rcp[7], e2 * rcp[8]));
-        const bool safe = fminf(fminf(fabsf(__builtin_amdgcn_fractf(a0) - 0.5f), fabsf(__builtin_amdgcn_fractf(a1) - 0.5f)), fabsf(__builtin_amdgcn_fractf(a2) - 0.5f)) > 2e-4f;
-        int r0 = cvt_round(a0), r1 = cvt_round(a1), r2 = cvt_round(a2);      // the voxel's offset from the anchor's
-        const int sb8 = (((ej >> 2) * 16 + (ek >> 2)) + (ei & ~3)) * 8;
-        if (!safe) {
-            // Next to a tie the reference's own float64 expression decides (Descriptor.py:132-133; scipy's nearest rule: a fraction
-            // <= 0.5 takes the lower voxel).  Rows turned by a multiple of 90 degrees have EVERY sample there (the lattice sits on
-            // half-integers), so this is straight-line code, an axis at a time, not a call.  The ball lies inside the grid.
-            const double *const dinv = rowd + 9 * g;
-            const double l0 = -7.5 + (double)ei, l1 = -7.5 + (double)ej, l2 = -7.5 + (double)ek;
-            auto nearest = [&](int ax, int ic, int nmax) {
-                const double pp = (l0 * dinv[3 * ax] + l1 * dinv[3 * ax + 1] + l2 * dinv[3 * ax + 2]) + (double)ic;
-                const int lo = min((int)floor(pp), nmax - 2);
-                const int v = (pp - (double)lo <= 0.5) ? lo : lo + 1;
-                return min(max(v - ic, -DSCB_M), DSCB_M);      // (the clamp never acts: |offset| <= 12.991)
-            };
-            r0 = nearest(0, ic0, F.nx); r1 = nearest(1, ic1, F.ny); r2 = nearest(2, ic2, F.nz);
-            // the voxel is settled, its 4-byte texel is in the ball: the table tier, as for every other sample
-            const unsigned t = ball[min(max((int)colc[mad_i24(r0, DSCB_SIDE, r1)] + r2, 0), DSCB_NBALL - 1)];
-            const unsigned fl = t >> 30;
-            if (fl == 3u) return;      // below the magnitude cut-off: not counted (Descriptor.py:190)
-            if (fl == 0u) {
-                const float gx = (float)(int)__builtin_amdgcn_sbfe(t, 0, 10), gy = (float)(int)__builtin_amdgcn_sbfe(t, 10, 10),
-                            gz = (float)(int)__builtin_amdgcn_sbfe(t, 20, 10);
-                const int zn = eqsp_tab32(tab, fmaf(gz, rcp[11], fmaf(gy, rcp[10], gx * rcp[9])), fmaf(gz, rcp[14], fmaf(gy, rcp[13], gx * rcp[12])),
-                                          fmaf(gz, rcp[17], fmaf(gy, rcp[16], gx * rcp[15])));
-                if (zn >= 0) {
-                    atomicAdd(&H[sb8 + (zn >> 1)], 1u << ((zn & 1) << 4));
-                    return;
-                }
-            }
-        }
-        // the 16-byte texel: the float32 tier with its 1e-4 guard, the float64 tier behind it
-        const float4 tx = F.tex[mad_u24(mad_u24((unsigned)(ic0 + r0), (unsigned)F.ny, (unsigned)(ic1 + r1)), (unsigned)F.nz, (unsigned)(ic2 + r2))];
-        if (tx.w < 1e-5f) return;      // (not counted, Descriptor.py:190 -- such texels carry flag 3 and never get here)
-        const float inv = __builtin_amdgcn_rcpf(fmaxf(tx.w, 1e-30f));
-        const float gx = tx.x * inv, gy = tx.y * inv, gz = tx.z * inv;
-        int zn = eqsp_fast32(fastp, fmaf(gz, rcp[11], fmaf(gy, rcp[10], gx * rcp[9])), fmaf(gz, rcp[14], fmaf(gy, rcp[13], gx * rcp[12])),
-                             fmaf(gz, rcp[20], fmaf(gy, rcp[19], gx * rcp[18])));
-#ifdef MAD_PROBE_STAMPS
-        if (zn < 0) atomicAdd(&dbg_s[3], 1);
-#endif
-        if (zn < 0) zn = dscb_describe_exact(exactp, tx.x, tx.y, tx.z, tx.w, A.row_R + 9 * (int64_t)rowi[g]);
-        atomicAdd(&H[sb8 + (zn >> 1)], 1u << ((zn & 1) << 4));
-    };
-    if (live) {
-        const unsigned short *const cum = ocum + g * 256, *const msk = omask + g * 256;
-        const int n_open = cum[255];
-#ifdef MAD_PROBE_STAMPS
-        if (col == 0) { atomicMax(&dbg_s[0], n_open); atomicAdd(&dbg_s[1], n_open); }
-#endif
-        for (int e = col; e < n_open; e += 256) {
-            int c = 0;      // the first column whose running count exceeds e
-#pragma unroll
-            for (int st = 128; st; st >>= 1)
-                if ((int)cum[c + st - 1] <= e) c += st;
-            unsigned m = msk[c];
-            for (int skip = e - ((int)cum[c] - __popc(m)); skip > 0; skip--) m &= m - 1;
-            settle(__builtin_ctz(m), c >> 4, c & 15);
-        }
-    }
-    DSCB_STAMP(4);
-    __syncthreads();
-    DSCB_STAMP(5);
-    DSCB_STAMP(6);
-
-    // ---- the first wave of a row: its 1 024 counts as int16 (the packed words ARE the row) and int8, its norm
-    if (live && (tid & 255) < MAD_WAVE) {
-        const int l = (int)lane_id();
-        const uint4 *const H4 = (const uint4 *)H;
-        const uint4 w0 = H4[2 * l], w1 = H4[2 * l + 1];
-        const int64_t row = rowi[g];
-        uint4 *const o16 = (uint4 *)(A.dsc + row * 1024);
-        o16[2 * l] = w0;
-        o16[2 * l + 1] = w1;
-        if (A.dsc8) {
-            auto b2 = [](unsigned x) { return (x & 0xffu) | ((x >> 8) & 0xff00u); };      // two counts -> two bytes
-            auto sq = [](unsigned x) { const int a = (int)(x & 0xffffu), b = (int)(x >> 16); return a * a + b * b; };
-            ((uint4 *)(A.dsc8 + row * 1024))[l] = make_uint4(b2(w0.x) | b2(w0.y) << 16, b2(w0.z) | b2(w0.w) << 16, b2(w1.x) | b2(w1.y) << 16, b2(w1.z) | b2(w1.w) << 16);
-            int ss = sq(w0.x) + sq(w0.y) + sq(w0.z) + sq(w0.w) + sq(w1.x) + sq(w1.y) + sq(w1.z) + sq(w1.w);      // counts <= 64: exact in int32
-            ss = wave_sum_i32(ss);
-            if (l == 0) A.norm[row] = sqrt((double)ss);
-        }
-    }
-    DSCB_STAMP(7);
-#ifdef MAD_PROBE_STAMPS
-    if (threadIdx.x == 0 && st_slot < 16384) dscb_real[2 * st_slot + 1] = __builtin_amdgcn_s_memrealtime();
-    if (threadIdx.x < 4 && st_slot < 16384) dscb_dbg[4 * st_slot + threadIdx.x] = dbg_s[threadIdx.x];
-#endif
-}
-
-static int ensure_ball(mad_ctx *ctx) {
-    if (ctx->ball_colinfo) return MAD_OK;
-    unsigned h[DSCB_COLS];
-    int base = 0;
-    for (int c = 0; c < DSCB_COLS; c++) {
-        const int hh = dscb_col_h(c / DSCB_SIDE, c % DSCB_SIDE);
-        h[c] = hh < 0 ? (31u << 16) : ((unsigned)base | (unsigned)hh << 16);      // LDS index of the column's voxel dz = -hh: base; it holds 2 hh + 1 texels
-        if (hh >= 0) base += 2 * hh + 1;
-    }
-    if (base != DSCB_NBALL) return mad_fail(ctx, MAD_EINVAL, "k_describe_ball: the ball has %d texels, built for %d", base, DSCB_NBALL);
-    MAD_HIP(hipMalloc((void **)&ctx->ball_colinfo, sizeof(h)));
-    MAD_HIP(hipMemcpy(ctx->ball_colinfo, h, sizeof(h), hipMemcpyHostToDevice));
-    MAD_HIP(hipFuncSetAttribute((const void *)k_describe_ball, hipFuncAttributeMaxDynamicSharedMemorySize, (int)DSCB_LDS_BYTES));
-    return MAD_OK;
-}
-
 int mad_describe_device_many(mad_ctx *ctx, int n_jobs, const DescribeJob *jobs, int r, int dsc_size) {
     if (dsc_size != 64 && (2 * r != 16 || (dsc_size != 27 && dsc_size != 8 && dsc_size != 1)))
         return mad_fail(ctx, MAD_EINVAL, "mad_describe: dsc_size %d (27, 8 and 1 are built for the default dsc_radius 16 only; 64 for 4 ... 16)", dsc_size);
@@ -1718,15 +1289,10 @@ int mad_describe_device_many(mad_ctx *ctx, int n_jobs, const DescribeJob *jobs, 
     if (r > 8 && (dsc_size != 64 || Zd != 16))
         return mad_fail(ctx, MAD_EINVAL, "mad_describe: dsc radius %d is built for 64 regions of 16 zones only (dsc_size %d, %d zones)", r, dsc_size, Zd);
     const bool tab = Zd == 16 && ctx->eq_host[1].tab_ok && dsc_size == 64 && 2 * r == 16;
-    const bool ball_ok = tab && ctx->dsc_ball;      // (mad_set_option "dsc_ball", MAD_BALL=1: off by default)
-    if (ball_ok) MAD_TRY(ensure_ball(ctx));
     for (int j0 = 0; j0 < n_jobs; j0 += MAD_BATCH_MAX) {
         Batch<DescribeArgs> B;
-        Batch<DescribeBallArgs> BB;      // the base-octave anchors of the same jobs (k_describe_ball)
         B.n_jobs = 0;
-        BB.n_jobs = 0;
-        int64_t blk = 0, bblk = 0;
-        int max_fan = 1;
+        int64_t blk = 0;
         for (int j = j0; j < n_jobs && j < j0 + MAD_BATCH_MAX; j++) {
             const DescribeJob &J = jobs[j];
             if (J.grid_rows <= 0) continue;
@@ -1735,10 +1301,6 @@ int mad_describe_device_many(mad_ctx *ctx, int n_jobs, const DescribeJob *jobs, 
                 if (f.tex && ((size_t)f.nx * f.ny * f.nz >= (size_t)1 << 32 || (size_t)f.nx * f.ny >= (size_t)1 << 24 || f.nz >= 1 << 24))
                     return mad_fail(ctx, MAD_EINVAL, "mad_describe: field of %dx%dx%d texels exceeds 2^32 (or 2^24 per x-y plane)", f.nx, f.ny, f.nz);
             }
-            // the anchors of the base octave (behind those of octave 0 in working order) go through the ball kernel when the set
-            // pipeline has told where each anchor's rows lie
-            const int n_base = J.n_anchors - J.n_rowwise;
-            const bool ball = ball_ok && J.d_anc_rows && J.d_row_rec && J.d_row_perm && n_base > 0 && J.n_rowwise >= 0 && J.fan > 0 && J.f[1].tex4;
             DescribeArgs &A = B.job[B.n_jobs];
             A.f[0] = J.f[0]; A.f[1] = J.f[1];
             A.anc_coords = J.d_anc_coords; A.anc_octave = J.d_anc_octave; A.uniform_octave = J.uniform_octave;
@@ -1747,22 +1309,9 @@ int mad_describe_device_many(mad_ctx *ctx, int n_jobs, const DescribeJob *jobs, 
             A.rsum = J.d_rsum;
             if (J.d_dsc8 && r >= MAD_WIDE_FROM_R && !J.d_rsum) return mad_fail(ctx, MAD_EINVAL, "mad_describe: int8 rows at dsc radius %d need the row sums of a wide set", r);
             A.queue_cap = std::max(ctx->dsc_queue_cap, 0);
-            A.row_limit = ball ? J.d_anc_rows + MAD_ANCROW_WORDS * (int64_t)J.n_rowwise : nullptr;      // first row position of the first base-octave anchor
             B.first[B.n_jobs++] = (int)blk;
-            // one workgroup per possible row, a multiple of 8 per job (one share per XCD).  With the ball kernel this grid only has
-            // the octave-0 rows to cover: their share of the hint by anchors, with room (a launch that falls short raises `overflow`)
-            int64_t rows_here = J.grid_rows;
-            if (ball) rows_here = std::min<int64_t>(J.grid_rows, (int64_t)((double)J.grid_rows * J.n_rowwise / J.n_anchors * 1.3) + 64);
-            blk += ((rows_here + 7) / 8) * 8 + 8;
+            blk += ((J.grid_rows + 7) / 8) * 8 + 8;      // one workgroup per possible row, a multiple of 8 per job (one share per XCD)
             if (blk > INT32_MAX) return mad_fail(ctx, MAD_EINVAL, "mad_describe: %lld rows in one batch", (long long)blk);
-            if (ball) {
-                DescribeBallArgs &Q = BB.job[BB.n_jobs];
-                Q.f = J.f[1]; Q.row_rec = J.d_row_rec; Q.anc_rows = J.d_anc_rows; Q.row_R = J.d_row_R;
-                Q.n_base = n_base; Q.n_rowwise = J.n_rowwise;
-                Q.eq = ctx->eq[1]; Q.overflow = J.d_overflow; Q.colinfo = ctx->ball_colinfo; Q.dsc = J.d_dsc; Q.dsc8 = J.d_dsc8; Q.norm = J.d_norm;
-                BB.first[BB.n_jobs++] = (int)bblk;
-                max_fan = std::max(max_fan, J.fan);
-            }
         }
         if (B.n_jobs == 0) continue;
         B.first[B.n_jobs] = (int)blk;
@@ -1785,20 +1334,6 @@ int mad_describe_device_many(mad_ctx *ctx, int n_jobs, const DescribeJob *jobs, 
             // (instantiated last: the instances above keep their places in the code object)
             case 20: hipLaunchKernelGGL(k_describe<20>, dim3(nblk), dim3(DSC_NT(20)), 0, ctx->stream, B); break;
             case 24: hipLaunchKernelGGL(k_describe<24>, dim3(nblk), dim3(DSC_NT(24)), 0, ctx->stream, B); break;
-        }
-        if (BB.n_jobs > 0) {
-            // every job's grid: `chunks` runs of DSCB_RPB rows x its base-octave anchors rounded up to 8 (an anchor has at most fan rows;
-            // the workgroups of runs an anchor does not have return at once)
-            static const int chunks_probe = getenv("MAD_BALL_CHUNKS") ? atoi(getenv("MAD_BALL_CHUNKS")) : 0;      // timing probe only: anchors with more rows lose them
-            const int chunks = chunks_probe > 0 ? chunks_probe : (max_fan + DSCB_RPB - 1) / DSCB_RPB;
-            int64_t at = 0;
-            for (int q = 0; q < BB.n_jobs; q++) {
-                BB.first[q] = (int)at;
-                at += (int64_t)chunks * ((BB.job[q].n_base + 7) / 8 * 8);
-                if (at > INT32_MAX) return mad_fail(ctx, MAD_EINVAL, "mad_describe: %lld ball workgroups in one batch", (long long)at);
-            }
-            BB.first[BB.n_jobs] = (int)at;
-            hipLaunchKernelGGL(k_describe_ball, dim3((unsigned)at), dim3(DSCB_THREADS), DSCB_LDS_BYTES, ctx->stream, BB, chunks);
         }
         mad_timer_end(ctx, MAD_T_DESCRIBE);
         MAD_HIP(hipGetLastError());

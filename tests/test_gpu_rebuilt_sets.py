@@ -35,18 +35,12 @@ def _ceil(n, m):
 def launch_rows(h, cap_rows, n_anchors):
     """What a set rebuilt in place with hint h (rows of its previous build; 0: none) is sized for.
 
-    -> (describe, matrix): rows the k_describe launch covers -- grid_rows of mad_match.hip:3244, rounded up to 8 plus 8 workgroups
-    (mad_orient.hip:1706-1708) -- and the hi rows of the score matrix mad_match_shard_begin sizes from the same hint
-    (mad_match.hip:3959, ceil128)."""
+    -> (describe, matrix): rows the k_describe launch covers -- grid_rows of mad_match.hip:3076, rounded up to 8 plus 8 workgroups
+    (mad_orient.hip:1313) -- and the hi rows of the score matrix mad_match_shard_begin sizes from the same hint
+    (mad_match.hip:3865, ceil128)."""
     grid = min(cap_rows, h + h // 8 + 64) if h > 0 else cap_rows
     hint = min(cap_rows, h + h // 8 + 64) if h > 0 else n_anchors * 8 + 128
     return _ceil(grid, 8) + 8, _ceil(max(hint, 1), 128)
-
-
-def ball_rows_here(h, cap_rows, n_rowwise, n_anchors):
-    """Rows the k_describe launch covers beside k_describe_ball (mad_orient.hip:1707): the row-wise anchors' share of the hint."""
-    grid = min(cap_rows, h + h // 8 + 64) if h > 0 else cap_rows
-    return _ceil(min(grid, int(grid * n_rowwise / n_anchors * 1.3) + 64), 8) + 8
 
 
 def band_of(h, n, cap_rows, n_anchors):
@@ -474,35 +468,29 @@ def test_export_of_a_share_rebuilt_past_its_hint(lib, W):
             s.close()
 
 
-def test_rows_of_the_ball_kernel_rebuilt_past_the_rowwise_grid(lib, W):
-    """mad_set_option "dsc_ball" = 1: k_describe_ball takes the base-octave anchors whose sample ball lies inside the grid, and
-    k_describe the others -- octave 0 here -- from a launch it sizes as their share of the hint (rows_here).  A rebuild whose
-    octave-0 rows outgrow that launch is flagged by the asynchronous shard and repaired by the bracket."""
+def test_mixed_octave_set_rebuilt_into_the_gap_with_mostly_octave_0_rows(lib, W):
+    """A hi set of both octaves -- mostly base-octave rows at first, mostly octave-0 rows after the rebuild (k_describe takes octave 0
+    first in working order) -- rebuilt in place into the gap band: the short describe launch is flagged by the asynchronous shard
+    and repaired by the bracket."""
     c0, per0 = W._pool(0, 403, 18)
-    c1, per1 = W._pool(1, 404, 20)      # 20 voxels from every face: inside the ball kernel's grid
-    first1 = W.pick("ball1", 80, 95, 0, pool=(c1, per1))
-    h0 = W.pick("ball0", 8, 16, 0, pool=(c0, per0), octave=0)
-    first = W.rows(("ball", "first"), np.concatenate([first1.coords, h0.coords]), np.concatenate([first1.octave, h0.octave]))
-    few1 = W.pick("ball1", 8, 20, 200, pool=(c1, per1))
+    c1, per1 = W._pool(1, 404, 20)      # 20 voxels from every face
+    first1 = W.pick("mixed1", 80, 95, 0, pool=(c1, per1))
+    h0 = W.pick("mixed0", 8, 16, 0, pool=(c0, per0), octave=0)
+    first = W.rows(("mixed", "first"), np.concatenate([first1.coords, h0.coords]), np.concatenate([first1.octave, h0.octave]))
+    few1 = W.pick("mixed1", 8, 20, 200, pool=(c1, per1))
     describe, matrix = launch_rows(first.n, 1 << 30, 0)
-    new0 = W.pick("ball0", describe + 1, matrix - few1.n, 100, pool=(c0, per0), octave=0)
-    new = W.rows(("ball", "new"), np.concatenate([few1.coords, new0.coords]), np.concatenate([few1.octave, new0.octave]))
+    new0 = W.pick("mixed0", describe + 1, matrix - few1.n, 100, pool=(c0, per0), octave=0)
+    new = W.rows(("mixed", "new"), np.concatenate([few1.coords, new0.coords]), np.concatenate([few1.octave, new0.octave]))
     assert band_of(first.n, new.n, new.cap_rows, len(new.octave)) == "gap"
-    # every row-wise anchor is of octave 0, and their rows outgrow the launch beside the ball kernel
-    assert new0.n > ball_rows_here(first.n, new.cap_rows, len(new0.octave), len(new.octave))
-    try:
-        lib.set_option("dsc_ball", 1)
-        case = Case(W, {"hi": first, "lo": W.base["lo"]}, {"hi": new}, "gap", "hi")
-        for consumer in (use_shard_async, use_bracket):
-            hi, lo = case.sets(W)
-            try:
-                consumer(lib, case, hi, lo)
-                assert hi.size()[0] == new.n
-            finally:
-                hi.close()
-                lo.close()
-    finally:
-        lib.set_option("dsc_ball", 0)
+    case = Case(W, {"hi": first, "lo": W.base["lo"]}, {"hi": new}, "gap", "hi")
+    for consumer in (use_shard_async, use_bracket):
+        hi, lo = case.sets(W)
+        try:
+            consumer(lib, case, hi, lo)
+            assert hi.size()[0] == new.n
+        finally:
+            hi.close()
+            lo.close()
 
 
 def test_map_set_past_the_lds_clouds_rebuilt_into_the_gap(lib, W):
