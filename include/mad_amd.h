@@ -398,6 +398,29 @@ int mad_map_ccc(mad_ctx *ctx, const float *grid1, const int32_t dims1[3], const 
                 const float *const *grids2, const int32_t *dims2, const double *origins2,
                 double voxsp, double isovalue, double *out);
 
+/*
+ * A map sampled on another lattice (mad_resample.hip).  Host pointers, synchronous.  grid: float32 [x][y][z]
+ * with dims, origin (Angstrom, centre of voxel (0,0,0)) and spacing voxsp; out: float32 [x][y][z] with out_dims, out_origin,
+ * out_voxsp, every voxel of it written.  R9 / T3 (both or neither; NULL, NULL: no motion) move the source rigidly before it is
+ * sampled, in the convention of get_rototrans_SVD / PDB.rotate_atoms: R9 is the 3 x 3 matrix R row-major, R9[3 a + k] = R[a][k],
+ * and a point x of the source (a row vector) moves to x @ R + T, i.e. x'_k = sum_a x_a R[a][k] + T_k.  Output voxel j lies at
+ * y = out_origin + out_voxsp j and takes the source value at index u = ((y - T) @ R^T - origin) / voxsp, folded on the host into
+ * u = b + A j with A[a][k] = (R[a][k] out_voxsp) / voxsp and
+ * b[a] = ((((y0_0 - T_0) R[a][0] + (y0_1 - T_1) R[a][1]) + (y0_2 - T_2) R[a][2]) - origin[a]) / voxsp  (y0 = out_origin), and
+ * evaluated as ((b_a + A_a0 jx) + A_a1 jy) + A_a2 jz in float64.  Where 0 <= u_a <= dims[a] - 1 on all three axes (both ends
+ * included) the output is the interpolated value, elsewhere exactly 0.0f.  order 1: trilinear; order 3: cubic B-spline
+ * interpolation (prefilter with pole sqrt(3) - 2, mirror boundary about the first and last sample); float64 sums, rounded to
+ * float32 once: scipy.ndimage.map_coordinates(grid as float64, u, order, mode="constant", cval=0, prefilter=True).  No low-pass
+ * filter before coarsening, no other boundary mode, no other order.  Without motion (or with R the identity bit for bit) the
+ * volume is done as three 1-D passes from per-axis tables unless MAD_RESAMPLE_GENERAL=1 is set in the environment at the call.
+ * MAD_EINVAL, with nothing launched: NULL, order other than 1 or 3, a source axis shorter than 2, an output dimension < 1,
+ * voxsp or out_voxsp <= 0, 2^32 voxels or more in either grid, a number that is not finite, max|R R^T - I| > 1e-9 or det R < 0,
+ * one of R9 / T3 without the other.
+ */
+int mad_map_resample(mad_ctx *ctx, const float *grid, const int32_t dims[3], const double origin[3], double voxsp,
+                     const double *R9, const double *T3,          /* NULL, NULL: no motion */
+                     int order, const int32_t out_dims[3], const double out_origin[3], double out_voxsp, float *out);
+
 /* ---- one subunit's pair grid sharded over GPUs by blocks of map rows (the exchange steps -- OR of the flag vectors,
  *      all-gather of the per-shard top-k -- are the caller's, mad_amd/dist.py::sharded_match, or the library's own:
  *      mad_dist_or_allreduce / mad_dist_allgather_topk below) ------------------------------------------------- */

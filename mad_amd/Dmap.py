@@ -4,14 +4,15 @@ Field contract of the reference's `Dmap` (mad/Dmap.py:6-71): `grid3d` float32 [x
 origin `xi, yi, zi` (Angstrom), box `xb, yb, zb`, `voxsp`, `map_name`, `name`.
 `get_CCC_with_grid` (Dmap.py:153-258) runs on the GPU through `mad_ccc`, `mask_with` (Dmap.py:99-151) through `mad_map_mask`
 and `get_CCC_with_dmap` (Dmap.py:260-372) through `mad_map_ccc`: together the reference's support for docking into a segment of
-a map.  None of them has a CPU fallback.  The reference's per-voxel text writer is replaced by `mapio.write_situs`.
+a map.  `resample` (no counterpart in the reference) brings a map onto another lattice through `mad_map_resample`, which is what the
+three need when two maps differ in spacing or are not a whole number of voxels apart.  None of them has a CPU fallback.  The reference's per-voxel text writer is replaced by `mapio.write_situs`.
 """
 import os
 import sys
 
 import numpy as np
 
-from . import _lib, mapio
+from . import _lib, mapio, resample as _resample
 
 
 class Dmap(object):
@@ -105,6 +106,31 @@ class Dmap(object):
         g1 = np.ascontiguousarray(self.grid3d, dtype=np.float32)
         g2 = np.ascontiguousarray(m2.grid3d, dtype=np.float32)
         return float(_lib.get_lib().map_ccc(g1, (self.xi, self.yi, self.zi), [(g2, (m2.xi, m2.yi, m2.zi))], self.voxsp, isovalue)[0])
+
+    def resample(self, voxsp=None, like=None, R=None, T=None, order=3):
+        """This map on another lattice, as a new `Dmap` (made without reading a file; `map_name` and `name` are kept, `self` is
+        untouched).  `voxsp=w`: the same origin at spacing w, floor((n - 1) * voxsp / w) + 1 voxels per axis.  `like=other`: the
+        dims, origin and spacing of `other`, after which `mask_with`, `get_CCC_with_dmap` and `get_CCC_with_grid` see equal spacings
+        and a whole-voxel offset.  Neither: the map's own lattice (useful with `R, T`).  `R, T` move the map first, a point x
+        going to x @ R + T.  order 1 is trilinear, order 3 cubic B-spline interpolation; voxels outside the source are 0.  There is
+        no low-pass filter before coarsening: smooth first where that matters."""
+        if voxsp is not None and like is not None:
+            raise ValueError("Dmap.resample: give voxsp or like, not both")
+        if (R is None) != (T is None):
+            raise ValueError("Dmap.resample: R and T come together or not at all")
+        if order not in (1, 3):
+            raise ValueError("Dmap.resample: order %r (1 or 3)" % (order,))
+        g = np.ascontiguousarray(self.grid3d, dtype=np.float32)
+        dims, origin, w = _resample.plan_lattice(g.shape, (self.xi, self.yi, self.zi), self.voxsp, voxsp, like)
+        out = Dmap.__new__(Dmap)
+        out.grid3d = _lib.get_lib().map_resample(g, (self.xi, self.yi, self.zi), self.voxsp, dims, origin, w, R, T, order)
+        out.voxsp = w
+        out.xi, out.yi, out.zi = origin
+        out.xb, out.yb, out.zb = out.grid3d.shape
+        for k in ("map_name", "name"):
+            if hasattr(self, k):
+                setattr(out, k, getattr(self, k))
+        return out
 
     def write_to_mrc(self, outname):
         mapio.write_mrc(outname, self.grid3d, (self.xi, self.yi, self.zi), self.voxsp)

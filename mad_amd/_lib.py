@@ -39,7 +39,7 @@ SYMBOLS = [
     "mad_dist_unique_id", "mad_dist_init", "mad_dist_destroy", "mad_dist_info", "mad_dist_rehearse_flags", "mad_dist_or_allreduce", "mad_dist_allgather",
     "mad_dist_allgather_topk", "mad_dist_scratch", "mad_dist_copy",
     "mad_set_wire_bytes", "mad_set_export", "mad_set_import", "mad_set_lane", "mad_set_stream", "mad_set_bind_lane",
-    "mad_upload_density", "mad_refine", "mad_last_refine_plan", "mad_last_density_chunks", "mad_structure_to_density", "mad_ccc", "mad_map_mask", "mad_map_ccc", "mad_density_ccc", "mad_dock_refine_score", "mad_grid_overlap", "mad_overlap_matrix",
+    "mad_upload_density", "mad_refine", "mad_last_refine_plan", "mad_last_density_chunks", "mad_structure_to_density", "mad_ccc", "mad_map_mask", "mad_map_ccc", "mad_map_resample", "mad_density_ccc", "mad_dock_refine_score", "mad_grid_overlap", "mad_overlap_matrix",
     "mad_space_create", "mad_space_destroy", "mad_space_build", "mad_space_info", "mad_space_download",
     "mad_space_peaks", "mad_space_patches", "mad_space_localize", "mad_localize_volume",
     "mad_pose_cluster_many",
@@ -1089,6 +1089,28 @@ class Lib(object):
         ptrs = (C.c_void_p * n)(*[g.ctypes.data for g, _ in seconds])
         self._chk(self.dll.mad_map_ccc(self.ctx, _p(g1), _p(d1), _p(o1), C.c_int(n), ptrs, _p(d2), _p(o2), C.c_double(voxsp),
                                        C.c_double(isovalue), _p(out)))
+        return out
+
+    def map_resample(self, g, origin, voxsp, out_dims, out_origin, out_voxsp, R=None, T=None, order=3):
+        """`g` (C-contiguous float32 [x, y, z] with `origin` and `voxsp`) sampled on the lattice (`out_dims`, `out_origin`,
+        `out_voxsp`) -> a new float32 array.  `R`, `T` (both or neither) move the source first: a point x goes to x @ R + T.
+        order 1 is trilinear, order 3 cubic B-spline interpolation; outside the source the result is 0 (mad_map_resample)."""
+        if g.dtype != np.float32 or not g.flags.c_contiguous:
+            raise ValueError("map_resample needs a C-contiguous float32 grid")
+        if g.ndim != 3:
+            raise ValueError("map_resample needs a 3-D grid")
+        d = np.array(g.shape, np.int32)
+        md = np.array([int(v) for v in out_dims], np.int64).reshape(3)
+        if np.any(md < -2 ** 31) or np.any(md >= 2 ** 31):
+            raise ValueError("map_resample: out_dims %s" % (tuple(md),))
+        md = md.astype(np.int32)
+        o, p = _c(np.asarray(origin, np.float64).reshape(3), np.float64), _c(np.asarray(out_origin, np.float64).reshape(3), np.float64)
+        Rp = None if R is None else _c(np.asarray(R, np.float64).reshape(9), np.float64)
+        Tp = None if T is None else _c(np.asarray(T, np.float64).reshape(3), np.float64)
+        n_out = int(np.prod(np.maximum(md.astype(np.int64), 0)))
+        out = np.empty(tuple(int(v) for v in md) if 0 < n_out < 2 ** 32 else (0,), np.float32)      # (a refused call writes nothing)
+        self._chk(self.dll.mad_map_resample(self.ctx, _p(g), _p(d), _p(o), C.c_double(voxsp), None if Rp is None else _p(Rp),
+                                            None if Tp is None else _p(Tp), C.c_int(order), _p(md), _p(p), C.c_double(out_voxsp), _p(out)))
         return out
 
 
