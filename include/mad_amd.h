@@ -421,6 +421,24 @@ int mad_map_resample(mad_ctx *ctx, const float *grid, const int32_t dims[3], con
                      const double *R9, const double *T3,          /* NULL, NULL: no motion */
                      int order, const int32_t out_dims[3], const double out_origin[3], double out_voxsp, float *out);
 
+/*
+ * A map cut around a structure, or with the structure erased (mad_zone.hip).  Host pointers, synchronous.
+ * grid: float32 [x][y][z] with dims, origin (Angstrom, centre of voxel (0,0,0)) and spacing voxsp, updated IN PLACE; atoms:
+ * n_atoms x 3 float64 (Angstrom), read only, NULL allowed when n_atoms == 0.  Voxel j sits at p_a = origin_a + voxsp * j_a
+ * (float64, one multiply and one add, no FMA); its squared distance to an atom is d2 = (dx*dx + dy*dy) + dz*dz with
+ * dx = p_x - a_x, and D2 is the minimum of d2 over all atoms.  With r2 = radius * radius, R = radius + soft, R2 = R * R the weight
+ * is w = 1 where D2 <= r2, w = 0 where D2 >= R2 or n_atoms == 0, and w = 0.5 + 0.5 * cos(pi * ((sqrt(D2) - radius) / soft)) in
+ * between (float64); erase != 0 takes 1 - w.  A voxel of final weight exactly 1 is not written (every bit stays), one of final
+ * weight exactly 0 becomes +0.0f whatever it held, any other becomes (float)((double)g * w).  counts (may be NULL): counts[0] =
+ * voxels with D2 <= r2, counts[1] = voxels with r2 < D2 < R2.  The same call gives the same bits alone or after any other call.
+ * MAD_EINVAL, with nothing launched and the grid untouched: NULL (atoms only when n_atoms == 0), a dimension < 1, voxsp <= 0,
+ * 2^32 voxels or more, n_atoms < 0 (or 2^31 and more), radius < 0, soft < 0, radius + soft == 0, a number that is not finite
+ * (atom coordinates included; also a box that, grown by radius + soft, leaves float64).
+ */
+int mad_map_zone(mad_ctx *ctx, float *grid, const int32_t dims[3], const double origin[3], double voxsp,
+                 const double *atoms, int64_t n_atoms, double radius, double soft, int erase,
+                 int64_t counts[2] /* may be NULL */);
+
 /* ---- one subunit's pair grid sharded over GPUs by blocks of map rows (the exchange steps -- OR of the flag vectors,
  *      all-gather of the per-shard top-k -- are the caller's, mad_amd/dist.py::sharded_match, or the library's own:
  *      mad_dist_or_allreduce / mad_dist_allgather_topk below) ------------------------------------------------- */

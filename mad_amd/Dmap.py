@@ -5,7 +5,9 @@ origin `xi, yi, zi` (Angstrom), box `xb, yb, zb`, `voxsp`, `map_name`, `name`.
 `get_CCC_with_grid` (Dmap.py:153-258) runs on the GPU through `mad_ccc`, `mask_with` (Dmap.py:99-151) through `mad_map_mask`
 and `get_CCC_with_dmap` (Dmap.py:260-372) through `mad_map_ccc`: together the reference's support for docking into a segment of
 a map.  `resample` (no counterpart in the reference) brings a map onto another lattice through `mad_map_resample`, which is what the
-three need when two maps differ in spacing or are not a whole number of voxels apart.  None of them has a CPU fallback.  The reference's per-voxel text writer is replaced by `mapio.write_situs`.
+three need when two maps differ in spacing or are not a whole number of voxels apart.  `zone` (no counterpart in the reference either)
+is the structure-against-map half: it keeps the density within a radius of a structure's atoms, or erases it, through `mad_map_zone`,
+so that the remaining subunits can be docked into what is left of a map.  None of them has a CPU fallback.  The reference's per-voxel text writer is replaced by `mapio.write_situs`.
 """
 import os
 import sys
@@ -43,6 +45,17 @@ class Dmap(object):
             self.grid3d = self.grid3d / np.amax(self.grid3d)
         self.map_name = map_name
         self.name = map_name.split('/')[-1].split('.')[0]
+
+    @classmethod
+    def from_file_as_is(cls, map_name):
+        """The file's densities as a Dmap, as they are: no threshold, no padding, no normalisation (what the file-to-file tools
+        work on).  Raises what `mapio.read_volume` raises."""
+        d = cls.__new__(cls)
+        d.grid3d, d.voxsp, (d.xi, d.yi, d.zi) = mapio.read_volume(map_name)
+        d.xb, d.yb, d.zb = d.grid3d.shape
+        d.map_name = map_name
+        d.name = map_name.split('/')[-1].split('.')[0]
+        return d
 
     def reduce_void(self, zeros_padding=10):
         """Crop to the bounding box of the non-zero voxels, then re-pad (Dmap.py:73-90)."""
@@ -131,6 +144,36 @@ class Dmap(object):
             if hasattr(self, k):
                 setattr(out, k, getattr(self, k))
         return out
+
+    @staticmethod
+    def _zone_atoms(structure):
+        """(n, 3) float64 coordinates of a PDB, an (n, 3) array, or a list / tuple of those (concatenated)."""
+        if hasattr(structure, "get_coords"):
+            structure = structure.get_coords()
+        elif isinstance(structure, (list, tuple)) and (len(structure) == 0 or hasattr(structure[0], "get_coords") or np.ndim(structure[0]) == 2):
+            parts = [Dmap._zone_atoms(s) for s in structure]
+            return np.concatenate(parts, axis=0) if parts else np.zeros((0, 3), np.float64)
+        a = np.asarray(structure, dtype=np.float64)
+        if a.ndim != 2 or a.shape[1] != 3:
+            raise ValueError("Dmap.zone: coordinates of shape %s, not (n, 3)" % (a.shape,))
+        return a
+
+    def zone(self, structure, radius, soft=0.0, erase=False):
+        """Keep the density within `radius` Angstrom of the atoms of `structure` and zero the rest -- or, with `erase=True`, zero
+        it there and keep the rest --, in place.  `soft` > 0 adds a raised-cosine edge from `radius` to `radius + soft`.
+        `structure`: a `PDB`, an (n, 3) array of coordinates, or a list / tuple of those (several placed subunits in one call).
+        Returns (voxels within `radius` of an atom, voxels in the soft edge).  DESIGN.md section 4i has the exact contract."""
+        radius, soft = float(radius), float(soft)
+        if not (radius >= 0 and soft >= 0) or radius + soft == 0:
+            raise ValueError("Dmap.zone: radius %r, soft %r (neither negative, not both 0)" % (radius, soft))
+        atoms = self._zone_atoms(structure)
+        g = self.grid3d
+        if g.dtype != np.float32 or not g.flags.c_contiguous or not g.flags.writeable:
+            g = np.ascontiguousarray(g, dtype=np.float32)
+            if not g.flags.writeable or g is self.grid3d:
+                g = g.copy()
+            self.grid3d = g
+        return _lib.get_lib().map_zone(g, (self.xi, self.yi, self.zi), self.voxsp, atoms, radius, soft, erase)
 
     def write_to_mrc(self, outname):
         mapio.write_mrc(outname, self.grid3d, (self.xi, self.yi, self.zi), self.voxsp)

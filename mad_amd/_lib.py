@@ -39,7 +39,7 @@ SYMBOLS = [
     "mad_dist_unique_id", "mad_dist_init", "mad_dist_destroy", "mad_dist_info", "mad_dist_rehearse_flags", "mad_dist_or_allreduce", "mad_dist_allgather",
     "mad_dist_allgather_topk", "mad_dist_scratch", "mad_dist_copy",
     "mad_set_wire_bytes", "mad_set_export", "mad_set_import", "mad_set_lane", "mad_set_stream", "mad_set_bind_lane",
-    "mad_upload_density", "mad_refine", "mad_last_refine_plan", "mad_last_density_chunks", "mad_structure_to_density", "mad_ccc", "mad_map_mask", "mad_map_ccc", "mad_map_resample", "mad_density_ccc", "mad_dock_refine_score", "mad_grid_overlap", "mad_overlap_matrix",
+    "mad_upload_density", "mad_refine", "mad_last_refine_plan", "mad_last_density_chunks", "mad_structure_to_density", "mad_ccc", "mad_map_mask", "mad_map_ccc", "mad_map_resample", "mad_map_zone", "mad_density_ccc", "mad_dock_refine_score", "mad_grid_overlap", "mad_overlap_matrix",
     "mad_space_create", "mad_space_destroy", "mad_space_build", "mad_space_info", "mad_space_download",
     "mad_space_peaks", "mad_space_patches", "mad_space_localize", "mad_localize_volume",
     "mad_pose_cluster_many",
@@ -1112,6 +1112,23 @@ class Lib(object):
         self._chk(self.dll.mad_map_resample(self.ctx, _p(g), _p(d), _p(o), C.c_double(voxsp), None if Rp is None else _p(Rp),
                                             None if Tp is None else _p(Tp), C.c_int(order), _p(md), _p(p), C.c_double(out_voxsp), _p(out)))
         return out
+
+    def map_zone(self, g, origin, voxsp, atoms, radius, soft=0.0, erase=False):
+        """`g` (writable C-contiguous float32 [x, y, z] with `origin` and `voxsp`) cut around `atoms` in place: a voxel within
+        `radius` of an atom keeps its bits, one `radius + soft` away or farther becomes 0, a raised cosine in between;
+        `erase=True` takes one minus that weight.  `atoms`: anything np.asarray(..., float64).reshape(-1, 3) accepts.
+        -> (voxels within radius, voxels in the soft edge) (mad_map_zone)."""
+        if g.dtype != np.float32 or not g.flags.c_contiguous or not g.flags.writeable:
+            raise ValueError("map_zone needs a writable C-contiguous float32 grid")
+        if g.ndim != 3:
+            raise ValueError("map_zone needs a 3-D grid")
+        d = np.array(g.shape, np.int32)
+        o = _c(np.asarray(origin, np.float64).reshape(3), np.float64)
+        a = _c(np.asarray(atoms, np.float64).reshape(-1, 3), np.float64)
+        counts = np.zeros(2, np.int64)
+        self._chk(self.dll.mad_map_zone(self.ctx, _p(g), _p(d), _p(o), C.c_double(voxsp), _p(a) if len(a) else None, C.c_int64(len(a)),
+                                        C.c_double(radius), C.c_double(soft), C.c_int(1 if erase else 0), _p(counts)))
+        return int(counts[0]), int(counts[1])
 
 
 _default = None

@@ -6,6 +6,7 @@ mad/PDB.py:165-206.  `mrcfile` is not a dependency here: the header fields the
 reference touches (nx..nz, mode, n*start, mx..mz, cella, mapc/r/s, origin) are read
 and written directly.  Out of the hot path.
 """
+import os
 import struct
 
 import numpy as np
@@ -75,6 +76,22 @@ def load_mrc_as_xyz(path):
     dims = [box[a] for a in axis_order]
     grid = np.transpose(m["data"].copy(), axis_order[::-1])
     return grid, voxsp, tuple(float(v) for v in org), tuple(int(v) for v in dims)
+
+
+def read_volume(path):
+    """A map file by its extension, the counterpart of `write_volume`: -> (grid [x,y,z] float32 C-contiguous, voxsp, (xi, yi, zi)),
+    the densities as they are in the file.  FileNotFoundError for a missing file, ValueError for an extension that is neither
+    .sit / .situs nor .map / .mrc."""
+    if not os.path.isfile(path):
+        raise FileNotFoundError("file %s not found" % path)
+    ext = os.path.splitext(path)[-1].lower()
+    if ext in (".sit", ".situs"):
+        grid, voxsp, origin = read_situs(path, np.float32)
+    elif ext in (".map", ".mrc"):
+        grid, voxsp, origin, _ = load_mrc_as_xyz(path)
+    else:
+        raise ValueError("incompatible extension for map %s" % path)
+    return np.ascontiguousarray(grid, dtype=np.float32), voxsp, origin
 
 
 def write_mrc(path, grid_xyz, origin, voxsp):

@@ -12,30 +12,16 @@ import argparse
 import os
 import sys
 
-import numpy as np
-
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from mad_amd import mapio      # noqa: E402
 from mad_amd.Dmap import Dmap      # noqa: E402
 
 
 def load(path):
-    """The file's densities as a Dmap, unthresholded and unnormalised."""
-    if not os.path.isfile(path):
-        sys.exit("resample_map> file %s not found" % path)
-    ext = os.path.splitext(path)[-1].lower()
-    d = Dmap.__new__(Dmap)
-    if ext in (".sit", ".situs"):
-        d.grid3d, d.voxsp, (d.xi, d.yi, d.zi) = mapio.read_situs(path, np.float32)
-    elif ext in (".map", ".mrc"):
-        d.grid3d, d.voxsp, (d.xi, d.yi, d.zi), _ = mapio.load_mrc_as_xyz(path)
-    else:
-        sys.exit("resample_map> incompatible extension for map %s" % path)
-    d.grid3d = np.ascontiguousarray(d.grid3d, dtype=np.float32)
-    d.xb, d.yb, d.zb = d.grid3d.shape
-    d.map_name = path
-    d.name = path.split('/')[-1].split('.')[0]
-    return d
+    try:
+        return Dmap.from_file_as_is(path)
+    except (OSError, ValueError) as e:
+        sys.exit("resample_map> %s" % e)
 
 
 def main(argv=None):
