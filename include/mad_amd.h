@@ -112,6 +112,12 @@ int mad_upload_field(mad_ctx *ctx, int slot, const float *gx, const float *gy, c
 /* Same, from a DEVICE buffer holding the three planes back to back ([3][nx][ny][nz]). */
 int mad_upload_field_device(mad_ctx *ctx, int slot, const float *g3_device, int nx, int ny, int nz);
 int mad_free_field(mad_ctx *ctx, int slot);
+/*
+ * Diagnostic: copies a slot's texels back to the host, tex_xyzw = [nx*ny*nz][4] float32 {gx, gy, gz, |g|} and
+ * tex4 = [nx*ny*nz] packed 4-byte texels; either pointer may be NULL.  Waits for the stream.  MAD_EINVAL for
+ * an empty or out-of-range slot.  Nothing on the path calls it.
+ */
+int mad_field_download(mad_ctx *ctx, int slot, float *tex_xyzw, uint32_t *tex4);
 
 /* ---- a1-a8: Orientator.assign_orientations (Orientator.py:68-110) ------------ */
 
@@ -668,7 +674,8 @@ void mad_space_destroy(mad_ctx *ctx, mad_space *s);
  *   slot_up, slot_base   field slots that receive the gradient texels of np.gradient(
  *             gaussian_filter(grid, sigma_init)) (MapSpace.py:182-187); -1 = do not fill.
  * Filter passes reproduce scipy.ndimage's summation order and per-pass rounding; the
- * spline agrees with scipy to ~4e-16 relative (see mad_space.hip).
+ * spline agrees with scipy to ~4e-16 relative (see mad_space.hip).  A build that fails, a
+ * refused argument included, leaves the space empty.
  */
 int mad_space_build(mad_ctx *ctx, mad_space *s, const void *grid, int is_f64, int nx, int ny, int nz, int pad,
                     int oct_mode, const double *g0, const double *g2, int radius, double sig2,
@@ -684,7 +691,9 @@ int mad_space_download(mad_ctx *ctx, const mad_space *s, int entry, int what, vo
 /*
  * skimage.feature.peak_local_max(map_space[entry], exclude_border=border, threshold_abs=
  * threshold) as Detector.py:29 calls it: voxels equal to the maximum of their zero-extended
- * 3x3x3 neighbourhood and strictly above the threshold.  Returns linear indices
+ * 3x3x3 neighbourhood and strictly above the threshold, compared in the storage type of the entry
+ * as numpy does: a float32 entry against (float)threshold (round to nearest), a float64 entry
+ * against threshold.  Returns linear indices
  * ((x*ny + y)*nz + z) and values in NO particular order; the host sorts (row-major, then by
  * descending value).  MAD_ENOSPC with *n_out = required capacity if cap is too small.
  */

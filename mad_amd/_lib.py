@@ -31,7 +31,7 @@ ERRORS = {-22: "EINVAL", -12: "ENOMEM", -28: "ENOSPC", -19: "ENODEV", -33: "EDOM
 SYMBOLS = [
     "mad_init", "mad_destroy", "mad_last_error", "mad_synchronize", "mad_stream", "mad_set_overlap",
     "mad_timing_enable", "mad_timing_reset", "mad_timing_get", "mad_last_ms", "mad_probe_peaks",
-    "mad_set_eqsp", "mad_upload_field", "mad_upload_field_device", "mad_free_field",
+    "mad_set_eqsp", "mad_upload_field", "mad_upload_field_device", "mad_free_field", "mad_field_download",
     "mad_set_orient_window", "mad_orient", "mad_describe", "mad_describe_sized", "mad_correlate", "mad_pose_score", "mad_topk",
     "mad_set_create", "mad_set_destroy", "mad_set_build", "mad_set_build_many", "mad_set_load", "mad_set_mark_wide", "mad_set_is_wide", "mad_set_size", "mad_set_download",
     "mad_match_topk", "mad_match_topk_many", "mad_match_topk_many_begin", "mad_match_topk_many_finish", "mad_match_topk_many_begin2", "mad_match_topk_many2", "mad_set_batching", "mad_set_option", "mad_last_pose_kernel", "mad_last_pose_selected", "mad_device_allocations", "mad_match_fetch", "mad_match_results", "mad_match_used",
@@ -257,6 +257,7 @@ class DeviceSpace(object):
         if g.ndim != 3 or g.dtype not in (np.float32, np.float64):
             raise ValueError("density grid must be a 3-D float32 or float64 array")
         g = np.ascontiguousarray(g)
+        self.shapes, self.kinds, self.dtypes = [], [], []      # a failed build leaves the space empty, as mad_space_build does
         mode = {"base": 1, "up": 2, "both": 3}[oct_mode]
         R = st.kernel_radius(sig_init)
         g0 = np.ascontiguousarray(st.gaussian_kernel1d(sig_init, 0, R)[::-1])
@@ -266,7 +267,7 @@ class DeviceSpace(object):
         P3, I3 = C.c_void_p * 3, C.c_void_p * 3
         lu = ev_w = ev_i = None
         keep = []
-        if mode & 2:
+        if mode & 2 and min(g.shape) + 2 * pad >= 4:      # shorter lines: mad_space_build refuses them (MAD_EINVAL)
             tabs = [st.spline_tables(int(n) + 2 * pad) for n in g.shape]
             keep = tabs
             lu = P3(*[t[0].ctypes.data for t in tabs])
@@ -283,6 +284,10 @@ class DeviceSpace(object):
         self.shapes = [tuple(int(v) for v in dims[3 * o:3 * o + 3]) for o in range(n.value)]
         self.kinds = [int(kind[o]) for o in range(n.value)]
         self.dtypes = [np.float64 if f64[o] else np.float32 for o in range(n.value)]
+        for shape, kind in zip(self.shapes, self.kinds):
+            slot = slot_up if kind == 0 else slot_base
+            if slot >= 0:
+                self.lib._field_dims[slot] = shape
         return self
 
     def download(self, entry, what):
@@ -290,9 +295,10 @@ class DeviceSpace(object):
         self.lib._chk(self.lib.dll.mad_space_download(self.lib.ctx, self.h, C.c_int(entry), C.c_int(what), _p(out)))
         return out
 
-    def peaks(self, entry, threshold=5e-2, border=12):
-        """-> (coords int (n, 3), values float64 (n,)) in skimage's order: descending value, row-major among equals."""
-        cap = 1 << 16
+    def peaks(self, entry, threshold=5e-2, border=12, cap0=1 << 16):
+        """-> (coords int (n, 3), values float64 (n,)) in skimage's order: descending value, row-major among equals.
+        A float32 entry compares with float32(threshold), as numpy does; cap0 is the first capacity tried (it grows on MAD_ENOSPC)."""
+        cap = int(cap0)
         while True:
             idx, val = np.zeros(cap, np.int64), np.zeros(cap, np.float64)
             n = C.c_int64(0)
@@ -355,6 +361,7 @@ class Lib(object):
                                   % (device, ERRORS.get(rc, rc), msg.decode() if msg else ""))
         self.device = device
         self._fields = {}      # id(array) -> slot bookkeeping is done by the callers
+        self._field_dims = {}  # slot -> (X, Y, Z) of the texels it holds (download_field)
         self._next_slot = 0
         self._free_slots = []
         self._eq_loaded = {}
@@ -455,12 +462,26 @@ class Lib(object):
         nx, ny, nz = planes[0].shape
         self._chk(self.dll.mad_upload_field(self.ctx, C.c_int(slot), _p(planes[0]), _p(planes[1]), _p(planes[2]),
                                             C.c_int(nx), C.c_int(ny), C.c_int(nz)))
+        self._field_dims[slot] = (nx, ny, nz)
 
     def upload_field_device(self, slot, dev_ptr, nx, ny, nz):
         self._chk(self.dll.mad_upload_field_device(self.ctx, C.c_int(slot), C.c_void_p(dev_ptr), C.c_int(nx), C.c_int(ny), C.c_int(nz)))
+        self._field_dims[slot] = (int(nx), int(ny), int(nz))
+
+    def download_field(self, slot):
+        """Diagnostic (mad_field_download): the texels of a slot as the kernels read them
+        -> (float32 (X, Y, Z, 4) {gx, gy, gz, |g|}, uint32 (X, Y, Z) packed 4-byte texels)."""
+        dims = self._field_dims.get(slot)
+        if dims is None:      # nothing known to be there: the library says so
+            self._chk(self.dll.mad_field_download(self.ctx, C.c_int(slot), None, None))
+            raise MadBackendError("MaD> download_field: the size of slot %d is unknown to this binding" % slot)
+        tex, tex4 = np.empty(tuple(dims) + (4,), np.float32), np.empty(tuple(dims), np.uint32)
+        self._chk(self.dll.mad_field_download(self.ctx, C.c_int(slot), _p(tex), _p(tex4)))
+        return tex, tex4
 
     def free_field(self, slot):
         self._chk(self.dll.mad_free_field(self.ctx, C.c_int(slot)))
+        self._field_dims.pop(slot, None)
         if slot not in self._free_slots:
             self._free_slots.append(slot)
 

@@ -434,6 +434,19 @@ extern "C" int mad_free_field(mad_ctx *ctx, int slot) {
     return MAD_OK;
 }
 
+// diagnostic read-back of a slot: the 16-byte texels and the 4-byte ones behind them
+extern "C" int mad_field_download(mad_ctx *ctx, int slot, float *tex_xyzw, uint32_t *tex4) {
+    if (!ctx) return MAD_EINVAL;
+    if (slot < 0 || slot >= MAD_MAX_FIELDS || !ctx->field_mem[slot]) return mad_fail(ctx, MAD_EINVAL, "mad_field_download: slot %d is empty or out of range", slot);
+    const FieldDev &f = ctx->fields[slot];
+    const size_t n = (size_t)f.nx * f.ny * f.nz;
+    MAD_HIP(hipStreamSynchronize(ctx->stream));
+    if (tex_xyzw) MAD_HIP(hipMemcpyAsync(tex_xyzw, f.tex, n * sizeof(float4), hipMemcpyDeviceToHost, ctx->stream));
+    if (tex4) MAD_HIP(hipMemcpyAsync(tex4, f.tex4, n * sizeof(unsigned), hipMemcpyDeviceToHost, ctx->stream));
+    MAD_HIP(hipStreamSynchronize(ctx->stream));
+    return MAD_OK;
+}
+
 // ---------------------------------------------------------------------------
 // small fills and copies as ordinary kernels: one launch each, in stream order, no copy-engine hand-over
 // ---------------------------------------------------------------------------

@@ -193,17 +193,21 @@ __global__ __launch_bounds__(256) void k_convert(const Tin *__restrict__ in, Tou
 }
 
 // 3x3x3 local maxima (value == maximum of the zero-extended neighbourhood), strictly above the threshold,
-// at least `border` voxels from every face (skimage.feature.peak_local_max, min_distance 1)
+// at least `border` voxels from every face (skimage.feature.peak_local_max, min_distance 1).  The threshold is
+// compared in the storage type, as numpy compares an array with a Python float: a float32 volume against
+// float32(thr), rounded to nearest, so a voxel holding exactly that float32 is no peak even where the double
+// lies just below it; a float64 volume against thr itself.
 template <typename T>
 __global__ __launch_bounds__(256) void k_peaks(const T *__restrict__ v, Dims d, double thr, int border, int64_t *__restrict__ out_idx,
                                                double *__restrict__ out_val, int32_t *__restrict__ count, int cap) {
     const size_t total = d.count();
     const size_t sx = (size_t)d.n[1] * d.n[2], sy = (size_t)d.n[2];
+    const T thr_t = (T)thr;
     for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (size_t)gridDim.x * blockDim.x) {
         const int z = (int)(i % d.n[2]), y = (int)((i / d.n[2]) % d.n[1]), x = (int)(i / sx);
         if (x < border || y < border || z < border || x >= d.n[0] - border || y >= d.n[1] - border || z >= d.n[2] - border) continue;
         const T c = v[i];
-        if (!((double)c > thr)) continue;
+        if (!(c > thr_t)) continue;
         bool is_max = !(c < (T)0);      // the zero extension takes part in the maximum
         for (int dx = -1; dx <= 1 && is_max; dx++) {
             for (int dy = -1; dy <= 1 && is_max; dy++) {
@@ -550,15 +554,15 @@ extern "C" int mad_space_build(mad_ctx *ctx, mad_space *s, const void *grid, int
                                const double *pre, int pre_radius, const double *const *lu, const double *const *ev_w,
                                const int32_t *const *ev_i, int slot_up, int slot_base) {
     if (!ctx || !s || !grid || !g0 || !g2) return MAD_EINVAL;
+    MAD_HIP(hipStreamSynchronize(ctx->stream));
+    space_release(s);      // a build that fails, for whatever reason, leaves the space empty
     if (nx < 2 || ny < 2 || nz < 2 || pad < 0 || radius < 1 || radius > 64 || pre_radius < 0 || pre_radius > 64)
         return mad_fail(ctx, MAD_EINVAL, "mad_space_build: dims %dx%dx%d pad %d radius %d/%d", nx, ny, nz, pad, radius, pre_radius);
     if (oct_mode < 1 || oct_mode > 3) return mad_fail(ctx, MAD_EINVAL, "mad_space_build: oct_mode %d", oct_mode);
-    if ((oct_mode & 2) && (!lu || !ev_w || !ev_i || (pre_radius > 0 && !pre))) return mad_fail(ctx, MAD_EINVAL, "mad_space_build: spline tables missing");
     if ((oct_mode & 2) && std::min(nx, std::min(ny, nz)) + 2 * pad < 4) return mad_fail(ctx, MAD_EINVAL, "mad_space_build: a cubic spline needs 4 samples per axis");
+    if ((oct_mode & 2) && (!lu || !ev_w || !ev_i || (pre_radius > 0 && !pre))) return mad_fail(ctx, MAD_EINVAL, "mad_space_build: spline tables missing");
     const size_t up = (size_t)(2 * (nx + 2 * pad) - 1) * (2 * (ny + 2 * pad) - 1) * (2 * (nz + 2 * pad) - 1);
     if ((oct_mode & 2) && up >= ((size_t)1 << 32)) return mad_fail(ctx, MAD_EINVAL, "mad_space_build: upsampled volume of %zu voxels exceeds 2^32", up);
-    MAD_HIP(hipStreamSynchronize(ctx->stream));
-    space_release(s);
     int rc;
     if (is_f64) rc = build_all<double>(ctx, s, (const double *)grid, nx, ny, nz, pad, oct_mode, g0, g2, radius, sig2, pre, pre_radius, lu, ev_w, ev_i, slot_up, slot_base);
     else rc = build_all<float>(ctx, s, (const float *)grid, nx, ny, nz, pad, oct_mode, g0, g2, radius, sig2, pre, pre_radius, lu, ev_w, ev_i, slot_up, slot_base);
