@@ -445,6 +445,47 @@ int mad_map_zone(mad_ctx *ctx, float *grid, const int32_t dims[3], const double 
                  const double *atoms, int64_t n_atoms, double radius, double soft, int erase,
                  int64_t counts[2] /* may be NULL */);
 
+/*
+ * A Gaussian on a map, and a map cut into segments (mad_segment.hip).  Host pointers, synchronous.  Both work
+ * in voxels: grid is float32 [x][y][z] with dims, the linear index of a voxel is L = (x * ny + y) * nz + z, neither origin nor
+ * spacing enters.
+ *
+ * mad_map_smooth: out = grid smoothed with a Gaussian of sigma_vox voxels; out may be grid.  R = (int)(4 sigma + 0.5); the taps are
+ * w_k = exp(-0.5 * k * k / (sigma * sigma)), k = 0 .. R, float64 with libm's exp on the host, divided by w_0 + 2 * (w_1 + w_2 + ...)
+ * (that sum accumulated for k = 1, 2, ... in this order).  Three passes, over axis 0, then 1, then 2, float64 in between; an output
+ * of a pass is a = c * w_0, then for k = R, R - 1, ..., 1: a += (in[-k] + in[+k]) * w_k, products and sums rounded separately (no
+ * FMA), a tap outside the grid being 0.0 (zero extension: scipy.ndimage.gaussian_filter(mode="constant", truncate=4.0)).  The last
+ * pass rounds to float32.  A voxel that is not finite is no error here: it propagates as IEEE says.
+ * MAD_EINVAL, with nothing launched and out untouched: NULL, a dimension < 1, 2^31 voxels or more, sigma_vox <= 0 or not finite
+ * (or 2^18 voxels and more).
+ *
+ * mad_map_segment: a watershed of the density, whose regions are then grouped by following their maxima through smoothed copies of
+ * the map.
+ *   Order.  Voxel a is above voxel b iff v_a > v_b, or v_a == v_b and L_a < L_b (IEEE compares: -0.0 == +0.0).  A strict total order.
+ *   Watershed.  A voxel is foreground iff (double)v > threshold (strict; threshold = -inf is allowed).  The parent of a foreground
+ *     voxel is the greatest, in the order, among itself and its foreground neighbours (up to 26, those inside the grid).  A root is
+ *     its own parent; a foreground voxel belongs to the root its chain of parents ends in.  The regions are numbered 1 .. n by
+ *     ascending L of their roots; a background voxel has label 0.
+ *   Grouping.  point_r starts as the root of region r.  For s = 1 .. steps: S_s = the map smoothed as by mad_map_smooth with sigma =
+ *     s * step voxels (always from the original grid; the same bits), the parents of S_s are taken with every voxel foreground, and
+ *     point_r becomes the root of point_r in S_s.  Regions with equal points are one group (equal points stay equal: groups only
+ *     merge).  history[s] = the number of groups after step s, history[0] = n.  The steps stop after the first one with
+ *     history[s] <= stop_at (stop_at = 0: never early).  The groups are numbered 1 .. m by ascending smallest member region.
+ * Outputs: labels int32 [x][y][z], the group of every voxel (0: background; with steps = 0 the region); per region r (0-based,
+ * region r + 1) root[r] int64 = L of its root, peak[r] float32 = the value there (the region's maximum), size[r] int64 = its voxels,
+ * group[r] int32 = its group -- each of the four may be NULL --; history int64 [steps + 1], of which [0 .. *steps_done] are
+ * written; *steps_done = smoothing steps run (0 when n = 0); *n_regions = n.  cap = entries each region table holds: with n > cap
+ * the call returns MAD_ENOSPC with *n_regions = n (the capacity needed), the tables untouched, and labels, history and *steps_done
+ * as valid as otherwise.  The same call gives the same bits alone or after any other call.
+ * MAD_EDOM, nothing written: a voxel that is not finite (found by the first pass over the map on the device).
+ * MAD_EINVAL, nothing launched or written: NULL (other than a table), a dimension < 1, 2^31 voxels or more, a NaN threshold,
+ * steps < 0, step <= 0 or not finite, stop_at < 0, cap < 0, steps * step of 2^18 voxels and more.
+ */
+int mad_map_smooth(mad_ctx *ctx, const float *grid, const int32_t dims[3], double sigma_vox, float *out);
+int mad_map_segment(mad_ctx *ctx, const float *grid, const int32_t dims[3], double threshold, int32_t steps, double step,
+                    int64_t stop_at, int32_t *labels, int64_t *root, float *peak, int64_t *size, int32_t *group, int64_t cap,
+                    int64_t *n_regions, int64_t *history, int32_t *steps_done);
+
 /* ---- one subunit's pair grid sharded over GPUs by blocks of map rows (the exchange steps -- OR of the flag vectors,
  *      all-gather of the per-shard top-k -- are the caller's, mad_amd/dist.py::sharded_match, or the library's own:
  *      mad_dist_or_allreduce / mad_dist_allgather_topk below) ------------------------------------------------- */

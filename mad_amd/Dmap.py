@@ -7,7 +7,9 @@ and `get_CCC_with_dmap` (Dmap.py:260-372) through `mad_map_ccc`: together the re
 a map.  `resample` (no counterpart in the reference) brings a map onto another lattice through `mad_map_resample`, which is what the
 three need when two maps differ in spacing or are not a whole number of voxels apart.  `zone` (no counterpart in the reference either)
 is the structure-against-map half: it keeps the density within a radius of a structure's atoms, or erases it, through `mad_map_zone`,
-so that the remaining subunits can be docked into what is left of a map.  None of them has a CPU fallback.  The reference's per-voxel text writer is replaced by `mapio.write_situs`.
+so that the remaining subunits can be docked into what is left of a map.  `smooth` applies a Gaussian through `mad_map_smooth` and
+`segment` cuts the map into segments through `mad_map_segment` (watershed regions grouped by smoothing, the scheme of Segger; no
+counterpart in the reference), which is where the masks `mask_with` consumes come from.  None of them has a CPU fallback.  The reference's per-voxel text writer is replaced by `mapio.write_situs`.
 """
 import os
 import sys
@@ -174,6 +176,44 @@ class Dmap(object):
                 g = g.copy()
             self.grid3d = g
         return _lib.get_lib().map_zone(g, (self.xi, self.yi, self.zi), self.voxsp, atoms, radius, soft, erase)
+
+    def smooth(self, sigma):
+        """A Gaussian of `sigma` Angstrom on the map, in place (zero beyond the box, float64 inside, 4 sigma wide on either side).
+        Returns self."""
+        sigma = float(sigma)
+        if not (sigma > 0) or not np.isfinite(sigma):
+            raise ValueError("Dmap.smooth: sigma %r (positive and finite)" % (sigma,))
+        g = self.grid3d
+        if g.dtype != np.float32 or not g.flags.c_contiguous or not g.flags.writeable:
+            g = np.ascontiguousarray(g, dtype=np.float32)
+            if not g.flags.writeable or g is self.grid3d:
+                g = g.copy()
+        _lib.get_lib().map_smooth(g, sigma / self.voxsp, out=g)
+        self.grid3d = g
+        return self
+
+    def segment(self, threshold=0.0, steps=4, step=1.0, stop_at=0):
+        """The map cut into segments -> `segment.Segmentation`; the map is untouched.  Watershed regions of the density above
+        `threshold` (every voxel climbs to the greatest of its 26 neighbours; a region is what ends in one maximum) are merged
+        into groups by following their maxima through `steps` copies of the map smoothed with a Gaussian of `step`, 2 `step`, ...
+        voxels (as in Segger), stopping early once no more than `stop_at` groups are left (0: never).  `seg.mask(ids)` is a mask
+        for `mask_with`.  DESIGN.md section 4j has the exact contract."""
+        threshold, step_f = float(threshold), float(step)
+        if threshold != threshold:
+            raise ValueError("Dmap.segment: the threshold is not a number")
+        if int(steps) != steps or steps < 0 or steps >= 2 ** 31:
+            raise ValueError("Dmap.segment: steps %r (a whole number, not negative)" % (steps,))
+        if not (step_f > 0) or not np.isfinite(step_f):
+            raise ValueError("Dmap.segment: step %r voxels (positive and finite)" % (step,))
+        if int(stop_at) != stop_at or stop_at < 0:
+            raise ValueError("Dmap.segment: stop_at %r (a whole number, not negative)" % (stop_at,))
+        g = np.ascontiguousarray(self.grid3d, dtype=np.float32)
+        if not np.isfinite(g).all():
+            raise ValueError("Dmap.segment: the map holds a density that is not finite")
+        from .segment import Segmentation
+        r = _lib.get_lib().map_segment(g, threshold, int(steps), step_f, int(stop_at))
+        return Segmentation(r["labels"], (self.xi, self.yi, self.zi), self.voxsp,
+                            dict((k, r[k]) for k in ("root", "peak", "size", "group")), r["history"], r["n_regions"])
 
     def write_to_mrc(self, outname):
         mapio.write_mrc(outname, self.grid3d, (self.xi, self.yi, self.zi), self.voxsp)

@@ -39,7 +39,7 @@ SYMBOLS = [
     "mad_dist_unique_id", "mad_dist_init", "mad_dist_destroy", "mad_dist_info", "mad_dist_rehearse_flags", "mad_dist_or_allreduce", "mad_dist_allgather",
     "mad_dist_allgather_topk", "mad_dist_scratch", "mad_dist_copy",
     "mad_set_wire_bytes", "mad_set_export", "mad_set_import", "mad_set_lane", "mad_set_stream", "mad_set_bind_lane",
-    "mad_upload_density", "mad_refine", "mad_last_refine_plan", "mad_last_density_chunks", "mad_structure_to_density", "mad_ccc", "mad_map_mask", "mad_map_ccc", "mad_map_resample", "mad_map_zone", "mad_density_ccc", "mad_dock_refine_score", "mad_grid_overlap", "mad_overlap_matrix",
+    "mad_upload_density", "mad_refine", "mad_last_refine_plan", "mad_last_density_chunks", "mad_structure_to_density", "mad_ccc", "mad_map_mask", "mad_map_ccc", "mad_map_resample", "mad_map_zone", "mad_map_smooth", "mad_map_segment", "mad_density_ccc", "mad_dock_refine_score", "mad_grid_overlap", "mad_overlap_matrix",
     "mad_space_create", "mad_space_destroy", "mad_space_build", "mad_space_info", "mad_space_download",
     "mad_space_peaks", "mad_space_patches", "mad_space_localize", "mad_localize_volume",
     "mad_pose_cluster_many",
@@ -1150,6 +1150,66 @@ class Lib(object):
         self._chk(self.dll.mad_map_zone(self.ctx, _p(g), _p(d), _p(o), C.c_double(voxsp), _p(a) if len(a) else None, C.c_int64(len(a)),
                                         C.c_double(radius), C.c_double(soft), C.c_int(1 if erase else 0), _p(counts)))
         return int(counts[0]), int(counts[1])
+
+    def map_smooth(self, g, sigma_vox, out=None):
+        """`g` (C-contiguous float32 [x, y, z]) smoothed with a Gaussian of `sigma_vox` voxels, zero beyond the grid, float64 inside
+        -> a new float32 array, or `out` (which may be `g` itself) (mad_map_smooth)."""
+        if g.dtype != np.float32 or not g.flags.c_contiguous:
+            raise ValueError("map_smooth needs a C-contiguous float32 grid")
+        if g.ndim != 3:
+            raise ValueError("map_smooth needs a 3-D grid")
+        if out is None:
+            out = np.empty(g.shape, np.float32)
+        elif out.dtype != np.float32 or not out.flags.c_contiguous or not out.flags.writeable or out.shape != g.shape:
+            raise ValueError("map_smooth: out must be a writable C-contiguous float32 array of the grid's shape")
+        d = np.array(g.shape, np.int32)
+        self._chk(self.dll.mad_map_smooth(self.ctx, _p(g), _p(d), C.c_double(sigma_vox), _p(out)))
+        return out
+
+    SEGMENT_CAP0 = 1 << 16      # regions the tables of map_segment hold at first (they grow on MAD_ENOSPC, at the price of a second call)
+
+    def map_segment(self, g, threshold=0.0, steps=4, step=1.0, stop_at=0, cap=None):
+        """Watershed regions of `g` (C-contiguous float32 [x, y, z]; foreground: value > threshold), grouped by following their maxima
+        through `steps` copies of the map smoothed with sigma = step, 2 step, ... voxels, stopping early once no more than `stop_at`
+        groups are left (0: never) (mad_map_segment).  -> dict: `labels` int32 (the group of every voxel, 0 for
+        background), per region `root` (int64 linear index), `peak` (float32), `size` (int64), `group` (int32), and `history` (groups
+        after step 0 .. steps_done), `steps_done`, `n_regions`, `n_groups`.  `cap`: the capacity of the region tables; by default it
+        grows until they fit, with a given one that is too small the four tables come back as None and `n_regions` says what is needed."""
+        if g.dtype != np.float32 or not g.flags.c_contiguous:
+            raise ValueError("map_segment needs a C-contiguous float32 grid")
+        if g.ndim != 3:
+            raise ValueError("map_segment needs a 3-D grid")
+        steps_i = int(steps)
+        if steps_i != steps or not -2 ** 31 <= steps_i < 2 ** 31:
+            raise ValueError("map_segment: steps %r" % (steps,))
+        stop_i = int(stop_at)
+        if stop_i != stop_at or not -2 ** 63 <= stop_i < 2 ** 63:
+            raise ValueError("map_segment: stop_at %r" % (stop_at,))
+        d = np.array(g.shape, np.int32)
+        labels = np.zeros(g.shape, np.int32)
+        history = np.zeros(max(steps_i, 0) + 1, np.int64)
+        try_cap = int(cap) if cap is not None else max(1, min(g.size, self.SEGMENT_CAP0))
+        while True:
+            tabs = (np.zeros(max(try_cap, 0), np.int64), np.zeros(max(try_cap, 0), np.float32), np.zeros(max(try_cap, 0), np.int64),
+                    np.zeros(max(try_cap, 0), np.int32))
+            n, done = C.c_int64(0), C.c_int32(0)
+            rc = self.dll.mad_map_segment(self.ctx, _p(g), _p(d), C.c_double(threshold), C.c_int32(steps_i), C.c_double(step), C.c_int64(stop_i),
+                                          _p(labels), _p(tabs[0]), _p(tabs[1]), _p(tabs[2]), _p(tabs[3]), C.c_int64(try_cap), C.byref(n),
+                                          _p(history), C.byref(done))
+            if rc == -28 and n.value > try_cap:      # MAD_ENOSPC: n holds the capacity needed; labels and history are valid
+                if cap is not None:
+                    tabs = None
+                    break
+                try_cap = n.value
+                continue
+            self._chk(rc)
+            break
+        n, done = int(n.value), int(done.value)
+        hist = history[:done + 1].copy()
+        out = dict(labels=labels, history=hist, steps_done=done, n_regions=n, n_groups=int(hist[-1]))
+        for k, name in enumerate(("root", "peak", "size", "group")):
+            out[name] = None if tabs is None else tabs[k][:n].copy()
+        return out
 
 
 _default = None
