@@ -98,6 +98,13 @@ int mad_probe_peaks(mad_ctx *ctx, double *copy_gbs, double *i8_tops);
  */
 int mad_set_eqsp(mad_ctx *ctx, int which, int Z, const double *bounds,
                  const double *to_dom, const double *adj_sec);
+/*
+ * The table classifier k_describe reads for the 4-byte texels, built from a zone table alone: host arithmetic, no context and no
+ * device (mad_set_eqsp calls it).  zbelt_out: 2048 bytes, z bin -> belt; ptab_out: 4 x 2048 bytes, belt x pseudo-angle bin -> zone;
+ * 255 = the table does not decide.  Returns 1 when built, 0 when this zone table does not fit the classifier (more than 4 belts or
+ * more than 127 zones: every entry is 255 and k_describe takes its other form), MAD_EINVAL otherwise.  No reference counterpart.
+ */
+int mad_eqsp_tab_build(const double *bounds, int Z, unsigned char *zbelt_out, unsigned char *ptab_out);
 
 /* ---- gradient fields (input of the path; produced by MapSpace.py:178-189) ---- */
 

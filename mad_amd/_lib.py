@@ -31,7 +31,7 @@ ERRORS = {-22: "EINVAL", -12: "ENOMEM", -28: "ENOSPC", -19: "ENODEV", -33: "EDOM
 SYMBOLS = [
     "mad_init", "mad_destroy", "mad_last_error", "mad_synchronize", "mad_stream", "mad_set_overlap",
     "mad_timing_enable", "mad_timing_reset", "mad_timing_get", "mad_last_ms", "mad_probe_peaks",
-    "mad_set_eqsp", "mad_upload_field", "mad_upload_field_device", "mad_free_field", "mad_field_download",
+    "mad_set_eqsp", "mad_eqsp_tab_build", "mad_upload_field", "mad_upload_field_device", "mad_free_field", "mad_field_download",
     "mad_set_orient_window", "mad_orient", "mad_describe", "mad_describe_sized", "mad_correlate", "mad_pose_score", "mad_topk",
     "mad_set_create", "mad_set_destroy", "mad_set_build", "mad_set_build_many", "mad_set_load", "mad_set_mark_wide", "mad_set_is_wide", "mad_set_size", "mad_set_download",
     "mad_match_topk", "mad_match_topk_many", "mad_match_topk_many_begin", "mad_match_topk_many_finish", "mad_match_topk_many_begin2", "mad_match_topk_many2", "mad_set_batching", "mad_set_option", "mad_last_pose_kernel", "mad_last_pose_selected", "mad_device_allocations", "mad_match_fetch", "mad_match_results", "mad_match_used",
@@ -111,6 +111,22 @@ def load_library():
         _dll.mad_set_destroy.restype = None
         _dll.mad_space_destroy.restype = None
     return _dll
+
+
+TAB_ZBINS, TAB_PBINS, TAB_BELTS = 2048, 2048, 4      # MAD_TAB_* of csrc/mad_common.h
+
+
+def eqsp_tab_build(bounds):
+    """The table classifier of the 4-byte texels as the library builds it for the zone table `bounds` (Z x 4), on the host: no
+    device is opened.  Returns (ok, zbelt[2048], ptab[4, 2048]) as uint8, 255 = undecided; ok is False when the zone table does
+    not fit the classifier (then every entry is 255)."""
+    dll = load_library()
+    b = _c(bounds, np.float64).reshape(-1, 4)
+    zbelt, ptab = np.empty(TAB_ZBINS, np.uint8), np.empty((TAB_BELTS, TAB_PBINS), np.uint8)
+    rc = dll.mad_eqsp_tab_build(_p(b), C.c_int(len(b)), _p(zbelt), _p(ptab))
+    if rc < 0:
+        raise ValueError("mad_eqsp_tab_build: %s" % ERRORS.get(rc, rc))
+    return rc == 1, zbelt, ptab
 
 
 def _p(a):

@@ -48,13 +48,55 @@ struct __attribute__((aligned(16))) EqspFastLds {
 
 // Table classifier of the 4-byte texels (k_describe, descriptor sphere only): belt from z through `zbelt`, zone inside the belt from
 // the pseudo-angle p = 1 - x / (|x| + |y|) (y >= 0) or 3 + x / (|x| + |y|) (y < 0), monotonic in theta, through `ptab`.  An entry is
-// a zone only where EVERY direction that can land in the bin -- the bin, its two neighbours and MAD_TAB_GUARD radians around them
-// (more than twice the 1.7e-3 rad three 10-bit components can be off together) -- lies strictly inside that zone; everything else is 255 =
-// "undecided", and the sample goes through the float32 / float64 tiers on its full texel.
+// a zone only where EVERY sample that can land in the bin is one the exact tiers put into that zone; everything else is 255 =
+// "undecided", and the sample goes through the float32 / float64 tiers on its full texel.  mad_eqsp_tab_build (mad_ctx.hip) builds
+// the tables on the host; tests/test_tab_table.py restates the property from the built table.
+//
+// What "can land in the bin" means.  Let v = (x, y, z) / w be the texel's direction with the float32 w it stores, as a real vector,
+// and u = R v.  The exact tiers decide from u_e (describe_exact), eqsp_tab32 from u_d, the decoded 10-bit components rotated in
+// float32.  MAD_TAB_GUARD bounds |u_d - u_e| as a VECTOR LENGTH on the unit scale (not radians), term by term:
+//   1.694 77e-3   the three roundings to a multiple of 1 / 511: sqrt(3) * 0.5 / 511, exact
+//   0.000 21e-3   mad_tex4_encode's float32 `inv = 511 / w` and `x * inv` (2 roundings, 2^-24 each, of components <= 1: 1.2e-7 each,
+//                 which moves a rounding tie by as much; sqrt(3) of that)
+//   0.000 50e-3   the float32 rotation: R's entries rounded to float32, the 1 / 511 folded into its third row (a rounding of the
+//                 constant and one of the product), three products and two sums per component, each 2^-24 of a value <= 1.002
+//                 on the unit scale: <= 2.9e-7 per component, sqrt(3) of that
+//   0.000 11e-3   u_e against R v: describe_exact divides by w in float32 (one rounding per component, sqrt(3) * 6e-8); its
+//                 rotation is float64.  (eqsp_fast32's rcp never decides: it only answers where float64 is certain to agree.)
+//   0.000 02e-3   R: taken as a rotation (Rfinal is the product of two table rotations, orthogonal to 1e-15; callers of mad_describe
+//                 hand rotations in), so that |R e| = |e|.  The entry covers a matrix 1e-5 off orthogonal.
+//   ------------
+//   1.695 61e-3   MAD_TAB_GUARD = 1.746e-3 is 1.03 x the first term: the margin, 5.0e-5, is 60 x the sum of the four float32 terms,
+//                 the only ones that are estimates (the first is exact).  A wider margin buys nothing and costs open samples
+//                 (4e-3 applied to phi left 3.94 % of uniform directions open; this leaves 1.86 %).
+// |v| is not 1 (w is a rounded square root of a rounded sum: 1 +- 1.5e-7), and acos takes u_e's third component as it is.  That is
+// no error between u_d and u_e -- both are images of the same v -- and so no term above.  It matters in one place: a sample whose
+// exact phi lies in a belt has a true (x, y) at least s_min - 4e-7 long, not s_min (s_min: the smaller sin(phi) of the belt's two
+// bounds, >= 0.48 for the 16 zones).
+//
+// How the tables use it (g = MAD_TAB_GUARD, slop = MAD_TAB_SLOP bins):
+//   zbelt[k] = b iff [z_k - slop - g, z_k+1 + slop + g] lies strictly inside (cos ph_hi[b], cos ph_lo[b]): the error of the third
+//     component is at most g, so the exact tiers see a phi strictly inside the belt.  The error lives in z, which is why the guard is
+//     applied there: as an angle of phi it is g / sin(phi), 2.1 x g at the caps' edges and g at the equator.
+//   ptab[b][k] = a iff theta over [p_k - slop, p_k+1 + slop], widened by asin(g / (s_min - g)) on either side, lies strictly inside
+//     zone a (or does after adding 2 pi): zbelt admits only samples whose exact phi lies in belt b; the (x, y) part of u_e is then
+//     at least s_min - 4e-7 long, the (x, y) part of u_d - u_e at most g, and a plane vector of length L moved by at most g turns
+//     by at most asin(g / L).  The g in the denominator stands for taking s_min for L: it over-covers the 4e-7 by 4 000 x.
+//     A belt of ONE zone (a polar cap) spans every azimuth and every entry is that zone.  A belt with s_min <= 0.05 stays open.
+//     The two bins on either side of the 0 / 2 pi seam stay open.
+//   slop: eqsp_tab32's two floor arguments in float32.  z: one fused multiply-add, half an ulp of a value below 2 048 = 6.1e-5
+//     bin (the error of z itself is in g).  p: |x| + |y|, v_rcp_f32 (1 ulp) and the product, 2.4e-7 of |xr| <= 1 = 1.2e-4 bin
+//     after the scaling by 512; the fused multiply-add and the subtraction from 1 024, 6.1e-5 bin each: 2.5e-4 bin.  MAD_TAB_SLOP =
+//     0.01 bin is 40 x that, and 1 % of what the two neighbour bins it replaces cost.
+// A strict inequality against the 4-decimal bounds is all the exact tiers ask: g and the widening are 100 x the 1.47e-5 rad sliver
+// at the seam and 1e5 x the float64 rounding of atan2 / acos.
+// Sampling cannot replace this derivation: on the host model a guard of 0.6 x the bound still decides nothing wrongly in 1.2 M
+// worst-case-directed samples, because a decided bin keeps half a bin of accidental slack on average.
 #define MAD_TAB_BELTS 4
 #define MAD_TAB_PBINS 2048
 #define MAD_TAB_ZBINS 2048
-#define MAD_TAB_GUARD 4e-3
+#define MAD_TAB_GUARD 1.746e-3
+#define MAD_TAB_SLOP 0.01
 struct __attribute__((aligned(16))) EqspTabLds {
     unsigned char zbelt[MAD_TAB_ZBINS];
     unsigned char ptab[MAD_TAB_BELTS][MAD_TAB_PBINS];

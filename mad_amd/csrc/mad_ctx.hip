@@ -226,6 +226,64 @@ extern "C" double mad_last_ms(mad_ctx *ctx, const char *what) {
 // EQSP tables
 // ---------------------------------------------------------------------------
 
+// The tables of EqspTabLds from a zone table alone: host arithmetic, no context, no device (mad_set_eqsp calls it; the tests and
+// tools/check_tab_classifier.py read the table the kernels really use through it).  1: built; 0: this zone table does not fit the
+// classifier (more than MAD_TAB_BELTS belts or more than 127 zones) and every entry is 255.  The property each decided entry has,
+// and the derivation of MAD_TAB_GUARD and MAD_TAB_SLOP, are stated at the struct (mad_common.h).
+extern "C" int mad_eqsp_tab_build(const double *bounds, int Z, unsigned char *zbelt_out, unsigned char *ptab_out) {
+    if (!bounds || !zbelt_out || !ptab_out || Z < 2 || Z > MAD_MAX_Z) return MAD_EINVAL;
+    memset(zbelt_out, 255, MAD_TAB_ZBINS);
+    memset(ptab_out, 255, (size_t)MAD_TAB_BELTS * MAD_TAB_PBINS);
+    // belts as mad_set_eqsp finds them: a new one starts when phi_min changes (eqsp.py:40)
+    double ph_lo[MAD_TAB_BELTS], ph_hi[MAD_TAB_BELTS];
+    int first[MAD_TAB_BELTS], count[MAD_TAB_BELTS], nb = -1;
+    for (int a = 0; a < Z; a++) {
+        if (nb < 0 || bounds[4 * a + 1] != ph_lo[nb]) {
+            if (++nb >= MAD_TAB_BELTS) return 0;
+            ph_lo[nb] = bounds[4 * a + 1]; ph_hi[nb] = bounds[4 * a + 3];
+            first[nb] = a; count[nb] = 0;
+        } else if (bounds[4 * a + 3] != ph_hi[nb]) return MAD_EINVAL;
+        count[nb]++;
+    }
+    const int nbelt = nb + 1;
+    if (Z > 127) return 0;
+    const double g = MAD_TAB_GUARD, pi = 3.14159265358979323846;
+    // belt: every z the exact tiers can see for a sample of bin k lies in [z_k - slop - g, z_k+1 + slop + g]; decided iff that lies
+    // strictly inside (cos ph_hi, cos ph_lo).  A polar cap's outer bound is the pole itself: the bins the interval of which reaches
+    // +-1 stay open, as they always did.
+    const double zw = 2.0 / MAD_TAB_ZBINS;
+    for (int k = 0; k < MAD_TAB_ZBINS; k++) {
+        const double zlo = -1.0 + (k - MAD_TAB_SLOP) * zw - g, zhi = -1.0 + (k + 1 + MAD_TAB_SLOP) * zw + g;
+        for (int b = 0; b < nbelt; b++)
+            if (zlo > cos(std::min(std::max(ph_hi[b], 0.0), pi)) && zhi < cos(std::min(std::max(ph_lo[b], 0.0), pi))) zbelt_out[k] = (unsigned char)b;
+    }
+    auto theta_of = [&](double p) {      // inverse of eqsp_tab32's pseudo-angle
+        if (p <= 2.0) { const double xr = 1.0 - p; return atan2(1.0 - fabs(xr), xr); }
+        const double xr = p - 3.0;
+        return atan2(-(1.0 - fabs(xr)), xr) + 2.0 * pi;
+    };
+    const double pw = 4.0 / MAD_TAB_PBINS;
+    for (int b = 0; b < nbelt; b++) {
+        const int a0 = first[b], cnt = count[b];
+        unsigned char *row = ptab_out + (size_t)b * MAD_TAB_PBINS;
+        if (cnt == 1) { memset(row, a0, MAD_TAB_PBINS); continue; }      // a polar cap spans every azimuth
+        // the belt table admits only samples whose TRUE phi lies in the belt: their true (x, y) is at least s_min long, the decoded
+        // one at least s_min - g, and a vector that long moved by g turns by at most asin(g / (s_min - g))
+        const double s_min = std::min(sin(ph_lo[b]), sin(ph_hi[b]));          // sin(phi) is concave on [0, pi]
+        if (!(s_min > 0.05)) continue;
+        const double gt = asin(g / (s_min - g));
+        for (int k = 2; k < MAD_TAB_PBINS - 2; k++) {                           // (the bins at the 0 / 2 pi seam stay undecided)
+            const double t0 = theta_of((k - MAD_TAB_SLOP) * pw) - gt, t1 = theta_of((k + 1 + MAD_TAB_SLOP) * pw) + gt;
+            for (int a = a0; a < a0 + cnt; a++) {
+                const double lo = bounds[4 * a], hi = bounds[4 * a + 2];
+                const bool in = (t0 > lo && t1 < hi) || (t0 + 2.0 * pi > lo && t1 + 2.0 * pi < hi);
+                if (in) row[k] = (unsigned char)a;
+            }
+        }
+    }
+    return 1;
+}
+
 extern "C" int mad_set_eqsp(mad_ctx *ctx, int which, int Z, const double *bounds, const double *to_dom,
                             const double *adj_sec) {
     if (!ctx) return MAD_EINVAL;
@@ -312,38 +370,8 @@ extern "C" int mad_set_eqsp(mad_ctx *ctx, int which, int Z, const double *bounds
         }
     }
     {   // table classifier of the 4-byte texels (EqspTabLds): conservative by construction, see the struct
-        EqspTabLds &T = h.tab;
-        memset(&T, 255, sizeof(T));
         static const bool no_tab = getenv("MAD_NO_TAB") != nullptr;      // diagnostic switch
-        h.tab_ok = (h.nbelt <= MAD_TAB_BELTS && Z <= 127 && !no_tab) ? 1 : 0;
-        const double g = MAD_TAB_GUARD, pi = 3.14159265358979323846;
-        for (int k = 0; h.tab_ok && k < MAD_TAB_ZBINS; k++) {
-            const double zlo = -1.0 + (k - 1) * (2.0 / MAD_TAB_ZBINS), zhi = -1.0 + (k + 2) * (2.0 / MAD_TAB_ZBINS);      // the bin and its neighbours
-            if (zlo <= -1.0 || zhi >= 1.0) continue;
-            const double ph_min = acos(zhi) - g, ph_max = acos(zlo) + g;
-            for (int b = 0; b < h.nbelt; b++)
-                if (ph_min > h.ph_lo[b] && ph_max < h.ph_hi[b]) T.zbelt[k] = (unsigned char)b;
-        }
-        auto theta_of = [&](double p) {      // inverse of eqsp_tab32's pseudo-angle
-            if (p <= 2.0) { const double xr = 1.0 - p; return atan2(1.0 - fabs(xr), xr); }
-            const double xr = p - 3.0;
-            return atan2(-(1.0 - fabs(xr)), xr) + 2.0 * pi;
-        };
-        for (int b = 0; h.tab_ok && b < h.nbelt; b++) {
-            const int a0 = h.belt_first[b], cnt = h.belt_count[b];
-            unsigned char *row = T.ptab[b];
-            if (cnt == 1) { memset(row, a0, MAD_TAB_PBINS); continue; }      // a polar cap spans every azimuth
-            const double s_min = std::min(sin(h.ph_lo[b]), sin(h.ph_hi[b]));        // sin(phi) is concave on [0, pi]
-            if (!(s_min > 0.05)) continue;                                          // an angular error is an azimuth error / sin(phi)
-            const double gt = g / s_min;
-            for (int k = 2; k < MAD_TAB_PBINS - 2; k++) {                           // (the bins at the 0 / 2 pi seam stay undecided)
-                const double t0 = theta_of((k - 1) * (4.0 / MAD_TAB_PBINS)) - gt, t1 = theta_of((k + 2) * (4.0 / MAD_TAB_PBINS)) + gt;
-                for (int a = a0; a < a0 + cnt; a++) {
-                    const bool in = (t0 > h.th_lo[a] && t1 < h.th_hi[a]) || (t0 + 2.0 * pi > h.th_lo[a] && t1 + 2.0 * pi < h.th_hi[a]);
-                    if (in) row[k] = (unsigned char)a;
-                }
-            }
-        }
+        h.tab_ok = mad_eqsp_tab_build(bounds, Z, h.tab.zbelt, &h.tab.ptab[0][0]) == 1 && !no_tab ? 1 : 0;
     }
     if (to_dom) memcpy(h.to_dom, to_dom, sizeof(double) * 9 * Z);
     if (adj_sec) memcpy(h.adj_sec, adj_sec, sizeof(double) * 9 * Z);

@@ -919,21 +919,31 @@ template <int S, int NSUB> __device__ __forceinline__ int sub_of_i(int i) {
 // TAB (round 3): the samples are gathered from the field's 4-byte texels (a unit direction in 3 x 10 bits, FieldDev::tex4) and
 // classified through the conservative tables of EqspTabLds -- a quarter of the bytes per gather, ~25 vector instructions per
 // sample instead of ~65 for normalisation + rotation + eqsp_fast32, a quarter of the registers for the texels in flight.  What the
-// table cannot decide (the bins a zone edge crosses +- MAD_TAB_GUARD, 2-4 % of the samples) is queued BY TEXEL INDEX and goes
+// table cannot decide (the bins within MAD_TAB_GUARD, the bound on what the 10-bit components can be off, of a zone edge: 1.9 % of
+// uniform directions, half of what the 4e-3 rad guard of round 3 left open) is queued BY TEXEL INDEX and goes
 // through the former tiers -- float32 with its 1e-4 guard, then float64 -- on the full 16-byte texel, in full lanes.  The result
 // is the same descriptor, bit for bit: every tier only ever answers when the exact arithmetic is certain to agree.
 #define DSC_QUEUE_TAB 768
 #ifdef MAD_PROBE_STAMPS      // diagnostic build: s_memtime at the phases of every row's workgroup (tools/probe_describe.py)
 __device__ long long dsc_stamps[16384 * 8];
+__device__ int dsc_open[16384];      // the row's open samples (s_nq) beside its stamps
 #define DSC_STAMP(k) do { __builtin_amdgcn_sched_barrier(0); if (threadIdx.x == 0 && blockIdx.x < 16384) dsc_stamps[blockIdx.x * 8 + (k)] = __builtin_amdgcn_s_memtime(); __builtin_amdgcn_sched_barrier(0); } while (0)
+#define DSC_NOTE_OPEN(n) do { if (threadIdx.x == 0 && blockIdx.x < 16384) dsc_open[blockIdx.x] = (n); } while (0)
 extern "C" int mad_debug_dsc_stamps(long long *out, int n) {
     return hipMemcpyFromSymbol(out, HIP_SYMBOL(dsc_stamps), (size_t)n * 8) == hipSuccess ? 0 : -1;
 }
+extern "C" int mad_debug_dsc_open(int *out, int n) {
+    return hipMemcpyFromSymbol(out, HIP_SYMBOL(dsc_open), (size_t)n * 4) == hipSuccess ? 0 : -1;
+}
 #else
 #define DSC_STAMP(k) do { } while (0)
+#define DSC_NOTE_OPEN(n) do { } while (0)
 #endif
 #ifndef DSC_OCC_TAB
-#define DSC_OCC_TAB 4     // ... of the TAB form (5: 96 registers, 32 of them spilled, 88 -> 102 us per launch)
+// ... of the TAB form: six, which is what it runs at (80 registers).  The budget was 4 while the allocator happened to stop at 80 of
+// its own accord; with Z a constant it stopped at 81 -- five workgroups per CU -- and under this budget it takes 77, without scratch
+// and without an instruction more.  (Round 3, before the texels shrank: 5 = 96 registers, 32 of them spilled, 88 -> 102 us per launch.)
+#define DSC_OCC_TAB 6
 #endif
 // threads of a row's workgroup: one per (j, k) lattice column -- 256 up to S = 16, whole waves over S * S beyond (448 at S = 20, 576 at 24)
 #define DSC_NT(S) ((S) <= 16 ? DSC_THREADS : ((S) * (S) + MAD_WAVE - 1) / MAD_WAVE * MAD_WAVE)
@@ -975,7 +985,7 @@ __global__ __launch_bounds__(DSC_NT(S), TAB ? DSC_OCC_TAB : DSC_OCC) void k_desc
     }
     if (A.dsc8) {      // zero rows up to the next multiple of 128: the GEMM reads whole tiles
         const int64_t n_pad = (n_rows + 127) / 128 * 128;
-        const int Dp = NSUB * A.eq->Z;
+        const int Dp = NSUB * (TAB ? 16 : A.eq->Z);
         for (int64_t r = n_rows + bid; r < n_pad; r += gdim) {
             for (int i = tid; i < Dp / 4; i += NT) ((int32_t *)(A.dsc8 + r * Dp))[i] = WIDE ? MAD_WIDE_ZERO4 : 0;
             if (tid == 0) A.norm[r] = 0.0;
@@ -988,7 +998,9 @@ __global__ __launch_bounds__(DSC_NT(S), TAB ? DSC_OCC_TAB : DSC_OCC) void k_desc
     if (TAB) { stage_lds(&tab, &A.eq->tab, sizeof(EqspTabLds)); stage_lds(&fast_s, &A.eq->image, sizeof(fast_s)); }
     else eqsp_fast_stage(A.eq, (EqspFastLds *)&fast_s);
     const FieldDev F0 = A.f[0], F1 = A.f[1];
-    const int Z = A.eq->Z;
+    // TAB: the table form is launched for the 16-zone table only (mad_describe_device_many), so Z is a constant there: the (j, k) part
+    // of a tally's address is formed once per thread, the i part is an immediate offset of the ds_add, and the loops over D are fixed
+    const int Z = TAB ? 16 : A.eq->Z;
     const int D = NSUB * Z;            // S = 2 r samples per axis (16), NSUB sub-regions of Z zones each
     for (int i = tid; i < D; i += NT) hist[i] = 0;
     // What a row starts from -- its index, its anchor's coordinates and octave, inv(Rfinal) -- is one 128-byte record (DscRowRec,
@@ -1071,6 +1083,7 @@ __global__ __launch_bounds__(DSC_NT(S), TAB ? DSC_OCC_TAB : DSC_OCC) void k_desc
     constexpr int NP = S > 16 ? (S % DSC_CHUNK == 0 ? S / DSC_CHUNK : 2) : ((S % (DSC_CHUNK * DSC_PASSES) == 0) ? DSC_PASSES : 1);
     constexpr int PS = S / NP;
     static_assert(S % NP == 0 && PS <= 32, "a pass's samples are one bit each of `unsure` / `undecided`");
+#define UBIT(i) (TAB ? PS - 1 - (i) : (i))      // sample i's bit of `unsure`
     bool oob = false;
     if (active) {
         // float32 guess of the offset from the anchor voxel, |error| < 1e-5 voxel: the nearest voxel is known unless the
@@ -1081,12 +1094,16 @@ __global__ __launch_bounds__(DSC_NT(S), TAB ? DSC_OCC_TAB : DSC_OCC) void k_desc
         const float m1 = lbf + lsf * (float)j, m2 = lbf + lsf * (float)k;      // exact
         const float b0 = fmaf(m1, h1, m2 * h2), b1 = fmaf(m1, h4, m2 * h5), b2 = fmaf(m1, h7, m2 * h8);
         const int sub_jk = sub_of_jk<S, NSUB>(j, k);      // Descriptor.py:44-93
+        const int sjk16 = sub_jk * 16;      // TAB: this column's part of a tally's address, formed once
 #pragma unroll
         for (int pass = 0; pass < NP; pass++) {
             float4 t[TAB ? 1 : PS];
             unsigned q4[TAB ? PS : 1], qi[TAB ? PS : 1];      // TAB: the 4-byte texels and where they came from
             unsigned unsure = 0;      // bit i: the float32 guess of sample i of this pass is too close to a tie to be trusted
+            // (TAB: bit PS - 1 - i, see UBIT.  Interior rows shift the bits in: `unsure = 2 unsure + (tie <= 2e-4)` is one compare into
+            // the carry and one add-with-carry, where compare, select and or took three instructions per sample)
             auto guess = [&](auto border) {
+                constexpr bool CARRY = TAB && !decltype(border)::value;
                 const float fc0 = (float)ic0, fc1 = (float)ic1, fc2 = (float)ic2;
                 const float lim0 = (float)(F.nx - 1) - 1e-3f, lim1 = (float)(F.ny - 1) - 1e-3f, lim2 = (float)(F.nz - 1) - 1e-3f;
 #pragma unroll
@@ -1095,7 +1112,9 @@ __global__ __launch_bounds__(DSC_NT(S), TAB ? DSC_OCC_TAB : DSC_OCC) void k_desc
                     const float a0 = fmaf(m0, h0, b0), a1 = fmaf(m0, h3, b1), a2 = fmaf(m0, h6, b2);
                     // nearest voxel = floor(a + 0.5) unless the fraction is within 2e-4 of the tie (then the float64 expression decides)
                     const float fr0 = __builtin_amdgcn_fractf(a0), fr1 = __builtin_amdgcn_fractf(a1), fr2 = __builtin_amdgcn_fractf(a2);
-                    bool safe = fminf(fminf(fabsf(fr0 - 0.5f), fabsf(fr1 - 0.5f)), fabsf(fr2 - 0.5f)) > 2e-4f;      // (three subtractions, one v_min3 with |.| modifiers, one compare)
+                    const float tie = fminf(fminf(fabsf(fr0 - 0.5f), fabsf(fr1 - 0.5f)), fabsf(fr2 - 0.5f));      // (three subtractions, one v_min3 with |.| modifiers)
+                    bool safe = tie > 2e-4f;      // (one compare)
+                    if (CARRY) asm("v_cmp_nlt_f32 vcc, %1, %2\n\tv_addc_co_u32 %0, vcc, %0, %0, vcc" : "+v"(unsure) : "s"(2e-4f), "v"(tie) : "vcc");
                     int n0 = ic0 + cvt_round(a0), n1 = ic1 + cvt_round(a1), n2 = ic2 + cvt_round(a2);
                     if (decltype(border)::value) {
                         const float q0 = a0 + fc0, q1 = a1 + fc1, q2 = a2 + fc2;
@@ -1105,7 +1124,7 @@ __global__ __launch_bounds__(DSC_NT(S), TAB ? DSC_OCC_TAB : DSC_OCC) void k_desc
                     const unsigned at = mad_u24(mad_u24((unsigned)n0, (unsigned)F.ny, (unsigned)n1), (unsigned)F.nz, (unsigned)n2);      // nx ny < 2^24 (checked at allocation)
                     if (TAB) { qi[i] = at; q4[i] = DSC_TEX4(at); }
                     else t[i] = F.tex[at];
-                    unsure |= safe ? 0u : (1u << i);
+                    if (!CARRY) unsure |= safe ? 0u : (1u << UBIT(i));
                 }
             };
             if (interior) guess(std::false_type()); else guess(std::true_type());
@@ -1113,7 +1132,7 @@ __global__ __launch_bounds__(DSC_NT(S), TAB ? DSC_OCC_TAB : DSC_OCC) void k_desc
             if (unsure) {      // rare: the reference's float64 expression for those samples, and their texels again
 #pragma unroll
                 for (int i = 0; i < PS; i++)
-                    if (unsure & (1u << i)) {
+                    if (unsure & (1u << UBIT(i))) {
                         const unsigned at = exact_index(pass * PS + i, &oob);
                         if (TAB) { qi[i] = at; q4[i] = DSC_TEX4(at); }
                         else t[i] = F.tex[at];
@@ -1170,13 +1189,15 @@ __global__ __launch_bounds__(DSC_NT(S), TAB ? DSC_OCC_TAB : DSC_OCC) void k_desc
 #pragma unroll
                 for (int u = 0; u < DSC_CHUNK; u++) {
                     if (i0 + u >= PS) continue;
-                    if (zone[u] >= 0) atomicAdd(&hist[(sub_jk + sub_of_i<S, NSUB>(pass * PS + i0 + u)) * Z + zone[u]], 1);
+                    if (TAB) {
+                        if (zone[u] >= 0) atomicAdd(&hist[sjk16 + sub_of_i<S, NSUB>(pass * PS + i0 + u) * 16 + zone[u]], 1);
+                    } else if (zone[u] >= 0) atomicAdd(&hist[(sub_jk + sub_of_i<S, NSUB>(pass * PS + i0 + u)) * Z + zone[u]], 1);
                     undecided |= zone[u] == -1 ? (1u << (i0 + u)) : 0u;
                 }
             }
             DSC_STAMP(3);
             if (TAB) {
-                // The table leaves 3-6 % of the samples open: ~200 per row.  ONE queue reservation per wave (a scan of the lanes' counts;
+                // The table leaves 2 % of the samples open: 82-87 per row on C3 (164 before the guard became the bound).  ONE queue reservation per wave (a scan of the lanes' counts;
                 // every thread of an S = 16 row is active) -- a returning LDS atomic per sample on one address serialises the CU.
                 const int cnt = __popc(undecided);
                 const int inc = wave_incl_scan_i32(cnt);      // (DPP: a shuffle is an LDS instruction and waits behind the histogram's atomics)
@@ -1206,6 +1227,7 @@ __global__ __launch_bounds__(DSC_NT(S), TAB ? DSC_OCC_TAB : DSC_OCC) void k_desc
     if (oob) s_oob = 1;
     __syncthreads();
     DSC_STAMP(5);
+    DSC_NOTE_OPEN(s_nq);
     const bool dead = s_oob != 0;      // Descriptor.py:142-149: a sample left the grid -> the whole descriptor is zero
     if (dead) {
         for (int i = tid; i < D; i += NT) A.dsc[row * D + i] = 0;

@@ -1,8 +1,11 @@
 #!/usr/bin/env python3
-"""Host model of the table classifier of the 4-byte texels (mad_common.h: EqspTabLds, eqsp_tab32, mad_tex4_encode; tables as
-mad_set_eqsp builds them): random unit directions, quantised to 3 x 10 bits, rotated, classified -- every decided sample must
-carry the zone of the exact float64 classification of the unquantised direction.  Prints the undecided fraction.
-    python tools/check_tab_classifier.py [n_directions]"""
+"""Host model of the table classifier of the 4-byte texels (mad_common.h: EqspTabLds, eqsp_tab32, mad_tex4_encode): unit directions,
+quantised to 3 x 10 bits, rotated, classified -- every decided sample must carry the zone of the exact float64 classification of the
+unquantised direction.  The table is the one the library builds (mad_eqsp_tab_build, host arithmetic: no GPU is needed); `tables`
+below is this file's own construction of the same property, compared entry by entry as a cross-check.  Three sets of directions:
+uniform ones, ones within 5e-3 rad of a zone edge, and worst-case-directed ones -- near an edge, the code off by 0.4995 of a step in
+every component, all eight sign patterns.  Prints the undecided share of each.
+    python tools/check_tab_classifier.py [n_uniform]"""
 import os
 import sys
 
@@ -10,46 +13,52 @@ import numpy as np
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
-from mad_amd import synth      # noqa: E402
+from mad_amd import _lib, synth      # noqa: E402
 from mad_amd.eqsp import EQSP_Sphere      # noqa: E402
 
-NZ, NP, G = 2048, 2048, 4e-3      # MAD_TAB_ZBINS, MAD_TAB_PBINS, MAD_TAB_GUARD
+NZ, NP = 2048, 2048                  # MAD_TAB_ZBINS, MAD_TAB_PBINS
+G, SLOP = 1.746e-3, 0.01             # MAD_TAB_GUARD (a vector length on the unit scale), MAD_TAB_SLOP (bins)
+
+
+def belts_of(B):
+    belts, prev = [], None
+    for a in range(len(B)):
+        if prev is None or B[a, 1] != prev:
+            belts.append(dict(first=a, count=0, ph_lo=B[a, 1], ph_hi=B[a, 3]))
+            prev = B[a, 1]
+        belts[-1]["count"] += 1
+    return belts
+
+
+def theta_of(p):      # inverse of eqsp_tab32's pseudo-angle
+    if p <= 2:
+        xr = 1 - p
+        return np.arctan2(1 - abs(xr), xr)
+    xr = p - 3
+    return np.arctan2(-(1 - abs(xr)), xr) + 2 * np.pi
 
 
 def tables(B):
-    Z = len(B)
-    th_lo, ph_lo_z, th_hi, ph_hi_z = B[:, 0], B[:, 1], B[:, 2], B[:, 3]
-    belts, prev = [], None
-    for a in range(Z):
-        if prev is None or ph_lo_z[a] != prev:
-            belts.append(dict(first=a, count=0, ph_lo=ph_lo_z[a], ph_hi=ph_hi_z[a]))
-            prev = ph_lo_z[a]
-        belts[-1]["count"] += 1
+    """This file's own construction (the derivation is at EqspTabLds in mad_common.h)."""
+    th_lo, th_hi = B[:, 0], B[:, 2]
+    belts = belts_of(B)
     zbelt = np.full(NZ, 255, np.uint8)
     for k in range(NZ):
-        zlo, zhi = -1 + (k - 1) * (2 / NZ), -1 + (k + 2) * (2 / NZ)
-        if zlo <= -1 or zhi >= 1:
-            continue
-        pmin, pmax = np.arccos(zhi) - G, np.arccos(zlo) + G
+        zlo, zhi = -1 + (k - SLOP) * (2 / NZ) - G, -1 + (k + 1 + SLOP) * (2 / NZ) + G
         for bi, b in enumerate(belts):
-            if pmin > b["ph_lo"] and pmax < b["ph_hi"]:
+            if zlo > np.cos(np.clip(b["ph_hi"], 0, np.pi)) and zhi < np.cos(np.clip(b["ph_lo"], 0, np.pi)):
                 zbelt[k] = bi
-
-    def theta_of(p):
-        if p <= 2:
-            xr = 1 - p
-            return np.arctan2(1 - abs(xr), xr)
-        xr = p - 3
-        return np.arctan2(-(1 - abs(xr)), xr) + 2 * np.pi
-
     ptab = np.full((4, NP), 255, np.uint8)
     for bi, b in enumerate(belts):
         if b["count"] == 1:
             ptab[bi, :] = b["first"]
             continue
-        gt = G / min(np.sin(b["ph_lo"]), np.sin(b["ph_hi"]))
+        s_min = min(np.sin(b["ph_lo"]), np.sin(b["ph_hi"]))
+        if not s_min > 0.05:
+            continue
+        gt = np.arcsin(G / (s_min - G))
         for k in range(2, NP - 2):
-            t0, t1 = theta_of((k - 1) * 4 / NP) - gt, theta_of((k + 2) * 4 / NP) + gt
+            t0, t1 = theta_of((k - SLOP) * 4 / NP) - gt, theta_of((k + 1 + SLOP) * 4 / NP) + gt
             for a in range(b["first"], b["first"] + b["count"]):
                 if (t0 > th_lo[a] and t1 < th_hi[a]) or (t0 + 2 * np.pi > th_lo[a] and t1 + 2 * np.pi < th_hi[a]):
                     ptab[bi, k] = a
@@ -68,37 +77,90 @@ def exact(d, B):      # Descriptor.py:158-187: default zone 0, the last matching
     return zone
 
 
-def classify(q, R, zbelt, ptab):
+def classify(q, R, zbelt, ptab):      # eqsp_tab32 on the decoded components q (on the 511 scale), float32 throughout
     f = R.astype(np.float32).copy()
     f[2] *= np.float32(1 / 511)
-    r = q @ f.T
+    r = q.astype(np.float32) @ f.T
     x, y, z = r[:, 0], r[:, 1], r[:, 2]
-    b = zbelt[np.clip(np.floor((z + 1) * (NZ / 2)).astype(int), 0, NZ - 1)]
-    xr = x / np.maximum(np.abs(x) + np.abs(y), 1e-30)
-    p = np.where(y >= 0, 1 - xr, 3 + xr)
-    zn = ptab[b & 3, np.clip(np.floor(p * (NP / 4)).astype(int), 0, NP - 1)].astype(int)
+    h = np.float32(NZ / 2)
+    b = zbelt[np.clip(np.floor(z * h + h).astype(int), 0, NZ - 1)]
+    xr = x / np.maximum(np.abs(x) + np.abs(y), np.float32(1e-30))
+    c = np.float32(NP / 4)
+    u = np.copysign(xr * c + c, y)
+    zn = ptab[b & 3, np.clip(np.floor(np.float32(NP / 2) - u).astype(int), 0, NP - 1)].astype(int)
     return np.where((b == 255) | (zn == 255), -1, zn)
+
+
+def encode(v):      # mad_tex4_encode's components
+    return np.clip(np.rint(v.astype(np.float32) * np.float32(511)), -511, 511).astype(np.float32)
+
+
+def near_edges(B, n, width, rng):
+    """n unit directions (float64) within `width` rad -- of theta or of phi -- of an edge of a zone, the edge going round-robin over
+    the zones' four edges, the other angle uniform over the zone."""
+    a = np.arange(n) % len(B)
+    e = (np.arange(n) // len(B)) % 4
+    off = rng.uniform(-width, width, n)
+    th = rng.uniform(B[a, 0], B[a, 2])
+    ph = rng.uniform(B[a, 1], B[a, 3])
+    th = np.where(e == 0, B[a, 0] + off, np.where(e == 1, B[a, 2] + off, th))
+    ph = np.where(e == 2, B[a, 1] + off, np.where(e == 3, B[a, 3] + off, ph))
+    ph = np.clip(ph, 1e-6, np.pi - 1e-6)
+    return np.stack([np.sin(ph) * np.cos(th), np.sin(ph) * np.sin(th), np.cos(ph)], 1)
+
+
+def rotations(rng, k):
+    return [np.array([[0.5, -0.8660254037844386, 0], [0.8660254037844386, 0.5, 0], [0, 0, 1.0]])] + [synth.random_rotation(rng) for _ in range(k - 1)]
+
+
+def diag_to_z():
+    """A rotation that brings (1, 1, 1) / sqrt(3) onto +z: the worst-case code error of one sign pattern is then all in z."""
+    z = np.ones(3) / np.sqrt(3)
+    x = np.array([1.0, -1.0, 0.0]) / np.sqrt(2)
+    return np.stack([x, np.cross(z, x), z])
+
+
+def run(B, zbelt, ptab, u, Rs, signs=None):
+    """u: directions AFTER the rotation, dealt over the rotations Rs.  Returns (undecided, decided wrongly).  signs: the code is
+    not the rounded direction but the direction moved by 0.4995 of a step in every component, with these signs (worst case)."""
+    und = bad = 0
+    for s, R in zip(np.array_split(np.arange(len(u)), len(Rs)), Rs):
+        v = u[s] @ R      # the texel's direction: R v = u
+        ex = exact(v @ R.T, B)
+        q = encode(v) if signs is None else (v * 511 + 0.4995 * signs[s]).astype(np.float32)
+        zn = classify(q, R, zbelt, ptab)
+        und += int(np.sum(zn < 0))
+        bad += int(np.sum((zn >= 0) & (zn != ex)))
+    return und, bad
 
 
 def main():
     n = int(sys.argv[1]) if len(sys.argv) > 1 else 2000000
     B = EQSP_Sphere(16).sphere_eqsp
-    zbelt, ptab = tables(B)
+    ok, zbelt, ptab = _lib.eqsp_tab_build(B)
+    assert ok
+    zb2, pt2 = tables(B)
+    same = np.array_equal(zbelt, zb2) and np.array_equal(ptab, pt2)
+    print("library table == this file's construction: %s  (decided: %d of %d z bins, %d of %d p bins)"
+          % (same, int(np.sum(zbelt != 255)), NZ, int(np.sum(ptab != 255)), 4 * NP))
     rng = np.random.default_rng(0)
-    v = rng.normal(size=(n, 3)).astype(np.float32)
+    v = rng.normal(size=(n, 3))
     v /= np.linalg.norm(v, axis=1, keepdims=True)
-    q = np.clip(np.rint(v * 511), -511, 511).astype(np.float32)
-    bad = und = 0
-    blk = 100000
-    for s0 in range(0, n, blk):
-        R = synth.random_rotation(rng) if s0 else np.array([[0.5, -0.8660254, 0], [0.8660254, 0.5, 0], [0, 0, 1.0]])
-        sl = slice(s0, s0 + blk)
-        ex = exact(v[sl].astype(np.float64) @ R.T, B)
-        zn = classify(q[sl], R, zbelt, ptab)
-        und += int(np.sum(zn < 0))
-        bad += int(np.sum((zn >= 0) & (zn != ex)))
-    print("directions %d  undecided %.4f  decided wrongly %d" % (n, und / n, bad))
-    return bad
+    Rs = rotations(rng, 20)
+    total_bad = 0 if same else 1
+    und, bad = run(B, zbelt, ptab, v, Rs)
+    print("uniform: directions %d  undecided %.4f  decided wrongly %d" % (n, und / n, bad))
+    total_bad += bad
+    e = near_edges(B, n // 2, 5e-3, rng)
+    und, bad = run(B, zbelt, ptab, e, Rs)
+    print("within 5e-3 rad of an edge: directions %d  undecided %.4f  decided wrongly %d" % (len(e), und / len(e), bad))
+    total_bad += bad
+    w = np.repeat(near_edges(B, 150000, 2.5e-3, rng), 8, axis=0)
+    sg = np.tile(np.array([[sx, sy, sz] for sx in (-1, 1) for sy in (-1, 1) for sz in (-1, 1)], float), (150000, 1))
+    und, bad = run(B, zbelt, ptab, w, Rs[:3] + [diag_to_z()], sg)
+    print("worst-case-directed: samples %d  undecided %.4f  decided wrongly %d" % (len(w), und / len(w), bad))
+    total_bad += bad
+    return total_bad
 
 
 if __name__ == "__main__":

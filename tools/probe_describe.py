@@ -25,7 +25,7 @@ def main():
     lib.set_eqsp(1, e16.sphere_eqsp)
     the_map, subs, _ = bench.build_inputs(lib, bench.WORKLOADS["c3"])
     lib.set_overlap(False)
-    for what, src in (("map", the_map), ("subunit 0", subs[0])):
+    for what, src in [("map", the_map)] + [("subunit %d" % i, sub) for i, sub in enumerate(subs)]:
         s = _lib.DeviceSet(lib)
         for _ in range(3):
             lib.set_build(src.slots, src.coords, src.octave, src.subv, src.index, into=s)
@@ -34,12 +34,18 @@ def main():
         out = np.zeros(n * 8, np.int64)
         assert lib.dll.mad_debug_dsc_stamps(out.ctypes.data_as(C.c_void_p), C.c_int(n * 8)) == 0
         st = out.reshape(n, 8).astype(np.float64)
+        nq = np.zeros(n, np.int32)      # the row's open samples (what the table left to the exact tiers)
+        if hasattr(lib.dll, "mad_debug_dsc_open"):
+            assert lib.dll.mad_debug_dsc_open(nq.ctypes.data_as(C.c_void_p), C.c_int(n)) == 0
         ok = (st[:, 7] > 0) & (st[:, 0] > 0)
-        st = st[ok]
-        st = st[np.argsort(st[:, 7])]      # the slots keep the stamps of earlier launches: take the last launch (no 40 us gap between its workgroups' ends)
+        st, nq = st[ok], nq[ok]
+        order = np.argsort(st[:, 7])      # the slots keep the stamps of earlier launches: take the last launch (no 40 us gap between its workgroups' ends)
+        st, nq = st[order], nq[order]
         gaps = np.nonzero(np.diff(st[:, 7]) > 100000)[0]
         if len(gaps):
-            st = st[gaps[-1] + 1:]
+            st, nq = st[gaps[-1] + 1:], nq[gaps[-1] + 1:]
+        print("%s: open samples per row: mean %.1f  median %.0f  p90 %.0f  max %d; rows above 256: %.1f %%; queue phase %.0f ticks (mean)"
+              % (what, nq.mean(), np.median(nq), np.percentile(nq, 90), nq.max(), 100.0 * np.mean(nq > 256), np.mean(st[:, 6] - st[:, 5])))
         d = np.diff(st, axis=1)
         print("%s: %d row workgroups; shader-clock ticks, median / p10 / p90" % (what, len(st)))
         for k, name in enumerate(NAMES):
