@@ -189,7 +189,12 @@ int mad_correlate(mad_ctx *ctx, const int16_t *hi, int64_t n_hi, const int16_t *
  * coordinates of rows present in at least one pair (MaD.py:427-428).
  * results (nullable): n_pairs x 23 as MaD.py:451.  counts (nullable): number of
  * hi cloud points brought within `dist` of a lo cloud point (repeatability =
- * 100 * count / l_hi).
+ * 100 * count / l_hi).  dist > 0, any size: a dist too small for the float32 tier's band only makes that tier test
+ * every candidate in float64.
+ * Coordinates (p of both sides, both clouds) must lie within +-10 000 A (the range of the PDB format and a little more):
+ * the search maps absolute coordinates to the voxels of its occupancy bitmaps in float32, with an error below
+ * 1.87e-6 A + 1.2e-4 Angstrom for coordinates up to A, and the bitmaps allow for 0.02 ("The float32 voxel map").
+ * Beyond: MAD_EDOM (also for a NaN).
  */
 int mad_pose_score(mad_ctx *ctx, const int32_t *pair_hi, const int32_t *pair_lo, const double *pair_score,
                    int64_t n_pairs,
@@ -255,6 +260,9 @@ int mad_set_download(mad_ctx *ctx, const mad_set *set, int32_t *row_anchor, int3
  * device.  results: k x 23 rows of MaD.py:451 in the order of MaD.py:480 (fewer if
  * n_pairs < k: *n_out).  pair_index (nullable): k row-major pair ranks.
  * stats (nullable) int64[4] = {n_pairs, l_hi, l_lo, n_correlations}.
+ * dist > 0.  The anchors' sub-voxel coordinates lie within +-10 000 A: mad_set_build*, mad_set_load and mad_set_import refuse
+ * others with MAD_EDOM, because the pose search maps absolute coordinates to bitmap voxels in float32 (error below
+ * 1.87e-6 A + 1.2e-4 Angstrom for coordinates up to A, against the 0.02 the bitmaps allow for; see mad_pose_score).
  */
 int mad_match_topk(mad_ctx *ctx, const mad_set *hi, const mad_set *lo, double cc, double dist,
                    int64_t k, double *results, int64_t *pair_index, int64_t *n_out, int64_t *stats);
@@ -314,6 +322,34 @@ int mad_set_option(mad_ctx *ctx, const char *name, double value);
  * diagnostics: the three give identical counts, so only this tells when a sizing change has demoted a workload.
  */
 int mad_last_pose_kernel(mad_ctx *ctx);
+/*
+ * Everything the host chose for the most recently ENQUEUED pose stage of the context (mad_pose_score, a match of
+ * mad_match_topk*, mad_match_shard_topk / _score, or the completion of a pruned match by mad_match_fetch / mad_match_results):
+ * the plan follows from the cloud sizes, the lo cloud's bounding box and dist alone, the last three flags also from what the
+ * previous match of the lane selected.  Host-only: it launches nothing and changes no decision.  Every field is -1 before the first
+ * pose stage.  For tests and diagnostics: all plans give identical counts, so only this tells which one a workload reached.
+ */
+typedef struct mad_pose_plan_info {
+    int32_t kernel;          /* as mad_last_pose_kernel: 0 k_pose_lds, 1 k_pose_lds32, 2 k_pose (global cell list) */
+    int32_t hi_in_lds;       /* the hi cloud sits in LDS: 1 for kernel 0 and k_pose_lds32<true>, 0 for k_pose_lds32<false> and kernel 2 */
+    int32_t pruned;          /* the bounds pass (k_pose_bounds) ran and the exact search saw the selected pairs only */
+    int32_t split;           /* the bounds pass ran as two launches; 0 when not pruned */
+    int32_t nbv;             /* width of k_pose_bounds<NB, .> in sets of 64 hi points: 2, 4, 6, 8, 10, 12 or 16; 0 when not pruned */
+    int32_t inner_plane;     /* the fine bitmap has its inner plane (bits_rad_in > 0.5); 0 for kernel 2 */
+    int32_t grid_dim[3];     /* cells of the search grid per axis (kernel 2: of the global cell list) */
+    int32_t own_selection;   /* k_pose_lds selected its own pairs (no k_prune_select launch) */
+    int32_t topk_one_wg;     /* the k rows came from k_topk_selected (one workgroup); 0: the general top-k, or no top-k in this stage */
+    int32_t sel_repeat;      /* this enqueue repeats the match because the selection outgrew the own / one-workgroup forms */
+    int32_t fine_grown;      /* the fine voxel was enlarged to keep the bitmap within 16 MB */
+    int32_t search_wgs;      /* workgroups of the exact search */
+    int32_t fine_dim[3];     /* voxels of the fine bitmap per axis; 0 for kernel 2 */
+    int32_t reserved;
+    double fine_h, coarse_h; /* voxel edges of the fine bitmap and of the coarse one of the bounds pass (A); 0 for kernel 2 */
+    double fine_mn[3];       /* origin of the fine bitmap (A) */
+    double bits_rad, bits_rad_in;      /* radii of the outer and inner plane around a lo point (A) */
+    int64_t lds64, lds32, lds32_hi;    /* LDS bytes the plan computed for k_pose_lds, k_pose_lds32<false>, k_pose_lds32<true> */
+} mad_pose_plan_info;
+int mad_last_pose_plan(mad_ctx *ctx, mad_pose_plan_info *out);
 /*
  * How many pairs of the most recently COMPLETED match went through the exact search.  mad_match_topk* only report the k best
  * pairs (MaD.py:480,502), so the pose search first brackets every pair's count with the occupancy bitmaps alone (lower bound =

@@ -34,7 +34,7 @@ SYMBOLS = [
     "mad_set_eqsp", "mad_eqsp_tab_build", "mad_upload_field", "mad_upload_field_device", "mad_free_field", "mad_field_download",
     "mad_set_orient_window", "mad_orient", "mad_describe", "mad_describe_sized", "mad_correlate", "mad_pose_score", "mad_topk",
     "mad_set_create", "mad_set_destroy", "mad_set_build", "mad_set_build_many", "mad_set_load", "mad_set_mark_wide", "mad_set_is_wide", "mad_set_size", "mad_set_download",
-    "mad_match_topk", "mad_match_topk_many", "mad_match_topk_many_begin", "mad_match_topk_many_finish", "mad_match_topk_many_begin2", "mad_match_topk_many2", "mad_set_batching", "mad_set_option", "mad_last_pose_kernel", "mad_last_pose_selected", "mad_device_allocations", "mad_match_fetch", "mad_match_results", "mad_match_used",
+    "mad_match_topk", "mad_match_topk_many", "mad_match_topk_many_begin", "mad_match_topk_many_finish", "mad_match_topk_many_begin2", "mad_match_topk_many2", "mad_set_batching", "mad_set_option", "mad_last_pose_kernel", "mad_last_pose_selected", "mad_last_pose_plan", "mad_device_allocations", "mad_match_fetch", "mad_match_results", "mad_match_used",
     "mad_match_shard_pairs", "mad_match_shard_topk", "mad_match_shard_begin", "mad_match_shard_score", "mad_match_shard_record_doubles", "mad_match_shard_collect", "mad_match_shard_wait", "mad_match_shard_merge",
     "mad_dist_unique_id", "mad_dist_init", "mad_dist_destroy", "mad_dist_info", "mad_dist_rehearse_flags", "mad_dist_or_allreduce", "mad_dist_allgather",
     "mad_dist_allgather_topk", "mad_dist_scratch", "mad_dist_copy",
@@ -111,6 +111,14 @@ def load_library():
         _dll.mad_set_destroy.restype = None
         _dll.mad_space_destroy.restype = None
     return _dll
+
+
+class _PosePlanInfo(C.Structure):      # mad_pose_plan_info of include/mad_amd.h
+    _fields_ = [("kernel", C.c_int32), ("hi_in_lds", C.c_int32), ("pruned", C.c_int32), ("split", C.c_int32), ("nbv", C.c_int32),
+                ("inner_plane", C.c_int32), ("grid_dim", C.c_int32 * 3), ("own_selection", C.c_int32), ("topk_one_wg", C.c_int32),
+                ("sel_repeat", C.c_int32), ("fine_grown", C.c_int32), ("search_wgs", C.c_int32), ("fine_dim", C.c_int32 * 3),
+                ("reserved", C.c_int32), ("fine_h", C.c_double), ("coarse_h", C.c_double), ("fine_mn", C.c_double * 3),
+                ("bits_rad", C.c_double), ("bits_rad_in", C.c_double), ("lds64", C.c_int64), ("lds32", C.c_int64), ("lds32_hi", C.c_int64)]
 
 
 TAB_ZBINS, TAB_PBINS, TAB_BELTS = 2048, 2048, 4      # MAD_TAB_* of csrc/mad_common.h
@@ -673,6 +681,19 @@ class Lib(object):
     def last_pose_kernel(self):
         """0 k_pose_lds, 1 k_pose_lds32, 2 k_pose (global cell list): the kernel of the most recently enqueued match."""
         return int(self.dll.mad_last_pose_kernel(self.ctx))
+
+    def last_pose_plan(self):
+        """What the host chose for the most recently enqueued pose stage (mad_last_pose_plan), as a dict; every value is -1 before
+        the first one.  Read it before match_fetch / match_results: completing a pruned match enqueues a pose stage of its own."""
+        info = _PosePlanInfo()
+        self._chk(self.dll.mad_last_pose_plan(self.ctx, C.byref(info)))
+        out = {}
+        for name, _ in _PosePlanInfo._fields_:
+            if name == "reserved":
+                continue
+            v = getattr(info, name)
+            out[name] = tuple(v) if hasattr(v, "__len__") else v
+        return out
 
     def last_pose_selected(self):
         """Pairs of the last completed match that went through the exact pose search (the rest were excluded by their bounds)."""

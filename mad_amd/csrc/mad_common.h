@@ -217,6 +217,16 @@ struct ShardAsync {            // a mad_match_shard_begin waiting for its mad_ma
     int64_t begin = 0, nb = 0, n_lo = 0, cap_pairs = 0;
 };
 
+// the record of mad_last_pose_plan before the first pose stage: every value -1
+static inline mad_pose_plan_info mad_pose_plan_none() {
+    mad_pose_plan_info r;
+    r.kernel = r.hi_in_lds = r.pruned = r.split = r.nbv = r.inner_plane = r.own_selection = r.topk_one_wg = r.sel_repeat = r.fine_grown = r.search_wgs = r.reserved = -1;
+    for (int d = 0; d < 3; d++) { r.grid_dim[d] = -1; r.fine_dim[d] = -1; r.fine_mn[d] = -1.0; }
+    r.fine_h = r.coarse_h = r.bits_rad = r.bits_rad_in = -1.0;
+    r.lds64 = r.lds32 = r.lds32_hi = -1;
+    return r;
+}
+
 struct mad_ctx {
     int device = -1;
     hipStream_t stream = nullptr;            // the stream of the current lane (lane_stream[lane])
@@ -268,6 +278,7 @@ struct mad_ctx {
     bool shard_busy[MAD_LANES][MAD_SHARD_RING] = {};
     int shard_next[MAD_LANES] = {};
     int last_pose_kernel = -1;               // 0 k_pose_lds, 1 k_pose_lds32, 2 k_pose (mad_last_pose_kernel)
+    mad_pose_plan_info last_pose_plan = mad_pose_plan_none();      // what pose_device / match_enqueue_tail chose last (mad_last_pose_plan)
     int last_refine_G = -1, last_refine_reg = -1;      // workgroups per candidate and kernel form (1 k_refine<8>, 0 k_refine<0>) of the last refine_device (mad_last_refine_plan)
     int64_t last_rank_launches = 0, last_rank_evaluated = 0, last_rank_skipped = 0;      // the last mad_rank_* call (mad_last_rank_plan)
     int last_rank_band_extra = 0;

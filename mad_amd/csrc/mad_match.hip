@@ -756,9 +756,13 @@ __host__ __device__ __forceinline__ size_t pad16(size_t b) { return (b + 15) & ~
 //          falls into a clear voxel -- or outside the bitmap -- has no lo point within dist;
 //   inner: bit set iff some lo point lies within dist - h sqrt(3)/2 - slack of the voxel centre.  A point in such a voxel has
 //          a lo point within dist for certain and is counted without a search.
-// Both hold whatever the float32 rounding of the point's voxel coordinates does (slack = 0.02 A against < 1e-3 A of error),
-// so only the points in the shell between the two (about one in eleven on the 256^3 workload) go through the exact float64
+// Both hold whatever the float32 rounding of the point's voxel coordinates does: slack = MAD_POSE_SLACK = 0.02 A, against an error
+// of pose_vox_fetch below 31.4 * 2^-24 * A + 1.2e-4 A for coordinates of magnitude up to A (DESIGN.md derives it): 1.7e-3 A at the
+// 900 A of a 512^3 map, 0.0187 A at MAD_POSE_COORD_MAX = 10 000 A, beyond which the entry points refuse the coordinates (MAD_EDOM).
+// So only the points in the shell between the two (about one in eleven on the 256^3 workload) go through the exact float64
 // search, and the counts are those of the unfiltered search.  z-rows are padded to whole 32-bit words.
+#define MAD_POSE_SLACK 0.02
+#define MAD_POSE_COORD_MAX 10000.0
 struct PoseBits {
     double mn[3];
     double h;
@@ -2209,6 +2213,12 @@ static int correlate_device(mad_ctx *ctx, const Side &hi, const Side &lo, int D,
     return correlate_pairs(ctx, hi, lo, cc, d_status, cap_pairs, d_used_hi, d_used_lo);
 }
 
+// The voxel edge the fine bitmap starts from (pose_plan enlarges it until the bitmap fits its budget).
+static double pose_fine_h0() {
+    static const double h0 = getenv("MAD_POSE_VOXEL") ? atof(getenv("MAD_POSE_VOXEL")) : 0.8;
+    return (h0 >= 0.25 && h0 <= 8.0) ? h0 : 0.8;
+}
+
 // Workgroups of the persistent pose search per CU.  Two fill a CU completely (16 waves x 64 registers per SIMD, 130 KB of
 // LDS) and run the kernel 4 % faster on its own; one leaves half of the registers and 95 KB of LDS to the kernels of the
 // other lanes (the orient / describe launches of the next batch are latency-bound and fill the issue slots the pose search
@@ -2265,10 +2275,9 @@ static void pose_plan(const mad_ctx *ctx, int l_hi_max, int n_cloud, const doubl
                             stacks + (size_t)POSE_OWN_CAP * 4 + 16;      // the regions of k_pose_lds (the last: its own selection list)
     const bool base64 = lds_base <= 150 * 1024;
     const size_t bits_budget = (size_t)16 << 20;
-    static const double h0 = getenv("MAD_POSE_VOXEL") ? atof(getenv("MAD_POSE_VOXEL")) : 0.8;
     PoseBits &B = P.B;
-    const double slack = 0.02;
-    for (B.h = (h0 >= 0.25 && h0 <= 8.0) ? h0 : 0.8;; B.h *= 1.08) {
+    const double slack = MAD_POSE_SLACK;
+    for (B.h = pose_fine_h0();; B.h *= 1.08) {
         const double guard = dist + B.h * 0.8660254037844387 + slack + B.h;
         for (int d = 0; d < 3; d++) {
             B.mn[d] = bb_min[d] - guard;
@@ -2316,7 +2325,9 @@ static void pose_plan(const mad_ctx *ctx, int l_hi_max, int n_cloud, const doubl
     P.lim_out = nextafterf((float)(dist * dist + band), 1e30f);
     // queue entries are 15 (k_pose_lds) / 16 (k_pose_lds32) bits of hi-cloud index
     P.fits64 = base64 && l_hi_max < 32768;
-    P.fits32 = P.lds32 <= 150 * 1024 && P.lim_in > 0.f && l_hi_max < 65536;
+    // (lim_in <= 0, a dist below the float32 error of the offsets: no candidate is decided "within" in float32, every one inside
+    // lim_out takes the float64 test -- slower, and as exact)
+    P.fits32 = P.lds32 <= 150 * 1024 && l_hi_max < 65536;
     P.lds_path = !have_fallback && (P.fits64 || P.fits32) && n_cloud < 65535 && G.ncell <= 30000;
     static const bool no_prune = getenv("MAD_NO_PRUNE") != nullptr;      // diagnostic switch
     P.prune = P.lds_path && prune_k > 0 && have_hist2 && P.bits_rad_in > 0.5 && P.PC.B.h <= 16.0 && l_hi_max <= PB_MAX_SETS * MAD_WAVE && !no_prune;
@@ -2421,6 +2432,7 @@ static int pose_device(mad_ctx *ctx, const Side &hi, const Side &lo, int32_t *d_
         mad_timer_begin(ctx, MAD_T_POSE);      // the pose stage: bounds + selection (when pruning) + the exact search
         const int32_t *d_sel = nullptr;
         PoseOwnSel own = {nullptr, nullptr, 0, 0, nullptr, 0, nullptr};
+        int rec_split = 0, rec_nbv = 0;      // for mad_last_pose_plan
         if (prune) {
             MAD_TRY(mad_reserve(ctx, mad_sb(ctx, S_TMP_C), (size_t)cap_pairs * 2 + 64));
             MAD_TRY(mad_reserve(ctx, mad_sb(ctx, S_TMP_D), (size_t)cap_pairs * 4 + 64));
@@ -2454,6 +2466,7 @@ static int pose_device(mad_ctx *ctx, const Side &hi, const Side &lo, int32_t *d_
             const int64_t target_a = std::max<int64_t>(ctx->pose_split_min, (int64_t)split_factor * prune_k);
             const int nb = (l_hi_max + MAD_WAVE - 1) / MAD_WAVE;      // point sets of 64 an entire hi cloud needs
             const int nbv = nb <= 2 ? 2 : (nb <= 4 ? 4 : (nb <= 6 ? 6 : (nb <= 8 ? 8 : (nb <= 10 ? 10 : (nb <= 12 ? 12 : 16)))));
+            rec_split = split ? 1 : 0; rec_nbv = nbv;
             const size_t lds_b = pad16((size_t)PC.n_words * 4) + pad16((size_t)(l_hi_max + 4) * 16) + (size_t)(PB_THREADS / MAD_WAVE) * (nbv + 1) * MAD_WAVE * 2 +
                                  pad16((size_t)nbins * 4) + 16;
 #define MAD_PB_LAUNCH(NBV, SPL)                                                                                                              \
@@ -2506,17 +2519,34 @@ static int pose_device(mad_ctx *ctx, const Side &hi, const Side &lo, int32_t *d_
         if ((d_sel || own.upper) && ctx->lane_sel_hint[ctx->lane] > 0)
             wgs_sel = (unsigned)std::min<int64_t>(ctx->n_cu, std::max<int64_t>(16, (ctx->lane_sel_hint[ctx->lane] * (fits64 ? POSE_PARTS : 1) * 5 / 4) / (POSE_LDS_THREADS / MAD_WAVE) + 4));
         const bool listed = d_sel || own.upper;
+        const unsigned wgs64 = listed ? wgs_sel : (unsigned)(ctx->n_cu * (P.lds > 80 * 1024 ? 1 : pose_wgs_per_cu()));
+        const unsigned wgs32 = d_sel ? wgs_sel : (unsigned)ctx->n_cu;
+        {
+            mad_pose_plan_info &r = ctx->last_pose_plan;
+            r.kernel = fits64 ? 0 : 1;
+            r.hi_in_lds = (fits64 || P.hi_in_lds) ? 1 : 0;
+            r.pruned = prune ? 1 : 0; r.split = rec_split; r.nbv = rec_nbv;
+            r.inner_plane = P.bits_rad_in > 0.5 ? 1 : 0;
+            r.own_selection = own.upper ? 1 : 0;
+            r.topk_one_wg = 0; r.sel_repeat = 0;      // (match_enqueue_tail fills these in)
+            r.fine_grown = B.h > pose_fine_h0() ? 1 : 0;
+            r.search_wgs = (int32_t)(fits64 ? wgs64 : wgs32);
+            r.reserved = 0;
+            for (int d = 0; d < 3; d++) { r.grid_dim[d] = G.dim[d]; r.fine_dim[d] = B.dim[d]; r.fine_mn[d] = B.mn[d]; }
+            r.fine_h = B.h; r.coarse_h = PC.B.h; r.bits_rad = P.bits_rad; r.bits_rad_in = P.bits_rad_in;
+            r.lds64 = (int64_t)P.lds; r.lds32 = (int64_t)P.lds32; r.lds32_hi = (int64_t)P.lds32_hi;
+        }
         if (fits64)
-            hipLaunchKernelGGL(k_pose_lds, dim3(listed ? wgs_sel : ctx->n_cu * (P.lds > 80 * 1024 ? 1 : pose_wgs_per_cu())), dim3(POSE_LDS_THREADS), P.lds, ctx->stream, d_status, cap_pairs, d_rec,
+            hipLaunchKernelGGL(k_pose_lds, dim3(wgs64), dim3(POSE_LDS_THREADS), P.lds, ctx->stream, d_status, cap_pairs, d_rec,
                                d_hi_cloud, scratch<double>(ctx, S_PG_PTS), scratch<int32_t>(ctx, S_PG_START), d_start16, G,
                                l_hi_max, n_cloud, (float)reach, dd_lim, B, d_bits, scratch<int32_t>(ctx, S_COUNTS), d_sel, own);
         else if (P.hi_in_lds)
-            hipLaunchKernelGGL(k_pose_lds32<true>, dim3(d_sel ? wgs_sel : ctx->n_cu), dim3(POSE_LDS_THREADS), P.lds32_hi, ctx->stream, d_status, cap_pairs, d_rec,
+            hipLaunchKernelGGL(k_pose_lds32<true>, dim3(wgs32), dim3(POSE_LDS_THREADS), P.lds32_hi, ctx->stream, d_status, cap_pairs, d_rec,
                                d_hi_cloud, scratch<double>(ctx, S_PG_PTS), scratch<float4>(ctx, S_PG_PTSF),
                                scratch<int32_t>(ctx, S_PG_START), d_start16, G, n_cloud, l_hi_max, (float)reach, dd_lim, P.lim_in, P.lim_out, B, d_bits,
                                scratch<int32_t>(ctx, S_COUNTS), d_sel);
         else
-            hipLaunchKernelGGL(k_pose_lds32<false>, dim3(d_sel ? wgs_sel : ctx->n_cu), dim3(POSE_LDS_THREADS), P.lds32, ctx->stream, d_status, cap_pairs, d_rec,
+            hipLaunchKernelGGL(k_pose_lds32<false>, dim3(wgs32), dim3(POSE_LDS_THREADS), P.lds32, ctx->stream, d_status, cap_pairs, d_rec,
                                d_hi_cloud, scratch<double>(ctx, S_PG_PTS), scratch<float4>(ctx, S_PG_PTSF),
                                scratch<int32_t>(ctx, S_PG_START), d_start16, G, n_cloud, l_hi_max, (float)reach, dd_lim, P.lim_in, P.lim_out, B, d_bits,
                                scratch<int32_t>(ctx, S_COUNTS), d_sel);
@@ -2536,6 +2566,16 @@ static int pose_device(mad_ctx *ctx, const Side &hi, const Side &lo, int32_t *d_
     else
         MAD_HIP(hipMemcpyAsync(d_status + ST_LLO, &n_cloud, 4, hipMemcpyHostToDevice, ctx->stream));
     ctx->last_pose_kernel = 2;
+    {
+        mad_pose_plan_info &r = ctx->last_pose_plan;
+        r = mad_pose_plan_none();
+        r.kernel = 2;
+        r.hi_in_lds = r.pruned = r.split = r.nbv = r.inner_plane = r.own_selection = r.topk_one_wg = r.sel_repeat = r.fine_grown = r.reserved = 0;
+        r.search_wgs = ctx->n_cu * 8;
+        for (int d = 0; d < 3; d++) { r.grid_dim[d] = fallback->dim[d]; r.fine_dim[d] = 0; r.fine_mn[d] = 0.0; }
+        r.fine_h = r.coarse_h = r.bits_rad = r.bits_rad_in = 0.0;
+        r.lds64 = (int64_t)P.lds; r.lds32 = (int64_t)P.lds32; r.lds32_hi = (int64_t)P.lds32_hi;
+    }
     mad_timer_begin(ctx, MAD_T_POSE);
     hipLaunchKernelGGL(k_pose, dim3(ctx->n_cu * 8), dim3(POSE_THREADS), lds2, ctx->stream, scratch<int32_t>(ctx, S_PAIR_HI),
                        scratch<int32_t>(ctx, S_PAIR_LO), d_status, cap_pairs, hi.p, hi.R, lo.p, lo.Rinv, hi.row_anchor, lo.row_anchor,
@@ -2545,13 +2585,21 @@ static int pose_device(mad_ctx *ctx, const Side &hi, const Side &lo, int32_t *d_
     return MAD_OK;
 }
 
-static bool clouds_fit_lds(int64_t l_hi, int64_t l_lo) {      // with the largest cell table pose_device makes (25^3 cells)
-    // as pose_device sizes them (+ its 16-byte paddings): the float64 kernel carries a queue and two pair records per wave, the
-    // float32 one a survivor stack
-    const size_t cells = 15632 * 2 + 16 + 64;      // pose_device caps the grid at 25 cells per axis
-    const size_t fixed = cells + (POSE_LDS_THREADS / MAD_WAVE) * POSE_WAVE_LDS + (size_t)POSE_OWN_CAP * 4, fixed32 = cells + (POSE_LDS_THREADS / MAD_WAVE) * POSE_STACK * 2;
-    return ((size_t)(l_hi + l_lo) * 24 + (size_t)l_hi * 16 + fixed <= 150 * 1024 || (size_t)(l_lo + 1) * 16 + fixed32 <= 150 * 1024) && l_lo < 65535 &&
-           l_hi < 65536;      // (the first alternative implies l_hi < 32768)
+// Whether the pose stage of these clouds takes an LDS path: pose_plan's own answer, so that the callers build the global cell list
+// exactly when pose_device is going to ask for it.
+static bool pose_takes_lds(const mad_ctx *ctx, int l_hi_max, int n_cloud, const double bb_min[3], const double bb_max[3], double dist) {
+    PosePlan Q;
+    pose_plan(ctx, l_hi_max, n_cloud, bb_min, bb_max, false, dist, 0, false, &Q);
+    return Q.lds_path;
+}
+
+// The search kernels map absolute coordinates to bitmap voxels in float32; beyond MAD_POSE_COORD_MAX the error of that map can
+// exceed the slack of the bitmaps (PoseBits), and a count could come out wrong.  (Also refuses NaN.)
+static int pose_check_coords(mad_ctx *ctx, const char *who, const char *what, const double *v, int64_t n) {
+    for (int64_t i = 0; i < n; i++)
+        if (!(fabs(v[i]) <= MAD_POSE_COORD_MAX))
+            return mad_fail(ctx, MAD_EDOM, "%s: %s coordinate %g outside +-%g A", who, what, v[i], (double)MAD_POSE_COORD_MAX);
+    return MAD_OK;
 }
 
 static int32_t *status_words(mad_ctx *ctx) {      // inside S_MISC
@@ -2630,6 +2678,10 @@ extern "C" int mad_pose_score(mad_ctx *ctx, const int32_t *pair_hi, const int32_
     if (!pair_hi || !pair_lo || !pair_score || !hi_p || !hi_R || !hi_meta || !lo_p || !lo_R || !lo_meta || !hi_cloud || !lo_cloud)
         return mad_fail(ctx, MAD_EINVAL, "mad_pose_score: NULL argument");
     if (l_hi <= 0 || l_lo <= 0 || !(dist > 0)) return mad_fail(ctx, MAD_EINVAL, "mad_pose_score: empty cloud or dist <= 0");
+    MAD_TRY(pose_check_coords(ctx, "mad_pose_score", "hi anchor", hi_p, 3 * n_hi));
+    MAD_TRY(pose_check_coords(ctx, "mad_pose_score", "lo anchor", lo_p, 3 * n_lo));
+    MAD_TRY(pose_check_coords(ctx, "mad_pose_score", "hi cloud", hi_cloud, 3 * l_hi));
+    MAD_TRY(pose_check_coords(ctx, "mad_pose_score", "lo cloud", lo_cloud, 3 * l_lo));
     struct Up { int slot; const void *src; size_t bytes; };
     const Up ups[] = {
         {S_PAIR_HI, pair_hi, (size_t)n_pairs * 4}, {S_PAIR_LO, pair_lo, (size_t)n_pairs * 4},
@@ -2663,7 +2715,7 @@ extern "C" int mad_pose_score(mad_ctx *ctx, const int32_t *pair_hi, const int32_
     const Side L = {nullptr, nullptr, scratch<double>(ctx, S_TMP_I), scratch<double>(ctx, S_TMP_A), scratch<int32_t>(ctx, S_TMP_J),
                     nullptr, nullptr, scratch<double>(ctx, S_TMP_H), st + ST_NLO, n_lo};
     CellGrid G;
-    const bool fits = clouds_fit_lds(l_hi, l_lo);
+    const bool fits = pose_takes_lds(ctx, (int)l_hi, (int)l_lo, bmn, bmx, dist);
     if (!fits) {      // global cell list (cell = dist) over the lo cloud
         double mn[3];
         int dim[3];
@@ -3045,6 +3097,7 @@ extern "C" int mad_set_build_many(mad_ctx *ctx, int n_sets, mad_set *const *sets
             const int o = anc_octave[i][a];
             if ((o != 0 && o != 1) || !f[o].tex) return mad_fail(ctx, MAD_EINVAL, "mad_set_build: anchor %d has octave %d without a field", a, o);
         }
+        if (n > 0) MAD_TRY(pose_check_coords(ctx, "mad_set_build", "anchor", anc_subv[i], (int64_t)3 * n));
     }
     for (int i = 0; i < n_sets; i++) {
         mad_set *s = sets[i];
@@ -3104,6 +3157,7 @@ extern "C" int mad_set_load(mad_ctx *ctx, mad_set *s, int64_t n_rows, const int3
     if (n_anchors > 0 && (!anc_subv || !anc_index || !anc_octave)) return mad_fail(ctx, MAD_EINVAL, "mad_set_load: NULL anchors");
     for (int64_t i = 0; i < n_rows; i++)
         if (row_anchor[i] < 0 || row_anchor[i] >= n_anchors) return mad_fail(ctx, MAD_EINVAL, "mad_set_load: row %lld -> anchor %d", (long long)i, row_anchor[i]);
+    if (n_anchors > 0) MAD_TRY(pose_check_coords(ctx, "mad_set_load", "anchor", anc_subv, (int64_t)3 * n_anchors));
     MAD_TRY(set_upload_anchors(ctx, s, nullptr, anc_octave, anc_subv, anc_index, n_anchors, (int32_t)n_rows));
     s->D = D;
     s->wide = s->wide_mark;
@@ -3237,6 +3291,7 @@ static int match_enqueue_tail(mad_ctx *ctx, const mad_set *hi, const mad_set *lo
                         lo->n_anchors, used_lo, lo->bb_min, lo->bb_max, P.fits ? nullptr : &G, dist, P.k, zr_hist2(st, hi->n_anchors), &pruned, &job,
                         &P.pose, true));
     P.pruned = pruned;
+    ctx->last_pose_plan.sel_repeat = P.no_small ? 1 : 0;
     // A pruned search has listed every pair that can be among the k best (all others lie strictly below the k-th count): when the
     // previous match of this lane listed few enough, the k best are taken from that list by ONE workgroup instead of four
     // launches over all pairs.  Should the list outgrow the kernel (ST_FLAG_SEL), the match is repeated with the general selection.
@@ -3245,6 +3300,7 @@ static int match_enqueue_tail(mad_ctx *ctx, const mad_set *hi, const mad_set *lo
                            scratch<int32_t>(ctx, S_COUNTS), H.p, H.R, H.meta, L.p, L.Rinv, L.meta, H.row_anchor, L.row_anchor,
                            (double *)ctx->host_res[ctx->res_slot][ctx->res_idx], P.k};
     if (pruned && !P.no_small && hint > 0 && hint <= TKS_CAP / 2 && P.k <= TKS_CAP) {
+        ctx->last_pose_plan.topk_one_wg = 1;
         mad_timer_begin(ctx, MAD_T_TOPK);
         static bool attr_t = false;
         if (!attr_t) {
@@ -3307,7 +3363,7 @@ static int match_prepare(mad_ctx *ctx, const mad_set *hi, const mad_set *lo, dou
     P->cap_c = std::max<int64_t>(ctx->match.cap_c, std::min<int64_t>((int64_t)(hi->n_anchors * 8 + 128) * (lo->n_anchors * 8 + 128), full_c));
     P->cap_pairs = std::max<int64_t>(ctx->match.cap_pairs, std::max<int64_t>(P->cap_c / 50, 1 << 16));
     // the global cell list is only needed when the clouds cannot live in LDS
-    P->fits = clouds_fit_lds(hi->n_anchors, lo->n_anchors);
+    P->fits = pose_takes_lds(ctx, hi->n_anchors, lo->n_anchors, lo->bb_min, lo->bb_max, dist);
     if (!P->fits) {
         if (!lo->cells_ready || lo->cell_size != dist) {      // shared by every lane afterwards: finish it here
             MAD_HIP(hipStreamWaitEvent(ctx->stream, lo->built, 0));
@@ -3616,6 +3672,12 @@ extern "C" int mad_last_pose_kernel(mad_ctx *ctx) { return ctx ? ctx->last_pose_
 
 extern "C" int64_t mad_last_pose_selected(mad_ctx *ctx) { return ctx ? ctx->match.n_sel : -1; }
 
+extern "C" int mad_last_pose_plan(mad_ctx *ctx, mad_pose_plan_info *out) {
+    if (!ctx || !out) return MAD_EINVAL;
+    *out = ctx->last_pose_plan;
+    return MAD_OK;
+}
+
 extern "C" int mad_match_topk_many_finish(mad_ctx *ctx) {
     if (!ctx) return MAD_EINVAL;
     if (ctx->many_open <= 0) return mad_fail(ctx, MAD_EINVAL, "mad_match_topk_many_finish: nothing was begun");
@@ -3752,7 +3814,7 @@ extern "C" int mad_match_shard_topk(mad_ctx *ctx, const mad_set *hi, const mad_s
     if (np > 0) {
         const Side H = side_of(hi), L = side_block(lo, begin, st + ST_NLO, nb);
         const int64_t cap_pairs = ctx->match.shard_cap_pairs;
-        const bool fits = clouds_fit_lds(hi->n_anchors, lo->n_anchors);
+        const bool fits = pose_takes_lds(ctx, hi->n_anchors, lo->n_anchors, lo->bb_min, lo->bb_max, dist);
         CellGrid G;
         if (!fits) {
             if (!lo->cells_ready || lo->cell_size != dist) {
@@ -3904,7 +3966,7 @@ extern "C" int mad_match_shard_score(mad_ctx *ctx, const mad_set *hi, const mad_
                        CloudJob{(const double *)hi->anc_subv.p, d_used_hi, hi->n_anchors, scratch<double>(ctx, S_HI_CLOUD), st + ST_LHI, nullptr, nullptr, st});
     MAD_HIP(hipGetLastError());
     const Side H = side_of(hi), L = side_block(lo, S.begin, st + ST_NLO, S.nb);
-    const bool fits = clouds_fit_lds(hi->n_anchors, lo->n_anchors);
+    const bool fits = pose_takes_lds(ctx, hi->n_anchors, lo->n_anchors, lo->bb_min, lo->bb_max, dist);
     CellGrid G;
     if (!fits) {
         if (!lo->cells_ready || lo->cell_size != dist) {      // (once per lo set and distance: shared by every later match)
@@ -4249,6 +4311,7 @@ extern "C" int mad_set_import(mad_ctx *ctx, mad_set *s, const void *wires, int w
     if (n_anchors > 0 && (!anc_octave || !anc_subv || !anc_index)) return mad_fail(ctx, MAD_EINVAL, "mad_set_import: NULL anchors");
     if (n_anchors > 65536) return mad_fail(ctx, MAD_EINVAL, "mad_set_import: %d anchors exceed the single-launch scan", n_anchors);
     if (!ctx->eq_set[0] || !ctx->eq_set[1]) return mad_fail(ctx, MAD_EINVAL, "mad_set_import: EQSP tables not set");
+    if (n_anchors > 0) MAD_TRY(pose_check_coords(ctx, "mad_set_import", "anchor", anc_subv, (int64_t)3 * n_anchors));
     mad_use_lane(ctx, s->lane);
     const int D = 64 * ctx->eq_host[1].Z;
     const WireLayout L = wire_layout(D, cap_rows);

@@ -284,6 +284,7 @@ def test_pose_score_large_lo_cloud(lib, n_lo_anchor, n_pairs, box):
     ref_res, ref_cnt = O.pose_score(**a, dist=4.0)
     got_res, got_cnt = lib.pose_score(**a, dist=4.0)
     assert lib.last_pose_kernel() == (1 if n_lo_anchor == 5600 else 2)      # the kernel this case is meant for
+    assert lib.last_pose_plan()["hi_in_lds"] == (1 if n_lo_anchor == 5600 else 0)      # ... and k_pose_lds32<true>: 300 hi points fit beside the lo cloud
     assert ref_cnt.max() > 100 and ref_cnt.mean() > 1
     np.testing.assert_array_equal(got_cnt, ref_cnt)
     np.testing.assert_allclose(got_res, ref_res, rtol=1e-12, atol=1e-12)

@@ -29,6 +29,28 @@ def test_library_exports_every_declared_symbol():
     assert not missing, missing
 
 
+def test_pose_plan_record_of_the_wrapper_is_the_headers():
+    """mad_last_pose_plan fills a struct: the ctypes mirror in _lib.py must list the header's fields, in order, with their types."""
+    import ctypes as C
+    header = open(os.path.join(ROOT, "include", "mad_amd.h")).read()
+    body = re.search(r"typedef struct mad_pose_plan_info \{(.*?)\} mad_pose_plan_info;", header, flags=re.S).group(1)
+    body = re.sub(r"/\*.*?\*/", "", body, flags=re.S)
+    ctype = {"int32_t": C.c_int32, "int64_t": C.c_int64, "double": C.c_double}
+    declared = []
+    for decl in body.split(";"):
+        decl = decl.strip()
+        if not decl:
+            continue
+        t, names = decl.split(None, 1)
+        for name in names.split(","):
+            m = re.match(r"\s*(\w+)(?:\[(\d+)\])?\s*$", name)
+            declared.append((m.group(1), ctype[t] * int(m.group(2)) if m.group(2) else ctype[t]))
+    assert [(n, t) for n, t in _lib._PosePlanInfo._fields_] == declared
+    assert C.sizeof(_lib._PosePlanInfo) == 18 * 4 + 7 * 8 + 3 * 8      # no padding: 18 ints, 7 doubles, 3 int64
+    info = _lib._PosePlanInfo()
+    assert _lib.load_library().mad_last_pose_plan(None, C.byref(info)) == -22      # host-only: no context, MAD_EINVAL, nothing touched
+
+
 def test_no_cpu_fallback_without_a_gpu():
     import torch
     if torch.cuda.device_count() > 0:
