@@ -2162,6 +2162,12 @@ static int correlate_reserve(mad_ctx *ctx, const Side &hi, const Side &lo, int D
 }
 
 static int correlate_gemm(mad_ctx *ctx, int n_jobs, const GemmJob *jobs, int D, double cc) {
+    // The candidate test compares in float32 with (float)(cc |l|): for a negative cc above -1e-30 or so that product is a float32
+    // denormal or -0, the threshold becomes -0, and an entry whose dot product is 0 -- score 0 > cc: a pair -- was not flagged
+    // (cc = -1e-300 lost every pair of a zero row).  Dot products are integers and |h| |l| < 1e10, so for every cc in (-1e-30, 0) the
+    // exact test is dot >= 0, which is what the float32 test at -1e-30 flags (norms are >= 1: nothing underflows); the pair kernels
+    // go on comparing with cc itself.
+    if (cc < 0 && cc > -1e-30) cc = -1e-30;
     mad_timer_begin(ctx, MAD_T_CORRELATE);
     static const bool no_split = getenv("MAD_GEMM_NO_SPLIT") != nullptr;      // diagnostic switch: whole tiles only, as in round 3
     const bool wide = n_jobs > 0 && jobs[0].hb != nullptr;
