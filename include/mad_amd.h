@@ -489,6 +489,32 @@ int mad_map_zone(mad_ctx *ctx, float *grid, const int32_t dims[3], const double 
                  int64_t counts[2] /* may be NULL */);
 
 /*
+ * A placed model scored per group of atoms -- residue, chain, any partition -- against a map (mad_groupfit.hip; DESIGN.md section
+ * 4k).  Host pointers, synchronous, nothing modified but the two outputs.  grid1 (the map) and grid2 (the model's density): float32
+ * [x][y][z] with their dims and origins (Angstrom, centre of voxel (0,0,0)) and the common spacing voxsp.  Group g owns the atoms
+ * first_atom[g] .. first_atom[g + 1] - 1 of atoms (n x 3 float64, Angstrom; the layout of mad_overlap_matrix), n_atoms =
+ * first_atom[n_groups]; atoms may be NULL when n_atoms == 0.
+ *   Membership: mad_map_zone's expressions on grid 1's lattice.  Voxel j sits at p_a = origin1_a + voxsp * j_a (float64, one
+ *     multiply and one add, no FMA), d2 = (dx*dx + dy*dy) + dz*dz with dx = p_x - a_x, and j is a member of group g iff some atom
+ *     of g has d2 <= radius * radius (inclusive).  Groups may overlap: a voxel counts in every group that reaches it.
+ *   Values: a = g1[j] < (float)isovalue ? 0.0 : (double)g1[j] (a float32 compare).  With s_a = round-half-even(origin2_a / voxsp -
+ *     origin1_a / voxsp) and k = j - s: b = 0.0 where k lies outside grid 2, else the same expression on g2[k].  The sums are not
+ *     restricted to the common box of the two grids.
+ *   Outputs: n_vox[g] = the members of g (exact); sums[5 g ..] = {sum a*a, sum b*b, sum a*b, sum a, sum b} over them, float64 (every
+ *     term is exact; the order of the additions is fixed).  An empty group, or one that reaches no voxel, has
+ *     n_vox = 0 and five zero sums.  A voxel that is not finite is no error: it propagates as IEEE says.  The same call gives the
+ *     same bits alone or after any other call.  n_groups == 0 returns MAD_OK and writes nothing.
+ * MAD_EINVAL, with nothing launched and the outputs untouched: NULL (atoms only when n_atoms == 0), a dimension < 1, voxsp <= 0,
+ * 2^32 voxels or more in either grid, n_groups < 0, first_atom[0] != 0 or first_atom decreasing, n_atoms >= 2^31, radius < 0,
+ * isovalue < 0, a number that is not finite (atom coordinates, origins and the offset between the grids in voxels included), a work
+ * list of 2^31 bricks or more (one brick of 8 x 8 x 16 voxels per group and part of the group's reach).
+ */
+int mad_map_group_fit(mad_ctx *ctx, const float *grid1, const int32_t dims1[3], const double origin1[3],
+                      const float *grid2, const int32_t dims2[3], const double origin2[3], double voxsp,
+                      const double *atoms, const int64_t *first_atom, int32_t n_groups, double radius, double isovalue,
+                      int64_t *n_vox /* [n_groups] */, double *sums /* [n_groups][5] */);
+
+/*
  * A Gaussian on a map, and a map cut into segments (mad_segment.hip).  Host pointers, synchronous.  Both work
  * in voxels: grid is float32 [x][y][z] with dims, the linear index of a voxel is L = (x * ny + y) * nz + z, neither origin nor
  * spacing enters.

@@ -9,7 +9,8 @@ three need when two maps differ in spacing or are not a whole number of voxels a
 is the structure-against-map half: it keeps the density within a radius of a structure's atoms, or erases it, through `mad_map_zone`,
 so that the remaining subunits can be docked into what is left of a map.  `smooth` applies a Gaussian through `mad_map_smooth` and
 `segment` cuts the map into segments through `mad_map_segment` (watershed regions grouped by smoothing, the scheme of Segger; no
-counterpart in the reference), which is where the masks `mask_with` consumes come from.  None of them has a CPU fallback.  The reference's per-voxel text writer is replaced by `mapio.write_situs`.
+counterpart in the reference), which is where the masks `mask_with` consumes come from.  `fit_by_group` scores a placed model per residue, chain or other group
+of atoms against the map through `mad_map_group_fit` (localfit.py; no counterpart in the reference).  None of them has a CPU fallback.  The reference's per-voxel text writer is replaced by `mapio.write_situs`.
 """
 import os
 import sys
@@ -176,6 +177,18 @@ class Dmap(object):
                 g = g.copy()
             self.grid3d = g
         return _lib.get_lib().map_zone(g, (self.xi, self.yi, self.zi), self.voxsp, atoms, radius, soft, erase)
+
+    def fit_by_group(self, structure, resolution, by="residue", radius=None, isovalue=0, model=None, masses=None):
+        """Which part of a placed model sits in density: the un-centred score of this map against the model's density per group of
+        atoms, over the voxels within `radius` Angstrom of the group -> `localfit.GroupFit` (labels, n_voxels, sums, ccc, and
+        writers for a table and for the B-factor column of a PDB file).  `structure`: a `PDB`, an (n, 3) array, or a list / tuple of
+        those.  `by`: "residue", "chain" (both from `PDB.info`; equal chain letters of two files stay apart), "atom", "all", or an
+        integer array with the group of each atom.  `radius=None` means max(resolution / 2, 2 * voxsp), a convention.  `model=None`
+        simulates the density of all atoms together at `resolution` (masses from `PDB.atom_masses()`; arrays take `masses` or
+        carbon); it may instead be a `Dmap` or (grid, (x0, y0, z0)) of this map's spacing.  Voxels below `isovalue` count as 0 in
+        both.  `self` is not modified.  DESIGN.md section 4k has the exact contract."""
+        from . import localfit
+        return localfit.fit_by_group(self, structure, resolution, by=by, radius=radius, isovalue=isovalue, model=model, masses=masses)
 
     def smooth(self, sigma):
         """A Gaussian of `sigma` Angstrom on the map, in place (zero beyond the box, float64 inside, 4 sigma wide on either side).

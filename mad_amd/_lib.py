@@ -39,7 +39,7 @@ SYMBOLS = [
     "mad_dist_unique_id", "mad_dist_init", "mad_dist_destroy", "mad_dist_info", "mad_dist_rehearse_flags", "mad_dist_or_allreduce", "mad_dist_allgather",
     "mad_dist_allgather_topk", "mad_dist_scratch", "mad_dist_copy",
     "mad_set_wire_bytes", "mad_set_export", "mad_set_import", "mad_set_lane", "mad_set_stream", "mad_set_bind_lane",
-    "mad_upload_density", "mad_refine", "mad_last_refine_plan", "mad_last_density_chunks", "mad_structure_to_density", "mad_ccc", "mad_map_mask", "mad_map_ccc", "mad_map_resample", "mad_map_zone", "mad_map_smooth", "mad_map_segment", "mad_density_ccc", "mad_dock_refine_score", "mad_grid_overlap", "mad_overlap_matrix",
+    "mad_upload_density", "mad_refine", "mad_last_refine_plan", "mad_last_density_chunks", "mad_structure_to_density", "mad_ccc", "mad_map_mask", "mad_map_ccc", "mad_map_resample", "mad_map_zone", "mad_map_group_fit", "mad_map_smooth", "mad_map_segment", "mad_density_ccc", "mad_dock_refine_score", "mad_grid_overlap", "mad_overlap_matrix",
     "mad_space_create", "mad_space_destroy", "mad_space_build", "mad_space_info", "mad_space_download",
     "mad_space_peaks", "mad_space_patches", "mad_space_localize", "mad_localize_volume",
     "mad_pose_cluster_many",
@@ -1187,6 +1187,41 @@ class Lib(object):
         self._chk(self.dll.mad_map_zone(self.ctx, _p(g), _p(d), _p(o), C.c_double(voxsp), _p(a) if len(a) else None, C.c_int64(len(a)),
                                         C.c_double(radius), C.c_double(soft), C.c_int(1 if erase else 0), _p(counts)))
         return int(counts[0]), int(counts[1])
+
+    def map_group_fit(self, g1, o1, g2, o2, voxsp, atoms, first_atom, radius, isovalue=0.0, out=None):
+        """A placed model scored per group of atoms: `g1` (the map) and `g2` (the model's density), C-contiguous float32
+        [x, y, z] with origins `o1`, `o2` and the common spacing `voxsp`; group g owns atoms first_atom[g] .. first_atom[g + 1] - 1.
+        -> (n_vox int64 [G], sums float64 [G, 5]): per group the voxels of g1 within `radius` of one of its atoms, and over them
+        sum a*a, sum b*b, sum a*b, sum a, sum b with a, b the two densities clamped at `isovalue`, b = 0 beyond g2
+        (mad_map_group_fit).  Nothing is modified.  `out`: a pair of arrays to fill instead of new ones."""
+        for g in (g1, g2):
+            if g.dtype != np.float32 or not g.flags.c_contiguous:
+                raise ValueError("map_group_fit needs C-contiguous float32 grids")
+            if g.ndim != 3:
+                raise ValueError("map_group_fit needs 3-D grids")
+        d1, d2 = np.array(g1.shape, np.int32), np.array(g2.shape, np.int32)
+        o1 = _c(np.asarray(o1, np.float64).reshape(3), np.float64)
+        o2 = _c(np.asarray(o2, np.float64).reshape(3), np.float64)
+        a = _c(np.asarray(atoms, np.float64).reshape(-1, 3), np.float64)
+        first = _c(np.asarray(first_atom, np.int64).reshape(-1), np.int64)
+        if len(first) < 1:
+            raise ValueError("map_group_fit: first_atom needs n_groups + 1 entries")
+        n_groups = len(first) - 1
+        if n_groups >= 2 ** 31:
+            raise ValueError("map_group_fit: %d groups" % n_groups)
+        if int(first[-1]) > len(a):
+            raise ValueError("map_group_fit: first_atom ends at %d, there are %d atoms" % (int(first[-1]), len(a)))
+        if out is None:
+            n_vox, sums = np.zeros(n_groups, np.int64), np.zeros((n_groups, 5), np.float64)
+        else:
+            n_vox, sums = out
+            if (n_vox.dtype != np.int64 or sums.dtype != np.float64 or n_vox.shape != (n_groups,) or sums.shape != (n_groups, 5)
+                    or not n_vox.flags.c_contiguous or not sums.flags.c_contiguous or not n_vox.flags.writeable or not sums.flags.writeable):
+                raise ValueError("map_group_fit: out must be writable C-contiguous (int64 [G], float64 [G, 5])")
+        self._chk(self.dll.mad_map_group_fit(self.ctx, _p(g1), _p(d1), _p(o1), _p(g2), _p(d2), _p(o2), C.c_double(voxsp),
+                                             _p(a) if len(a) else None, _p(first), C.c_int32(n_groups), C.c_double(radius),
+                                             C.c_double(isovalue), _p(n_vox), _p(sums)))
+        return n_vox, sums
 
     def map_smooth(self, g, sigma_vox, out=None):
         """`g` (C-contiguous float32 [x, y, z]) smoothed with a Gaussian of `sigma_vox` voxels, zero beyond the grid, float64 inside

@@ -782,4 +782,19 @@ __device__ __forceinline__ bool eqsp_tier2(const EqspFastLds *t, double x, doubl
     return true;
 }
 
+// Squared distance from x to the box [lo, hi]: the expression of the zone contract on the per-axis excess,
+// shared by k_zone_count, k_map_zone and k_group_fit.  Rounding is monotone, so for every voxel p inside the box this is <= the
+// voxel's own d2 to x as the device computes it: an atom with boxd2 > R2 gives every voxel of the box d2 > R2 and may be dropped.
+// One with boxd2 == R2 may not: a voxel at d2 == r2 is inside (the contract's tie is inclusive, and with soft = 0 R2 is r2 bit for
+// bit), so every cull keeps boxd2 <= R2.
+__device__ __forceinline__ double zone_box_d2(const double x[3], const double lo[3], const double hi[3]) {
+    double e[3];
+#pragma unroll
+    for (int a = 0; a < 3; a++) {
+        const double below = lo[a] - x[a], above = x[a] - hi[a];
+        e[a] = below > 0.0 ? below : (above > 0.0 ? above : 0.0);
+    }
+    return (e[0] * e[0] + e[1] * e[1]) + e[2] * e[2];
+}
+
 #endif  // __HIPCC__

@@ -33,19 +33,7 @@ struct ZoneGeo {
     double radius, soft, r2, R, R2;
 };
 
-// squared distance from x to the box [lo, hi], the expression of the contract on the per-axis excess.  Rounding is monotone, so
-// for every voxel p inside the box this is <= the voxel's own d2 to x as the device computes it: an atom with boxd2 > R2 gives
-// every voxel of the box d2 > R2, weight 0, and may be dropped.  One with boxd2 == R2 may not: with soft = 0, R2 is r2 bit for bit
-// and a voxel at d2 == r2 is inside (the contract's tie is inclusive), so both culls below keep boxd2 <= R2.
-__device__ __forceinline__ double zone_box_d2(const double x[3], const double lo[3], const double hi[3]) {
-    double e[3];
-#pragma unroll
-    for (int a = 0; a < 3; a++) {
-        const double below = lo[a] - x[a], above = x[a] - hi[a];
-        e[a] = below > 0.0 ? below : (above > 0.0 ? above : 0.0);
-    }
-    return (e[0] * e[0] + e[1] * e[1]) + e[2] * e[2];
-}
+// zone_box_d2, the squared distance from an atom to a box that both culls below use, is in mad_common.h (k_group_fit shares it)
 
 // cell of coordinate v on axis a, before clamping; monotone in v
 __device__ __forceinline__ double zone_cell_f(const ZoneGeo &G, int a, double v) { return floor((v - G.glo[a]) / G.h); }
