@@ -121,8 +121,9 @@ int mad_upload_field_device(mad_ctx *ctx, int slot, const float *g3_device, int 
 int mad_free_field(mad_ctx *ctx, int slot);
 /*
  * Diagnostic: copies a slot's texels back to the host, tex_xyzw = [nx*ny*nz][4] float32 {gx, gy, gz, |g|} and
- * tex4 = [nx*ny*nz] packed 4-byte texels; either pointer may be NULL.  Waits for the stream.  MAD_EINVAL for
- * an empty or out-of-range slot.  Nothing on the path calls it.
+ * tex4 = [nx*ny*nz] packed 4-byte texels, both in linear [nx][ny][nz] order (on the device the 4-byte texels lie in padded
+ * bricks of 4x4x2 voxels; they are taken apart here and exactly nx*ny*nz words are written); either pointer may be NULL.
+ * Waits for the stream.  MAD_EINVAL for an empty or out-of-range slot.  Nothing on the path calls it.
  */
 int mad_field_download(mad_ctx *ctx, int slot, float *tex_xyzw, uint32_t *tex4);
 

@@ -153,7 +153,15 @@ struct FieldDev {
     // The same field as 4-byte texels (round 3): the unit direction in three signed 10-bit components + two flag bits (mad_tex4_encode).
     // k_describe gathers THESE (a quarter of the bytes per sample) and classifies them through a table with a guard band wider than
     // the quantisation; only the samples the table cannot decide (2-4 %) fetch the 16-byte texel.  Behind `tex` in the same allocation.
+    // tex4 is stored in BRICKS of 4 x 4 x 2 voxels (x, y, z) = 32 texels = one 128-byte line, 128-byte aligned, the bricks in the order
+    // (bx NBy + by) NBz + bz; the last brick of an axis is zero-padded.  `tex` keeps the linear [nx][ny][nz] order.  The brick counts
+    // follow from the dimensions (two scalar instructions each in a kernel, and the struct keeps its size); mad_tex4_index /
+    // mad_tex4_voxel (below) are the only places that know the order.
     const unsigned *tex4;
+    __host__ __device__ unsigned nbx() const { return ((unsigned)nx + 3u) >> 2; }
+    __host__ __device__ unsigned nby() const { return ((unsigned)ny + 3u) >> 2; }
+    __host__ __device__ unsigned nbz() const { return ((unsigned)nz + 1u) >> 1; }
+    __host__ __device__ size_t tex4_words() const { return (size_t)32 * nbx() * nby() * nbz(); }      // with the padding
 };
 
 // ---------------------------------------------------------------------------
@@ -650,6 +658,27 @@ __device__ __forceinline__ unsigned mad_tex4_encode(float x, float y, float z, f
     const float inv = 511.0f / w;
     const int ix = min(max((int)rintf(x * inv), -511), 511), iy = min(max((int)rintf(y * inv), -511), 511), iz = min(max((int)rintf(z * inv), -511), 511);
     return ((unsigned)ix & 0x3ffu) | (((unsigned)iy & 0x3ffu) << 10) | (((unsigned)iz & 0x3ffu) << 20);
+}
+
+// Where voxel (x, y, z) of a field lies in its 4-byte texels (FieldDev::tex4, bricks of 4 x 4 x 2): brick number x 32 + the offset
+// (x&3)<<3 | (y&3)<<1 | (z&1).  The voxel must lie inside the grid.  On the device the two multiplies are 24-bit ones: NBx NBy and NBz
+// stay below 2^24 and the padded array below 2^32 words (checked at allocation).
+__host__ __device__ __forceinline__ unsigned mad_tex4_index(const FieldDev &F, unsigned x, unsigned y, unsigned z) {
+#ifdef __HIP_DEVICE_COMPILE__
+    const unsigned brick = mad_u24(mad_u24(x >> 2, F.nby(), y >> 2), F.nbz(), z >> 1);
+#else
+    const unsigned brick = ((x >> 2) * F.nby() + (y >> 2)) * F.nbz() + (z >> 1);
+#endif
+    return (brick << 5) | ((x & 3u) << 3) | ((y & 3u) << 1) | (z & 1u);
+}
+// ... and back: the linear index (x ny + y) nz + z of the voxel whose texel is tex4[at] (32-bit divisions only; a padding texel maps
+// to a voxel outside the grid, which no caller asks for)
+__host__ __device__ __forceinline__ unsigned mad_tex4_voxel(const FieldDev &F, unsigned at) {
+    const unsigned brick = at >> 5, nby = F.nby(), nbz = F.nbz();
+    const unsigned t = brick / nbz, bz = brick - t * nbz;
+    const unsigned bx = t / nby, by = t - bx * nby;
+    const unsigned x = (bx << 2) | ((at >> 3) & 3u), y = (by << 2) | ((at >> 1) & 3u), z = (bz << 1) | (at & 1u);
+    return (x * (unsigned)F.ny + y) * (unsigned)F.nz + z;
 }
 
 // zone of the direction (x, y, z) -- z on the unit scale, x and y on any common scale -- or -1 (undecided); see EqspTabLds

@@ -387,7 +387,10 @@ extern "C" int mad_set_eqsp(mad_ctx *ctx, int which, int Z, const double *bounds
 
 // planar {gx,gy,gz} -> texel {gx,gy,gz,|g|}; |g| with one float32 rounding per operation
 __global__ __launch_bounds__(256) void k_pack_field(const float *__restrict__ gx, const float *__restrict__ gy,
-                                                    const float *__restrict__ gz, float4 *__restrict__ tex, unsigned *__restrict__ tex4, size_t n) {
+                                                    const float *__restrict__ gz, FieldDev F, size_t n) {
+    float4 *const tex = (float4 *)F.tex;
+    unsigned *const tex4 = (unsigned *)F.tex4;
+    const size_t sx = (size_t)F.ny * F.nz;
     size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
     const size_t step = (size_t)gridDim.x * blockDim.x;
     for (; i < n; i += step) {
@@ -395,7 +398,8 @@ __global__ __launch_bounds__(256) void k_pack_field(const float *__restrict__ gx
         const float s = __fadd_rn(__fadd_rn(__fmul_rn(x, x), __fmul_rn(y, y)), __fmul_rn(z, z));
         const float w = sqrtf(s);      // sqrtf is correctly rounded here; the "_rn" sqrt intrinsic is NOT (1 ulp off for 15 % of inputs, measured)
         tex[i] = make_float4(x, y, z, w);
-        tex4[i] = mad_tex4_encode(x, y, z, w);
+        const unsigned vx = (unsigned)(i / sx), vyz = (unsigned)(i - (size_t)vx * sx);      // the 4-byte texel goes to its brick
+        tex4[mad_tex4_index(F, vx, vyz / (unsigned)F.nz, vyz % (unsigned)F.nz)] = mad_tex4_encode(x, y, z, w);
     }
 }
 
@@ -406,18 +410,28 @@ int mad_field_alloc(mad_ctx *ctx, int slot, int nx, int ny, int nz, size_t *n_ou
     // the kernels index texels with 24-bit multiplies: (x ny + y) and nz below 2^24, the whole field below 2^32 texels
     if (n >= ((size_t)1 << 32) || (size_t)nx * ny >= ((size_t)1 << 24) || nz >= (1 << 24))
         return mad_fail(ctx, MAD_EINVAL, "field of %dx%dx%d texels: more than 2^32 texels or 2^24 per x-y plane", nx, ny, nz);
+    // ... and the 4-byte texels in their bricks (mad_tex4_index): (bx NBy + by) and NBz below 2^24 -- both follow from the above, a
+    // brick count being no larger than the voxel count -- and the PADDED array below 2^32 words, which does not (each axis rounds up)
+    FieldDev geo{nullptr, nx, ny, nz, nullptr};
+    const size_t n4 = geo.tex4_words();
+    if (n4 >= ((size_t)1 << 32) || (size_t)geo.nbx() * geo.nby() >= ((size_t)1 << 24) || geo.nbz() >= (1u << 24))
+        return mad_fail(ctx, MAD_EINVAL, "field of %dx%dx%d texels: more than 2^32 4-byte texels in bricks of 4x4x2", nx, ny, nz);
     if (ctx->field_mem[slot]) {
         MAD_HIP(hipStreamSynchronize(ctx->stream));
         (void)hipFree(ctx->field_mem[slot]);
         ctx->field_mem[slot] = nullptr;
         ctx->fields[slot] = FieldDev{nullptr, 0, 0, 0};
     }
-    hipError_t e = hipMalloc(&ctx->field_mem[slot], n * (sizeof(float4) + sizeof(unsigned)));      // the 16-byte texels, then the 4-byte ones
+    // the 16-byte texels, then -- on the next 128-byte boundary, a brick being one line -- the 4-byte ones
+    const size_t off4 = (n * sizeof(float4) + 127) / 128 * 128;
+    hipError_t e = hipMalloc(&ctx->field_mem[slot], off4 + n4 * sizeof(unsigned));
     if (e != hipSuccess) {
         ctx->field_mem[slot] = nullptr;
         return mad_fail(ctx, MAD_ENOMEM, "field of %zu texels: %s", n, hipGetErrorString(e));
     }
-    ctx->fields[slot] = FieldDev{(const float4 *)ctx->field_mem[slot], nx, ny, nz, (const unsigned *)((const float4 *)ctx->field_mem[slot] + n)};
+    ctx->fields[slot] = FieldDev{(const float4 *)ctx->field_mem[slot], nx, ny, nz, (const unsigned *)((const char *)ctx->field_mem[slot] + off4)};
+    mad_zero_words(ctx, (void *)ctx->fields[slot].tex4, n4 * sizeof(unsigned));      // once, before the builder: the padding texels are defined
+    MAD_HIP(hipGetLastError());
     *n_out = n;
     return MAD_OK;
 }
@@ -427,8 +441,7 @@ extern "C" int mad_upload_field_device(mad_ctx *ctx, int slot, const float *g3, 
     size_t n = 0;
     MAD_TRY(mad_field_alloc(ctx, slot, nx, ny, nz, &n));
     const int blocks = (int)std::min<size_t>(mad_ceil_div((int64_t)n, 256), (size_t)ctx->n_cu * 16);
-    hipLaunchKernelGGL(k_pack_field, dim3(blocks), dim3(256), 0, ctx->stream, g3, g3 + n, g3 + 2 * n,
-                       (float4 *)ctx->field_mem[slot], (unsigned *)((float4 *)ctx->field_mem[slot] + n), n);
+    hipLaunchKernelGGL(k_pack_field, dim3(blocks), dim3(256), 0, ctx->stream, g3, g3 + n, g3 + 2 * n, ctx->fields[slot], n);
     MAD_HIP(hipGetLastError());
     MAD_HIP(hipStreamSynchronize(ctx->stream));
     return MAD_OK;
@@ -463,7 +476,8 @@ extern "C" int mad_free_field(mad_ctx *ctx, int slot) {
     return MAD_OK;
 }
 
-// diagnostic read-back of a slot: the 16-byte texels and the 4-byte ones behind them
+// diagnostic read-back of a slot: the 16-byte texels and the 4-byte ones behind them, both in linear order (the bricks of the
+// 4-byte texels are taken apart here, on the host: the caller's buffer holds nx ny nz words and never sees the padded array)
 extern "C" int mad_field_download(mad_ctx *ctx, int slot, float *tex_xyzw, uint32_t *tex4) {
     if (!ctx) return MAD_EINVAL;
     if (slot < 0 || slot >= MAD_MAX_FIELDS || !ctx->field_mem[slot]) return mad_fail(ctx, MAD_EINVAL, "mad_field_download: slot %d is empty or out of range", slot);
@@ -471,8 +485,18 @@ extern "C" int mad_field_download(mad_ctx *ctx, int slot, float *tex_xyzw, uint3
     const size_t n = (size_t)f.nx * f.ny * f.nz;
     MAD_HIP(hipStreamSynchronize(ctx->stream));
     if (tex_xyzw) MAD_HIP(hipMemcpyAsync(tex_xyzw, f.tex, n * sizeof(float4), hipMemcpyDeviceToHost, ctx->stream));
-    if (tex4) MAD_HIP(hipMemcpyAsync(tex4, f.tex4, n * sizeof(unsigned), hipMemcpyDeviceToHost, ctx->stream));
+    std::vector<unsigned> bricks;
+    if (tex4) {
+        bricks.resize(f.tex4_words());
+        MAD_HIP(hipMemcpyAsync(bricks.data(), f.tex4, bricks.size() * sizeof(unsigned), hipMemcpyDeviceToHost, ctx->stream));
+    }
     MAD_HIP(hipStreamSynchronize(ctx->stream));
+    if (tex4) {
+        size_t i = 0;
+        for (int x = 0; x < f.nx; x++)
+            for (int y = 0; y < f.ny; y++)
+                for (int z = 0; z < f.nz; z++) tex4[i++] = bricks[mad_tex4_index(f, (unsigned)x, (unsigned)y, (unsigned)z)];
+    }
     return MAD_OK;
 }
 

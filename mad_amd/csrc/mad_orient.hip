@@ -874,7 +874,9 @@ __device__ __forceinline__ bool lattice_voxel_exact(double l0, double l1, double
     *v2 = (p2 - (double)a2i <= 0.5) ? a2i : a2i + 1;
     return true;
 }
-// ... as a texel index; *oob is set when the point leaves the grid
+// ... as a texel index -- of the 4-byte texels in their bricks (BRICK) or the linear one of the 16-byte texels; *oob is set when the
+// point leaves the grid
+template <bool BRICK>
 __device__ __forceinline__ unsigned lattice_index_exact(double l0, double l1, double l2, const double *inv, double c0, double c1, double c2,
                                                         const FieldDev &F, bool *oob) {
     int a0i, a1i, a2i;
@@ -882,6 +884,7 @@ __device__ __forceinline__ unsigned lattice_index_exact(double l0, double l1, do
         *oob = true;
         return 0;
     }
+    if (BRICK) return mad_tex4_index(F, (unsigned)a0i, (unsigned)a1i, (unsigned)a2i);
     return (unsigned)(((size_t)a0i * F.ny + a1i) * F.nz + a2i);
 }
 
@@ -923,6 +926,16 @@ template <int S, int NSUB> __device__ __forceinline__ int sub_of_i(int i) {
 // uniform directions, half of what the 4e-3 rad guard of round 3 left open) is queued BY TEXEL INDEX and goes
 // through the former tiers -- float32 with its 1e-4 guard, then float64 -- on the full 16-byte texel, in full lanes.  The result
 // is the same descriptor, bit for bit: every tier only ever answers when the exact arithmetic is certain to agree.
+// The 4-byte texels lie in bricks of 4 x 4 x 2 voxels, one 128-byte line each (FieldDev, mad_tex4_index): a wave-instruction's 64
+// samples -- one i, four j, sixteen k: a rotated planar patch of 8 x 32 voxels in octave 0, 4 x 16 in octave 1 -- then share lines
+// where in the linear order nearly every sample had a 1 x 1 x 32 stick of its own: 4.04 M requests from the L1 to the L2 per launch
+// on C3 against 7.41 M, 61.7 us against 75.0, for 12 instructions of address per sample instead of 2.  The queue
+// holds tex4 indices; the queue phase, which reads the 16-byte texels in their linear order, decodes them with mad_tex4_voxel.
+// The 4-byte texels lie in bricks of 4 x 4 x 2 voxels, one 128-byte line each (FieldDev, mad_tex4_index): a wave-instruction's 64
+// samples -- one i, four j, sixteen k: a rotated planar patch of 8 x 32 voxels in octave 0, 4 x 16 in octave 1 -- then share lines
+// where in the linear order nearly every sample had a 1 x 1 x 32 stick of its own: 4.04 M requests from the L1 to the L2 per launch
+// on C3 against 7.41 M, 61.7 us against 75.0, for 12 instructions of address per sample instead of 2.  The queue
+// holds tex4 indices; the queue phase, which reads the 16-byte texels in their linear order, decodes them with mad_tex4_voxel.
 #define DSC_QUEUE_TAB 768
 #ifdef MAD_PROBE_STAMPS      // diagnostic build: s_memtime at the phases of every row's workgroup (tools/probe_describe.py)
 __device__ long long dsc_stamps[16384 * 8];
@@ -969,7 +982,7 @@ __global__ __launch_bounds__(DSC_NT(S), TAB ? DSC_OCC_TAB : DSC_OCC) void k_desc
     __shared__ float4 qv[TAB ? 1 : DSC_QUEUE];         // texels the fast classifier could not decide
     __shared__ int qsub[TAB ? 1 : DSC_QUEUE];
     __shared__ typename std::conditional<TAB, EqspTabLds, int>::type tab;
-    __shared__ unsigned qidx[TAB ? DSC_QUEUE_TAB : 1];             // TAB: texel indices of the samples the table could not decide
+    __shared__ unsigned qidx[TAB ? DSC_QUEUE_TAB : 1];             // TAB: tex4 indices (mad_tex4_index) of the samples the table could not decide
     __shared__ unsigned short qsub16[TAB ? DSC_QUEUE_TAB : 1];
     const int QCAP = min(TAB ? DSC_QUEUE_TAB : DSC_QUEUE, A.queue_cap);      // (mad_set_option "dsc_queue": tests of the full-queue path)
     // XCD-aware order: workgroups are dealt round-robin to the 8 XCDs (b and b + 8 share one), so give
@@ -1046,7 +1059,7 @@ __global__ __launch_bounds__(DSC_NT(S), TAB ? DSC_OCC_TAB : DSC_OCC) void k_desc
     F.tex = oct == 1 ? F1.tex : F0.tex; F.nx = oct == 1 ? F1.nx : F0.nx; F.ny = oct == 1 ? F1.ny : F0.ny; F.nz = oct == 1 ? F1.nz : F0.nz;
     F.tex4 = oct == 1 ? F1.tex4 : F0.tex4;
 #ifdef DSC_TEX_AUX      // probe builds (tools/build_variant.sh -DDSC_TEX_AUX=n): the texel gathers as buffer loads with cache-policy bits n (1 sc0, 2 nt, 16 sc1)
-    const __amdgpu_buffer_rsrc_t tex_rsrc = __builtin_amdgcn_make_buffer_rsrc((void *)F.tex4, 0, F.nx * F.ny * F.nz * 4, 0x00020000);
+    const __amdgpu_buffer_rsrc_t tex_rsrc = __builtin_amdgcn_make_buffer_rsrc((void *)F.tex4, 0, (int)(F.tex4_words() * 4), 0x00020000);      // the padded array
 #define DSC_TEX4(at) ((unsigned)__builtin_amdgcn_raw_buffer_load_b32(tex_rsrc, (int)((at) * 4u), 0, DSC_TEX_AUX))
 #else
 #define DSC_TEX4(at) (F.tex4[at])
@@ -1065,11 +1078,12 @@ __global__ __launch_bounds__(DSC_NT(S), TAB ? DSC_OCC_TAB : DSC_OCC) void k_desc
     // (float32 here: half-integers below 32, exact.  The float64 forms the rare exact paths need are made inside those paths, from
     // values the optimiser cannot see through, so that they do not occupy registers outside them)
     const float lbf = oct == 0 ? (float)(-2 * A.r + 1) : (float)-A.r + 0.5f, lsf = oct == 0 ? 2.0f : 1.0f;
-    auto exact_index = [&](int i, bool *left) -> unsigned {
+    // (brick: where the sample lies in tex4, for the table form's gathers; otherwise in tex, linear)
+    auto exact_index = [&](int i, bool *left, auto brick) -> unsigned {
         float lb = lbf, ls = lsf;
         asm volatile("" : "+v"(lb), "+v"(ls));
         const double lbase = (double)lb, lstep = (double)ls;
-        return lattice_index_exact(lbase + lstep * i, lbase + lstep * j, lbase + lstep * k, sInv, (double)ic0, (double)ic1, (double)ic2, F, left);
+        return lattice_index_exact<decltype(brick)::value>(lbase + lstep * i, lbase + lstep * j, lbase + lstep * k, sInv, (double)ic0, (double)ic1, (double)ic2, F, left);
     };
     // The rotated lattice stays within `reach` voxels of the anchor.  When that ball lies inside the grid with a voxel to
     // spare (every row of an anchor the Orientator accepted, unless it hugs the border) no sample can leave the grid.
@@ -1121,7 +1135,9 @@ __global__ __launch_bounds__(DSC_NT(S), TAB ? DSC_OCC_TAB : DSC_OCC) void k_desc
                         safe &= (q0 > 1e-3f) & (q0 < lim0) & (q1 > 1e-3f) & (q1 < lim1) & (q2 > 1e-3f) & (q2 < lim2);
                         n0 = min(max(n0, 0), F.nx - 1); n1 = min(max(n1, 0), F.ny - 1); n2 = min(max(n2, 0), F.nz - 1);
                     }
-                    const unsigned at = mad_u24(mad_u24((unsigned)n0, (unsigned)F.ny, (unsigned)n1), (unsigned)F.nz, (unsigned)n2);      // nx ny < 2^24 (checked at allocation)
+                    // (a border row's voxel is clamped into the grid above, BEFORE it is split into brick and offset: padding is never read as data)
+                    const unsigned at = TAB ? mad_tex4_index(F, (unsigned)n0, (unsigned)n1, (unsigned)n2)
+                                            : mad_u24(mad_u24((unsigned)n0, (unsigned)F.ny, (unsigned)n1), (unsigned)F.nz, (unsigned)n2);      // nx ny < 2^24 (checked at allocation)
                     if (TAB) { qi[i] = at; q4[i] = DSC_TEX4(at); }
                     else t[i] = F.tex[at];
                     if (!CARRY) unsure |= safe ? 0u : (1u << UBIT(i));
@@ -1133,7 +1149,7 @@ __global__ __launch_bounds__(DSC_NT(S), TAB ? DSC_OCC_TAB : DSC_OCC) void k_desc
 #pragma unroll
                 for (int i = 0; i < PS; i++)
                     if (unsure & (1u << UBIT(i))) {
-                        const unsigned at = exact_index(pass * PS + i, &oob);
+                        const unsigned at = exact_index(pass * PS + i, &oob, std::integral_constant<bool, TAB>());
                         if (TAB) { qi[i] = at; q4[i] = DSC_TEX4(at); }
                         else t[i] = F.tex[at];
                     }
@@ -1244,7 +1260,7 @@ __global__ __launch_bounds__(DSC_NT(S), TAB ? DSC_OCC_TAB : DSC_OCC) void k_desc
         if (active)
             for (int i = 0; i < S; i++) {      // not unrolled: indices again from the float64 expression
                 bool none = false;
-                const float4 tx = F.tex[exact_index(i, &none)];
+                const float4 tx = F.tex[exact_index(i, &none, std::false_type())];
                 if (tx.w < 1e-5f) continue;
                 atomicAdd(&hist[(sub_of_jk<S, NSUB>(j, k) + sub_of_i<S, NSUB>(i)) * Z + describe_exact(exactp, tx, Rrow)], 1);
             }
@@ -1254,7 +1270,7 @@ __global__ __launch_bounds__(DSC_NT(S), TAB ? DSC_OCC_TAB : DSC_OCC) void k_desc
         const float f0 = (float)Rrow[0], f1 = (float)Rrow[1], f2 = (float)Rrow[2], f3 = (float)Rrow[3], f4 = (float)Rrow[4], f5 = (float)Rrow[5],
                     f6 = (float)Rrow[6], f7 = (float)Rrow[7], f8 = (float)Rrow[8];
         for (int e = tid; e < nq; e += NT) {
-            const float4 tx = F.tex[qidx[e]];
+            const float4 tx = F.tex[mad_tex4_voxel(F, qidx[e])];      // the queue holds tex4 (brick) indices; tex is linear
             if (tx.w < 1e-5f) continue;      // (cannot happen for a queued sample: such texels carry flag 3; kept for symmetry with the slow path)
             const float inv = __builtin_amdgcn_rcpf(fmaxf(tx.w, 1e-30f));
             const float gx = tx.x * inv, gy = tx.y * inv, gz = tx.z * inv;
