@@ -314,7 +314,9 @@ int mad_set_batching(mad_ctx *ctx, int on);
  * soon as its running upper bound falls below the k-th lower bound of the first batch.  "pose_split_min": that first batch
  * holds at least this many pairs (default 4096) and at least 64 k.  "ori_queue" / "dsc_queue": entries in use of the queues through
  * which k_orient / k_describe hand the directions their fast classifiers cannot decide to the exact one (defaults: all 512 / 768);
- * a small value drives the kernels' full-queue paths for every anchor / row -- a test hook, the results are the same. */
+ * a small value drives the kernels' full-queue paths for every anchor / row -- a test hook, the results are the same.  "fft_bpt"
+ * (0 default, 1, 2, 4): butterflies per thread of k_fft_lines, i.e. which of its three forms mad_map_fft / mad_map_fsc launch (by
+ * default 1 up to N = 256, 2 at 512, 4 at 1024; a value below that is raised to it) -- a test hook, the bits are the same. */
 int mad_set_option(mad_ctx *ctx, const char *name, double value);
 
 /*
@@ -555,6 +557,40 @@ int mad_map_smooth(mad_ctx *ctx, const float *grid, const int32_t dims[3], doubl
 int mad_map_segment(mad_ctx *ctx, const float *grid, const int32_t dims[3], double threshold, int32_t steps, double step,
                     int64_t stop_at, int32_t *labels, int64_t *root, float *peak, int64_t *size, int32_t *group, int64_t cap,
                     int64_t *n_regions, int64_t *history, int32_t *steps_done);
+
+/*
+ * Fourier shell correlation of two maps, and the 3-D transform under it (mad_fourier.hip; restated with numpy
+ * in mad_amd/fourier.py).  Host pointers, synchronous, nothing modified but the outputs.  grid1, grid2: float32 [x][y][z] with
+ * their dims and origins (Angstrom, centre of voxel (0,0,0)) and the common spacing voxsp.
+ *   Lattice.  Per axis d = origin2 / voxsp - origin1 / voxsp, s = round(d) (half to even, mad_map_mask's expression), delta = d - s
+ *     in [-0.5, 0.5].  The lattice begins min(0, s) voxels from grid 1's origin: voxel (0,0,0) of grid 1 has lattice index -min(0, s),
+ *     that of grid 2 s - min(0, s).  N is the smallest power of two >= the extent of the union box on every axis, 8 <= N <= 1024.
+ *     The lattice is complex128 [N][N][N]: grid 1 in the real part, grid 2 in the imaginary part, zero elsewhere.
+ *   Transform.  Z(k) = sum over the lattice of (g1 + i g2)(n) exp(-2 pi i k.n / N), unnormalised, float64 throughout (radix-4
+ *     Stockham passes along z, y, x; twiddles from a host table; the same input gives the same bits every run).
+ *   Shells.  F1(k) = (Z(k) + conj Z(-k)) / 2, F2(k) = (Z(k) - conj Z(-k)) / (2i), -k taken modulo N per axis.  Lattice index a stands
+ *     for the frequency i = a (a < N / 2) or a - N; the shell of (i, j, k) is floor(sqrt(i*i + j*j + k*k) + 0.5); shells 0 .. N / 2
+ *     are kept, the corners beyond are dropped.  Per shell: sums[3 s] = P1 = sum |F1|^2, sums[3 s + 1] = P2 = sum |F2|^2,
+ *     sums[3 s + 2] = C = sum Re(F1 conj(F2 phi)), phi = (phi_x[a] phi_y[b]) phi_z[c], phi_x[a] = exp(-2 pi i (i delta_x) / N)
+ *     (cos and sin of 2 pi (i delta_x) / N with the host's libm); count[s] = the lattice points of the shell.  The sums are added in
+ *     a fixed order without floating-point atomics: the same call gives the same bits alone or after any other call.
+ * mad_map_fsc writes *N_out (may be NULL), sums [(N / 2 + 1)][3] and count [N / 2 + 1]; cap_shells = the shells both hold: with
+ * cap_shells < N / 2 + 1 the call returns MAD_ENOSPC with *N_out set and nothing else written.  It allocates the N^3 x 16 byte lattice
+ * for the call and frees it.
+ * mad_map_fft (a diagnostic, like mad_field_download) returns Z: spectrum = N^3 complex128, interleaved (re, im), [x][y][z].  grid2
+ * may be NULL (dims2, origin2 are then ignored): grid 1 alone, N from its dims.  spectrum NULL: only *N_out is written (the size to
+ * allocate), nothing is launched.
+ * MAD_EINVAL: NULL, a dimension < 1, voxsp <= 0 or not finite, an origin that is not finite (or 1e15 voxels and more from 0), a grid
+ * of 2^32 voxels or more.  MAD_EDOM: a union box longer than 1024 voxels on an axis.  MAD_ENOMEM: less free device memory than the
+ * lattice, the grids and the tables need (judged before anything is allocated), or the allocation fails.  Each leaves the outputs
+ * untouched (but *N_out with MAD_ENOSPC), launches nothing, and the next call works.
+ */
+int mad_map_fsc(mad_ctx *ctx, const float *grid1, const int32_t dims1[3], const double origin1[3],
+                const float *grid2, const int32_t dims2[3], const double origin2[3], double voxsp,
+                int32_t *N_out, double *sums /* [N / 2 + 1][3]: P1, P2, C */, int64_t *count /* [N / 2 + 1] */, int64_t cap_shells);
+int mad_map_fft(mad_ctx *ctx, const float *grid1, const int32_t dims1[3], const double origin1[3],
+                const float *grid2 /* may be NULL */, const int32_t dims2[3], const double origin2[3], double voxsp,
+                int32_t *N_out, double *spectrum /* N^3 complex128, interleaved; NULL: size query */);
 
 /* ---- one subunit's pair grid sharded over GPUs by blocks of map rows (the exchange steps -- OR of the flag vectors,
  *      all-gather of the per-shard top-k -- are the caller's, mad_amd/dist.py::sharded_match, or the library's own:

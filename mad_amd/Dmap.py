@@ -10,7 +10,9 @@ is the structure-against-map half: it keeps the density within a radius of a str
 so that the remaining subunits can be docked into what is left of a map.  `smooth` applies a Gaussian through `mad_map_smooth` and
 `segment` cuts the map into segments through `mad_map_segment` (watershed regions grouped by smoothing, the scheme of Segger; no
 counterpart in the reference), which is where the masks `mask_with` consumes come from.  `fit_by_group` scores a placed model per residue, chain or other group
-of atoms against the map through `mad_map_group_fit` (localfit.py; no counterpart in the reference).  None of them has a CPU fallback.  The reference's per-voxel text writer is replaced by `mapio.write_situs`.
+of atoms against the map through `mad_map_group_fit` (localfit.py; no counterpart in the reference).  `fsc` is the Fourier shell
+correlation of the map against a second map or a placed model through `mad_map_fsc` (fourier.py; no counterpart in the reference).
+None of them has a CPU fallback.  The reference's per-voxel text writer is replaced by `mapio.write_situs`.
 """
 import os
 import sys
@@ -189,6 +191,39 @@ class Dmap(object):
         both.  `self` is not modified.  DESIGN.md section 4k has the exact contract."""
         from . import localfit
         return localfit.fit_by_group(self, structure, resolution, by=by, radius=radius, isovalue=isovalue, model=model, masses=masses)
+
+    def fsc(self, other, resolution=None, masses=None):
+        """Fourier shell correlation of this map against `other` -> `fourier.FSC` (freq, fsc, n, power1, power2, `resolution()`,
+        `write_csv()`).  `other`: a `Dmap` of the same spacing (half map against half map; `resample(like=...)` first where the
+        spacings differ), a (grid, (x0, y0, z0)) pair on this map's spacing, or a placed model -- a `PDB`, an (n, 3) array, or a
+        list / tuple of those -- whose density is simulated at `resolution` on this map's spacing (masses as in `fit_by_group`).
+        The two grids need not share a lattice: whole voxels of offset place them, the rest goes into a phase ramp.  No mask, no
+        soft edge (`zone(soft=...)` or `mask_with` first); neither map is modified.  DESIGN.md section 4l has the exact contract."""
+        from . import fourier, localfit
+        voxsp = float(self.voxsp)
+        if isinstance(other, Dmap):
+            if other.voxsp != self.voxsp:
+                raise ValueError("Dmap.fsc: voxsp differ (%r vs %r): bring one map onto the other's lattice with resample(like=...) first"
+                                 % (self.voxsp, other.voxsp))
+            g2, o2 = other.grid3d, (other.xi, other.yi, other.zi)
+        elif isinstance(other, (list, tuple)) and len(other) == 2 and np.ndim(other[0]) == 3:
+            g2, o2 = other
+        else:
+            if resolution is None or not (float(resolution) > 0) or not np.isfinite(float(resolution)):
+                raise ValueError("Dmap.fsc: a model needs the resolution to simulate its density at (positive and finite), got %r" % (resolution,))
+            parts = localfit.structure_parts(other)
+            m = localfit.structure_masses(parts, masses)
+            if sum(len(c) for c, _, _ in parts) == 0:
+                raise ValueError("Dmap.fsc: no atoms to simulate a density from")
+            coords = np.concatenate([c for c, _, _ in parts], axis=0)
+            g2, x0, y0, z0 = _lib.get_lib().structure_to_density(coords, m, float(resolution), voxsp)
+            o2 = (x0, y0, z0)
+        g1 = np.ascontiguousarray(self.grid3d, dtype=np.float32)
+        g2 = np.ascontiguousarray(g2, dtype=np.float32)
+        if g2.ndim != 3:
+            raise ValueError("Dmap.fsc: the second grid has %d dimensions" % g2.ndim)
+        N, sums, count = _lib.get_lib().map_fsc(g1, (self.xi, self.yi, self.zi), g2, o2, voxsp)
+        return fourier.FSC(N, voxsp, sums, count)
 
     def smooth(self, sigma):
         """A Gaussian of `sigma` Angstrom on the map, in place (zero beyond the box, float64 inside, 4 sigma wide on either side).

@@ -39,7 +39,7 @@ SYMBOLS = [
     "mad_dist_unique_id", "mad_dist_init", "mad_dist_destroy", "mad_dist_info", "mad_dist_rehearse_flags", "mad_dist_or_allreduce", "mad_dist_allgather",
     "mad_dist_allgather_topk", "mad_dist_scratch", "mad_dist_copy",
     "mad_set_wire_bytes", "mad_set_export", "mad_set_import", "mad_set_lane", "mad_set_stream", "mad_set_bind_lane",
-    "mad_upload_density", "mad_refine", "mad_last_refine_plan", "mad_last_density_chunks", "mad_structure_to_density", "mad_ccc", "mad_map_mask", "mad_map_ccc", "mad_map_resample", "mad_map_zone", "mad_map_group_fit", "mad_map_smooth", "mad_map_segment", "mad_density_ccc", "mad_dock_refine_score", "mad_grid_overlap", "mad_overlap_matrix",
+    "mad_upload_density", "mad_refine", "mad_last_refine_plan", "mad_last_density_chunks", "mad_structure_to_density", "mad_ccc", "mad_map_mask", "mad_map_ccc", "mad_map_resample", "mad_map_zone", "mad_map_group_fit", "mad_map_smooth", "mad_map_segment", "mad_map_fsc", "mad_map_fft", "mad_density_ccc", "mad_dock_refine_score", "mad_grid_overlap", "mad_overlap_matrix",
     "mad_space_create", "mad_space_destroy", "mad_space_build", "mad_space_info", "mad_space_download",
     "mad_space_peaks", "mad_space_patches", "mad_space_localize", "mad_localize_volume",
     "mad_pose_cluster_many",
@@ -1169,6 +1169,43 @@ class Lib(object):
         out = np.empty(tuple(int(v) for v in md) if 0 < n_out < 2 ** 32 else (0,), np.float32)      # (a refused call writes nothing)
         self._chk(self.dll.mad_map_resample(self.ctx, _p(g), _p(d), _p(o), C.c_double(voxsp), None if Rp is None else _p(Rp),
                                             None if Tp is None else _p(Tp), C.c_int(order), _p(md), _p(p), C.c_double(out_voxsp), _p(out)))
+        return out
+
+    @staticmethod
+    def _fourier_args(who, g1, o1, g2, o2):
+        for g in (g1, g2):
+            if g is None:
+                continue
+            if g.dtype != np.float32 or not g.flags.c_contiguous:
+                raise ValueError("%s needs C-contiguous float32 grids" % who)
+            if g.ndim != 3:
+                raise ValueError("%s needs 3-D grids" % who)
+        d1, o1 = np.array(g1.shape, np.int32), _c(np.asarray(o1, np.float64).reshape(3), np.float64)
+        d2 = None if g2 is None else np.array(g2.shape, np.int32)
+        o2 = None if g2 is None else _c(np.asarray(o2, np.float64).reshape(3), np.float64)
+        return d1, o1, d2, o2
+
+    def map_fsc(self, g1, o1, g2, o2, voxsp):
+        """Fourier shell correlation sums of two maps of one spacing -> (N, sums float64 [N / 2 + 1, 3] = P1, P2, C per shell,
+        count int64 [N / 2 + 1]) (mad_map_fsc; `fourier.FSC(N, voxsp, sums, count)` makes the curve).
+        Both grids C-contiguous float32 [x, y, z]; neither is modified."""
+        d1, o1, d2, o2 = self._fourier_args("map_fsc", g1, o1, g2, o2)
+        cap = 1024 // 2 + 1
+        n, sums, count = C.c_int32(0), np.zeros((cap, 3), np.float64), np.zeros(cap, np.int64)
+        self._chk(self.dll.mad_map_fsc(self.ctx, _p(g1), _p(d1), _p(o1), _p(g2), _p(d2), _p(o2), C.c_double(voxsp), C.byref(n),
+                                       _p(sums), _p(count), C.c_int64(cap)))
+        sh = n.value // 2 + 1
+        return int(n.value), sums[:sh].copy(), count[:sh].copy()
+
+    def map_fft(self, g1, o1, g2=None, o2=None, voxsp=1.0):
+        """The transform `map_fsc` works on, for testing it alone -> complex128 [N, N, N]: the FFT of the lattice that holds `g1`
+        in the real and `g2` (may be None) in the imaginary part (mad_map_fft)."""
+        d1, o1, d2, o2 = self._fourier_args("map_fft", g1, o1, g2, o2)
+        args = (self.ctx, _p(g1), _p(d1), _p(o1), _p(g2), _p(d2), _p(o2), C.c_double(voxsp))
+        n = C.c_int32(0)
+        self._chk(self.dll.mad_map_fft(*args, C.byref(n), None))
+        out = np.empty((n.value,) * 3, np.complex128)
+        self._chk(self.dll.mad_map_fft(*args, C.byref(n), _p(out)))
         return out
 
     def map_zone(self, g, origin, voxsp, atoms, radius, soft=0.0, erase=False):

@@ -174,7 +174,7 @@ struct DevBuf {
 };
 
 enum { MAD_T_ORIENT = 0, MAD_T_DESCRIBE, MAD_T_CORRELATE, MAD_T_PAIRS, MAD_T_POSE, MAD_T_TOPK, MAD_T_REFINE,
-       MAD_T_DENSITY, MAD_T_CCC, MAD_T_SEG_PARENT, MAD_T_SEG_JUMP, MAD_T_SEG_SCAN, MAD_T_SEG_SMOOTH, MAD_T_COUNT };
+       MAD_T_DENSITY, MAD_T_CCC, MAD_T_SEG_PARENT, MAD_T_SEG_JUMP, MAD_T_SEG_SCAN, MAD_T_SEG_SMOOTH, MAD_T_FFT, MAD_T_FSC, MAD_T_COUNT };
 
 #define MAD_T_RING 32
 #define MAD_LANES 8
@@ -300,6 +300,10 @@ struct mad_ctx {
     // mad_dist_* (mad_dist.hip): the communicator, and the grow-only device buffers mad_dist_scratch hands out, per lane
     void *dist = nullptr;
     DevBuf dist_buf[MAD_LANES][MAD_DIST_BUFS];
+    // mad_fourier.hip: the twiddles exp(-2 pi i k / N), k < N, of the lattice edge they were last built for (uploaded once per N)
+    DevBuf fft_tw;
+    int fft_tw_n = 0;
+    int fft_bpt = 0;      // test hook (mad_set_option "fft_bpt"): 1, 2 or 4 forces that k_fft_lines form, 0 = by N
 };
 
 // Wide rows (descriptor radius >= MAD_WIDE_FROM_R: a sub-region holds 6^3 = 216 samples, more than an int8 count).  The int8

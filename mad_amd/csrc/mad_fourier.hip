@@ -1,0 +1,489 @@
+// mad_fourier.hip -- Fourier shell correlation of two maps (mad_map_fsc) and the 3-D transform under it (mad_map_fft).
+// DESIGN.md section 4l has the contract; mad_amd/fourier.py restates it with numpy.
+//
+// Both float32 grids go onto ONE cubic complex128 lattice of edge N (a power of two, 8 .. 1024): grid 1 in the real part, grid 2
+// in the imaginary part, zero elsewhere (k_fft_pack).  Three passes of in-place 1-D transforms (k_fft_lines, one form per axis)
+// give Z = FFT(g1 + i g2); k_fsc_shells separates the two spectra, F1(k) = (Z(k) + conj Z(-k)) / 2 and
+// F2(k) = (Z(k) - conj Z(-k)) / (2i), and sums |F1|^2, |F2|^2 and Re(F1 conj(F2 phi)) per shell; k_fsc_sum adds the workgroups'
+// tables.  All arithmetic is float64 without fused multiply-adds; no FFT library is linked.
+//
+// k_fft_lines.  A workgroup transforms a TILE of FFT_L = 8 lines of length N held in LDS.  For the x and y passes the eight lines
+// are eight neighbouring z, so that every global access is a full 128-byte piece (8 complex128); for the z pass they are eight
+// neighbouring y, one contiguous run of 8 N elements.  The LDS image is [n][line] with a row of ROW elements: element n of a line
+// sits next to element n of the neighbouring lines, a butterfly's lanes run over the line index first, and eight lanes always
+// touch 128 contiguous bytes -- whatever power of two separates the n of two lanes, it never separates their banks.  ROW = 8 does
+// that for the x and y passes.  In the z pass the tile is FILLED along n (lane k writes row k): with ROW = 8 the eight lanes of a
+// 16-byte store group would all land on the same four banks, so its rows are padded to ROW = 9 elements (row k begins k * 144 bytes
+// in: eight consecutive rows begin on eight different 16-byte slots of the 128-byte store window).
+// The transform is a radix-4 Stockham scheme (decimation in frequency; autosort, no bit reversal) with one radix-2 stage at the
+// end when log2 N is odd.  A stage reads butterfly j's inputs at j + k N / 4 (k = 0 .. 3), the same places in every stage, and
+// writes its outputs at q + s (4 p + k) with j = p s + q, s = 4^stage.  Instead of a second LDS image every thread takes all the
+// inputs of its BPT butterflies into registers, the workgroup meets at a barrier, and then the outputs go back into the same
+// image: a tile of 8 x 1024 is 128 KiB (144 KiB padded) and fits the CU's 160 KiB once, not twice.
+// Twiddles exp(-2 pi i k / N) come from a table the host computes (angles reduced exactly to the first octant before cos / sin),
+// uploaded once per N; w, w^2 and w^3 are three table reads, not products.  The order of every sum is fixed by the indices alone:
+// the same input gives the same bits every run.
+//
+// k_fsc_shells.  A wave takes a brick of 2 x 4 x 8 lattice points (8 along z: 128-byte pieces of Z(k); Z(-k) is the mirrored
+// brick).  A brick spans at most 9 shells: the lanes leave their terms in the wave's staging rows in LDS, lane 16 q + d adds those
+// of shell smin + d among lanes 16 q .. 16 q + 15 in lane order, and lane d adds the four quarters in order into the WAVE's own
+// table in LDS (no cross-lane shuffles: sixteen broadcast reads per lane).  Waves take bricks in a fixed order, a workgroup adds
+// its four tables in order into its slot of the partial tables, and k_fsc_sum adds the slots in order: no floating-point
+// atomics anywhere, the same bits every run.
+#include <algorithm>
+#include <vector>
+
+#include "mad_common.h"
+
+#define FFT_L 8                 // lines per tile
+#define FFT_MIN_N 8
+#define FFT_MAX_N 1024
+#define FFT_MAX_THREADS 512
+#define FSC_THREADS 256
+#define FSC_MAX_WGS 1024        // partial tables (fewer when the lattice has fewer than 4 bricks per workgroup)
+
+// ---------------------------------------------------------------------------
+// the lattice
+// ---------------------------------------------------------------------------
+
+struct PackArgs {
+    const float *g1, *g2;       // g2 may be NULL
+    int d1[3], d2[3];
+    int p1[3], p2[3];           // lattice index of voxel (0, 0, 0) of either grid
+    int logN;
+};
+
+__global__ __launch_bounds__(256) void k_fft_pack(const PackArgs A, double2 *__restrict__ Z) {
+    const int logN = A.logN;
+    const unsigned m = (1u << logN) - 1u;
+    const size_t n = (size_t)1 << (3 * logN);
+    for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (size_t)gridDim.x * 256) {
+        const unsigned c = (unsigned)i & m, b = (unsigned)(i >> logN) & m, a = (unsigned)(i >> (2 * logN));
+        double2 v = make_double2(0.0, 0.0);
+        const unsigned x1 = a - (unsigned)A.p1[0], y1 = b - (unsigned)A.p1[1], z1 = c - (unsigned)A.p1[2];      // below the start: wraps past any extent
+        if (x1 < (unsigned)A.d1[0] && y1 < (unsigned)A.d1[1] && z1 < (unsigned)A.d1[2])
+            v.x = (double)A.g1[((size_t)x1 * A.d1[1] + y1) * A.d1[2] + z1];
+        if (A.g2) {
+            const unsigned x2 = a - (unsigned)A.p2[0], y2 = b - (unsigned)A.p2[1], z2 = c - (unsigned)A.p2[2];
+            if (x2 < (unsigned)A.d2[0] && y2 < (unsigned)A.d2[1] && z2 < (unsigned)A.d2[2])
+                v.y = (double)A.g2[((size_t)x2 * A.d2[1] + y2) * A.d2[2] + z2];
+        }
+        Z[i] = v;
+    }
+}
+
+// ---------------------------------------------------------------------------
+// 1-D transforms
+// ---------------------------------------------------------------------------
+
+__device__ __forceinline__ double2 c_add(double2 a, double2 b) { return make_double2(a.x + b.x, a.y + b.y); }
+__device__ __forceinline__ double2 c_sub(double2 a, double2 b) { return make_double2(a.x - b.x, a.y - b.y); }
+__device__ __forceinline__ double2 c_mul(double2 a, double2 b) { return make_double2(a.x * b.x - a.y * b.y, a.x * b.y + a.y * b.x); }
+__device__ __forceinline__ double2 c_muli(double2 a) { return make_double2(-a.y, a.x); }      // i a
+
+// AXIS 0 / 1 / 2: lines along x / y / z.  One workgroup per tile, N^2 / 8 tiles; blockDim.x * BPT = max(2 N, 64) butterflies of a
+// radix-4 stage (a thread of the smallest lattices may have none).  Dynamic LDS: N * ROW * 16 bytes.
+template <int AXIS, int BPT>
+__global__ __launch_bounds__(FFT_MAX_THREADS) void k_fft_lines(double2 *__restrict__ Z, const double2 *__restrict__ tw, int logN) {
+    extern __shared__ __attribute__((aligned(16))) double2 fft_img[];
+    constexpr int ROW = AXIS == 2 ? FFT_L + 1 : FFT_L;
+    const int N = 1 << logN, T = (int)blockDim.x, t = (int)threadIdx.x;
+    const int tile = (int)blockIdx.x;
+    size_t base, sN, sL;
+    if (AXIS == 2) {
+        base = (size_t)tile * FFT_L << logN; sN = 1; sL = (size_t)N;
+    } else {
+        const size_t z0 = (size_t)(tile & ((N >> 3) - 1)) << 3, u = (size_t)(tile >> (logN - 3));
+        if (AXIS == 0) { base = (u << logN) + z0; sN = (size_t)N << logN; }      // u = y
+        else { base = (u << (2 * logN)) + z0; sN = (size_t)N; }                    // u = x
+        sL = 1;
+    }
+    const int E = FFT_L << logN;
+#pragma unroll 4
+    for (int e = t; e < E; e += T) {
+        const int n = AXIS == 2 ? (e & (N - 1)) : (e >> 3), l = AXIS == 2 ? (e >> logN) : (e & 7);
+        fft_img[n * ROW + l] = Z[base + (size_t)n * sN + (size_t)l * sL];
+    }
+    __syncthreads();
+    const int quarter = N >> 2, nb = 2 * N;      // butterflies of a radix-4 stage in the tile
+    int len = N, ls = 0;
+    for (; len >= 4; len >>= 2, ls += 2) {
+        const int s = 1 << ls;
+        double2 r[BPT][4];
+#pragma unroll
+        for (int i = 0; i < BPT; i++) {
+            const int bi = i * T + t;
+            if (bi < nb) {
+                const int l = bi & 7, j = bi >> 3;
+#pragma unroll
+                for (int k = 0; k < 4; k++) r[i][k] = fft_img[(j + k * quarter) * ROW + l];
+            }
+        }
+        __syncthreads();
+#pragma unroll
+        for (int i = 0; i < BPT; i++) {
+            const int bi = i * T + t;
+            if (bi < nb) {
+                const int l = bi & 7, j = bi >> 3, q = j & (s - 1), ps = j - q;      // ps = p s: the twiddle of p / len is tw[p s]
+                const double2 w1 = tw[ps], w2 = tw[2 * ps], w3 = tw[3 * ps];
+                const double2 apc = c_add(r[i][0], r[i][2]), amc = c_sub(r[i][0], r[i][2]);
+                const double2 bpd = c_add(r[i][1], r[i][3]), jbmd = c_muli(c_sub(r[i][1], r[i][3]));
+                const int o = q + 4 * ps;
+                fft_img[o * ROW + l] = c_add(apc, bpd);
+                fft_img[(o + s) * ROW + l] = c_mul(w1, c_sub(amc, jbmd));
+                fft_img[(o + 2 * s) * ROW + l] = c_mul(w2, c_sub(apc, bpd));
+                fft_img[(o + 3 * s) * ROW + l] = c_mul(w3, c_add(amc, jbmd));
+            }
+        }
+        __syncthreads();
+    }
+    if (len == 2) {      // log2 N odd: one radix-2 stage, every pair read and written by one thread
+        const int half = N >> 1;
+#pragma unroll
+        for (int i = 0; i < 2 * BPT; i++) {
+            const int bi = i * T + t;
+            if (bi < 2 * nb) {
+                const int l = bi & 7, j = bi >> 3;
+                const double2 a = fft_img[j * ROW + l], b = fft_img[(j + half) * ROW + l];
+                fft_img[j * ROW + l] = c_add(a, b);
+                fft_img[(j + half) * ROW + l] = c_sub(a, b);
+            }
+        }
+        __syncthreads();
+    }
+#pragma unroll 4
+    for (int e = t; e < E; e += T) {
+        const int n = AXIS == 2 ? (e & (N - 1)) : (e >> 3), l = AXIS == 2 ? (e >> logN) : (e & 7);
+        Z[base + (size_t)n * sN + (size_t)l * sL] = fft_img[n * ROW + l];
+    }
+}
+
+// ---------------------------------------------------------------------------
+// shells
+// ---------------------------------------------------------------------------
+
+// part_f [workgroup][shell][3] = P1, P2, C; part_i [workgroup][shell] = lattice points.  Dynamic LDS: 4 waves x (N / 2 + 1) shells
+// x (3 doubles + 1 int), besides 14 KiB of static staging rows.  phi [3][N]: the phase ramp per axis.
+__global__ __launch_bounds__(FSC_THREADS) void k_fsc_shells(const double2 *__restrict__ Z, const double2 *__restrict__ phi, int logN,
+                                                            double *__restrict__ part_f, long long *__restrict__ part_i) {
+    extern __shared__ __attribute__((aligned(16))) double fsc_tab[];
+    // staging rows per wave: every lane's three terms and shell, then the sums of the four quarters of the wave per shell offset
+    __shared__ double st_v[FSC_THREADS / MAD_WAVE][MAD_WAVE][3], st_p[FSC_THREADS / MAD_WAVE][4][16][3];
+    __shared__ int st_s[FSC_THREADS / MAD_WAVE][MAD_WAVE], st_n[FSC_THREADS / MAD_WAVE][4][16];
+    const int N = 1 << logN, SH = (N >> 1) + 1, W = FSC_THREADS / MAD_WAVE;
+    double *acc = fsc_tab;                          // [W][SH][3]
+    int *cnt = (int *)(fsc_tab + W * SH * 3);       // [W][SH]
+    for (int i = threadIdx.x; i < W * SH * 3; i += FSC_THREADS) acc[i] = 0.0;
+    for (int i = threadIdx.x; i < W * SH; i += FSC_THREADS) cnt[i] = 0;
+    __syncthreads();
+    const int lane = (int)lane_id(), w = (int)(threadIdx.x >> 6);
+    double *my_acc = acc + (size_t)w * SH * 3;
+    int *my_cnt = cnt + w * SH;
+    const size_t n_brick = (size_t)1 << (3 * logN - 6);
+    const unsigned m = (unsigned)N - 1u;
+    for (size_t br = (size_t)blockIdx.x * W + w; br < n_brick; br += (size_t)gridDim.x * W) {
+        const unsigned bc = (unsigned)br & ((unsigned)(N >> 3) - 1u), bb = (unsigned)(br >> (logN - 3)) & ((unsigned)(N >> 2) - 1u);
+        const unsigned ba = (unsigned)(br >> (2 * logN - 5));
+        const unsigned a = 2u * ba + (unsigned)(lane >> 5), b = 4u * bb + (unsigned)((lane >> 3) & 3), c = 8u * bc + (unsigned)(lane & 7);
+        const unsigned ma = (N - a) & m, mb = (N - b) & m, mc = (N - c) & m;
+        const double2 z = Z[(((((size_t)a) << logN) + b) << logN) + c], zm = Z[(((((size_t)ma) << logN) + mb) << logN) + mc];
+        const double f1x = (z.x + zm.x) * 0.5, f1y = (z.y - zm.y) * 0.5;      // (Z(k) + conj Z(-k)) / 2
+        const double f2x = (z.y + zm.y) * 0.5, f2y = (zm.x - z.x) * 0.5;      // (Z(k) - conj Z(-k)) / (2i)
+        const double2 ph = c_mul(c_mul(phi[a], phi[N + b]), phi[2 * N + c]);
+        const double2 g = c_mul(make_double2(f2x, f2y), ph);
+        double p1 = f1x * f1x + f1y * f1y, p2 = f2x * f2x + f2y * f2y, cr = f1x * g.x + f1y * g.y;      // Re(F1 conj(F2 phi))
+        const int fi = (int)a < (N >> 1) ? (int)a : (int)a - N, fj = (int)b < (N >> 1) ? (int)b : (int)b - N, fk = (int)c < (N >> 1) ? (int)c : (int)c - N;
+        const int r2 = fi * fi + fj * fj + fk * fk;
+        int sh = (int)(sqrt((double)r2) + 0.5);      // floor(sqrt(r2) + 0.5) = the t with t^2 - t < r2 <= t^2 + t, fixed up in integers
+        while (sh * sh + sh < r2) sh++;
+        while (sh > 0 && sh * sh - sh >= r2) sh--;
+        // The brick's terms by shell, through the wave's staging rows in LDS (a wave's LDS operations complete in order: what its
+        // lanes stored is what its lanes read next; no other wave touches these rows).  The shells of a brick lie within 8 of the
+        // smallest (its diagonal is sqrt(1 + 9 + 49) < 8 frequencies long).  Lane 16 q + d adds, for shell smin + d, the terms of
+        // lanes 16 q .. 16 q + 15 in lane order; lane d < 16 then adds the four quarters in order and the sum goes into the table.
+        const int smin = -wave_max_i32(-sh);
+        st_v[w][lane][0] = p1; st_v[w][lane][1] = p2; st_v[w][lane][2] = cr;
+        st_s[w][lane] = sh < SH ? sh : -1;      // the lattice corners beyond N / 2 are dropped
+        __builtin_amdgcn_wave_barrier();
+        const int d = lane & 15, q = lane >> 4, mine = smin + d;
+        double a1 = 0.0, a2 = 0.0, a3 = 0.0;
+        int an = 0;
+#pragma unroll
+        for (int e = 0; e < 16; e++) {
+            const bool hit = st_s[w][16 * q + e] == mine;
+            a1 += hit ? st_v[w][16 * q + e][0] : 0.0;
+            a2 += hit ? st_v[w][16 * q + e][1] : 0.0;
+            a3 += hit ? st_v[w][16 * q + e][2] : 0.0;
+            an += hit ? 1 : 0;
+        }
+        st_p[w][q][d][0] = a1; st_p[w][q][d][1] = a2; st_p[w][q][d][2] = a3;
+        st_n[w][q][d] = an;
+        __builtin_amdgcn_wave_barrier();
+        if (lane < 16 && mine < SH) {
+            const int n = st_n[w][0][d] + st_n[w][1][d] + st_n[w][2][d] + st_n[w][3][d];
+            if (n) {
+                my_acc[mine * 3] += ((st_p[w][0][d][0] + st_p[w][1][d][0]) + st_p[w][2][d][0]) + st_p[w][3][d][0];
+                my_acc[mine * 3 + 1] += ((st_p[w][0][d][1] + st_p[w][1][d][1]) + st_p[w][2][d][1]) + st_p[w][3][d][1];
+                my_acc[mine * 3 + 2] += ((st_p[w][0][d][2] + st_p[w][1][d][2]) + st_p[w][2][d][2]) + st_p[w][3][d][2];
+                my_cnt[mine] += n;
+            }
+        }
+        __builtin_amdgcn_wave_barrier();
+    }
+    __syncthreads();
+    for (int i = threadIdx.x; i < SH * 3; i += FSC_THREADS)
+        part_f[(size_t)blockIdx.x * SH * 3 + i] = ((acc[i] + acc[SH * 3 + i]) + acc[2 * SH * 3 + i]) + acc[3 * SH * 3 + i];
+    for (int i = threadIdx.x; i < SH; i += FSC_THREADS)
+        part_i[(size_t)blockIdx.x * SH + i] = (long long)cnt[i] + cnt[SH + i] + cnt[2 * SH + i] + cnt[3 * SH + i];
+}
+static_assert(FSC_THREADS == 4 * MAD_WAVE, "k_fsc_shells adds four wave tables");
+
+// out_f [shell][3], out_i [shell]: the workgroups' slots added in order, one thread per number
+__global__ __launch_bounds__(256) void k_fsc_sum(int n_part, int SH, const double *__restrict__ part_f, const long long *__restrict__ part_i,
+                                                 double *__restrict__ out_f, long long *__restrict__ out_i) {
+    const int i = (int)(blockIdx.x * 256 + threadIdx.x);
+    if (i < SH * 3) {
+        double v = 0.0;
+        for (int p = 0; p < n_part; p++) v += part_f[(size_t)p * SH * 3 + i];
+        out_f[i] = v;
+    } else if (i < SH * 4) {
+        long long v = 0;
+        for (int p = 0; p < n_part; p++) v += part_i[(size_t)p * SH + (i - SH * 3)];
+        out_i[i - SH * 3] = v;
+    }
+}
+
+// ---------------------------------------------------------------------------
+// host
+// ---------------------------------------------------------------------------
+
+struct FourierPlan {
+    int N, logN;
+    int p1[3], p2[3];
+    double delta[3];
+};
+
+// cos and sin of 2 pi k / N, the angle reduced exactly (in integers) to [0, pi / 4] first; N a power of two >= 8
+static void unit_root(int k, int N, double *c, double *s) {
+    const int quad = N / 4, q = (k / quad) & 3, m = k % quad;
+    double cm, sm;
+    if (m <= N / 8) { cm = cos(2.0 * M_PI * (double)m / (double)N); sm = sin(2.0 * M_PI * (double)m / (double)N); }
+    else { cm = sin(2.0 * M_PI * (double)(quad - m) / (double)N); sm = cos(2.0 * M_PI * (double)(quad - m) / (double)N); }
+    if (m == 0) { cm = 1.0; sm = 0.0; }
+    switch (q) {
+    case 0: *c = cm; *s = sm; break;
+    case 1: *c = -sm; *s = cm; break;
+    case 2: *c = -cm; *s = -sm; break;
+    default: *c = sm; *s = -cm; break;
+    }
+}
+
+static int fourier_check(mad_ctx *ctx, const char *who, const int32_t d[3], const double o[3], double voxsp) {
+    for (int k = 0; k < 3; k++) {
+        if (d[k] <= 0) return mad_fail(ctx, MAD_EINVAL, "%s: empty grid (%d x %d x %d)", who, d[0], d[1], d[2]);
+        if (!(fabs(o[k]) <= 1.7e308) || !(fabs(o[k] / voxsp) < 1e15)) return mad_fail(ctx, MAD_EINVAL, "%s: origin %g at voxsp %g", who, o[k], voxsp);
+    }
+    const unsigned long long v = (unsigned long long)d[0] * (unsigned long long)d[1];
+    if (v >= (1ull << 32) || v * (unsigned long long)d[2] >= (1ull << 32))
+        return mad_fail(ctx, MAD_EINVAL, "%s: %d x %d x %d voxels: grids of 2^32 voxels or more are not supported", who, d[0], d[1], d[2]);
+    return MAD_OK;
+}
+
+// the placement of fourier.plan_box; d2 / o2 NULL: grid 1 alone
+static int fourier_plan(mad_ctx *ctx, const char *who, const int32_t d1[3], const double o1[3], const int32_t *d2, const double *o2,
+                        double voxsp, FourierPlan *P) {
+    long extent = 0;
+    for (int k = 0; k < 3; k++) {
+        long s = 0;
+        P->delta[k] = 0.0;
+        if (d2) {
+            const double d = o2[k] / voxsp - o1[k] / voxsp;
+            s = py_round(d);
+            P->delta[k] = d - (double)s;
+        }
+        const long lo = s < 0 ? s : 0;
+        const long e1 = (long)d1[k] - lo, e2 = d2 ? (long)d2[k] + s - lo : 0;
+        if (e1 > FFT_MAX_N || e2 > FFT_MAX_N)
+            return mad_fail(ctx, MAD_EDOM, "%s: the union box is %ld voxels long on axis %d, more than %d", who, e1 > e2 ? e1 : e2, k, FFT_MAX_N);
+        P->p1[k] = (int)-lo;
+        P->p2[k] = (int)(s - lo);
+        extent = std::max(extent, std::max(e1, e2));
+    }
+    P->N = FFT_MIN_N; P->logN = 3;
+    while (P->N < extent) { P->N <<= 1; P->logN++; }
+    return MAD_OK;
+}
+
+template <int AXIS, int BPT> static int fft_launch(mad_ctx *ctx, double2 *Z, const double2 *tw, int logN, int threads) {
+    const int N = 1 << logN;
+    const size_t lds = (size_t)N * (AXIS == 2 ? FFT_L + 1 : FFT_L) * sizeof(double2);
+    static bool attr = false;
+    if (!attr) { MAD_HIP(hipFuncSetAttribute((const void *)k_fft_lines<AXIS, BPT>, hipFuncAttributeMaxDynamicSharedMemorySize, FFT_MAX_N * (FFT_L + 1) * 16)); attr = true; }
+    hipLaunchKernelGGL((k_fft_lines<AXIS, BPT>), dim3((unsigned)(N * N / FFT_L)), dim3(threads), lds, ctx->stream, Z, tw, logN);
+    return MAD_OK;
+}
+template <int AXIS> static int fft_axis(mad_ctx *ctx, double2 *Z, const double2 *tw, int logN) {
+    // butterflies per thread: as few as 512 threads allow, or what the test hook asks for where that still fits
+    const int N = 1 << logN, least = N <= 256 ? 1 : (N == 512 ? 2 : 4), bpt = std::max(ctx->fft_bpt, least);
+    const int threads = std::max(2 * N / bpt, MAD_WAVE);
+    if (bpt == 1) return fft_launch<AXIS, 1>(ctx, Z, tw, logN, threads);
+    if (bpt == 2) return fft_launch<AXIS, 2>(ctx, Z, tw, logN, threads);
+    return fft_launch<AXIS, 4>(ctx, Z, tw, logN, threads);
+}
+
+// Validates, plans, allocates the lattice (*Zout, the caller frees it), uploads and transforms.  Nothing is allocated on a refusal.
+static int fourier_transform(mad_ctx *ctx, const char *who, const float *g1, const int32_t *d1, const double *o1, const float *g2,
+                             const int32_t *d2, const double *o2, double voxsp, size_t extra_bytes, FourierPlan *P, double2 **Zout) {
+    *Zout = nullptr;
+    if (!(voxsp > 0) || !(voxsp < 1e15)) return mad_fail(ctx, MAD_EINVAL, "%s: voxsp %g", who, voxsp);
+    MAD_TRY(fourier_check(ctx, who, d1, o1, voxsp));
+    if (g2) MAD_TRY(fourier_check(ctx, who, d2, o2, voxsp));
+    MAD_TRY(fourier_plan(ctx, who, d1, o1, g2 ? d2 : nullptr, g2 ? o2 : nullptr, voxsp, P));
+    const int N = P->N, logN = P->logN;
+    const size_t n1 = (size_t)d1[0] * d1[1] * d1[2], n2 = g2 ? (size_t)d2[0] * d2[1] * d2[2] : 0;
+    const size_t bytes_Z = ((size_t)16 << (3 * logN));
+    size_t free_b = 0, total_b = 0;
+    MAD_HIP(hipMemGetInfo(&free_b, &total_b));
+    const size_t grow1 = mad_sb(ctx, S_TMP_H).cap >= (n1 + 4) * 4 ? 0 : (n1 + 4) * 5, grow2 = mad_sb(ctx, S_TMP_I).cap >= (n2 + 4) * 4 ? 0 : (n2 + 4) * 5;
+    const size_t need = bytes_Z + grow1 + grow2 + extra_bytes + ((size_t)8 << 20);
+    if (need > free_b)
+        return mad_fail(ctx, MAD_ENOMEM, "%s: a lattice of %d^3 needs %zu MiB of device memory, %zu MiB are free", who, N, need >> 20, free_b >> 20);
+    if (ctx->fft_tw_n != N) {
+        std::vector<double> tw((size_t)2 * N);
+        for (int k = 0; k < N; k++) {
+            double c, s;
+            unit_root(k, N, &c, &s);
+            tw[2 * k] = c; tw[2 * k + 1] = -s;      // exp(-2 pi i k / N)
+        }
+        MAD_TRY(mad_reserve(ctx, ctx->fft_tw, (size_t)FFT_MAX_N * 16));
+        ctx->fft_tw_n = 0;
+        MAD_HIP(hipMemcpy(ctx->fft_tw.p, tw.data(), (size_t)N * 16, hipMemcpyHostToDevice));
+        ctx->fft_tw_n = N;
+    }
+    MAD_TRY(mad_reserve(ctx, mad_sb(ctx, S_TMP_H), (n1 + 4) * 4));
+    MAD_TRY(mad_reserve(ctx, mad_sb(ctx, S_TMP_I), (n2 + 4) * 4));
+    double2 *Z = nullptr;
+    if (hipMalloc((void **)&Z, bytes_Z) != hipSuccess) {
+        (void)hipGetLastError();
+        return mad_fail(ctx, MAD_ENOMEM, "%s: hipMalloc of the %d^3 lattice (%zu MiB) failed", who, N, bytes_Z >> 20);
+    }
+    *Zout = Z;
+    PackArgs A;
+    memset(&A, 0, sizeof(A));
+    A.g1 = scratch<float>(ctx, S_TMP_H);
+    A.g2 = g2 ? scratch<float>(ctx, S_TMP_I) : nullptr;
+    A.logN = logN;
+    for (int k = 0; k < 3; k++) { A.d1[k] = d1[k]; A.p1[k] = P->p1[k]; A.d2[k] = g2 ? d2[k] : 0; A.p2[k] = P->p2[k]; }
+    MAD_HIP(hipMemcpyAsync((void *)A.g1, g1, n1 * 4, hipMemcpyHostToDevice, ctx->stream));
+    if (g2) MAD_HIP(hipMemcpyAsync((void *)A.g2, g2, n2 * 4, hipMemcpyHostToDevice, ctx->stream));
+    const double2 *tw = (const double2 *)ctx->fft_tw.p;
+    mad_timer_begin(ctx, MAD_T_FFT);
+    const int blocks = (int)std::min<int64_t>(mad_ceil_div((int64_t)1 << (3 * logN), 256), (int64_t)ctx->n_cu * 16);
+    hipLaunchKernelGGL(k_fft_pack, dim3(blocks), dim3(256), 0, ctx->stream, A, Z);
+    int rc = fft_axis<2>(ctx, Z, tw, logN);
+    if (rc == MAD_OK) rc = fft_axis<1>(ctx, Z, tw, logN);
+    if (rc == MAD_OK) rc = fft_axis<0>(ctx, Z, tw, logN);
+    mad_timer_end(ctx, MAD_T_FFT);
+    if (rc != MAD_OK) return rc;
+    MAD_HIP(hipGetLastError());
+    return MAD_OK;
+}
+
+static int fourier_free(mad_ctx *ctx, double2 *Z, int rc) {
+    if (Z) {
+        (void)hipStreamSynchronize(ctx->stream);
+        (void)hipFree(Z);
+    }
+    return rc;
+}
+
+static int map_fft_run(mad_ctx *ctx, const float *g1, const int32_t *d1, const double *o1, const float *g2, const int32_t *d2,
+                       const double *o2, double voxsp, int32_t *N_out, double *spectrum, double2 **Z) {
+    FourierPlan P;
+    if (!spectrum) {      // the size query: the checks and the plan, nothing allocated or launched
+        if (!(voxsp > 0) || !(voxsp < 1e15)) return mad_fail(ctx, MAD_EINVAL, "mad_map_fft: voxsp %g", voxsp);
+        MAD_TRY(fourier_check(ctx, "mad_map_fft", d1, o1, voxsp));
+        if (g2) MAD_TRY(fourier_check(ctx, "mad_map_fft", d2, o2, voxsp));
+        MAD_TRY(fourier_plan(ctx, "mad_map_fft", d1, o1, g2 ? d2 : nullptr, g2 ? o2 : nullptr, voxsp, &P));
+        *N_out = P.N;
+        return MAD_OK;
+    }
+    MAD_TRY(fourier_transform(ctx, "mad_map_fft", g1, d1, o1, g2, d2, o2, voxsp, 0, &P, Z));
+    if (N_out) *N_out = P.N;
+    MAD_HIP(hipMemcpyAsync(spectrum, *Z, (size_t)16 << (3 * P.logN), hipMemcpyDeviceToHost, ctx->stream));
+    MAD_HIP(hipStreamSynchronize(ctx->stream));
+    return MAD_OK;
+}
+
+extern "C" int mad_map_fft(mad_ctx *ctx, const float *grid1, const int32_t dims1[3], const double origin1[3], const float *grid2,
+                           const int32_t dims2[3], const double origin2[3], double voxsp, int32_t *N_out, double *spectrum) {
+    if (ctx) mad_use_lane(ctx, 0);
+    if (!ctx || !grid1 || !dims1 || !origin1 || (grid2 && (!dims2 || !origin2)) || (!N_out && !spectrum))
+        return ctx ? mad_fail(ctx, MAD_EINVAL, "mad_map_fft: NULL argument") : MAD_EINVAL;
+    double2 *Z = nullptr;
+    const int rc = map_fft_run(ctx, grid1, dims1, origin1, grid2, dims2, origin2, voxsp, N_out, spectrum, &Z);
+    return fourier_free(ctx, Z, rc);
+}
+
+static int map_fsc_run(mad_ctx *ctx, const float *g1, const int32_t *d1, const double *o1, const float *g2, const int32_t *d2,
+                       const double *o2, double voxsp, int32_t *N_out, double *sums, int64_t *count, int64_t cap_shells, double2 **Z) {
+    // the partial tables of the largest lattice: 1024 x 513 x 32 bytes
+    const size_t extra = (size_t)FSC_MAX_WGS * (FFT_MAX_N / 2 + 1) * 32 + ((size_t)1 << 20);
+    FourierPlan P;
+    {      // the capacity is judged before anything is allocated or launched
+        FourierPlan Q;
+        if (!(voxsp > 0) || !(voxsp < 1e15)) return mad_fail(ctx, MAD_EINVAL, "mad_map_fsc: voxsp %g", voxsp);
+        MAD_TRY(fourier_check(ctx, "mad_map_fsc", d1, o1, voxsp));
+        MAD_TRY(fourier_check(ctx, "mad_map_fsc", d2, o2, voxsp));
+        MAD_TRY(fourier_plan(ctx, "mad_map_fsc", d1, o1, d2, o2, voxsp, &Q));
+        if (N_out) *N_out = Q.N;
+        if (cap_shells < Q.N / 2 + 1)
+            return mad_fail(ctx, MAD_ENOSPC, "mad_map_fsc: room for %lld shells, the %d^3 lattice has %d", (long long)cap_shells, Q.N, Q.N / 2 + 1);
+    }
+    MAD_TRY(fourier_transform(ctx, "mad_map_fsc", g1, d1, o1, g2, d2, o2, voxsp, extra, &P, Z));
+    const int N = P.N, logN = P.logN, SH = N / 2 + 1;
+    const int64_t n_brick = (int64_t)1 << (3 * logN - 6);
+    const int wgs = (int)std::min<int64_t>(std::max<int64_t>(n_brick / 4, 1), FSC_MAX_WGS);
+    const size_t b_phi = (size_t)3 * N * 16, b_pf = (size_t)wgs * SH * 24, b_pi = (size_t)wgs * SH * 8, b_of = (((size_t)SH * 24) + 15) & ~(size_t)15;
+    MAD_TRY(mad_reserve(ctx, mad_sb(ctx, S_TMP_G), b_phi + b_pf + b_pi + b_of + (size_t)SH * 8));
+    char *blk = scratch<char>(ctx, S_TMP_G);
+    double2 *phi = (double2 *)blk;
+    double *part_f = (double *)(blk + b_phi), *out_f = (double *)(blk + b_phi + b_pf + b_pi);
+    long long *part_i = (long long *)(blk + b_phi + b_pf), *out_i = (long long *)(blk + b_phi + b_pf + b_pi + b_of);
+    std::vector<double> h_phi((size_t)6 * N);
+    for (int ax = 0; ax < 3; ax++)
+        for (int a = 0; a < N; a++) {
+            const double f = (double)(a < N / 2 ? a : a - N);
+            const double ang = 2.0 * M_PI * (f * P.delta[ax]) / (double)N;
+            h_phi[((size_t)ax * N + a) * 2] = cos(ang);
+            h_phi[((size_t)ax * N + a) * 2 + 1] = -sin(ang);
+        }
+    MAD_HIP(hipMemcpyAsync(phi, h_phi.data(), b_phi, hipMemcpyHostToDevice, ctx->stream));
+    MAD_HIP(hipStreamSynchronize(ctx->stream));      // h_phi is pageable: the copy has left it before it goes out of scope
+    const size_t lds = (size_t)(FSC_THREADS / MAD_WAVE) * SH * 28 + 16;
+    static bool attr = false;
+    if (!attr) { MAD_HIP(hipFuncSetAttribute((const void *)k_fsc_shells, hipFuncAttributeMaxDynamicSharedMemorySize, 4 * (FFT_MAX_N / 2 + 1) * 28 + 16)); attr = true; }
+    mad_timer_begin(ctx, MAD_T_FSC);
+    hipLaunchKernelGGL(k_fsc_shells, dim3(wgs), dim3(FSC_THREADS), lds, ctx->stream, (const double2 *)*Z, (const double2 *)phi, logN, part_f, part_i);
+    hipLaunchKernelGGL(k_fsc_sum, dim3((unsigned)mad_ceil_div(SH * 4, 256)), dim3(256), 0, ctx->stream, wgs, SH, (const double *)part_f,
+                       (const long long *)part_i, out_f, out_i);
+    mad_timer_end(ctx, MAD_T_FSC);
+    MAD_HIP(hipGetLastError());
+    std::vector<long long> h_cnt(SH);
+    MAD_HIP(hipMemcpyAsync(sums, out_f, (size_t)SH * 24, hipMemcpyDeviceToHost, ctx->stream));
+    MAD_HIP(hipMemcpyAsync(h_cnt.data(), out_i, (size_t)SH * 8, hipMemcpyDeviceToHost, ctx->stream));
+    MAD_HIP(hipStreamSynchronize(ctx->stream));
+    for (int s = 0; s < SH; s++) count[s] = (int64_t)h_cnt[s];
+    return MAD_OK;
+}
+
+extern "C" int mad_map_fsc(mad_ctx *ctx, const float *grid1, const int32_t dims1[3], const double origin1[3], const float *grid2,
+                           const int32_t dims2[3], const double origin2[3], double voxsp, int32_t *N_out, double *sums, int64_t *count,
+                           int64_t cap_shells) {
+    if (ctx) mad_use_lane(ctx, 0);
+    if (!ctx || !grid1 || !dims1 || !origin1 || !grid2 || !dims2 || !origin2 || !sums || !count)
+        return ctx ? mad_fail(ctx, MAD_EINVAL, "mad_map_fsc: NULL argument") : MAD_EINVAL;
+    double2 *Z = nullptr;
+    const int rc = map_fsc_run(ctx, grid1, dims1, origin1, grid2, dims2, origin2, voxsp, N_out, sums, count, cap_shells, &Z);
+    return fourier_free(ctx, Z, rc);
+}

@@ -3665,6 +3665,11 @@ extern "C" int mad_set_option(mad_ctx *ctx, const char *name, double value) {
         (name[0] == 'o' ? ctx->ori_queue_cap : ctx->dsc_queue_cap) = (int)value;
         return MAD_OK;
     }
+    if (!strcmp(name, "fft_bpt")) {      // test hook: the k_fft_lines form (butterflies per thread) for every N; 0 = chosen by N
+        if (value != 0 && value != 1 && value != 2 && value != 4) return mad_fail(ctx, MAD_EINVAL, "mad_set_option: fft_bpt = %g (0, 1, 2 or 4)", value);
+        ctx->fft_bpt = (int)value;
+        return MAD_OK;
+    }
     return mad_fail(ctx, MAD_EINVAL, "mad_set_option: unknown option '%s'", name);
 }
 
