@@ -315,7 +315,7 @@ int mad_set_batching(mad_ctx *ctx, int on);
  * holds at least this many pairs (default 4096) and at least 64 k.  "ori_queue" / "dsc_queue": entries in use of the queues through
  * which k_orient / k_describe hand the directions their fast classifiers cannot decide to the exact one (defaults: all 512 / 768);
  * a small value drives the kernels' full-queue paths for every anchor / row -- a test hook, the results are the same.  "fft_bpt"
- * (0 default, 1, 2, 4): butterflies per thread of k_fft_lines, i.e. which of its three forms mad_map_fft / mad_map_fsc launch (by
+ * (0 default, 1, 2, 4): butterflies per thread of k_fft_lines, i.e. which of its three forms mad_map_fft / mad_map_fsc / mad_map_filter / mad_map_ifft launch (by
  * default 1 up to N = 256, 2 at 512, 4 at 1024; a value below that is raised to it) -- a test hook, the bits are the same. */
 int mad_set_option(mad_ctx *ctx, const char *name, double value);
 
@@ -591,6 +591,32 @@ int mad_map_fsc(mad_ctx *ctx, const float *grid1, const int32_t dims1[3], const 
 int mad_map_fft(mad_ctx *ctx, const float *grid1, const int32_t dims1[3], const double origin1[3],
                 const float *grid2 /* may be NULL */, const int32_t dims2[3], const double origin2[3], double voxsp,
                 int32_t *N_out, double *spectrum /* N^3 complex128, interleaved; NULL: size query */);
+
+/*
+ * A radial filter on one or two maps in Fourier space, and the inverse transform under it (mad_fourier.hip; DESIGN.md section 4m;
+ * restated with numpy in mad_amd/fourier.py::filter_numpy).  Host pointers, synchronous.
+ *   Lattice.  grid1 and grid2 (float32 [x][y][z]) are each placed at lattice index (0, 0, 0): a radial filter is shift-invariant, the
+ *     grids need no common frame.  N is the smallest power of two >= max(all dims) + pad, 8 <= N <= 1024; pad >= 0 is the zero margin
+ *     between the far face of the box and its near face on the circular lattice.  Grid 1 in the real, grid 2 in the imaginary part.
+ *   Spectrum.  Z = FFT(g1 + i g2), as mad_map_fft.
+ *   Gain.  gain[r2], float64, r2 = i*i + j*j + k*k over the signed frequencies (a if a < N / 2, else a - N): n_gain = 3 (N / 2)^2 + 1
+ *     entries, finite, negative values allowed.  It depends on r2 alone, so it is real and even, and the real and imaginary parts of
+ *     the inverse are the filtered grid 1 and grid 2: one pair of transforms serves two maps.
+ *   Inverse.  ifft(X) = conj(FFT(conj(X))) / N^3: Z(k) <- (Re Z g, -(Im Z g)), the same three forward passes, then
+ *     out1 = (float)(Re Z 2^(-3 log2 N)) over grid 1's box and out2 = (float)(-(Im Z) 2^(-3 log2 N)) over grid 2's.  Float64 throughout,
+ *     no fused multiply-add, no atomics: the same bits every run and after any other call.
+ * mad_map_filter.  gain == NULL: the size query -- *N_out set, nothing allocated or launched.  grid2 / dims2 / out2 may be NULL
+ * together.  out1 may be grid1 and out2 may be grid2 (host memory: the grids are uploaded before anything is written).
+ * mad_map_ifft (a diagnostic, like mad_map_fft).  spectrum, out: complex128 [N][N][N] on the host, interleaved (re, im);
+ * out = ifft(spectrum), normalised by 1 / N^3.  For testing the inverse alone.
+ * MAD_EINVAL: NULL, a dimension < 1, a grid of 2^32 voxels or more, pad < 0, n_gain != 3 (N / 2)^2 + 1 (with *N_out set), a gain that
+ * is not finite (its index is in the message), grid2 without out2 or out2 without grid2, mad_map_ifft with N not a power of two in
+ * 8 .. 1024.  MAD_EDOM: max(dims) + pad > 1024.  MAD_ENOMEM: as mad_map_fsc (the lattice, both grids and the gain table are judged
+ * before anything is allocated).  Each leaves the outputs untouched, launches nothing, and the next call works.
+ */
+int mad_map_filter(mad_ctx *ctx, const float *grid1, const int32_t dims1[3], const float *grid2 /* may be NULL */, const int32_t dims2[3],
+                   int32_t pad, const double *gain /* NULL: size query */, int64_t n_gain, int32_t *N_out, float *out1, float *out2);
+int mad_map_ifft(mad_ctx *ctx, const double *spectrum, int32_t N, double *out);
 
 /* ---- one subunit's pair grid sharded over GPUs by blocks of map rows (the exchange steps -- OR of the flag vectors,
  *      all-gather of the per-shard top-k -- are the caller's, mad_amd/dist.py::sharded_match, or the library's own:

@@ -12,6 +12,8 @@ so that the remaining subunits can be docked into what is left of a map.  `smoot
 counterpart in the reference), which is where the masks `mask_with` consumes come from.  `fit_by_group` scores a placed model per residue, chain or other group
 of atoms against the map through `mad_map_group_fit` (localfit.py; no counterpart in the reference).  `fsc` is the Fourier shell
 correlation of the map against a second map or a placed model through `mad_map_fsc` (fourier.py; no counterpart in the reference).
+`lowpass`, `highpass`, `sharpen` and `filter_radial` filter the map in Fourier space through `mad_map_filter` (fourier.py; no
+counterpart in the reference).
 None of them has a CPU fallback.  The reference's per-voxel text writer is replaced by `mapio.write_situs`.
 """
 import os
@@ -131,7 +133,7 @@ class Dmap(object):
         dims, origin and spacing of `other`, after which `mask_with`, `get_CCC_with_dmap` and `get_CCC_with_grid` see equal spacings
         and a whole-voxel offset.  Neither: the map's own lattice (useful with `R, T`).  `R, T` move the map first, a point x
         going to x @ R + T.  order 1 is trilinear, order 3 cubic B-spline interpolation; voxels outside the source are 0.  There is
-        no low-pass filter before coarsening: smooth first where that matters."""
+        no low-pass filter before coarsening: call `lowpass` at twice the new spacing or more first where that matters."""
         if voxsp is not None and like is not None:
             raise ValueError("Dmap.resample: give voxsp or like, not both")
         if (R is None) != (T is None):
@@ -239,6 +241,91 @@ class Dmap(object):
         _lib.get_lib().map_smooth(g, sigma / self.voxsp, out=g)
         self.grid3d = g
         return self
+
+    def _filter(self, who, design, pad):
+        """The radial gain `design(N)(f)` (f in 1 / Angstrom) on the map through `mad_map_filter`, in place; `pad` voxels of zero
+        margin."""
+        from . import fourier
+        if isinstance(pad, bool) or int(pad) != pad or pad < 0:
+            raise ValueError("Dmap.%s: pad %r (a whole number of voxels, 0 or more)" % (who, pad))
+        g = np.ascontiguousarray(self.grid3d, dtype=np.float32)
+        if g.ndim != 3 or g.size == 0:
+            raise ValueError("Dmap.%s: the grid has shape %r" % (who, g.shape))
+        N = fourier.filter_lattice(g.shape, int(pad))
+        out = _lib.get_lib().map_filter(g, fourier.radial_gain(N, self.voxsp, design(N)), int(pad))
+        if g is self.grid3d and g.flags.writeable:
+            g[...] = out
+        else:
+            self.grid3d = out
+        return self
+
+    @staticmethod
+    def _filter_args(who, resolution, kind, edge):
+        resolution, edge = float(resolution), float(edge)
+        if not (resolution > 0) or not np.isfinite(resolution):
+            raise ValueError("Dmap.%s: resolution %r (positive and finite)" % (who, resolution))
+        if kind not in ("gaussian", "cosine"):
+            raise ValueError("Dmap.%s: kind %r ('gaussian' or 'cosine')" % (who, kind))
+        if not (edge >= 0) or not np.isfinite(edge):
+            raise ValueError("Dmap.%s: edge %r (0 or more lattice units, finite)" % (who, edge))
+        return resolution, edge
+
+    def _lowpass_gain(self, resolution, kind, edge):
+        """-> (design: N -> fn(f), default pad) of a low-pass at `resolution` Angstrom.  The pads are conventions: 4 sigma of the
+        Gaussian's real-space kernel, two periods of the cut-off for the cosine edge."""
+        from . import fourier
+        vs = float(self.voxsp)
+        if kind == "gaussian":
+            sigma = resolution / (np.pi * np.sqrt(2.0))
+            return (lambda N: lambda f: fourier.gain_gaussian(f, resolution)), int(np.ceil(4.0 * sigma / vs))
+        # the cosine is designed in lattice units: r = f (N voxsp), r_c = (N voxsp) / resolution
+        return (lambda N: lambda f: fourier.gain_cosine(f * (N * vs), (N * vs) / resolution, edge)), int(np.ceil(2.0 * resolution / vs))
+
+    def lowpass(self, resolution, kind="gaussian", edge=2.0, pad=None):
+        """The map low-passed to `resolution` Angstrom in Fourier space, in place.  Returns self.  kind "gaussian": the gain
+        exp(-(f resolution)^2), the transform of the Gaussian `structure_to_density` blurs atoms with (sigma = resolution / (pi sqrt 2)
+        Angstrom), so that the map and a model simulated at `resolution` carry the same envelope; `smooth(sigma)` is its truncated
+        real-space counterpart, with zero beyond the box.  kind "cosine": 1 up to the frequency 1 / resolution, a raised-cosine edge
+        `edge` lattice units (1 / (N voxsp)) wide centred on it, 0 beyond; edge 0 is the top hat.  The map sits on a circular lattice
+        of the next power of two >= max(dims) + pad (at most 1024): `pad` voxels of zero keep what the filter's tail carries past
+        one face from entering through the opposite one.  pad=None: ceil(4 sigma / voxsp) for the Gaussian, ceil(2 resolution / voxsp)
+        for the cosine -- conventions that reduce the wrap-around of filters with long tails; they do not remove it."""
+        resolution, edge = self._filter_args("lowpass", resolution, kind, edge)
+        design, default = self._lowpass_gain(resolution, kind, edge)
+        return self._filter("lowpass", design, default if pad is None else pad)
+
+    def highpass(self, resolution, kind="gaussian", edge=2.0, pad=None):
+        """One minus the gain of `lowpass(resolution, kind, edge)`, in place: removes the mean (shell 0) and the background below
+        1 / resolution.  Returns self.  `pad` as in `lowpass`, with the same conventional defaults."""
+        resolution, edge = self._filter_args("highpass", resolution, kind, edge)
+        design, default = self._lowpass_gain(resolution, kind, edge)
+        return self._filter("highpass", lambda N: lambda f: 1.0 - design(N)(f), default if pad is None else pad)
+
+    def sharpen(self, b_factor, lowpass=None, edge=2.0, pad=None):
+        """The gain exp(-b_factor f^2 / 4) on the map, in place: a negative `b_factor` (square Angstrom) sharpens, a positive one
+        blurs.  Returns self.  `lowpass`: times the cosine low-pass at that many Angstrom with an edge of `edge` lattice units, which
+        keeps a sharpening gain from amplifying the noise beyond the map's resolution.  pad=None: that of the cosine low-pass,
+        ceil(2 lowpass / voxsp), else 8 voxels -- conventions, as in `lowpass`."""
+        from . import fourier
+        b_factor = float(b_factor)
+        if not np.isfinite(b_factor):
+            raise ValueError("Dmap.sharpen: b_factor %r (finite)" % (b_factor,))
+        if lowpass is None:
+            return self._filter("sharpen", lambda N: lambda f: fourier.gain_bfactor(f, b_factor), 8 if pad is None else pad)
+        lowpass, edge = self._filter_args("sharpen", lowpass, "cosine", edge)
+        design, default = self._lowpass_gain(lowpass, "cosine", edge)
+        return self._filter("sharpen", lambda N: lambda f: fourier.gain_bfactor(f, b_factor) * design(N)(f), default if pad is None else pad)
+
+    def filter_radial(self, freq, gain, pad=None):
+        """Any radial gain on the map, in place: the curve `gain` over `freq` (1 / Angstrom, increasing), interpolated linearly and
+        constant beyond its ends (`fourier.gain_curve`).  Returns self.  pad=None: 8 voxels, a convention, as in `lowpass`."""
+        from . import fourier
+        freq, gain = np.asarray(freq, np.float64).reshape(-1), np.asarray(gain, np.float64).reshape(-1)
+        if len(freq) == 0 or len(freq) != len(gain):
+            raise ValueError("Dmap.filter_radial: %d frequencies and %d gains" % (len(freq), len(gain)))
+        if not (np.isfinite(freq).all() and np.isfinite(gain).all()) or np.any(np.diff(freq) <= 0):
+            raise ValueError("Dmap.filter_radial: the frequencies must increase, and both columns be finite")
+        return self._filter("filter_radial", lambda N: lambda f: fourier.gain_curve(f, freq, gain), 8 if pad is None else pad)
 
     def segment(self, threshold=0.0, steps=4, step=1.0, stop_at=0):
         """The map cut into segments -> `segment.Segmentation`; the map is untouched.  Watershed regions of the density above

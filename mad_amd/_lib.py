@@ -39,7 +39,7 @@ SYMBOLS = [
     "mad_dist_unique_id", "mad_dist_init", "mad_dist_destroy", "mad_dist_info", "mad_dist_rehearse_flags", "mad_dist_or_allreduce", "mad_dist_allgather",
     "mad_dist_allgather_topk", "mad_dist_scratch", "mad_dist_copy",
     "mad_set_wire_bytes", "mad_set_export", "mad_set_import", "mad_set_lane", "mad_set_stream", "mad_set_bind_lane",
-    "mad_upload_density", "mad_refine", "mad_last_refine_plan", "mad_last_density_chunks", "mad_structure_to_density", "mad_ccc", "mad_map_mask", "mad_map_ccc", "mad_map_resample", "mad_map_zone", "mad_map_group_fit", "mad_map_smooth", "mad_map_segment", "mad_map_fsc", "mad_map_fft", "mad_density_ccc", "mad_dock_refine_score", "mad_grid_overlap", "mad_overlap_matrix",
+    "mad_upload_density", "mad_refine", "mad_last_refine_plan", "mad_last_density_chunks", "mad_structure_to_density", "mad_ccc", "mad_map_mask", "mad_map_ccc", "mad_map_resample", "mad_map_zone", "mad_map_group_fit", "mad_map_smooth", "mad_map_segment", "mad_map_fsc", "mad_map_fft", "mad_map_filter", "mad_map_ifft", "mad_density_ccc", "mad_dock_refine_score", "mad_grid_overlap", "mad_overlap_matrix",
     "mad_space_create", "mad_space_destroy", "mad_space_build", "mad_space_info", "mad_space_download",
     "mad_space_peaks", "mad_space_patches", "mad_space_localize", "mad_localize_volume",
     "mad_pose_cluster_many",
@@ -1206,6 +1206,30 @@ class Lib(object):
         self._chk(self.dll.mad_map_fft(*args, C.byref(n), None))
         out = np.empty((n.value,) * 3, np.complex128)
         self._chk(self.dll.mad_map_fft(*args, C.byref(n), _p(out)))
+        return out
+
+    def map_filter(self, g1, gain, pad=0, g2=None):
+        """A radial filter in Fourier space -> out1, or (out1, out2) with `g2`: new float32 arrays of the grids' shapes
+        (mad_map_filter; `fourier.filter_numpy` restates it).  `gain`: float64 [3 (N / 2)^2 + 1] by
+        r2 = i^2 + j^2 + k^2 (`fourier.radial_gain`), N = `fourier.filter_lattice(g1.shape, pad, g2.shape)`.  The grids
+        (C-contiguous float32 [x, y, z]) need no common frame; neither is modified."""
+        d1, _, d2, _ = self._fourier_args("map_filter", g1, np.zeros(3), g2, np.zeros(3))
+        gain = _c(np.asarray(gain, np.float64).reshape(-1), np.float64)
+        out1 = np.empty(g1.shape, np.float32)
+        out2 = None if g2 is None else np.empty(g2.shape, np.float32)
+        n = C.c_int32(0)
+        self._chk(self.dll.mad_map_filter(self.ctx, _p(g1), _p(d1), _p(g2), _p(d2), C.c_int32(int(pad)), _p(gain), C.c_int64(len(gain)),
+                                          C.byref(n), _p(out1), _p(out2)))
+        return out1 if g2 is None else (out1, out2)
+
+    def map_ifft(self, spectrum):
+        """The inverse transform `map_filter` works with, for testing it alone -> complex128 [N, N, N] = ifft(spectrum), normalised by
+        1 / N^3 (mad_map_ifft).  `spectrum`: complex128 [N, N, N], N a power of two from 8 to 1024."""
+        s = _c(np.asarray(spectrum), np.complex128)
+        if s.ndim != 3 or s.shape[0] != s.shape[1] or s.shape[0] != s.shape[2]:
+            raise ValueError("map_ifft needs a cubic 3-D spectrum, got %r" % (s.shape,))
+        out = np.empty(s.shape, np.complex128)
+        self._chk(self.dll.mad_map_ifft(self.ctx, _p(s), C.c_int32(s.shape[0]), _p(out)))
         return out
 
     def map_zone(self, g, origin, voxsp, atoms, radius, soft=0.0, erase=False):

@@ -30,6 +30,11 @@
 // table in LDS (no cross-lane shuffles: sixteen broadcast reads per lane).  Waves take bricks in a fixed order, a workgroup adds
 // its four tables in order into its slot of the partial tables, and k_fsc_sum adds the slots in order: no floating-point
 // atomics anywhere, the same bits every run.
+//
+// Radial filters (mad_map_filter) and the inverse transform (mad_map_ifft): DESIGN.md section 4m.  The grids sit at lattice index
+// (0, 0, 0), Z = FFT(g1 + i g2) as above; k_fft_gain multiplies Z(k) by a real gain looked up by r2 = |k|^2 and conjugates, the same
+// three k_fft_lines passes follow (ifft(X) = conj(FFT(conj X)) / N^3), and k_fft_unpack writes Re Z / N^3 over grid 1's box and
+// -(Im Z) / N^3 over grid 2's as float32.  A gain that depends on r2 alone is real and even, so the two maps stay apart.
 #include <algorithm>
 #include <vector>
 
@@ -155,6 +160,47 @@ __global__ __launch_bounds__(FFT_MAX_THREADS) void k_fft_lines(double2 *__restri
     for (int e = t; e < E; e += T) {
         const int n = AXIS == 2 ? (e & (N - 1)) : (e >> 3), l = AXIS == 2 ? (e >> logN) : (e & 7);
         Z[base + (size_t)n * sN + (size_t)l * sL] = fft_img[n * ROW + l];
+    }
+}
+
+// ---------------------------------------------------------------------------
+// filters and the inverse transform
+// ---------------------------------------------------------------------------
+
+// Z(k) <- (Re Z g, -(Im Z g)), g = gain[r2(k)], r2 = i^2 + j^2 + k^2 over the signed frequencies (a if a < N / 2, else a - N);
+// gain NULL: g = scale for every k (scale 1.0: the conjugate alone, the same bits).  Every 16-byte element is read and written once,
+// coalesced along z.  The gain is an 8-byte gather that within a z line spans (N / 2)^2 + 1 entries, a cache line per lane beyond
+// the first few z: it, not the stream, set the kernel's time when every element made its own.  The lines (a, b), (N - a, b),
+// (a, N - b) and (N - a, N - b) have the same r2 at every z, so a workgroup takes a piece of all four and gathers once for them:
+// blockIdx.y = a and blockIdx.z = b run over 0 .. N / 2 (index N / 2 is the frequency -N / 2, its own mirror image, as 0 is), and
+// blockIdx.x * blockDim.x + threadIdx.x = z with blockDim.x = min(N, 256).
+__global__ __launch_bounds__(256) void k_fft_gain(double2 *__restrict__ Z, const double *__restrict__ gain, double scale, int logN) {
+    const int N = 1 << logN, half = N >> 1;
+    const int c = (int)(blockIdx.x * blockDim.x + threadIdx.x), a = (int)blockIdx.y, b = (int)blockIdx.z;
+    if (c >= N || a > half || b > half) return;
+    const int fk = c < half ? c : c - N;
+    const double g = gain ? gain[a * a + b * b + fk * fk] : scale;      // at most 3 (N / 2)^2 = 786 432
+    const int a2 = (N - a) & (N - 1), b2 = (N - b) & (N - 1);
+    const bool ma = a2 != a, mb = b2 != b;      // uniform over the workgroup
+    const size_t i0 = (((((size_t)a) << logN) + b) << logN) + c, i1 = (((((size_t)a2) << logN) + b) << logN) + c;
+    const size_t i2 = (((((size_t)a) << logN) + b2) << logN) + c, i3 = (((((size_t)a2) << logN) + b2) << logN) + c;
+    const double2 z = make_double2(0.0, 0.0);
+    const double2 v0 = Z[i0], v1 = ma ? Z[i1] : z, v2 = mb ? Z[i2] : z, v3 = ma && mb ? Z[i3] : z;
+    Z[i0] = make_double2(v0.x * g, -(v0.y * g));
+    if (ma) Z[i1] = make_double2(v1.x * g, -(v1.y * g));
+    if (mb) Z[i2] = make_double2(v2.x * g, -(v2.y * g));
+    if (ma && mb) Z[i3] = make_double2(v3.x * g, -(v3.y * g));
+}
+
+// out[x][y][z] = (float)(Re Z(x, y, z) * scale) (IMAG: -(Im Z) * scale) over the box d at lattice index (0, 0, 0): one output
+// voxel per lane, runs of d[2] lattice elements along z read, float32 written coalesced.  n = d[0] d[1] d[2] < 2^32.
+template <bool IMAG>
+__global__ __launch_bounds__(256) void k_fft_unpack(const double2 *__restrict__ Z, int logN, double scale, float *__restrict__ out,
+                                                    unsigned d1, unsigned d2, size_t n) {
+    for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (size_t)gridDim.x * 256) {
+        const unsigned j = (unsigned)i, t = j / d2, z = j - t * d2, x = t / d1, y = t - x * d1;
+        const double2 v = Z[(((((size_t)x) << logN) + y) << logN) + z];
+        out[i] = (float)(IMAG ? -v.y * scale : v.x * scale);
     }
 }
 
@@ -331,16 +377,25 @@ template <int AXIS> static int fft_axis(mad_ctx *ctx, double2 *Z, const double2 
     return fft_launch<AXIS, 4>(ctx, Z, tw, logN, threads);
 }
 
-// Validates, plans, allocates the lattice (*Zout, the caller frees it), uploads and transforms.  Nothing is allocated on a refusal.
-static int fourier_transform(mad_ctx *ctx, const char *who, const float *g1, const int32_t *d1, const double *o1, const float *g2,
-                             const int32_t *d2, const double *o2, double voxsp, size_t extra_bytes, FourierPlan *P, double2 **Zout) {
-    *Zout = nullptr;
-    if (!(voxsp > 0) || !(voxsp < 1e15)) return mad_fail(ctx, MAD_EINVAL, "%s: voxsp %g", who, voxsp);
-    MAD_TRY(fourier_check(ctx, who, d1, o1, voxsp));
-    if (g2) MAD_TRY(fourier_check(ctx, who, d2, o2, voxsp));
-    MAD_TRY(fourier_plan(ctx, who, d1, o1, g2 ? d2 : nullptr, g2 ? o2 : nullptr, voxsp, P));
-    const int N = P->N, logN = P->logN;
-    const size_t n1 = (size_t)d1[0] * d1[1] * d1[2], n2 = g2 ? (size_t)d2[0] * d2[1] * d2[2] : 0;
+// the twiddles exp(-2 pi i k / N) of the lattice edge N on the device, uploaded when N changes
+static int fourier_twiddles(mad_ctx *ctx, int N) {
+    if (ctx->fft_tw_n == N) return MAD_OK;
+    std::vector<double> tw((size_t)2 * N);
+    for (int k = 0; k < N; k++) {
+        double c, s;
+        unit_root(k, N, &c, &s);
+        tw[2 * k] = c; tw[2 * k + 1] = -s;      // exp(-2 pi i k / N)
+    }
+    MAD_TRY(mad_reserve(ctx, ctx->fft_tw, (size_t)FFT_MAX_N * 16));
+    ctx->fft_tw_n = 0;
+    MAD_HIP(hipMemcpy(ctx->fft_tw.p, tw.data(), (size_t)N * 16, hipMemcpyHostToDevice));
+    ctx->fft_tw_n = N;
+    return MAD_OK;
+}
+
+// the free-memory check, judged before anything is allocated: the lattice, what the scratch buffers of the grids (n1, n2 voxels;
+// either may be 0) would grow by, and extra_bytes
+static int fourier_room(mad_ctx *ctx, const char *who, int N, int logN, size_t n1, size_t n2, size_t extra_bytes) {
     const size_t bytes_Z = ((size_t)16 << (3 * logN));
     size_t free_b = 0, total_b = 0;
     MAD_HIP(hipMemGetInfo(&free_b, &total_b));
@@ -348,26 +403,46 @@ static int fourier_transform(mad_ctx *ctx, const char *who, const float *g1, con
     const size_t need = bytes_Z + grow1 + grow2 + extra_bytes + ((size_t)8 << 20);
     if (need > free_b)
         return mad_fail(ctx, MAD_ENOMEM, "%s: a lattice of %d^3 needs %zu MiB of device memory, %zu MiB are free", who, N, need >> 20, free_b >> 20);
-    if (ctx->fft_tw_n != N) {
-        std::vector<double> tw((size_t)2 * N);
-        for (int k = 0; k < N; k++) {
-            double c, s;
-            unit_root(k, N, &c, &s);
-            tw[2 * k] = c; tw[2 * k + 1] = -s;      // exp(-2 pi i k / N)
-        }
-        MAD_TRY(mad_reserve(ctx, ctx->fft_tw, (size_t)FFT_MAX_N * 16));
-        ctx->fft_tw_n = 0;
-        MAD_HIP(hipMemcpy(ctx->fft_tw.p, tw.data(), (size_t)N * 16, hipMemcpyHostToDevice));
-        ctx->fft_tw_n = N;
-    }
-    MAD_TRY(mad_reserve(ctx, mad_sb(ctx, S_TMP_H), (n1 + 4) * 4));
-    MAD_TRY(mad_reserve(ctx, mad_sb(ctx, S_TMP_I), (n2 + 4) * 4));
+    return MAD_OK;
+}
+
+static int fourier_alloc(mad_ctx *ctx, const char *who, int N, int logN, double2 **Zout) {
+    const size_t bytes_Z = ((size_t)16 << (3 * logN));
     double2 *Z = nullptr;
     if (hipMalloc((void **)&Z, bytes_Z) != hipSuccess) {
         (void)hipGetLastError();
         return mad_fail(ctx, MAD_ENOMEM, "%s: hipMalloc of the %d^3 lattice (%zu MiB) failed", who, N, bytes_Z >> 20);
     }
     *Zout = Z;
+    return MAD_OK;
+}
+
+// the three passes of k_fft_lines along z, y, x
+static int fourier_passes(mad_ctx *ctx, double2 *Z, int logN) {
+    const double2 *tw = (const double2 *)ctx->fft_tw.p;
+    MAD_TRY(fft_axis<2>(ctx, Z, tw, logN));
+    MAD_TRY(fft_axis<1>(ctx, Z, tw, logN));
+    return fft_axis<0>(ctx, Z, tw, logN);
+}
+
+// workgroups of 256 for a streaming kernel over n elements (grid-stride beyond 16 per CU)
+static unsigned fourier_blocks(mad_ctx *ctx, size_t n) {
+    return (unsigned)std::min<int64_t>(mad_ceil_div((int64_t)n, 256), (int64_t)ctx->n_cu * 16);
+}
+
+// The lattice of a plan: judges the memory, allocates (*Zout, the caller frees it), uploads, packs and transforms.  The grids stay
+// in S_TMP_H and S_TMP_I.
+static int fourier_forward(mad_ctx *ctx, const char *who, const float *g1, const int32_t *d1, const float *g2, const int32_t *d2,
+                           size_t extra_bytes, const FourierPlan *P, double2 **Zout) {
+    *Zout = nullptr;
+    const int N = P->N, logN = P->logN;
+    const size_t n1 = (size_t)d1[0] * d1[1] * d1[2], n2 = g2 ? (size_t)d2[0] * d2[1] * d2[2] : 0;
+    MAD_TRY(fourier_room(ctx, who, N, logN, n1, n2, extra_bytes));
+    MAD_TRY(fourier_twiddles(ctx, N));
+    MAD_TRY(mad_reserve(ctx, mad_sb(ctx, S_TMP_H), (n1 + 4) * 4));
+    MAD_TRY(mad_reserve(ctx, mad_sb(ctx, S_TMP_I), (n2 + 4) * 4));
+    MAD_TRY(fourier_alloc(ctx, who, N, logN, Zout));
+    double2 *Z = *Zout;
     PackArgs A;
     memset(&A, 0, sizeof(A));
     A.g1 = scratch<float>(ctx, S_TMP_H);
@@ -376,17 +451,24 @@ static int fourier_transform(mad_ctx *ctx, const char *who, const float *g1, con
     for (int k = 0; k < 3; k++) { A.d1[k] = d1[k]; A.p1[k] = P->p1[k]; A.d2[k] = g2 ? d2[k] : 0; A.p2[k] = P->p2[k]; }
     MAD_HIP(hipMemcpyAsync((void *)A.g1, g1, n1 * 4, hipMemcpyHostToDevice, ctx->stream));
     if (g2) MAD_HIP(hipMemcpyAsync((void *)A.g2, g2, n2 * 4, hipMemcpyHostToDevice, ctx->stream));
-    const double2 *tw = (const double2 *)ctx->fft_tw.p;
     mad_timer_begin(ctx, MAD_T_FFT);
-    const int blocks = (int)std::min<int64_t>(mad_ceil_div((int64_t)1 << (3 * logN), 256), (int64_t)ctx->n_cu * 16);
-    hipLaunchKernelGGL(k_fft_pack, dim3(blocks), dim3(256), 0, ctx->stream, A, Z);
-    int rc = fft_axis<2>(ctx, Z, tw, logN);
-    if (rc == MAD_OK) rc = fft_axis<1>(ctx, Z, tw, logN);
-    if (rc == MAD_OK) rc = fft_axis<0>(ctx, Z, tw, logN);
+    hipLaunchKernelGGL(k_fft_pack, dim3(fourier_blocks(ctx, (size_t)1 << (3 * logN))), dim3(256), 0, ctx->stream, A, Z);
+    const int rc = fourier_passes(ctx, Z, logN);
     mad_timer_end(ctx, MAD_T_FFT);
     if (rc != MAD_OK) return rc;
     MAD_HIP(hipGetLastError());
     return MAD_OK;
+}
+
+// Validates, plans, allocates the lattice (*Zout, the caller frees it), uploads and transforms.  Nothing is allocated on a refusal.
+static int fourier_transform(mad_ctx *ctx, const char *who, const float *g1, const int32_t *d1, const double *o1, const float *g2,
+                             const int32_t *d2, const double *o2, double voxsp, size_t extra_bytes, FourierPlan *P, double2 **Zout) {
+    *Zout = nullptr;
+    if (!(voxsp > 0) || !(voxsp < 1e15)) return mad_fail(ctx, MAD_EINVAL, "%s: voxsp %g", who, voxsp);
+    MAD_TRY(fourier_check(ctx, who, d1, o1, voxsp));
+    if (g2) MAD_TRY(fourier_check(ctx, who, d2, o2, voxsp));
+    MAD_TRY(fourier_plan(ctx, who, d1, o1, g2 ? d2 : nullptr, g2 ? o2 : nullptr, voxsp, P));
+    return fourier_forward(ctx, who, g1, d1, g2, d2, extra_bytes, P, Zout);
 }
 
 static int fourier_free(mad_ctx *ctx, double2 *Z, int rc) {
@@ -485,5 +567,115 @@ extern "C" int mad_map_fsc(mad_ctx *ctx, const float *grid1, const int32_t dims1
         return ctx ? mad_fail(ctx, MAD_EINVAL, "mad_map_fsc: NULL argument") : MAD_EINVAL;
     double2 *Z = nullptr;
     const int rc = map_fsc_run(ctx, grid1, dims1, origin1, grid2, dims2, origin2, voxsp, N_out, sums, count, cap_shells, &Z);
+    return fourier_free(ctx, Z, rc);
+}
+
+// ---------------------------------------------------------------------------
+// radial filters
+// ---------------------------------------------------------------------------
+
+// k_fft_gain over the whole lattice: z in pieces of min(N, 256), a and b over 0 .. N / 2
+static int filter_gain_launch(mad_ctx *ctx, double2 *Z, const double *gain, double scale, int logN) {
+    const int N = 1 << logN, threads = std::min(N, 256);
+    hipLaunchKernelGGL(k_fft_gain, dim3((unsigned)(N / threads), (unsigned)(N / 2 + 1), (unsigned)(N / 2 + 1)), dim3(threads), 0, ctx->stream, Z, gain,
+                       scale, logN);
+    return MAD_OK;
+}
+
+static int map_filter_run(mad_ctx *ctx, const float *g1, const int32_t *d1, const float *g2, const int32_t *d2, int32_t pad,
+                          const double *gain, int64_t n_gain, int32_t *N_out, float *out1, float *out2, double2 **Z) {
+    static const double zero[3] = {0.0, 0.0, 0.0};
+    MAD_TRY(fourier_check(ctx, "mad_map_filter", d1, zero, 1.0));
+    if (g2) MAD_TRY(fourier_check(ctx, "mad_map_filter", d2, zero, 1.0));
+    if (pad < 0) return mad_fail(ctx, MAD_EINVAL, "mad_map_filter: pad %d (0 or more)", pad);
+    int64_t longest = 0;
+    for (int k = 0; k < 3; k++) longest = std::max<int64_t>(longest, std::max<int64_t>(d1[k], g2 ? d2[k] : 0));
+    if (longest + pad > FFT_MAX_N)
+        return mad_fail(ctx, MAD_EDOM, "mad_map_filter: the longest axis and the pad are %lld + %d voxels, more than %d", (long long)longest, pad, FFT_MAX_N);
+    FourierPlan P;
+    memset(&P, 0, sizeof(P));
+    P.N = FFT_MIN_N; P.logN = 3;
+    while (P.N < longest + pad) { P.N <<= 1; P.logN++; }
+    if (N_out) *N_out = P.N;
+    if (!gain) return MAD_OK;      // the size query
+    const int N = P.N, logN = P.logN;
+    const int64_t want = (int64_t)3 * (N / 2) * (N / 2) + 1;
+    if (n_gain != want)
+        return mad_fail(ctx, MAD_EINVAL, "mad_map_filter: a gain table of %lld entries, the %d^3 lattice needs %lld", (long long)n_gain, N, (long long)want);
+    for (int64_t i = 0; i < n_gain; i++)
+        if (!(fabs(gain[i]) <= 1.7976931348623157e308)) return mad_fail(ctx, MAD_EINVAL, "mad_map_filter: gain[%lld] is not finite", (long long)i);
+    const size_t b_gain = (size_t)n_gain * 8, grow_g = mad_sb(ctx, S_TMP_G).cap >= b_gain ? 0 : b_gain + b_gain / 4;
+    MAD_TRY(fourier_forward(ctx, "mad_map_filter", g1, d1, g2, d2, grow_g, &P, Z));
+    MAD_TRY(mad_reserve(ctx, mad_sb(ctx, S_TMP_G), b_gain));
+    double *d_gain = scratch<double>(ctx, S_TMP_G);
+    MAD_HIP(hipMemcpyAsync(d_gain, gain, b_gain, hipMemcpyHostToDevice, ctx->stream));
+    mad_timer_begin(ctx, MAD_T_FILTER);
+    filter_gain_launch(ctx, *Z, d_gain, 1.0, logN);
+    mad_timer_end(ctx, MAD_T_FILTER);
+    mad_timer_begin(ctx, MAD_T_FFT);
+    const int rc = fourier_passes(ctx, *Z, logN);
+    mad_timer_end(ctx, MAD_T_FFT);
+    if (rc != MAD_OK) return rc;
+    // the grids were consumed by k_fft_pack: their buffers take the outputs
+    const size_t n1 = (size_t)d1[0] * d1[1] * d1[2], n2 = g2 ? (size_t)d2[0] * d2[1] * d2[2] : 0;
+    const double scale = ldexp(1.0, -3 * logN);
+    float *o1 = scratch<float>(ctx, S_TMP_H), *o2 = scratch<float>(ctx, S_TMP_I);
+    mad_timer_begin(ctx, MAD_T_FILTER);
+    hipLaunchKernelGGL(k_fft_unpack<false>, dim3(fourier_blocks(ctx, n1)), dim3(256), 0, ctx->stream, (const double2 *)*Z, logN, scale, o1,
+                       (unsigned)d1[1], (unsigned)d1[2], n1);
+    if (g2)
+        hipLaunchKernelGGL(k_fft_unpack<true>, dim3(fourier_blocks(ctx, n2)), dim3(256), 0, ctx->stream, (const double2 *)*Z, logN, scale, o2,
+                           (unsigned)d2[1], (unsigned)d2[2], n2);
+    mad_timer_end(ctx, MAD_T_FILTER);
+    MAD_HIP(hipGetLastError());
+    MAD_HIP(hipMemcpyAsync(out1, o1, n1 * 4, hipMemcpyDeviceToHost, ctx->stream));
+    if (g2) MAD_HIP(hipMemcpyAsync(out2, o2, n2 * 4, hipMemcpyDeviceToHost, ctx->stream));
+    MAD_HIP(hipStreamSynchronize(ctx->stream));
+    return MAD_OK;
+}
+
+extern "C" int mad_map_filter(mad_ctx *ctx, const float *grid1, const int32_t dims1[3], const float *grid2, const int32_t dims2[3],
+                              int32_t pad, const double *gain, int64_t n_gain, int32_t *N_out, float *out1, float *out2) {
+    if (ctx) mad_use_lane(ctx, 0);
+    if (!ctx || !grid1 || !dims1 || (grid2 && !dims2) || (!gain && !N_out) || (gain && !out1))
+        return ctx ? mad_fail(ctx, MAD_EINVAL, "mad_map_filter: NULL argument") : MAD_EINVAL;
+    if (gain && (grid2 != nullptr) != (out2 != nullptr))
+        return mad_fail(ctx, MAD_EINVAL, "mad_map_filter: grid2 and out2 go together (%s is NULL)", grid2 ? "out2" : "grid2");
+    double2 *Z = nullptr;
+    const int rc = map_filter_run(ctx, grid1, dims1, grid2, dims2, pad, gain, n_gain, N_out, out1, out2, &Z);
+    return fourier_free(ctx, Z, rc);
+}
+
+static int map_ifft_run(mad_ctx *ctx, const double *spectrum, int32_t N, double *out, double2 **Z) {
+    int logN = 0;
+    while ((1 << logN) < N && logN < 11) logN++;
+    if (N < FFT_MIN_N || N > FFT_MAX_N || (1 << logN) != N)
+        return mad_fail(ctx, MAD_EINVAL, "mad_map_ifft: N = %d (a power of two from %d to %d)", N, FFT_MIN_N, FFT_MAX_N);
+    MAD_TRY(fourier_room(ctx, "mad_map_ifft", N, logN, 0, 0, 0));
+    MAD_TRY(fourier_twiddles(ctx, N));
+    MAD_TRY(fourier_alloc(ctx, "mad_map_ifft", N, logN, Z));
+    const size_t bytes_Z = (size_t)16 << (3 * logN);
+    MAD_HIP(hipMemcpyAsync(*Z, spectrum, bytes_Z, hipMemcpyHostToDevice, ctx->stream));
+    mad_timer_begin(ctx, MAD_T_FILTER);
+    filter_gain_launch(ctx, *Z, nullptr, 1.0, logN);      // conj(X)
+    mad_timer_end(ctx, MAD_T_FILTER);
+    mad_timer_begin(ctx, MAD_T_FFT);
+    const int rc = fourier_passes(ctx, *Z, logN);
+    mad_timer_end(ctx, MAD_T_FFT);
+    if (rc != MAD_OK) return rc;
+    mad_timer_begin(ctx, MAD_T_FILTER);
+    filter_gain_launch(ctx, *Z, nullptr, ldexp(1.0, -3 * logN), logN);      // conj(.) / N^3: a power of two, exact
+    mad_timer_end(ctx, MAD_T_FILTER);
+    MAD_HIP(hipGetLastError());
+    MAD_HIP(hipMemcpyAsync(out, *Z, bytes_Z, hipMemcpyDeviceToHost, ctx->stream));
+    MAD_HIP(hipStreamSynchronize(ctx->stream));
+    return MAD_OK;
+}
+
+extern "C" int mad_map_ifft(mad_ctx *ctx, const double *spectrum, int32_t N, double *out) {
+    if (ctx) mad_use_lane(ctx, 0);
+    if (!ctx || !spectrum || !out) return ctx ? mad_fail(ctx, MAD_EINVAL, "mad_map_ifft: NULL argument") : MAD_EINVAL;
+    double2 *Z = nullptr;
+    const int rc = map_ifft_run(ctx, spectrum, N, out, &Z);
     return fourier_free(ctx, Z, rc);
 }

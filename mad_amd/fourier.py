@@ -1,4 +1,6 @@
-"""Fourier shell correlation of two maps: the host side.
+"""Fourier shell correlation of two maps and radial filters in Fourier space (section 4m): the host side.
+The filters -- `filter_lattice`, `radial_gain`, the designs `gain_*` and the restatement `filter_numpy` -- have their contract
+further down.
 
 `plan_box` puts two grids of one spacing onto a common cubic lattice, `fsc_numpy` restates the contract of `mad_map_fsc` with
 `numpy.fft.fftn` in float64 -- the checker of the GPU tests, and the one place the contract is spelled out in code -- and `FSC` is
@@ -119,6 +121,105 @@ def fsc_numpy(g1, o1, g2, o2, voxsp, ramp=True):
     F1, F2 = split_pair(np.fft.fftn(Z))
     sums, count = shell_sums(F1, F2, delta, ramp)
     return FSC(Z.shape[0], voxsp, sums, count)
+
+
+# ---------------------------------------------------------------------------
+# radial filters: the contract of `mad_map_filter`
+#
+# One or two float32 grids [x, y, z], each placed at lattice index (0, 0, 0) -- a radial filter is shift-invariant, the grids need
+# no common frame.  N is the smallest power of two >= max(all dims) + pad, 8 <= N <= 1024; pad >= 0 is the zero margin between
+# the far face of the box and its near face on the circular lattice.  Z = FFT(g1 + i g2); Z(k) *= gain[r2], r2 = i^2 + j^2 + k^2
+# over the signed frequencies, a float64 table of 3 (N / 2)^2 + 1 entries; the inverse transform's real part over grid 1's box is
+# the filtered grid 1, its imaginary part over grid 2's box the filtered grid 2 (the gain is real and even).
+# ---------------------------------------------------------------------------
+
+def filter_lattice(dims, pad=0, dims2=None):
+    """-> N of `mad_map_filter` for grids of `dims` (and `dims2`) with `pad` voxels of zero margin.  ValueError beyond 1024."""
+    pad = int(pad)
+    if pad < 0:
+        raise ValueError("filter_lattice: pad %d (0 or more)" % pad)
+    longest = max(int(v) for v in tuple(dims) + (tuple(dims2) if dims2 is not None else ()))
+    if min(int(v) for v in tuple(dims) + (tuple(dims2) if dims2 is not None else ())) < 1:
+        raise ValueError("filter_lattice: empty grid")
+    if longest + pad > MAX_N:
+        raise ValueError("filter_lattice: the longest axis and the pad are %d + %d voxels, more than %d" % (longest, pad, MAX_N))
+    N = MIN_N
+    while N < longest + pad:
+        N *= 2
+    return N
+
+
+def gain_len(N):
+    """Entries of the gain table of a lattice of edge N: r2 = 0 .. 3 (N / 2)^2."""
+    return 3 * (N // 2) ** 2 + 1
+
+
+def radial_gain(N, voxsp, fn):
+    """float64 [gain_len(N)]: `fn` evaluated at f = sqrt(r2) / (N voxsp) (1 / Angstrom) for every r2.  ValueError where the
+    result is not finite (what `mad_map_filter` refuses)."""
+    voxsp = float(voxsp)
+    if not (voxsp > 0) or not np.isfinite(voxsp):
+        raise ValueError("radial_gain: voxsp %r (positive and finite)" % (voxsp,))
+    f = np.sqrt(np.arange(gain_len(N), dtype=np.float64)) / (N * voxsp)
+    g = np.ascontiguousarray(np.broadcast_to(np.asarray(fn(f), np.float64), f.shape))
+    if not np.isfinite(g).all():
+        raise ValueError("radial_gain: the gain is not finite at r2 = %d" % int(np.nonzero(~np.isfinite(g))[0][0]))
+    return g
+
+
+def gain_gaussian(f, d):
+    """exp(-(f d)^2): the transform of the Gaussian `structure_to_density` blurs atoms with at resolution d, sigma = d / (pi sqrt 2)
+    Angstrom.  A map low-passed to d and a model simulated at d carry the same envelope."""
+    f = np.asarray(f, np.float64)
+    return np.exp(-(f * d) ** 2)
+
+
+def gain_cosine(r, r_c, w):
+    """A raised-cosine edge in lattice units, r = sqrt(r2), r_c = N voxsp / d: 1 for r <= r_c - w / 2, 0 for r >= r_c + w / 2,
+    0.5 + 0.5 cos(pi (r - (r_c - w / 2)) / w) between; w = 0 is the top hat (1 for r <= r_c)."""
+    r = np.asarray(r, np.float64)
+    if w == 0:
+        return np.where(r <= r_c, 1.0, 0.0)
+    lo = r_c - w / 2.0
+    t = np.clip((r - lo) / w, 0.0, 1.0)
+    return np.where(r <= lo, 1.0, np.where(r >= r_c + w / 2.0, 0.0, 0.5 + 0.5 * np.cos(np.pi * t)))
+
+
+def gain_bfactor(f, B):
+    """exp(-B f^2 / 4): a temperature factor of B square Angstrom applied; negative B sharpens."""
+    f = np.asarray(f, np.float64)
+    return np.exp(-B * f * f / 4.0)
+
+
+def gain_curve(f, freq, gain):
+    """A tabulated curve `gain` over `freq` (1 / Angstrom, increasing), interpolated linearly and constant beyond its ends."""
+    return np.interp(np.asarray(f, np.float64), np.asarray(freq, np.float64), np.asarray(gain, np.float64))
+
+
+def r2_index(N):
+    """int64 [N, N, N]: i^2 + j^2 + k^2 of every lattice point, the index into a gain table."""
+    f = frequencies(N).astype(np.int64)
+    return f[:, None, None] ** 2 + f[None, :, None] ** 2 + f[None, None, :] ** 2
+
+
+def filter_numpy(g1, gain, pad=0, g2=None):
+    """The contract of `mad_map_filter` with numpy.fft in float64 -> the filtered grid 1 (with `g2`: both) as float64, before the
+    cast to float32: pack, fftn, multiply by gain[r2], ifftn, real / imaginary part, crop."""
+    g1 = np.asarray(g1)
+    g2 = None if g2 is None else np.asarray(g2)
+    N = filter_lattice(g1.shape, pad, None if g2 is None else g2.shape)
+    gain = np.asarray(gain, np.float64).reshape(-1)
+    if len(gain) != gain_len(N):
+        raise ValueError("filter_numpy: a gain table of %d entries, the %d^3 lattice needs %d" % (len(gain), N, gain_len(N)))
+    Z = np.zeros((N, N, N), np.complex128)
+    Z[:g1.shape[0], :g1.shape[1], :g1.shape[2]] = g1.astype(np.float64)
+    if g2 is not None:
+        Z[:g2.shape[0], :g2.shape[1], :g2.shape[2]] += 1j * g2.astype(np.float64)
+    Y = np.fft.ifftn(np.fft.fftn(Z) * gain[r2_index(N)])
+    out1 = np.ascontiguousarray(Y.real[:g1.shape[0], :g1.shape[1], :g1.shape[2]])
+    if g2 is None:
+        return out1
+    return out1, np.ascontiguousarray(Y.imag[:g2.shape[0], :g2.shape[1], :g2.shape[2]])
 
 
 class FSC(object):
