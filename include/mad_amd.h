@@ -315,7 +315,7 @@ int mad_set_batching(mad_ctx *ctx, int on);
  * holds at least this many pairs (default 4096) and at least 64 k.  "ori_queue" / "dsc_queue": entries in use of the queues through
  * which k_orient / k_describe hand the directions their fast classifiers cannot decide to the exact one (defaults: all 512 / 768);
  * a small value drives the kernels' full-queue paths for every anchor / row -- a test hook, the results are the same.  "fft_bpt"
- * (0 default, 1, 2, 4): butterflies per thread of k_fft_lines, i.e. which of its three forms mad_map_fft / mad_map_fsc / mad_map_filter / mad_map_ifft launch (by
+ * (0 default, 1, 2, 4): butterflies per thread of k_fft_lines, i.e. which of its three forms mad_map_fft / mad_map_fsc / mad_map_filter / mad_map_ifft / mad_map_scan launch (by
  * default 1 up to N = 256, 2 at 512, 4 at 1024; a value below that is raised to it) -- a test hook, the bits are the same. */
 int mad_set_option(mad_ctx *ctx, const char *name, double value);
 
@@ -617,6 +617,41 @@ int mad_map_fft(mad_ctx *ctx, const float *grid1, const int32_t dims1[3], const 
 int mad_map_filter(mad_ctx *ctx, const float *grid1, const int32_t dims1[3], const float *grid2 /* may be NULL */, const int32_t dims2[3],
                    int32_t pad, const double *gain /* NULL: size query */, int64_t n_gain, int32_t *N_out, float *out1, float *out2);
 int mad_map_ifft(mad_ctx *ctx, const double *spectrum, int32_t N, double *out);
+
+/*
+ * A model scanned over every whole-voxel translation of a map by fast local correlation (Roseman's scheme; mad_fourier.hip; DESIGN.md
+ * section 4n; restated with numpy in mad_amd/fourier.py::scan_numpy).  Host pointers, synchronous, lane 0; nothing is modified and no
+ * state survives the call.
+ *   Inputs.  map: float32 [x][y][z] of dims1.  templates: n_t >= 1 pointers to float32 grids, all of dims2, dims2[a] <= dims1[a].
+ *     mode 0: the un-centred score (the library's convention everywhere else); mode 1: the centred one (Roseman's local correlation).
+ *   Lattice.  N is the smallest power of two >= max(dims1), 8 <= N <= 1024; map and template each sit at lattice index (0, 0, 0).
+ *   Offsets.  u in [0, D[a]) per axis, D = dims1 - dims2 + 1: the template's box lies wholly inside the map's, no scored offset wraps
+ *     around the circular lattice.  best and best_t are [D[0]][D[1]][D[2]].
+ *   Per template, with w(x) = 1 where g(x) > iso else 0, g^ = g w, n_w = sum w, G = sum g^2, gbar = sum g^ / n_w (float64, in voxel
+ *     order): C(u) = sum_x m(u + x) g^(x), E(u) = sum_x m(u + x)^2 w(x), mode 1 also A(u) = sum_x m(u + x) w(x).
+ *     mode 0: score = C / sqrt(E G) where E > e_min.  mode 1: C' = C - A gbar, E' = E - A^2 / n_w, G' = G - n_w gbar^2,
+ *     score = C' / sqrt(E' G') where E' > e_min.  Elsewhere the offset is not scored: in empty regions E is round-off.
+ *   Across templates.  best(u) = the greatest float32 score of the templates that scored u, best_t(u) = the lowest template index
+ *     that attains it; 0.0 and -1 where none scored.
+ *   Peaks.  u is a peak when best_t(u) >= 0, best(u) >= min_score and every one of its 26 neighbours v inside the offset box has
+ *     best(v) < best(u), or best(v) == best(u) and a larger linear index.  Sorted by score descending, then linear index ascending;
+ *     the first k go to peaks[p] = (ux, uy, uz, score, template), *n_peaks = how many were written, *n_found = how many there are.
+ *   Spectra.  One transform of m + i m^2 serves all templates; per template one of g^ + i w, the product
+ *     M conj(G^) + i M2 conj(W) in place, and one inverse by the same line passes whose real part is C and imaginary part E; mode 1
+ *     adds M conj(W) on a third lattice and a second inverse for A.  Float64, no fused multiply-add, no floating-point atomics: two
+ *     calls return the same bits.
+ * best == NULL with N_out: the size query -- *N_out set, nothing allocated or launched (map and templates are not read).
+ * peaks may be NULL with k = 0.  N_out may be NULL otherwise.
+ * MAD_EINVAL: NULL (a template's pointer included), n_t < 1, a dimension < 1, iso, e_min or min_score not finite, e_min < 0, k < 0, a
+ * mode other than 0 or 1, a template with no voxel above iso, in mode 1 a template that is constant under its mask (G' <= 0) -- the
+ * template's index is in the message.  MAD_EDOM: max(dims1) > 1024, or dims2[a] > dims1[a].  MAD_ENOMEM: as mad_map_fsc (two
+ * lattices, in mode 1 three, both grids and the outputs are judged before anything is allocated).  Each leaves the outputs
+ * untouched, launches nothing, and the next call works.
+ */
+int mad_map_scan(mad_ctx *ctx, const float *map, const int32_t dims1[3], int32_t n_t, const float *const *templates, const int32_t dims2[3],
+                 double iso, double e_min, int32_t mode, double min_score, int64_t k, float *best, int32_t *best_t,
+                 double *peaks /* [k][5]: ux, uy, uz, score, template; may be NULL with k = 0 */, int64_t *n_peaks, int64_t *n_found,
+                 int32_t *N_out);
 
 /* ---- one subunit's pair grid sharded over GPUs by blocks of map rows (the exchange steps -- OR of the flag vectors,
  *      all-gather of the per-shard top-k -- are the caller's, mad_amd/dist.py::sharded_match, or the library's own:

@@ -13,7 +13,8 @@ counterpart in the reference), which is where the masks `mask_with` consumes com
 of atoms against the map through `mad_map_group_fit` (localfit.py; no counterpart in the reference).  `fsc` is the Fourier shell
 correlation of the map against a second map or a placed model through `mad_map_fsc` (fourier.py; no counterpart in the reference).
 `lowpass`, `highpass`, `sharpen` and `filter_radial` filter the map in Fourier space through `mad_map_filter` (fourier.py; no
-counterpart in the reference).
+counterpart in the reference).  `scan` scores every whole-voxel translation of a structure, in a handful of orientations, against the
+map through `mad_map_scan` (fourier.py; no counterpart in the reference: the exhaustive cross-check of a docked pose).
 None of them has a CPU fallback.  The reference's per-voxel text writer is replaced by `mapio.write_situs`.
 """
 import os
@@ -226,6 +227,60 @@ class Dmap(object):
             raise ValueError("Dmap.fsc: the second grid has %d dimensions" % g2.ndim)
         N, sums, count = _lib.get_lib().map_fsc(g1, (self.xi, self.yi, self.zi), g2, o2, voxsp)
         return fourier.FSC(N, voxsp, sums, count)
+
+    def scan(self, structure, resolution, rotations=None, mode="uncentred", isovalue=None, min_fill=0.25, min_score=0.0, k=20, masses=None):
+        """Where in the map does the structure fit best?  Every whole-voxel translation of it, in each of the given orientations,
+        scored by fast local correlation (Roseman's scheme) through `mad_map_scan` -> `fourier.Scan` (`best`, `best_t`, `peaks`,
+        `n_found`, `place(i, pdb)`, `write(outname)`).  `structure` as in `fsc`: a `PDB`, an (n, 3) array, or a list / tuple of those,
+        taken together (masses as in `fit_by_group`).  `rotations`: (n, 3, 3), applied about the structure's centroid c,
+        x -> (x - c) @ R + c; default: the identity alone.  Every rotated copy is simulated at `resolution` on the map's spacing
+        (`structure_to_density`) and put at the low corner of a common zero-filled box, the per-axis maximum over the rotations.  The
+        box has to fit into the map on every axis (`pad_grid` first where the structure may hang over a face).  mode "uncentred":
+        C / sqrt(E G), the library's convention everywhere else; "centred": Roseman's local correlation.  Template voxels above
+        `isovalue` (None: 0) make the mask.  An offset is scored where the map's energy under the mask exceeds
+        e_min = min_fill n_w mean(m^2) over all voxels of the map (centred: min_fill n_w var(m)), n_w the smallest mask over the
+        rotations -- a convention: it keeps round-off over round-off in empty regions from being reported as a score.  The first
+        `k` peaks of at least `min_score` come back, each with its rotation index and, through `Scan.pose(i)`, the translation
+        T = (map origin + u voxsp) - the rotated copy's grid origin.  The map is not modified.  DESIGN.md section 4n."""
+        from . import fourier, localfit
+        if mode not in ("uncentred", "centred"):
+            raise ValueError("Dmap.scan: mode %r ('uncentred' or 'centred')" % (mode,))
+        if resolution is None or not (float(resolution) > 0) or not np.isfinite(float(resolution)):
+            raise ValueError("Dmap.scan: resolution %r (positive and finite)" % (resolution,))
+        iso, min_fill = (0.0 if isovalue is None else float(isovalue)), float(min_fill)
+        if not np.isfinite(iso) or not (min_fill >= 0) or not np.isfinite(min_fill):
+            raise ValueError("Dmap.scan: isovalue %r, min_fill %r (finite, min_fill 0 or more)" % (isovalue, min_fill))
+        parts = localfit.structure_parts(structure)
+        mass = localfit.structure_masses(parts, masses)
+        if sum(len(c) for c, _, _ in parts) == 0:
+            raise ValueError("Dmap.scan: no atoms to simulate a density from")
+        coords = np.concatenate([c for c, _, _ in parts], axis=0)
+        rot = np.eye(3)[None] if rotations is None else np.asarray(rotations, np.float64)
+        if rot.ndim != 3 or rot.shape[1:] != (3, 3) or len(rot) == 0 or not np.isfinite(rot).all():
+            raise ValueError("Dmap.scan: rotations of shape %r, not (n, 3, 3) with n >= 1" % (rot.shape,))
+        g1 = np.ascontiguousarray(self.grid3d, dtype=np.float32)
+        if g1.ndim != 3 or g1.size == 0:
+            raise ValueError("Dmap.scan: the grid has shape %r" % (g1.shape,))
+        lib, voxsp, centroid = _lib.get_lib(), float(self.voxsp), coords.mean(axis=0)
+        grids, origins = [], []
+        for R in rot:
+            g, x0, y0, z0 = lib.structure_to_density((coords - centroid) @ R + centroid, mass, float(resolution), voxsp)
+            grids.append(g)
+            origins.append((x0, y0, z0))
+        d2 = tuple(max(g.shape[a] for g in grids) for a in range(3))
+        N, _ = fourier.scan_lattice(g1.shape, d2)      # ValueError where the box does not fit
+        templates = []
+        for g in grids:
+            t = np.zeros(d2, np.float32)
+            t[:g.shape[0], :g.shape[1], :g.shape[2]] = g
+            templates.append(t)
+        n_w = min(int((t.astype(np.float64) > iso).sum()) for t in templates)      # in float64, as the device compares
+        m64 = g1.astype(np.float64)
+        spread = float(np.mean(m64 * m64)) if mode == "uncentred" else float(np.var(m64))
+        e_min = min_fill * n_w * spread
+        md = 0 if mode == "uncentred" else 1
+        best, best_t, peaks, n_found, N = lib.map_scan(g1, templates, iso, e_min, md, float(min_score), int(k))
+        return fourier.Scan(best, best_t, peaks, n_found, (self.xi, self.yi, self.zi), voxsp, rot, centroid, origins, N=N, e_min=e_min, mode=md)
 
     def smooth(self, sigma):
         """A Gaussian of `sigma` Angstrom on the map, in place (zero beyond the box, float64 inside, 4 sigma wide on either side).

@@ -39,7 +39,7 @@ SYMBOLS = [
     "mad_dist_unique_id", "mad_dist_init", "mad_dist_destroy", "mad_dist_info", "mad_dist_rehearse_flags", "mad_dist_or_allreduce", "mad_dist_allgather",
     "mad_dist_allgather_topk", "mad_dist_scratch", "mad_dist_copy",
     "mad_set_wire_bytes", "mad_set_export", "mad_set_import", "mad_set_lane", "mad_set_stream", "mad_set_bind_lane",
-    "mad_upload_density", "mad_refine", "mad_last_refine_plan", "mad_last_density_chunks", "mad_structure_to_density", "mad_ccc", "mad_map_mask", "mad_map_ccc", "mad_map_resample", "mad_map_zone", "mad_map_group_fit", "mad_map_smooth", "mad_map_segment", "mad_map_fsc", "mad_map_fft", "mad_map_filter", "mad_map_ifft", "mad_density_ccc", "mad_dock_refine_score", "mad_grid_overlap", "mad_overlap_matrix",
+    "mad_upload_density", "mad_refine", "mad_last_refine_plan", "mad_last_density_chunks", "mad_structure_to_density", "mad_ccc", "mad_map_mask", "mad_map_ccc", "mad_map_resample", "mad_map_zone", "mad_map_group_fit", "mad_map_smooth", "mad_map_segment", "mad_map_fsc", "mad_map_fft", "mad_map_filter", "mad_map_ifft", "mad_map_scan", "mad_density_ccc", "mad_dock_refine_score", "mad_grid_overlap", "mad_overlap_matrix",
     "mad_space_create", "mad_space_destroy", "mad_space_build", "mad_space_info", "mad_space_download",
     "mad_space_peaks", "mad_space_patches", "mad_space_localize", "mad_localize_volume",
     "mad_pose_cluster_many",
@@ -1231,6 +1231,41 @@ class Lib(object):
         out = np.empty(s.shape, np.complex128)
         self._chk(self.dll.mad_map_ifft(self.ctx, _p(s), C.c_int32(s.shape[0]), _p(out)))
         return out
+
+    def map_scan_lattice(self, d1, d2):
+        """N of `map_scan` for a map of dims `d1` and templates of dims `d2`: the size query of mad_map_scan (nothing is allocated
+        or launched; it refuses what `fourier.scan_lattice` refuses)."""
+        d1, d2 = np.array(d1, np.int32).reshape(3), np.array(d2, np.int32).reshape(3)
+        n = C.c_int32(0)
+        self._chk(self.dll.mad_map_scan(self.ctx, None, _p(d1), C.c_int32(1), None, _p(d2), C.c_double(0.0), C.c_double(0.0), C.c_int32(0),
+                                        C.c_double(0.0), C.c_int64(0), None, None, None, None, None, C.byref(n)))
+        return int(n.value)
+
+    def map_scan(self, m, templates, iso=0.0, e_min=0.0, mode=0, min_score=0.0, k=20):
+        """Every whole-voxel translation of the templates inside the map `m`, scored by fast local correlation -> (best float32 [D],
+        best_t int32 [D], peaks float64 [min(k, n_found), 5] = ux, uy, uz, score, template; n_found, N) (mad_map_scan; DESIGN.md
+        section 4n; `fourier.scan_numpy` and `fourier.peaks_numpy` restate it).  `m` and the `templates` (a list of grids of one
+        shape, no longer than the map on any axis): C-contiguous float32 [x, y, z]; D = m.shape - template shape + 1.  mode 0: the
+        un-centred score C / sqrt(E G); 1: the centred one.  An offset is scored where E (E') > `e_min`.  Nothing is modified."""
+        templates = list(templates)
+        if len(templates) < 1:
+            raise ValueError("map_scan needs one template or more")
+        for g in templates:
+            self._fourier_args("map_scan", m, np.zeros(3), g, np.zeros(3))
+            if g.shape != templates[0].shape:
+                raise ValueError("map_scan needs templates of one shape, got %r and %r" % (templates[0].shape, g.shape))
+        d1, d2 = np.array(m.shape, np.int32), np.array(templates[0].shape, np.int32)
+        k = int(k)
+        if k < 0:
+            raise ValueError("map_scan: k = %d (0 or more)" % k)
+        D = tuple(max(int(a) - int(b) + 1, 1) for a, b in zip(m.shape, templates[0].shape))
+        ptrs = (C.c_void_p * len(templates))(*[g.ctypes.data for g in templates])
+        best, best_t, peaks = np.zeros(D, np.float32), np.full(D, -1, np.int32), np.zeros((max(k, 1), 5), np.float64)
+        n_peaks, n_found, n = C.c_int64(0), C.c_int64(0), C.c_int32(0)
+        self._chk(self.dll.mad_map_scan(self.ctx, _p(m), _p(d1), C.c_int32(len(templates)), ptrs, _p(d2), C.c_double(float(iso)),
+                                        C.c_double(float(e_min)), C.c_int32(int(mode)), C.c_double(float(min_score)), C.c_int64(k), _p(best),
+                                        _p(best_t), _p(peaks), C.byref(n_peaks), C.byref(n_found), C.byref(n)))
+        return best, best_t, peaks[:n_peaks.value].copy(), int(n_found.value), int(n.value)
 
     def map_zone(self, g, origin, voxsp, atoms, radius, soft=0.0, erase=False):
         """`g` (writable C-contiguous float32 [x, y, z] with `origin` and `voxsp`) cut around `atoms` in place: a voxel within

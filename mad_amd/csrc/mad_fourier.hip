@@ -1,4 +1,5 @@
-// mad_fourier.hip -- Fourier shell correlation of two maps (mad_map_fsc) and the 3-D transform under it (mad_map_fft).
+// mad_fourier.hip -- Fourier shell correlation of two maps (mad_map_fsc), the 3-D transform under it (mad_map_fft), radial filters
+// (mad_map_filter, mad_map_ifft) and the scan of a model over every translation of a map (mad_map_scan).
 // DESIGN.md section 4l has the contract; mad_amd/fourier.py restates it with numpy.
 //
 // Both float32 grids go onto ONE cubic complex128 lattice of edge N (a power of two, 8 .. 1024): grid 1 in the real part, grid 2
@@ -35,6 +36,9 @@
 // (0, 0, 0), Z = FFT(g1 + i g2) as above; k_fft_gain multiplies Z(k) by a real gain looked up by r2 = |k|^2 and conjugates, the same
 // three k_fft_lines passes follow (ifft(X) = conj(FFT(conj X)) / N^3), and k_fft_unpack writes Re Z / N^3 over grid 1's box and
 // -(Im Z) / N^3 over grid 2's as float32.  A gain that depends on r2 alone is real and even, so the two maps stay apart.
+//
+// The translation scan (mad_map_scan: k_scan_pack, k_scan_product, k_scan_score, k_scan_peaks) is at the end of the file: DESIGN.md
+// section 4n.
 #include <algorithm>
 #include <vector>
 
@@ -678,4 +682,296 @@ extern "C" int mad_map_ifft(mad_ctx *ctx, const double *spectrum, int32_t N, dou
     double2 *Z = nullptr;
     const int rc = map_ifft_run(ctx, spectrum, N, out, &Z);
     return fourier_free(ctx, Z, rc);
+}
+
+// ---------------------------------------------------------------------------
+// translation scan
+// ---------------------------------------------------------------------------
+// mad_map_scan scores every whole-voxel translation u of a template inside a map by fast local correlation (Roseman's scheme):
+// C(u) = sum m(u + x) g(x), E(u) = sum m(u + x)^2 w(x) and, centred, A(u) = sum m(u + x) w(x), with w = [g > iso] and g zeroed
+// outside w.  Map and template sit at lattice index (0, 0, 0); Zm = FFT(m + i m^2) stays for the call, per template
+// Zt = FFT(g w + i w); k_scan_product leaves conj(M conj(G) + i M2 conj(W)) in Zt (and conj(M conj(W)) in a third lattice), the
+// three k_fft_lines passes turn that into N^3 conj(C + i E), and k_scan_score forms the score over the box of offsets whose
+// template lies wholly inside the map (none of them wraps around the lattice) and keeps the best template per offset.
+
+#define SCAN_CAP0 4096      // peak candidates the list holds before it is grown to the count and k_scan_peaks runs again
+
+// TPL false: Z = m + i m^2 over the map's box.  TPL true: Z = g w + i w over the template's, w = 1 where g > iso.  Zero elsewhere.
+template <bool TPL>
+__global__ __launch_bounds__(256) void k_scan_pack(const float *__restrict__ g, unsigned d0, unsigned d1, unsigned d2, double iso, int logN,
+                                                   double2 *__restrict__ Z) {
+    const unsigned m = (1u << logN) - 1u;
+    const size_t n = (size_t)1 << (3 * logN);
+    for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (size_t)gridDim.x * 256) {
+        const unsigned c = (unsigned)i & m, b = (unsigned)(i >> logN) & m, a = (unsigned)(i >> (2 * logN));
+        double2 v = make_double2(0.0, 0.0);
+        if (a < d0 && b < d1 && c < d2) {
+            const double x = (double)g[((size_t)a * d1 + b) * d2 + c];
+            if (!TPL) v = make_double2(x, x * x);      // 24 x 24 bits: exact
+            else if (x > iso) v = make_double2(x, 1.0);
+        }
+        Z[i] = v;
+    }
+}
+
+// In place on the template's lattice.  With M, M2 split from Zm and G, W from Zt as k_fsc_shells splits a pair, X = M conj(G) and
+// Y = M2 conj(W): P(k) = X + i Y, and because all four signals are real P(-k) = conj(X) + i conj(Y).  A thread owns k and -k, reads
+// both lattices at both and writes conj P(k) = conj(X) - i conj(Y) and conj P(-k) = X - i Y (Zq, mode 1: conj Q(k) = conj(R),
+// conj Q(-k) = R, R = M conj(W)), ready for ifft(P) = conj(FFT(conj P)) / N^3.  A workgroup takes the z line (a, b) and its mirror
+// image (N - a, N - b) whole -- thread c pairs (a, b, c) with (N - a, N - b, N - c) --, so that both lines are read and written
+// end to end.  blockIdx.y = a runs over 0 .. N / 2 and blockIdx.x = b over 0 .. N - 1; where a is its own mirror image (0, N / 2)
+// the pair of lines belongs to the smaller b, and a line that is its own mirror image pairs c with N - c inside itself (c <= N / 2;
+// 0 and N / 2 are their own pair and are written once).
+// blockDim.x = min(N, 256), on purpose one pair of lines per workgroup at every N: below N = 64 that is part of a wave (8 to 32
+// lanes) and at N = 64 one wave, on lattices of at most 4 MiB whose whole product is a few microseconds beside the launches of the
+// six line passes around it; packing several pairs of lines into a workgroup for them was not built and not measured.
+__global__ __launch_bounds__(256) void k_scan_product(const double2 *__restrict__ Zm, double2 *__restrict__ Zt, double2 *__restrict__ Zq, int logN) {
+    const int N = 1 << logN, msk = N - 1;
+    const int b = (int)blockIdx.x, a = (int)blockIdx.y;
+    const int a2 = (N - a) & msk, b2 = (N - b) & msk;
+    if (a > (N >> 1) || b >= N || (a2 == a && b > b2)) return;
+    const bool self = a2 == a && b2 == b;      // uniform over the workgroup
+    const size_t l0 = ((((size_t)a) << logN) + b) << logN, l1 = ((((size_t)a2) << logN) + b2) << logN;
+    for (int c = (int)threadIdx.x; c < N; c += (int)blockDim.x) {
+        const int c2 = (N - c) & msk;
+        if (self && c > c2) continue;
+        const size_t i = l0 + c, j = l1 + c2;
+        const double2 zm = Zm[i], zn = Zm[j], zt = Zt[i], zu = Zt[j];
+        const double mx = (zm.x + zn.x) * 0.5, my = (zm.y - zn.y) * 0.5;      // M  = (Zm(k) + conj Zm(-k)) / 2
+        const double sx = (zm.y + zn.y) * 0.5, sy = (zn.x - zm.x) * 0.5;      // M2 = (Zm(k) - conj Zm(-k)) / (2i)
+        const double gx = (zt.x + zu.x) * 0.5, gy = (zt.y - zu.y) * 0.5;      // G
+        const double wx = (zt.y + zu.y) * 0.5, wy = (zu.x - zt.x) * 0.5;      // W
+        const double Xx = mx * gx + my * gy, Xy = my * gx - mx * gy;          // M conj(G)
+        const double Yx = sx * wx + sy * wy, Yy = sy * wx - sx * wy;          // M2 conj(W)
+        Zt[i] = make_double2(Xx - Yy, -(Xy + Yx));
+        if (j != i) Zt[j] = make_double2(Xx + Yy, Xy - Yx);
+        if (Zq) {
+            const double Rx = mx * wx + my * wy, Ry = my * wx - mx * wy;      // M conj(W)
+            Zq[i] = make_double2(Rx, -Ry);
+            if (j != i) Zq[j] = make_double2(Rx, Ry);
+        }
+    }
+}
+
+struct ScanScoreArgs {
+    int logN, mode, tpl;         // tpl: the template's index; template 0 initialises best / best_t
+    unsigned D1, D2;             // the offset box [D0][D1][D2]
+    size_t nD;
+    double scale;                // 1 / N^3
+    double e_min, G, gbar, n_w;  // G: G' in mode 1
+};
+
+// Over the box of offsets alone.  Zt holds N^3 conj(C + i E), Zq (mode 1) N^3 conj(A).  An offset is scored where E > e_min
+// (E' in mode 1); best / best_t take a strictly greater float32 score only, so the lowest template index keeps a tie.
+__global__ __launch_bounds__(256) void k_scan_score(const double2 *__restrict__ Zt, const double2 *__restrict__ Zq, const ScanScoreArgs A,
+                                                    float *__restrict__ best, int *__restrict__ best_t) {
+    for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < A.nD; i += (size_t)gridDim.x * 256) {
+        const unsigned q = (unsigned)i, t = q / A.D2, z = q - t * A.D2, x = t / A.D1, y = t - x * A.D1;
+        const size_t at = (((((size_t)x) << A.logN) + y) << A.logN) + z;
+        const double2 v = Zt[at];
+        double c = v.x * A.scale, e = -(v.y * A.scale);
+        if (A.mode) {
+            const double a = Zq[at].x * A.scale;
+            c = c - a * A.gbar;
+            e = e - (a * a) / A.n_w;
+        }
+        const bool scored = e > A.e_min;
+        const float s = scored ? (float)(c / sqrt(e * A.G)) : 0.0f;
+        if (A.tpl == 0) {
+            best[i] = s;
+            best_t[i] = scored ? 0 : -1;
+        } else if (scored && (best_t[i] < 0 || s > best[i])) {
+            best[i] = s;
+            best_t[i] = A.tpl;
+        }
+    }
+}
+
+// An offset is a peak when a template scored it, its score is at least min_score and every neighbour of the 26 inside the box is
+// smaller, or equal with a larger linear index.  Peaks are appended through an integer counter in any order (the host sorts);
+// *count ends as the number found, of which the first cap are in the list.
+__global__ __launch_bounds__(256) void k_scan_peaks(const float *__restrict__ best, const int *__restrict__ best_t, unsigned D0, unsigned D1,
+                                                    unsigned D2, size_t nD, double min_score, unsigned cap, unsigned *__restrict__ count,
+                                                    unsigned *__restrict__ list) {
+    for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < nD; i += (size_t)gridDim.x * 256) {
+        if (best_t[i] < 0) continue;
+        const float s = best[i];
+        if (!((double)s >= min_score)) continue;
+        const unsigned q = (unsigned)i, t = q / D2, z = q - t * D2, x = t / D1, y = t - x * D1;
+        bool peak = true;
+        for (int dx = -1; dx <= 1 && peak; dx++)
+            for (int dy = -1; dy <= 1 && peak; dy++)
+                for (int dz = -1; dz <= 1; dz++) {
+                    const unsigned nx = x + (unsigned)dx, ny = y + (unsigned)dy, nz = z + (unsigned)dz;      // below 0: wraps past any extent
+                    if ((dx == 0 && dy == 0 && dz == 0) || nx >= D0 || ny >= D1 || nz >= D2) continue;
+                    const size_t j = ((size_t)nx * D1 + ny) * D2 + nz;
+                    const float v = best[j];
+                    if (!(v < s || (v == s && j > i))) { peak = false; break; }
+                }
+        if (peak) {
+            const unsigned pos = atomicAdd(count, 1u);
+            if (pos < cap) list[pos] = q;
+        }
+    }
+}
+
+struct ScanLattices {
+    double2 *Z[3] = {nullptr, nullptr, nullptr};      // the map's, the template's, mode 1: the third
+};
+
+struct ScanStat { double n_w, G, gbar; };      // G: G' in mode 1
+
+static int map_scan_run(mad_ctx *ctx, const float *map, const int32_t *d1, int32_t n_t, const float *const *tpl, const int32_t *d2, double iso,
+                        double e_min, int32_t mode, double min_score, int64_t k, float *best, int32_t *best_t, double *peaks, int64_t *n_peaks,
+                        int64_t *n_found, int32_t *N_out, ScanLattices *L) {
+    static const double zero[3] = {0.0, 0.0, 0.0};
+    if (n_t < 1) return mad_fail(ctx, MAD_EINVAL, "mad_map_scan: %d templates (1 or more)", n_t);
+    MAD_TRY(fourier_check(ctx, "mad_map_scan", d1, zero, 1.0));
+    MAD_TRY(fourier_check(ctx, "mad_map_scan", d2, zero, 1.0));
+    if (!(fabs(iso) <= 1.7e308) || !(fabs(min_score) <= 1.7e308) || !(e_min >= 0.0 && e_min <= 1.7e308))
+        return mad_fail(ctx, MAD_EINVAL, "mad_map_scan: iso %g, e_min %g, min_score %g (finite, e_min 0 or more)", iso, e_min, min_score);
+    if (mode != 0 && mode != 1) return mad_fail(ctx, MAD_EINVAL, "mad_map_scan: mode %d (0 un-centred, 1 centred)", mode);
+    if (k < 0) return mad_fail(ctx, MAD_EINVAL, "mad_map_scan: k = %lld (0 or more)", (long long)k);
+    int longest = 0;
+    for (int a = 0; a < 3; a++) longest = std::max(longest, (int)d1[a]);
+    if (longest > FFT_MAX_N) return mad_fail(ctx, MAD_EDOM, "mad_map_scan: the map's longest axis is %d voxels, more than %d", longest, FFT_MAX_N);
+    for (int a = 0; a < 3; a++)
+        if (d2[a] > d1[a])
+            return mad_fail(ctx, MAD_EDOM, "mad_map_scan: the templates are %d voxels long on axis %d, the map %d: no offset keeps them inside", d2[a], a, d1[a]);
+    int N = FFT_MIN_N, logN = 3;
+    while (N < longest) { N <<= 1; logN++; }
+    if (N_out) *N_out = N;
+    if (!best) return MAD_OK;      // the size query
+    const unsigned D[3] = {(unsigned)(d1[0] - d2[0] + 1), (unsigned)(d1[1] - d2[1] + 1), (unsigned)(d1[2] - d2[2] + 1)};
+    const size_t n1 = (size_t)d1[0] * d1[1] * d1[2], n2 = (size_t)d2[0] * d2[1] * d2[2], nD = (size_t)D[0] * D[1] * D[2];
+
+    // n_w, G and the sum of every template, in voxel order in float64, before anything is allocated
+    std::vector<ScanStat> st((size_t)n_t);
+    for (int32_t j = 0; j < n_t; j++) {
+        if (!tpl[j]) return mad_fail(ctx, MAD_EINVAL, "mad_map_scan: template %d is NULL", j);
+        double n_w = 0.0, G = 0.0, S = 0.0;
+        for (size_t i = 0; i < n2; i++) {
+            const double x = (double)tpl[j][i];
+            if (x > iso) { n_w += 1.0; G += x * x; S += x; }
+        }
+        if (!(n_w > 0.0)) return mad_fail(ctx, MAD_EINVAL, "mad_map_scan: template %d has no voxel above iso = %g", j, iso);
+        st[j].n_w = n_w; st[j].G = G; st[j].gbar = 0.0;
+        if (!(G > 0.0 && G <= 1.7e308)) return mad_fail(ctx, MAD_EINVAL, "mad_map_scan: template %d has G = %g under its mask", j, G);
+        if (mode) {
+            st[j].gbar = S / n_w;
+            st[j].G = G - n_w * (st[j].gbar * st[j].gbar);
+            if (!(st[j].G > 0.0)) return mad_fail(ctx, MAD_EINVAL, "mad_map_scan: template %d is constant under its mask (G' = %g)", j, st[j].G);
+        }
+    }
+
+    const int n_lat = mode ? 3 : 2;
+    const size_t bytes_Z = (size_t)16 << (3 * logN);
+    const size_t b_best = (nD * 4 + 15) & ~(size_t)15, b_out = 2 * b_best + 16, b_list = (size_t)SCAN_CAP0 * 4;
+    const size_t grow_g = mad_sb(ctx, S_TMP_G).cap >= b_out ? 0 : b_out + b_out / 4, grow_j = mad_sb(ctx, S_TMP_J).cap >= b_list ? 0 : b_list + b_list / 4;
+    MAD_TRY(fourier_room(ctx, "mad_map_scan", N, logN, n1, n2, (size_t)(n_lat - 1) * bytes_Z + grow_g + grow_j));
+    MAD_TRY(fourier_twiddles(ctx, N));
+    MAD_TRY(mad_reserve(ctx, mad_sb(ctx, S_TMP_H), (n1 + 4) * 4));
+    MAD_TRY(mad_reserve(ctx, mad_sb(ctx, S_TMP_I), (n2 + 4) * 4));
+    MAD_TRY(mad_reserve(ctx, mad_sb(ctx, S_TMP_G), b_out));
+    MAD_TRY(mad_reserve(ctx, mad_sb(ctx, S_TMP_J), b_list));
+    for (int l = 0; l < n_lat; l++) MAD_TRY(fourier_alloc(ctx, "mad_map_scan", N, logN, &L->Z[l]));
+    double2 *Zm = L->Z[0], *Zt = L->Z[1], *Zq = L->Z[2];
+    float *d_map = scratch<float>(ctx, S_TMP_H), *d_tpl = scratch<float>(ctx, S_TMP_I);
+    char *blk = scratch<char>(ctx, S_TMP_G);
+    float *d_best = (float *)blk;
+    int *d_best_t = (int *)(blk + b_best);
+    unsigned *d_count = (unsigned *)(blk + 2 * b_best);
+    const unsigned wg_Z = fourier_blocks(ctx, (size_t)1 << (3 * logN)), wg_D = fourier_blocks(ctx, nD);
+    const int threads = std::min(N, 256);
+
+    MAD_HIP(hipMemcpyAsync(d_map, map, n1 * 4, hipMemcpyHostToDevice, ctx->stream));
+    mad_timer_begin(ctx, MAD_T_SCAN);
+    hipLaunchKernelGGL(k_scan_pack<false>, dim3(wg_Z), dim3(256), 0, ctx->stream, (const float *)d_map, (unsigned)d1[0], (unsigned)d1[1], (unsigned)d1[2],
+                       0.0, logN, Zm);
+    mad_timer_end(ctx, MAD_T_SCAN);
+    mad_timer_begin(ctx, MAD_T_FFT);
+    int rc = fourier_passes(ctx, Zm, logN);
+    mad_timer_end(ctx, MAD_T_FFT);
+    if (rc != MAD_OK) return rc;
+    MAD_HIP(hipGetLastError());
+
+    ScanScoreArgs A;
+    memset(&A, 0, sizeof(A));
+    A.logN = logN; A.mode = mode; A.D1 = D[1]; A.D2 = D[2]; A.nD = nD; A.scale = ldexp(1.0, -3 * logN); A.e_min = e_min;
+    for (int32_t j = 0; j < n_t; j++) {
+        MAD_HIP(hipMemcpyAsync(d_tpl, tpl[j], n2 * 4, hipMemcpyHostToDevice, ctx->stream));
+        mad_timer_begin(ctx, MAD_T_SCAN);
+        hipLaunchKernelGGL(k_scan_pack<true>, dim3(wg_Z), dim3(256), 0, ctx->stream, (const float *)d_tpl, (unsigned)d2[0], (unsigned)d2[1],
+                           (unsigned)d2[2], iso, logN, Zt);
+        mad_timer_end(ctx, MAD_T_SCAN);
+        mad_timer_begin(ctx, MAD_T_FFT);
+        rc = fourier_passes(ctx, Zt, logN);
+        mad_timer_end(ctx, MAD_T_FFT);
+        if (rc != MAD_OK) return rc;
+        mad_timer_begin(ctx, MAD_T_SCAN);
+        hipLaunchKernelGGL(k_scan_product, dim3((unsigned)N, (unsigned)(N / 2 + 1)), dim3(threads), 0, ctx->stream, (const double2 *)Zm, Zt, Zq, logN);
+        mad_timer_end(ctx, MAD_T_SCAN);
+        mad_timer_begin(ctx, MAD_T_FFT);
+        rc = fourier_passes(ctx, Zt, logN);
+        if (rc == MAD_OK && mode) rc = fourier_passes(ctx, Zq, logN);
+        mad_timer_end(ctx, MAD_T_FFT);
+        if (rc != MAD_OK) return rc;
+        A.tpl = j; A.G = st[j].G; A.gbar = st[j].gbar; A.n_w = st[j].n_w;
+        mad_timer_begin(ctx, MAD_T_SCAN);
+        hipLaunchKernelGGL(k_scan_score, dim3(wg_D), dim3(256), 0, ctx->stream, (const double2 *)Zt, (const double2 *)Zq, A, d_best, d_best_t);
+        mad_timer_end(ctx, MAD_T_SCAN);
+        MAD_HIP(hipGetLastError());
+    }
+
+    // the peaks: the list holds `cap` candidates; where more were found and some are wanted it grows to the count and the kernel
+    // runs again, while best is still on the device
+    unsigned cap = SCAN_CAP0, found = 0;
+    for (int pass = 0; pass < 2; pass++) {
+        MAD_HIP(hipMemsetAsync(d_count, 0, 16, ctx->stream));
+        mad_timer_begin(ctx, MAD_T_SCAN);
+        hipLaunchKernelGGL(k_scan_peaks, dim3(wg_D), dim3(256), 0, ctx->stream, (const float *)d_best, (const int *)d_best_t, D[0], D[1], D[2], nD,
+                           min_score, cap, d_count, scratch<unsigned>(ctx, S_TMP_J));
+        mad_timer_end(ctx, MAD_T_SCAN);
+        MAD_HIP(hipGetLastError());
+        MAD_HIP(hipMemcpyAsync(&found, d_count, 4, hipMemcpyDeviceToHost, ctx->stream));
+        MAD_HIP(hipStreamSynchronize(ctx->stream));
+        if (found <= cap || k == 0) break;
+        if (pass == 1) return mad_fail(ctx, MAD_EHIP, "mad_map_scan: %u peaks after %u were counted", found, cap);
+        size_t free_b = 0, total_b = 0;
+        MAD_HIP(hipMemGetInfo(&free_b, &total_b));
+        if ((size_t)found * 5 + ((size_t)8 << 20) > free_b)
+            return mad_fail(ctx, MAD_ENOMEM, "mad_map_scan: a list of %u peaks needs %zu MiB of device memory, %zu MiB are free", found,
+                            ((size_t)found * 5) >> 20, free_b >> 20);
+        MAD_TRY(mad_reserve(ctx, mad_sb(ctx, S_TMP_J), (size_t)found * 4));
+        cap = found;
+    }
+    const size_t n_list = k == 0 ? 0 : (size_t)std::min(found, cap);
+    std::vector<unsigned> list(n_list);
+    MAD_HIP(hipMemcpyAsync(best, d_best, nD * 4, hipMemcpyDeviceToHost, ctx->stream));
+    MAD_HIP(hipMemcpyAsync(best_t, d_best_t, nD * 4, hipMemcpyDeviceToHost, ctx->stream));
+    if (n_list) MAD_HIP(hipMemcpyAsync(list.data(), scratch<unsigned>(ctx, S_TMP_J), n_list * 4, hipMemcpyDeviceToHost, ctx->stream));
+    MAD_HIP(hipStreamSynchronize(ctx->stream));
+    // score descending, then linear index ascending: the order of the list does not depend on the order of the appends
+    std::sort(list.begin(), list.end(), [best](unsigned p, unsigned q) { return best[p] > best[q] || (best[p] == best[q] && p < q); });
+    const int64_t n_out = std::min<int64_t>(k, (int64_t)n_list);
+    for (int64_t p = 0; p < n_out; p++) {
+        const unsigned q = list[(size_t)p], t = q / D[2];
+        peaks[5 * p] = (double)(t / D[1]); peaks[5 * p + 1] = (double)(t % D[1]); peaks[5 * p + 2] = (double)(q % D[2]);
+        peaks[5 * p + 3] = (double)best[q]; peaks[5 * p + 4] = (double)best_t[q];
+    }
+    *n_peaks = n_out;
+    *n_found = (int64_t)found;
+    return MAD_OK;
+}
+
+extern "C" int mad_map_scan(mad_ctx *ctx, const float *map, const int32_t dims1[3], int32_t n_t, const float *const *templates,
+                            const int32_t dims2[3], double iso, double e_min, int32_t mode, double min_score, int64_t k, float *best,
+                            int32_t *best_t, double *peaks, int64_t *n_peaks, int64_t *n_found, int32_t *N_out) {
+    if (ctx) mad_use_lane(ctx, 0);
+    if (!ctx || !dims1 || !dims2 || (!best && !N_out) || (best && (!map || !templates || !best_t || !n_peaks || !n_found || (k > 0 && !peaks))))
+        return ctx ? mad_fail(ctx, MAD_EINVAL, "mad_map_scan: NULL argument") : MAD_EINVAL;
+    ScanLattices L;
+    int rc = map_scan_run(ctx, map, dims1, n_t, templates, dims2, iso, e_min, mode, min_score, k, best, best_t, peaks, n_peaks, n_found, N_out, &L);
+    for (int l = 0; l < 3; l++) rc = fourier_free(ctx, L.Z[l], rc);
+    return rc;
 }

@@ -1,6 +1,6 @@
 """Fourier shell correlation of two maps and radial filters in Fourier space (section 4m): the host side.
 The filters -- `filter_lattice`, `radial_gain`, the designs `gain_*` and the restatement `filter_numpy` -- have their contract
-further down.
+further down, and so has the translation scan (section 4n): `scan_lattice`, the restatement `scan_numpy`, `peaks_numpy` and `Scan`.
 
 `plan_box` puts two grids of one spacing onto a common cubic lattice, `fsc_numpy` restates the contract of `mad_map_fsc` with
 `numpy.fft.fftn` in float64 -- the checker of the GPU tests, and the one place the contract is spelled out in code -- and `FSC` is
@@ -220,6 +220,181 @@ def filter_numpy(g1, gain, pad=0, g2=None):
     if g2 is None:
         return out1
     return out1, np.ascontiguousarray(Y.imag[:g2.shape[0], :g2.shape[1], :g2.shape[2]])
+
+
+# ---------------------------------------------------------------------------
+# translation scan: the contract of `mad_map_scan`
+#
+# A map m (float32 [x, y, z], dims d1) and n_t >= 1 templates g_j of common dims d2 <= d1 per axis, each at lattice index (0, 0, 0) of
+# a cubic lattice whose edge N is the smallest power of two >= max(d1), 8 <= N <= 1024.  Offsets u in [0, D), D = d1 - d2 + 1: the
+# template's box lies wholly inside the map's, so no scored offset wraps around the lattice.  Per template, w = [g > iso], g^ = g w,
+# n_w = sum w, G = sum g^2, gbar = sum g^ / n_w:  C(u) = sum_x m(u + x) g^(x), E(u) = sum_x m(u + x)^2 w(x), A(u) = sum_x m(u + x) w(x).
+# mode 0: score = C / sqrt(E G) where E > e_min.  mode 1: C' = C - A gbar, E' = E - A^2 / n_w, G' = G - n_w gbar^2,
+# score = C' / sqrt(E' G') where E' > e_min.  best = the greatest float32 score over the templates that scored an offset, best_t the
+# lowest template that attains it; 0.0 and -1 where none scored.  Spectra: M, M2 = split_pair(FFT(m + i m^2)),
+# G^, W = split_pair(FFT(g^ + i w)), ifft(M conj(G^) + i M2 conj(W)) = C + i E, ifft(M conj(W)) = A.
+# ---------------------------------------------------------------------------
+
+def scan_lattice(d1, d2):
+    """-> (N, D) of `mad_map_scan`: the lattice edge and the box of offsets D = d1 - d2 + 1 (int tuple).  ValueError where the
+    call refuses: an empty grid, max(d1) > 1024, or a template longer than the map on an axis."""
+    d1, d2 = tuple(int(v) for v in d1), tuple(int(v) for v in d2)
+    if len(d1) != 3 or len(d2) != 3 or min(d1 + d2) < 1:
+        raise ValueError("scan_lattice: empty grid (%r, %r)" % (d1, d2))
+    if max(d1) > MAX_N:
+        raise ValueError("scan_lattice: the map's longest axis is %d voxels, more than %d" % (max(d1), MAX_N))
+    for a in range(3):
+        if d2[a] > d1[a]:
+            raise ValueError("scan_lattice: the template is %d voxels long on axis %d, the map %d" % (d2[a], a, d1[a]))
+    N = MIN_N
+    while N < max(d1):
+        N *= 2
+    return N, tuple(d1[a] - d2[a] + 1 for a in range(3))
+
+
+def scan_template(g, iso):
+    """-> (g^ float64, w float64, n_w, G, gbar) of one template: w = [g > iso], g^ = g w."""
+    g = np.asarray(g).astype(np.float64)
+    w = (g > float(iso)).astype(np.float64)
+    gh = g * w
+    n_w = float(w.sum())
+    if n_w == 0:
+        raise ValueError("scan_template: no voxel above iso = %r" % (iso,))
+    return gh, w, n_w, float((gh * gh).sum()), float(gh.sum()) / n_w
+
+
+def scan_inverse(m, g, iso, mode=0):
+    """-> (p, q): the full inverse lattices complex128 [N, N, N] of one template, p = ifft(M conj(G^) + i M2 conj(W)) = C + i E and,
+    in mode 1, q = ifft(M conj(W)) = A (else None)."""
+    m = np.asarray(m).astype(np.float64)
+    N, _ = scan_lattice(m.shape, np.shape(g))
+    gh, w = scan_template(g, iso)[:2]
+    Zm, Zt = np.zeros((N, N, N), np.complex128), np.zeros((N, N, N), np.complex128)
+    Zm[:m.shape[0], :m.shape[1], :m.shape[2]] = m + 1j * (m * m)
+    Zt[:gh.shape[0], :gh.shape[1], :gh.shape[2]] = gh + 1j * w
+    M, M2 = split_pair(np.fft.fftn(Zm))
+    Gh, W = split_pair(np.fft.fftn(Zt))
+    p = np.fft.ifftn(M * np.conj(Gh) + 1j * (M2 * np.conj(W)))
+    return p, (np.fft.ifftn(M * np.conj(W)) if mode else None)
+
+
+def scan_numpy(m, templates, iso, e_min, mode):
+    """The contract of `mad_map_scan` with numpy.fft in float64 -> (best float64 [D] before the cast to float32 -- the maximum is
+    taken on the float32 values, as the device takes it --, best_t int32 [D], and per template the lists C, E (C', E' in mode 1:
+    what is scored), G (G' in mode 1) and n_w).  An offset is scored by a template where E > e_min."""
+    if mode not in (0, 1):
+        raise ValueError("scan_numpy: mode %r (0 un-centred, 1 centred)" % (mode,))
+    e_min = float(e_min)
+    if not (e_min >= 0) or not np.isfinite(e_min) or not np.isfinite(float(iso)):
+        raise ValueError("scan_numpy: iso %r, e_min %r (finite, e_min 0 or more)" % (iso, e_min))
+    templates = list(templates)
+    if len(templates) < 1:
+        raise ValueError("scan_numpy: no template")
+    m = np.asarray(m)
+    _, D = scan_lattice(m.shape, np.shape(templates[0]))
+    best, best32, best_t = np.zeros(D), np.zeros(D, np.float32), np.full(D, -1, np.int32)
+    Cs, Es, Gs, ns = [], [], [], []
+    for j, g in enumerate(templates):
+        if np.shape(g) != np.shape(templates[0]):
+            raise ValueError("scan_numpy: template %d has shape %r, template 0 %r" % (j, np.shape(g), np.shape(templates[0])))
+        _, _, n_w, G, gbar = scan_template(g, iso)
+        p, q = scan_inverse(m, g, iso, mode)
+        C = np.ascontiguousarray(p.real[:D[0], :D[1], :D[2]])
+        E = np.ascontiguousarray(p.imag[:D[0], :D[1], :D[2]])
+        if mode:
+            A = q.real[:D[0], :D[1], :D[2]]
+            C = C - A * gbar
+            E = E - (A * A) / n_w
+            G = G - n_w * (gbar * gbar)
+            if not G > 0:
+                raise ValueError("scan_numpy: template %d is constant under its mask (G' = %r)" % (j, G))
+        scored = E > e_min
+        s = np.zeros(D)
+        s[scored] = C[scored] / np.sqrt(E[scored] * G)
+        s32 = s.astype(np.float32)
+        take = scored & ((best_t < 0) | (s32 > best32))
+        best[take], best32[take], best_t[take] = s[take], s32[take], j
+        Cs.append(C); Es.append(E); Gs.append(G); ns.append(n_w)
+    return best, best_t, Cs, Es, Gs, ns
+
+
+def peaks_numpy(best, best_t, min_score, k):
+    """The peaks of a score volume -> (peaks float64 [min(k, n_found), 5] = ux, uy, uz, score, template; n_found).  An offset is a
+    peak when best_t >= 0, best >= min_score and every one of the 26 neighbours inside the box is smaller, or equal with a larger
+    linear index; sorted by score descending, then linear index ascending."""
+    best, best_t = np.asarray(best), np.asarray(best_t)
+    D = best.shape
+    idx = np.arange(best.size, dtype=np.int64).reshape(D)
+    ok = (best_t >= 0) & (best.astype(np.float64) >= float(min_score))
+    pb = np.pad(best.astype(np.float64), 1, mode="constant", constant_values=-np.inf)      # outside the box: ignored
+    pi = np.pad(idx, 1, mode="constant", constant_values=-1)
+    for dx in (0, 1, 2):
+        for dy in (0, 1, 2):
+            for dz in (0, 1, 2):
+                if (dx, dy, dz) == (1, 1, 1):
+                    continue
+                v = pb[dx:dx + D[0], dy:dy + D[1], dz:dz + D[2]]
+                j = pi[dx:dx + D[0], dy:dy + D[1], dz:dz + D[2]]
+                ok &= (j < 0) | (v < best) | ((v == best) & (j > idx))
+    found = idx[ok]
+    order = np.lexsort((found, -best[ok].astype(np.float64)))
+    found = found[order][:max(int(k), 0)]
+    out = np.zeros((len(found), 5))
+    out[:, 0], out[:, 1], out[:, 2] = np.unravel_index(found, D) if len(found) else ((), (), ())
+    out[:, 3] = best.reshape(-1)[found]
+    out[:, 4] = best_t.reshape(-1)[found]
+    return out, int(ok.sum())
+
+
+class Scan(object):
+    """What `Dmap.scan` returns.  `best` float32 [D]: the best score over the rotations at every whole-voxel offset; `best_t` int32
+    [D]: the rotation that attains it, -1 where none was scored; `peaks`: float64 [n, 5] = ux, uy, uz, score, rotation, the best
+    first; `n_found`: how many peaks there are (`peaks` holds the first k).  `origin`, `voxsp`: where offset (0, 0, 0) puts the
+    template's voxel (0, 0, 0), i.e. the map's origin and spacing.  `rotations` [n, 3, 3], `centroid` and `template_origins` [n, 3]
+    (the grid origin of every rotated copy's box before it is moved) turn a peak into a placement: a point x of the structure goes to
+    (x - centroid) @ R + centroid + T, T = origin + u voxsp - template_origins[rotation]."""
+
+    def __init__(self, best, best_t, peaks, n_found, origin, voxsp, rotations, centroid, template_origins, N=0, e_min=0.0, mode=0):
+        self.best, self.best_t = best, best_t
+        self.peaks = np.asarray(peaks, np.float64).reshape(-1, 5)
+        self.n_found = int(n_found)
+        self.origin = np.asarray(origin, np.float64).reshape(3)
+        self.voxsp = float(voxsp)
+        self.rotations = np.asarray(rotations, np.float64).reshape(-1, 3, 3)
+        self.centroid = np.asarray(centroid, np.float64).reshape(3)
+        self.template_origins = np.asarray(template_origins, np.float64).reshape(-1, 3)
+        self.N, self.e_min, self.mode = int(N), float(e_min), int(mode)
+
+    def pose(self, i):
+        """-> (rotation index, R [3, 3], T [3], score) of peak i."""
+        ux, uy, uz, score, j = self.peaks[i]
+        j = int(j)
+        T = self.origin + np.array([ux, uy, uz]) * self.voxsp - self.template_origins[j]
+        return j, self.rotations[j], T, float(score)
+
+    def place(self, i, pdb):
+        """The structure at peak i: a copy of `pdb` (a `PDB`: a new `PDB` with the coordinates moved; an (n, 3) array: a new array)."""
+        _, R, T, _ = self.pose(i)
+        if hasattr(pdb, "get_coords"):
+            import copy
+            out = copy.deepcopy(pdb)
+            out.set_coords((np.asarray(pdb.get_coords(), np.float64) - self.centroid) @ R + self.centroid + T)
+            return out
+        return (np.asarray(pdb, np.float64) - self.centroid) @ R + self.centroid + T
+
+    def write_peaks(self, path):
+        """Columns rank, ux, uy, uz (voxels), score, rotation, tx, ty, tz (Angstrom)."""
+        with open(path, "w") as f:
+            f.write("rank,ux,uy,uz,score,rotation,tx,ty,tz\n")
+            for i in range(len(self.peaks)):
+                j, _, T, score = self.pose(i)
+                f.write("%d,%d,%d,%d,%.9g,%d,%.6f,%.6f,%.6f\n" % ((i,) + tuple(int(v) for v in self.peaks[i][:3]) + (score, j) + tuple(T)))
+
+    def write(self, outname):
+        """The score volume as a map whose origin is the map's origin (.sit / .situs: Situs, anything else MRC): the value at a voxel
+        is the best score of the template whose voxel (0, 0, 0) is placed there."""
+        from . import mapio
+        mapio.write_volume(outname, np.ascontiguousarray(self.best, np.float32), tuple(self.origin), self.voxsp)
 
 
 class FSC(object):
