@@ -316,7 +316,9 @@ int mad_set_batching(mad_ctx *ctx, int on);
  * which k_orient / k_describe hand the directions their fast classifiers cannot decide to the exact one (defaults: all 512 / 768);
  * a small value drives the kernels' full-queue paths for every anchor / row -- a test hook, the results are the same.  "fft_bpt"
  * (0 default, 1, 2, 4): butterflies per thread of k_fft_lines, i.e. which of its three forms mad_map_fft / mad_map_fsc / mad_map_filter / mad_map_ifft / mad_map_scan launch (by
- * default 1 up to N = 256, 2 at 512, 4 at 1024; a value below that is raised to it) -- a test hook, the bits are the same. */
+ * default 1 up to N = 256, 2 at 512, 4 at 1024; a value below that is raised to it) -- a test hook, the bits are the same.
+ * "search_prune" (1 default, 0): 0 makes mad_map_search run full line passes instead of the pruned ones -- a test hook, it changes
+ * speed, never numbers. */
 int mad_set_option(mad_ctx *ctx, const char *name, double value);
 
 /*
@@ -652,6 +654,44 @@ int mad_map_scan(mad_ctx *ctx, const float *map, const int32_t dims1[3], int32_t
                  double iso, double e_min, int32_t mode, double min_score, int64_t k, float *best, int32_t *best_t,
                  double *peaks /* [k][5]: ux, uy, uz, score, template; may be NULL with k = 0 */, int64_t *n_peaks, int64_t *n_found,
                  int32_t *N_out);
+
+/*
+ * A model searched over rotations and every whole-voxel translation of a map: mad_map_scan's scores with the templates made on the
+ * device, one per rotation of ONE base template (mad_fourier.hip; restated with numpy in
+ * mad_amd/fourier.py::search_numpy, rotate_numpy and tree_sum).  Host pointers, synchronous, lane 0; nothing is modified and no state
+ * survives the call.  Between the first rotation and the last nothing comes back to the host.
+ *   Inputs.  map: float32 [x][y][z] of dims1.  base: float32 of dims0 (any shape).  c0: the centre of rotation in base's voxel
+ *     coordinates (may be fractional).  edge e >= 1, e <= dims1[a]: the rotated template is a cube of e^3 voxels.  rotations: n_r >= 1
+ *     row-major 3 x 3 matrices R_j (the library moves points by y = (x - c) @ R + c).
+ *   Rotated template.  c2 = (e - 1) / 2; for the cube's voxel x, d = x - c2 and p_a = c0_a + ((d_0 R[a][0] + d_1 R[a][1]) + d_2 R[a][2]);
+ *     f = floor(p), t = p - f; the eight corners f, f + 1 are read from base, a corner outside it is 0 (so a p at or beyond -1 or
+ *     dims0[a] gives 0); lerp(a, b, t) = a + t (b - a) along z, then y, then x; float64 in exactly this order without fused
+ *     multiply-add; the result rounded to float32 is the template voxel g_j(x).
+ *   Mask and sums.  w = [g_j > iso] (compared in float64), n_w = sum w, G = tree_sum(g^2 w), S = tree_sum(g w) over the cube in linear
+ *     [x][y][z] order.  tree_sum: runs of 256 consecutive elements (the last zero-padded) are each summed by halving -- x[0:128] +
+ *     x[128:256], then 64, ... 1 --, and the partial sums the same way until one value is left.  mode 1: gbar = S / n_w,
+ *     G' = G - n_w (gbar gbar).
+ *   Skipped rotations.  A rotation with n_w = 0, G not in (0, 1.7e308] or, in mode 1, G' <= 0 scores no offset; *n_skipped counts
+ *     them.  That is not an error (the sums exist only on the device): with every rotation skipped best is 0.0, best_r -1, *n_found 0.
+ *   Scores, best, best_r and peaks: as mad_map_scan over D = dims1 - e + 1 with the floor e_min_j = e_fill n_w_j (one float64
+ *     product); peaks[p] = (ux, uy, uz, score, rotation).
+ *   Line passes.  With the option "search_prune" (default 1) the forward passes skip the lines and elements that are zero (the
+ *     template fills e^3 of N^3) and the inverse passes the lines no scored offset reads; 0 runs full passes: the same numbers.
+ * best == NULL with N_out: the size query -- *N_out set, nothing allocated or launched.  peaks may be NULL with k = 0.
+ * MAD_EINVAL: NULL, n_r < 1, edge < 1, a dimension < 1, c0, iso, e_fill or min_score not finite, e_fill < 0, k < 0, a mode other than
+ * 0 or 1, a rotation with an entry that is not finite or with max |R R^T - I| > 1e-6 (its index is in the message).  MAD_EDOM:
+ * max(dims1) > 1024, or edge > dims1[a].  MAD_ENOMEM: as mad_map_scan.  Each is decided before anything is allocated or launched,
+ * leaves the outputs untouched, and the next call works.
+ */
+int mad_map_search(mad_ctx *ctx, const float *map, const int32_t dims1[3], const float *base, const int32_t dims0[3], const double c0[3],
+                   int32_t edge, const double *rotations /* [n_r][9] */, int32_t n_r, double iso, double e_fill, int32_t mode, double min_score,
+                   int64_t k, float *best, int32_t *best_r, double *peaks /* [k][5]: ux, uy, uz, score, rotation; may be NULL with k = 0 */,
+                   int64_t *n_peaks, int64_t *n_found, int32_t *n_skipped, int32_t *N_out);
+
+/* One rotated template of mad_map_search and its sums, for testing them alone: out float32 [edge^3] = g_j(x) (before the mask),
+ * stats = (n_w, G, S).  MAD_EINVAL as above; MAD_EDOM: edge > 1024. */
+int mad_map_rotate(mad_ctx *ctx, const float *base, const int32_t dims0[3], const double c0[3], int32_t edge, const double R[9], double iso,
+                   float *out /* float32 [e^3] */, double stats[3] /* n_w, G, S */);
 
 /* ---- one subunit's pair grid sharded over GPUs by blocks of map rows (the exchange steps -- OR of the flag vectors,
  *      all-gather of the per-shard top-k -- are the caller's, mad_amd/dist.py::sharded_match, or the library's own:

@@ -14,7 +14,8 @@ of atoms against the map through `mad_map_group_fit` (localfit.py; no counterpar
 correlation of the map against a second map or a placed model through `mad_map_fsc` (fourier.py; no counterpart in the reference).
 `lowpass`, `highpass`, `sharpen` and `filter_radial` filter the map in Fourier space through `mad_map_filter` (fourier.py; no
 counterpart in the reference).  `scan` scores every whole-voxel translation of a structure, in a handful of orientations, against the
-map through `mad_map_scan` (fourier.py; no counterpart in the reference: the exhaustive cross-check of a docked pose).
+map through `mad_map_scan` (fourier.py; no counterpart in the reference: the exhaustive cross-check of a docked pose), and `search`
+does so over a whole set of rotations made on the device (`mad_map_search`).
 None of them has a CPU fallback.  The reference's per-voxel text writer is replaced by `mapio.write_situs`.
 """
 import os
@@ -281,6 +282,55 @@ class Dmap(object):
         md = 0 if mode == "uncentred" else 1
         best, best_t, peaks, n_found, N = lib.map_scan(g1, templates, iso, e_min, md, float(min_score), int(k))
         return fourier.Scan(best, best_t, peaks, n_found, (self.xi, self.yi, self.zi), voxsp, rot, centroid, origins, N=N, e_min=e_min, mode=md)
+
+    def search(self, structure, resolution, angle=30.0, rotations=None, mode="uncentred", isovalue=None, min_fill=0.25, min_score=0.0, k=20,
+               masses=None):
+        """Where in the map, and in which orientation, does the structure fit best?  `scan` over a set of rotations made on the
+        device: every rotation of `rotations` ((n, 3, 3), applied about the structure's centroid c, x -> (x - c) @ R + c; default:
+        `fourier.rotation_set(angle)`, which leaves no rotation farther than `angle` degrees from a member) and every whole-voxel
+        translation, scored by fast local correlation through `mad_map_search` -> `fourier.Search` (`best`, `best_r`, `peaks`,
+        `n_found`, `n_skipped`, `pose(i)`, `place(i, pdb)`, `write(outname)`).  The structure is simulated ONCE, as given, at
+        `resolution` on the map's spacing (`structure_to_density`); each rotation samples that grid by trilinear interpolation about
+        c0 = (c - grid origin) / voxsp into a cube of edge e, the smallest odd integer >= 2 rho + 3 with rho the largest distance in
+        voxels from c0 to a voxel above `isovalue` (None: 0) -- which blurs the template slightly.  The cube has to fit into the map
+        on every axis (`pad_grid` first where it does not).  An offset is scored by a rotation where the map's energy under its mask
+        exceeds min_fill n_w mean(m^2) (centred: var(m)).  Peaks are whole-voxel and no finer in angle than the set's spacing: the
+        rigid refinement is the step after this, and is not called here.  The map is not modified.  DESIGN.md section 4o."""
+        from . import fourier, localfit
+        if mode not in ("uncentred", "centred"):
+            raise ValueError("Dmap.search: mode %r ('uncentred' or 'centred')" % (mode,))
+        if resolution is None or not (float(resolution) > 0) or not np.isfinite(float(resolution)):
+            raise ValueError("Dmap.search: resolution %r (positive and finite)" % (resolution,))
+        iso, min_fill = (0.0 if isovalue is None else float(isovalue)), float(min_fill)
+        if not np.isfinite(iso) or not (min_fill >= 0) or not np.isfinite(min_fill):
+            raise ValueError("Dmap.search: isovalue %r, min_fill %r (finite, min_fill 0 or more)" % (isovalue, min_fill))
+        parts = localfit.structure_parts(structure)
+        mass = localfit.structure_masses(parts, masses)
+        if sum(len(c) for c, _, _ in parts) == 0:
+            raise ValueError("Dmap.search: no atoms to simulate a density from")
+        coords = np.concatenate([c for c, _, _ in parts], axis=0)
+        rot = fourier.rotation_set(angle) if rotations is None else np.asarray(rotations, np.float64)
+        if rot.ndim != 3 or rot.shape[1:] != (3, 3) or len(rot) == 0 or not np.isfinite(rot).all():
+            raise ValueError("Dmap.search: rotations of shape %r, not (n, 3, 3) with n >= 1" % (rot.shape,))
+        g1 = np.ascontiguousarray(self.grid3d, dtype=np.float32)
+        if g1.ndim != 3 or g1.size == 0:
+            raise ValueError("Dmap.search: the grid has shape %r" % (g1.shape,))
+        lib, voxsp, centroid = _lib.get_lib(), float(self.voxsp), coords.mean(axis=0)
+        g0, x0, y0, z0 = lib.structure_to_density(coords, mass, float(resolution), voxsp)
+        g0 = np.ascontiguousarray(g0, np.float32)
+        c0 = (centroid - np.array([x0, y0, z0], np.float64)) / voxsp
+        e = fourier.search_edge(g0, c0, iso)
+        for a in range(3):
+            if e > g1.shape[a]:
+                raise ValueError("Dmap.search: the cube that holds every rotation is %d voxels long, the map %d on axis %d (pad_grid first)"
+                                 % (e, g1.shape[a], a))
+        m64 = g1.astype(np.float64)
+        spread = float(np.mean(m64 * m64)) if mode == "uncentred" else float(np.var(m64))
+        e_fill = min_fill * spread
+        md = 0 if mode == "uncentred" else 1
+        best, best_r, peaks, n_found, n_skipped, N = lib.map_search(g1, g0, c0, e, rot, iso, e_fill, md, float(min_score), int(k))
+        return fourier.Search(best, best_r, peaks, n_found, n_skipped, (self.xi, self.yi, self.zi), voxsp, rot, centroid, e, N=N, e_fill=e_fill,
+                              mode=md)
 
     def smooth(self, sigma):
         """A Gaussian of `sigma` Angstrom on the map, in place (zero beyond the box, float64 inside, 4 sigma wide on either side).

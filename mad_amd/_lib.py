@@ -39,7 +39,7 @@ SYMBOLS = [
     "mad_dist_unique_id", "mad_dist_init", "mad_dist_destroy", "mad_dist_info", "mad_dist_rehearse_flags", "mad_dist_or_allreduce", "mad_dist_allgather",
     "mad_dist_allgather_topk", "mad_dist_scratch", "mad_dist_copy",
     "mad_set_wire_bytes", "mad_set_export", "mad_set_import", "mad_set_lane", "mad_set_stream", "mad_set_bind_lane",
-    "mad_upload_density", "mad_refine", "mad_last_refine_plan", "mad_last_density_chunks", "mad_structure_to_density", "mad_ccc", "mad_map_mask", "mad_map_ccc", "mad_map_resample", "mad_map_zone", "mad_map_group_fit", "mad_map_smooth", "mad_map_segment", "mad_map_fsc", "mad_map_fft", "mad_map_filter", "mad_map_ifft", "mad_map_scan", "mad_density_ccc", "mad_dock_refine_score", "mad_grid_overlap", "mad_overlap_matrix",
+    "mad_upload_density", "mad_refine", "mad_last_refine_plan", "mad_last_density_chunks", "mad_structure_to_density", "mad_ccc", "mad_map_mask", "mad_map_ccc", "mad_map_resample", "mad_map_zone", "mad_map_group_fit", "mad_map_smooth", "mad_map_segment", "mad_map_fsc", "mad_map_fft", "mad_map_filter", "mad_map_ifft", "mad_map_scan", "mad_map_search", "mad_map_rotate", "mad_density_ccc", "mad_dock_refine_score", "mad_grid_overlap", "mad_overlap_matrix",
     "mad_space_create", "mad_space_destroy", "mad_space_build", "mad_space_info", "mad_space_download",
     "mad_space_peaks", "mad_space_patches", "mad_space_localize", "mad_localize_volume",
     "mad_pose_cluster_many",
@@ -1266,6 +1266,43 @@ class Lib(object):
                                         C.c_double(float(e_min)), C.c_int32(int(mode)), C.c_double(float(min_score)), C.c_int64(k), _p(best),
                                         _p(best_t), _p(peaks), C.byref(n_peaks), C.byref(n_found), C.byref(n)))
         return best, best_t, peaks[:n_peaks.value].copy(), int(n_found.value), int(n.value)
+
+    def map_rotate(self, base, c0, edge, R, iso=0.0):
+        """One rotated template of `map_search` and its sums -> (g float32 [e, e, e], n_w, G, S) (mad_map_rotate; DESIGN.md section
+        4o; `fourier.rotate_numpy` and `fourier.tree_sum` restate it bit for bit).  `base`: C-contiguous float32 [x, y, z]; `c0`: the
+        centre of rotation in its voxel coordinates; `R`: 3 x 3."""
+        self._fourier_args("map_rotate", base, np.zeros(3), None, None)
+        d0, e = np.array(base.shape, np.int32), int(edge)
+        c0 = _c(np.asarray(c0, np.float64).reshape(3), np.float64)
+        R = _c(np.asarray(R, np.float64).reshape(9), np.float64)
+        out, stats = np.zeros((max(e, 0),) * 3 if e <= 1024 else (0,), np.float32), np.zeros(3, np.float64)
+        self._chk(self.dll.mad_map_rotate(self.ctx, _p(base), _p(d0), _p(c0), C.c_int32(e), _p(R), C.c_double(float(iso)), _p(out), _p(stats)))
+        return out, int(stats[0]), float(stats[1]), float(stats[2])
+
+    def map_search(self, m, base, c0, edge, rotations, iso=0.0, e_fill=0.0, mode=0, min_score=0.0, k=20):
+        """Every rotation in `rotations` and every whole-voxel translation of the template `base` inside the map `m`, scored by fast
+        local correlation -> (best float32 [D], best_r int32 [D], peaks float64 [min(k, n_found), 5] = ux, uy, uz, score, rotation;
+        n_found, n_skipped, N) (mad_map_search; `fourier.search_numpy` restates it).  `m`, `base`: C-contiguous
+        float32 [x, y, z]; `c0`: the centre of rotation in `base`'s voxel coordinates; the rotated templates are cubes of `edge`
+        voxels, D = m.shape - edge + 1; `rotations`: (n, 3, 3).  An offset is scored by a rotation where E (E') > e_fill n_w.  A
+        rotation whose mask is empty (or, centred, flat) is skipped and counted in n_skipped.  Nothing is modified."""
+        self._fourier_args("map_search", m, np.zeros(3), base, np.zeros(3))
+        rot = _c(np.asarray(rotations, np.float64), np.float64)
+        if rot.ndim != 3 or rot.shape[1:] != (3, 3) or len(rot) < 1:
+            raise ValueError("map_search: rotations of shape %r, not (n, 3, 3) with n >= 1" % (rot.shape,))
+        k, e = int(k), int(edge)
+        if k < 0:
+            raise ValueError("map_search: k = %d (0 or more)" % k)
+        d1, d0 = np.array(m.shape, np.int32), np.array(base.shape, np.int32)
+        c0 = _c(np.asarray(c0, np.float64).reshape(3), np.float64)
+        D = tuple(max(int(a) - e + 1, 1) for a in m.shape)
+        best, best_r, peaks = np.zeros(D, np.float32), np.full(D, -1, np.int32), np.zeros((max(k, 1), 5), np.float64)
+        n_peaks, n_found, n_skipped, n = C.c_int64(0), C.c_int64(0), C.c_int32(0), C.c_int32(0)
+        self._chk(self.dll.mad_map_search(self.ctx, _p(m), _p(d1), _p(base), _p(d0), _p(c0), C.c_int32(e), _p(rot), C.c_int32(len(rot)),
+                                          C.c_double(float(iso)), C.c_double(float(e_fill)), C.c_int32(int(mode)), C.c_double(float(min_score)),
+                                          C.c_int64(k), _p(best), _p(best_r), _p(peaks), C.byref(n_peaks), C.byref(n_found), C.byref(n_skipped),
+                                          C.byref(n)))
+        return best, best_r, peaks[:n_peaks.value].copy(), int(n_found.value), int(n_skipped.value), int(n.value)
 
     def map_zone(self, g, origin, voxsp, atoms, radius, soft=0.0, erase=False):
         """`g` (writable C-contiguous float32 [x, y, z] with `origin` and `voxsp`) cut around `atoms` in place: a voxel within

@@ -1,5 +1,6 @@
 // mad_fourier.hip -- Fourier shell correlation of two maps (mad_map_fsc), the 3-D transform under it (mad_map_fft), radial filters
-// (mad_map_filter, mad_map_ifft) and the scan of a model over every translation of a map (mad_map_scan).
+// (mad_map_filter, mad_map_ifft), the scan of a model over every translation of a map (mad_map_scan) and over rotations as well
+// (mad_map_search, mad_map_rotate).
 // DESIGN.md section 4l has the contract; mad_amd/fourier.py restates it with numpy.
 //
 // Both float32 grids go onto ONE cubic complex128 lattice of edge N (a power of two, 8 .. 1024): grid 1 in the real part, grid 2
@@ -38,7 +39,8 @@
 // -(Im Z) / N^3 over grid 2's as float32.  A gain that depends on r2 alone is real and even, so the two maps stay apart.
 //
 // The translation scan (mad_map_scan: k_scan_pack, k_scan_product, k_scan_score, k_scan_peaks) is at the end of the file: DESIGN.md
-// section 4n.
+// section 4n.  The rotational search (mad_map_search: k_search_rotate, k_search_stats, k_search_score and the pruned form of
+// k_fft_lines) follows it: section 4o.
 #include <algorithm>
 #include <vector>
 
@@ -92,12 +94,18 @@ __device__ __forceinline__ double2 c_muli(double2 a) { return make_double2(-a.y,
 
 // AXIS 0 / 1 / 2: lines along x / y / z.  One workgroup per tile, N^2 / 8 tiles; blockDim.x * BPT = max(2 N, 64) butterflies of a
 // radix-4 stage (a thread of the smallest lattices may have none).  Dynamic LDS: N * ROW * 16 bytes.
-template <int AXIS, int BPT>
+// PRUNE (mad_map_search): a 2-D grid selects a corner of the tile grid -- tile = blockIdx.y * (N / 8) +
+// blockIdx.x, i.e. blockIdx.x is the tile along z (AXIS 2: along y) and blockIdx.y the plane (AXIS 0: y, AXIS 1 and 2: x) -- and the
+// third argument carries the live length above its low byte (live << 8 | logN): elements n >= live of a line are taken as +0, not
+// loaded.  Every tile is still written whole.  The other forms take neither an argument nor a branch for it.
+template <int AXIS, int BPT, bool PRUNE = false>
 __global__ __launch_bounds__(FFT_MAX_THREADS) void k_fft_lines(double2 *__restrict__ Z, const double2 *__restrict__ tw, int logN) {
     extern __shared__ __attribute__((aligned(16))) double2 fft_img[];
     constexpr int ROW = AXIS == 2 ? FFT_L + 1 : FFT_L;
+    int live = 0;
+    if (PRUNE) { live = logN >> 8; logN &= 255; }
     const int N = 1 << logN, T = (int)blockDim.x, t = (int)threadIdx.x;
-    const int tile = (int)blockIdx.x;
+    const int tile = PRUNE ? (int)(blockIdx.y << (logN - 3)) + (int)blockIdx.x : (int)blockIdx.x;
     size_t base, sN, sL;
     if (AXIS == 2) {
         base = (size_t)tile * FFT_L << logN; sN = 1; sL = (size_t)N;
@@ -111,7 +119,8 @@ __global__ __launch_bounds__(FFT_MAX_THREADS) void k_fft_lines(double2 *__restri
 #pragma unroll 4
     for (int e = t; e < E; e += T) {
         const int n = AXIS == 2 ? (e & (N - 1)) : (e >> 3), l = AXIS == 2 ? (e >> logN) : (e & 7);
-        fft_img[n * ROW + l] = Z[base + (size_t)n * sN + (size_t)l * sL];
+        if (!PRUNE || n < live) fft_img[n * ROW + l] = Z[base + (size_t)n * sN + (size_t)l * sL];
+        else fft_img[n * ROW + l] = make_double2(0.0, 0.0);
     }
     __syncthreads();
     const int quarter = N >> 2, nb = 2 * N;      // butterflies of a radix-4 stage in the tile
@@ -379,6 +388,23 @@ template <int AXIS> static int fft_axis(mad_ctx *ctx, double2 *Z, const double2 
     if (bpt == 1) return fft_launch<AXIS, 1>(ctx, Z, tw, logN, threads);
     if (bpt == 2) return fft_launch<AXIS, 2>(ctx, Z, tw, logN, threads);
     return fft_launch<AXIS, 4>(ctx, Z, tw, logN, threads);
+}
+
+// The pruned form (section 4o): tiles_x x planes tiles from the low corner of the tile grid, lines of live length `live`.
+template <int AXIS, int BPT> static int fft_launch_pruned(mad_ctx *ctx, double2 *Z, const double2 *tw, int logN, int threads, int tiles_x, int planes, int live) {
+    const int N = 1 << logN;
+    const size_t lds = (size_t)N * (AXIS == 2 ? FFT_L + 1 : FFT_L) * sizeof(double2);
+    static bool attr = false;
+    if (!attr) { MAD_HIP(hipFuncSetAttribute((const void *)k_fft_lines<AXIS, BPT, true>, hipFuncAttributeMaxDynamicSharedMemorySize, FFT_MAX_N * (FFT_L + 1) * 16)); attr = true; }
+    hipLaunchKernelGGL((k_fft_lines<AXIS, BPT, true>), dim3((unsigned)tiles_x, (unsigned)planes), dim3(threads), lds, ctx->stream, Z, tw, (live << 8) | logN);
+    return MAD_OK;
+}
+template <int AXIS> static int fft_axis_pruned(mad_ctx *ctx, double2 *Z, const double2 *tw, int logN, int tiles_x, int planes, int live) {
+    const int N = 1 << logN, least = N <= 256 ? 1 : (N == 512 ? 2 : 4), bpt = std::max(ctx->fft_bpt, least);
+    const int threads = std::max(2 * N / bpt, MAD_WAVE);
+    if (bpt == 1) return fft_launch_pruned<AXIS, 1>(ctx, Z, tw, logN, threads, tiles_x, planes, live);
+    if (bpt == 2) return fft_launch_pruned<AXIS, 2>(ctx, Z, tw, logN, threads, tiles_x, planes, live);
+    return fft_launch_pruned<AXIS, 4>(ctx, Z, tw, logN, threads, tiles_x, planes, live);
 }
 
 // the twiddles exp(-2 pi i k / N) of the lattice edge N on the device, uploaded when N changes
@@ -819,6 +845,51 @@ struct ScanLattices {
     double2 *Z[3] = {nullptr, nullptr, nullptr};      // the map's, the template's, mode 1: the third
 };
 
+// The peaks of the score volume on the device (d_best, d_best_t over the box D; d_count: 16 bytes) and the volume itself, to the
+// host.  The list in S_TMP_J holds `cap` candidates; where more were found and some are wanted it grows to the count and the kernel
+// runs again, while best is still on the device.
+static int scan_peaks_out(mad_ctx *ctx, const char *who, int timer, const float *d_best, const int *d_best_t, unsigned *d_count, const unsigned D[3],
+                          size_t nD, double min_score, int64_t k, float *best, int32_t *best_t, double *peaks, int64_t *n_peaks, int64_t *n_found) {
+    const unsigned wg_D = fourier_blocks(ctx, nD);
+    unsigned cap = SCAN_CAP0, found = 0;
+    for (int pass = 0; pass < 2; pass++) {
+        MAD_HIP(hipMemsetAsync(d_count, 0, 16, ctx->stream));
+        mad_timer_begin(ctx, timer);
+        hipLaunchKernelGGL(k_scan_peaks, dim3(wg_D), dim3(256), 0, ctx->stream, d_best, d_best_t, D[0], D[1], D[2], nD, min_score, cap, d_count,
+                           scratch<unsigned>(ctx, S_TMP_J));
+        mad_timer_end(ctx, timer);
+        MAD_HIP(hipGetLastError());
+        MAD_HIP(hipMemcpyAsync(&found, d_count, 4, hipMemcpyDeviceToHost, ctx->stream));
+        MAD_HIP(hipStreamSynchronize(ctx->stream));
+        if (found <= cap || k == 0) break;
+        if (pass == 1) return mad_fail(ctx, MAD_EHIP, "%s: %u peaks after %u were counted", who, found, cap);
+        size_t free_b = 0, total_b = 0;
+        MAD_HIP(hipMemGetInfo(&free_b, &total_b));
+        if ((size_t)found * 5 + ((size_t)8 << 20) > free_b)
+            return mad_fail(ctx, MAD_ENOMEM, "%s: a list of %u peaks needs %zu MiB of device memory, %zu MiB are free", who, found,
+                            ((size_t)found * 5) >> 20, free_b >> 20);
+        MAD_TRY(mad_reserve(ctx, mad_sb(ctx, S_TMP_J), (size_t)found * 4));
+        cap = found;
+    }
+    const size_t n_list = k == 0 ? 0 : (size_t)std::min(found, cap);
+    std::vector<unsigned> list(n_list);
+    MAD_HIP(hipMemcpyAsync(best, d_best, nD * 4, hipMemcpyDeviceToHost, ctx->stream));
+    MAD_HIP(hipMemcpyAsync(best_t, d_best_t, nD * 4, hipMemcpyDeviceToHost, ctx->stream));
+    if (n_list) MAD_HIP(hipMemcpyAsync(list.data(), scratch<unsigned>(ctx, S_TMP_J), n_list * 4, hipMemcpyDeviceToHost, ctx->stream));
+    MAD_HIP(hipStreamSynchronize(ctx->stream));
+    // score descending, then linear index ascending: the order of the list does not depend on the order of the appends
+    std::sort(list.begin(), list.end(), [best](unsigned p, unsigned q) { return best[p] > best[q] || (best[p] == best[q] && p < q); });
+    const int64_t n_out = std::min<int64_t>(k, (int64_t)n_list);
+    for (int64_t p = 0; p < n_out; p++) {
+        const unsigned q = list[(size_t)p], t = q / D[2];
+        peaks[5 * p] = (double)(t / D[1]); peaks[5 * p + 1] = (double)(t % D[1]); peaks[5 * p + 2] = (double)(q % D[2]);
+        peaks[5 * p + 3] = (double)best[q]; peaks[5 * p + 4] = (double)best_t[q];
+    }
+    *n_peaks = n_out;
+    *n_found = (int64_t)found;
+    return MAD_OK;
+}
+
 struct ScanStat { double n_w, G, gbar; };      // G: G' in mode 1
 
 static int map_scan_run(mad_ctx *ctx, const float *map, const int32_t *d1, int32_t n_t, const float *const *tpl, const int32_t *d2, double iso,
@@ -923,45 +994,7 @@ static int map_scan_run(mad_ctx *ctx, const float *map, const int32_t *d1, int32
         MAD_HIP(hipGetLastError());
     }
 
-    // the peaks: the list holds `cap` candidates; where more were found and some are wanted it grows to the count and the kernel
-    // runs again, while best is still on the device
-    unsigned cap = SCAN_CAP0, found = 0;
-    for (int pass = 0; pass < 2; pass++) {
-        MAD_HIP(hipMemsetAsync(d_count, 0, 16, ctx->stream));
-        mad_timer_begin(ctx, MAD_T_SCAN);
-        hipLaunchKernelGGL(k_scan_peaks, dim3(wg_D), dim3(256), 0, ctx->stream, (const float *)d_best, (const int *)d_best_t, D[0], D[1], D[2], nD,
-                           min_score, cap, d_count, scratch<unsigned>(ctx, S_TMP_J));
-        mad_timer_end(ctx, MAD_T_SCAN);
-        MAD_HIP(hipGetLastError());
-        MAD_HIP(hipMemcpyAsync(&found, d_count, 4, hipMemcpyDeviceToHost, ctx->stream));
-        MAD_HIP(hipStreamSynchronize(ctx->stream));
-        if (found <= cap || k == 0) break;
-        if (pass == 1) return mad_fail(ctx, MAD_EHIP, "mad_map_scan: %u peaks after %u were counted", found, cap);
-        size_t free_b = 0, total_b = 0;
-        MAD_HIP(hipMemGetInfo(&free_b, &total_b));
-        if ((size_t)found * 5 + ((size_t)8 << 20) > free_b)
-            return mad_fail(ctx, MAD_ENOMEM, "mad_map_scan: a list of %u peaks needs %zu MiB of device memory, %zu MiB are free", found,
-                            ((size_t)found * 5) >> 20, free_b >> 20);
-        MAD_TRY(mad_reserve(ctx, mad_sb(ctx, S_TMP_J), (size_t)found * 4));
-        cap = found;
-    }
-    const size_t n_list = k == 0 ? 0 : (size_t)std::min(found, cap);
-    std::vector<unsigned> list(n_list);
-    MAD_HIP(hipMemcpyAsync(best, d_best, nD * 4, hipMemcpyDeviceToHost, ctx->stream));
-    MAD_HIP(hipMemcpyAsync(best_t, d_best_t, nD * 4, hipMemcpyDeviceToHost, ctx->stream));
-    if (n_list) MAD_HIP(hipMemcpyAsync(list.data(), scratch<unsigned>(ctx, S_TMP_J), n_list * 4, hipMemcpyDeviceToHost, ctx->stream));
-    MAD_HIP(hipStreamSynchronize(ctx->stream));
-    // score descending, then linear index ascending: the order of the list does not depend on the order of the appends
-    std::sort(list.begin(), list.end(), [best](unsigned p, unsigned q) { return best[p] > best[q] || (best[p] == best[q] && p < q); });
-    const int64_t n_out = std::min<int64_t>(k, (int64_t)n_list);
-    for (int64_t p = 0; p < n_out; p++) {
-        const unsigned q = list[(size_t)p], t = q / D[2];
-        peaks[5 * p] = (double)(t / D[1]); peaks[5 * p + 1] = (double)(t % D[1]); peaks[5 * p + 2] = (double)(q % D[2]);
-        peaks[5 * p + 3] = (double)best[q]; peaks[5 * p + 4] = (double)best_t[q];
-    }
-    *n_peaks = n_out;
-    *n_found = (int64_t)found;
-    return MAD_OK;
+    return scan_peaks_out(ctx, "mad_map_scan", MAD_T_SCAN, d_best, d_best_t, d_count, D, nD, min_score, k, best, best_t, peaks, n_peaks, n_found);
 }
 
 extern "C" int mad_map_scan(mad_ctx *ctx, const float *map, const int32_t dims1[3], int32_t n_t, const float *const *templates,
@@ -974,4 +1007,368 @@ extern "C" int mad_map_scan(mad_ctx *ctx, const float *map, const int32_t dims1[
     int rc = map_scan_run(ctx, map, dims1, n_t, templates, dims2, iso, e_min, mode, min_score, k, best, best_t, peaks, n_peaks, n_found, N_out, &L);
     for (int l = 0; l < 3; l++) rc = fourier_free(ctx, L.Z[l], rc);
     return rc;
+}
+
+// ---------------------------------------------------------------------------
+// rotational search
+// ---------------------------------------------------------------------------
+// mad_map_search scores every whole-voxel translation of every rotation of ONE base template: per rotation the template is sampled
+// from the base grid into a cube of edge e (k_search_rotate: gather, trilinear interpolation, cast to float32, mask, the lattice
+// write of g w + i w and the first level of the sums n_w, G, S), k_search_stats finishes the sums into a record in device memory,
+// the pruned line passes transform only what is not zero on the way in and only what k_search_score reads on the way out, and
+// k_search_score takes n_w, G and S from the record.  Nothing comes back to the host between the first rotation and the last.
+
+#define SEARCH_RUN 256      // elements of a run of tree_sum (fourier.py), and the workgroup of k_search_rotate / k_search_stats
+
+struct SearchRotateArgs {
+    const float *g0;             // the base grid, dims d0
+    int d0[3];
+    unsigned e, n_runs;          // the cube's edge; ceil(e^3 / 256) runs
+    size_t n_box;                // e^3 <= 2^30
+    int logN;                    // of the lattice Z (unused without one)
+    double c0[3], c2, iso;
+};
+
+// s[k][0] <- the sum of s[k][0 .. 255] by halving, k = 0 .. 2: x[:128] + x[128:], then 64, ... 1 (fourier.tree_sum's run)
+__device__ __forceinline__ void search_run_sum(double (*s)[SEARCH_RUN], unsigned t) {
+    __syncthreads();
+    for (unsigned h = SEARCH_RUN / 2; h >= 1; h >>= 1) {
+        if (t < h) {
+            s[0][t] = s[0][t] + s[0][t + h];
+            s[1][t] = s[1][t] + s[1][t + h];
+            s[2][t] = s[2][t] + s[2][t + h];
+        }
+        __syncthreads();
+    }
+}
+
+// Workgroup b < n_runs takes run b of the cube in linear [x][y][z] order: voxel x samples the base grid at
+// p = c0 + (x - c2) @ R^T (R row-major in device memory), trilinear with corners beyond the grid 0 (a point at or beyond -1 or d on an
+// axis has none inside: 0), float64 in the contract's order, rounded to float32.  out_g (may be NULL): that float32.  Z (may be NULL):
+// g w + i w at lattice index x.  part[b][3] = the run's sums of w, g^2 w and g w.  Workgroups b >= n_runs (launched only for full
+// passes, search_prune = 0) write +0 to every lattice element outside the cube, grid-stride.
+__global__ __launch_bounds__(SEARCH_RUN) void k_search_rotate(const SearchRotateArgs A, const double *__restrict__ R, double2 *__restrict__ Z,
+                                                               float *__restrict__ out_g, double *__restrict__ part) {
+    __shared__ double s[3][SEARCH_RUN];
+    const unsigned t = threadIdx.x;
+    if (blockIdx.x >= A.n_runs) {      // uniform over the workgroup
+        const unsigned m = (1u << A.logN) - 1u;
+        const size_t n = (size_t)1 << (3 * A.logN), step = (size_t)(gridDim.x - A.n_runs) * SEARCH_RUN;
+        for (size_t i = (size_t)(blockIdx.x - A.n_runs) * SEARCH_RUN + t; i < n; i += step) {
+            const unsigned c = (unsigned)i & m, b = (unsigned)(i >> A.logN) & m, a = (unsigned)(i >> (2 * A.logN));
+            if (a >= A.e || b >= A.e || c >= A.e) Z[i] = make_double2(0.0, 0.0);
+        }
+        return;
+    }
+    const size_t i = (size_t)blockIdx.x * SEARCH_RUN + t;
+    double vw = 0.0, vg = 0.0, vs = 0.0;
+    if (i < A.n_box) {
+        const unsigned q = (unsigned)i, xy = q / A.e, z = q - xy * A.e, x = xy / A.e, y = xy - x * A.e;
+        const double d0 = (double)x - A.c2, d1 = (double)y - A.c2, d2 = (double)z - A.c2;
+        const double px = A.c0[0] + ((d0 * R[0] + d1 * R[1]) + d2 * R[2]);
+        const double py = A.c0[1] + ((d0 * R[3] + d1 * R[4]) + d2 * R[5]);
+        const double pz = A.c0[2] + ((d0 * R[6] + d1 * R[7]) + d2 * R[8]);
+        float g = 0.0f;
+        if (px > -1.0 && px < (double)A.d0[0] && py > -1.0 && py < (double)A.d0[1] && pz > -1.0 && pz < (double)A.d0[2]) {
+            const double fx = floor(px), fy = floor(py), fz = floor(pz);
+            const double tx = px - fx, ty = py - fy, tz = pz - fz;
+            const int ix = (int)fx, iy = (int)fy, iz = (int)fz;      // -1 .. d - 1
+            double v[2][2][2];
+#pragma unroll
+            for (int a = 0; a < 2; a++)
+#pragma unroll
+                for (int b = 0; b < 2; b++)
+#pragma unroll
+                    for (int c = 0; c < 2; c++) {
+                        const unsigned ux = (unsigned)(ix + a), uy = (unsigned)(iy + b), uz = (unsigned)(iz + c);      // -1 wraps past any extent
+                        v[a][b][c] = ux < (unsigned)A.d0[0] && uy < (unsigned)A.d0[1] && uz < (unsigned)A.d0[2]
+                                         ? (double)A.g0[((size_t)ux * (unsigned)A.d0[1] + uy) * (unsigned)A.d0[2] + uz] : 0.0;
+                    }
+            const double v00 = v[0][0][0] + tz * (v[0][0][1] - v[0][0][0]), v01 = v[0][1][0] + tz * (v[0][1][1] - v[0][1][0]);
+            const double v10 = v[1][0][0] + tz * (v[1][0][1] - v[1][0][0]), v11 = v[1][1][0] + tz * (v[1][1][1] - v[1][1][0]);
+            const double v0 = v00 + ty * (v01 - v00), v1 = v10 + ty * (v11 - v10);
+            g = (float)(v0 + tx * (v1 - v0));
+        }
+        if (out_g) out_g[i] = g;
+        const double gd = (double)g;
+        const bool w = gd > A.iso;
+        if (Z) Z[(((((size_t)x) << A.logN) + y) << A.logN) + z] = w ? make_double2(gd, 1.0) : make_double2(0.0, 0.0);
+        if (w) { vw = 1.0; vg = gd * gd; vs = gd; }      // 24 x 24 bits: exact
+    }
+    s[0][t] = vw; s[1][t] = vg; s[2][t] = vs;
+    search_run_sum(s, t);
+    if (t < 3) part[(size_t)blockIdx.x * 3 + t] = s[t][0];
+}
+
+// One level of tree_sum: out[b][3] = the sums of run b of in[n_in][3] (the last run zero-padded).  The host launches level after
+// level until one record is left; the last level writes the rotation's record (n_w, G, S).
+__global__ __launch_bounds__(SEARCH_RUN) void k_search_stats(const double *__restrict__ in, unsigned n_in, double *__restrict__ out) {
+    __shared__ double s[3][SEARCH_RUN];
+    const unsigned t = threadIdx.x;
+    const size_t i = (size_t)blockIdx.x * SEARCH_RUN + t;
+    const bool has = i < n_in;
+    s[0][t] = has ? in[i * 3] : 0.0; s[1][t] = has ? in[i * 3 + 1] : 0.0; s[2][t] = has ? in[i * 3 + 2] : 0.0;
+    search_run_sum(s, t);
+    if (t < 3) out[(size_t)blockIdx.x * 3 + t] = s[t][0];
+}
+
+struct SearchScoreArgs {
+    int logN, mode, rot;         // rot: the rotation's index; rotation 0 initialises best / best_r
+    unsigned D1, D2;
+    size_t nD;
+    double scale, e_fill;        // 1 / N^3; the floor is e_fill n_w
+};
+
+// k_scan_score with n_w, G and S read from the rotation's record rec[3]: gbar, G' and the floor are formed here in the contract's
+// order.  A rotation with n_w = 0, G outside (0, 1.7e308] or (mode 1) G' <= 0 is skipped: it scores no offset, and *skipped is 1.
+__global__ __launch_bounds__(256) void k_search_score(const double2 *__restrict__ Zt, const double2 *__restrict__ Zq, const SearchScoreArgs A,
+                                                      const double *__restrict__ rec, float *__restrict__ best, int *__restrict__ best_r,
+                                                      int *__restrict__ skipped) {
+    const double n_w = rec[0], S = rec[2];
+    double G = rec[1], gbar = 0.0;
+    bool skip = !(n_w > 0.0) || !(G > 0.0 && G <= 1.7e308);
+    if (!skip && A.mode) {
+        gbar = S / n_w;
+        G = G - n_w * (gbar * gbar);
+        skip = !(G > 0.0);
+    }
+    const double e_min = A.e_fill * n_w;
+    if (blockIdx.x == 0 && threadIdx.x == 0) *skipped = skip ? 1 : 0;
+    if (skip && A.rot != 0) return;
+    for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < A.nD; i += (size_t)gridDim.x * 256) {
+        bool scored = false;
+        float s = 0.0f;
+        if (!skip) {
+            const unsigned q = (unsigned)i, t = q / A.D2, z = q - t * A.D2, x = t / A.D1, y = t - x * A.D1;
+            const size_t at = (((((size_t)x) << A.logN) + y) << A.logN) + z;
+            const double2 v = Zt[at];
+            double c = v.x * A.scale, e = -(v.y * A.scale);
+            if (A.mode) {
+                const double a = Zq[at].x * A.scale;
+                c = c - a * gbar;
+                e = e - (a * a) / n_w;
+            }
+            scored = e > e_min;
+            if (scored) s = (float)(c / sqrt(e * G));
+        }
+        if (A.rot == 0) {
+            best[i] = s;
+            best_r[i] = scored ? 0 : -1;
+        } else if (scored && (best_r[i] < 0 || s > best[i])) {
+            best[i] = s;
+            best_r[i] = A.rot;
+        }
+    }
+}
+
+// k_search_rotate and the levels of k_search_stats of one rotation; the record ends in rec.  part_a holds n_runs records, part_b
+// ceil(n_runs / 256).  fill_wgs > 0: that many more workgroups zero the lattice outside the cube.
+static void search_rotate_launch(mad_ctx *ctx, const SearchRotateArgs &A, const double *R, double2 *Z, float *out_g, double *part_a, double *part_b,
+                                 double *rec, unsigned fill_wgs) {
+    hipLaunchKernelGGL(k_search_rotate, dim3(A.n_runs + fill_wgs), dim3(SEARCH_RUN), 0, ctx->stream, A, R, Z, out_g, A.n_runs == 1 ? rec : part_a);
+    double *in = part_a, *out = part_b;
+    for (unsigned n = A.n_runs; n > 1;) {
+        const unsigned m = (n + SEARCH_RUN - 1) / SEARCH_RUN;
+        hipLaunchKernelGGL(k_search_stats, dim3(m), dim3(SEARCH_RUN), 0, ctx->stream, (const double *)in, n, m == 1 ? rec : out);
+        std::swap(in, out);
+        n = m;
+    }
+}
+
+// finite, and max |R R^T - I| <= 1e-6
+static bool search_rotation_ok(const double *R) {
+    for (int i = 0; i < 9; i++)
+        if (!(fabs(R[i]) <= 1.7e308)) return false;
+    for (int a = 0; a < 3; a++)
+        for (int b = 0; b < 3; b++) {
+            const double d = (R[3 * a] * R[3 * b] + R[3 * a + 1] * R[3 * b + 1]) + R[3 * a + 2] * R[3 * b + 2] - (a == b ? 1.0 : 0.0);
+            if (!(fabs(d) <= 1e-6)) return false;
+        }
+    return true;
+}
+
+// what mad_map_search and mad_map_rotate refuse about the base template, the cube and the mask
+static int search_check(mad_ctx *ctx, const char *who, const int32_t *d0, const double *c0, int32_t e, double iso) {
+    static const double zero[3] = {0.0, 0.0, 0.0};
+    MAD_TRY(fourier_check(ctx, who, d0, zero, 1.0));
+    if (e < 1) return mad_fail(ctx, MAD_EINVAL, "%s: edge %d (1 or more)", who, e);
+    for (int a = 0; a < 3; a++)
+        if (!(fabs(c0[a]) <= 1.7e308)) return mad_fail(ctx, MAD_EINVAL, "%s: centre c0[%d] = %g is not finite", who, a, c0[a]);
+    if (!(fabs(iso) <= 1.7e308)) return mad_fail(ctx, MAD_EINVAL, "%s: iso %g is not finite", who, iso);
+    return MAD_OK;
+}
+
+static void search_rotate_args(SearchRotateArgs *A, const float *d_base, const int32_t *d0, const double *c0, int32_t e, double iso, int logN) {
+    memset(A, 0, sizeof(*A));
+    A->g0 = d_base;
+    for (int a = 0; a < 3; a++) { A->d0[a] = d0[a]; A->c0[a] = c0[a]; }
+    A->e = (unsigned)e;
+    A->n_box = (size_t)e * e * e;
+    A->n_runs = (unsigned)((A->n_box + SEARCH_RUN - 1) / SEARCH_RUN);
+    A->logN = logN;
+    A->c2 = ((double)e - 1.0) / 2.0;
+    A->iso = iso;
+}
+
+static int map_search_run(mad_ctx *ctx, const float *map, const int32_t *d1, const float *base, const int32_t *d0, const double *c0, int32_t e,
+                          const double *rot, int32_t n_r, double iso, double e_fill, int32_t mode, double min_score, int64_t k, float *best,
+                          int32_t *best_r, double *peaks, int64_t *n_peaks, int64_t *n_found, int32_t *n_skipped, int32_t *N_out, ScanLattices *L) {
+    static const double zero[3] = {0.0, 0.0, 0.0};
+    const char *who = "mad_map_search";
+    if (n_r < 1) return mad_fail(ctx, MAD_EINVAL, "%s: %d rotations (1 or more)", who, n_r);
+    MAD_TRY(fourier_check(ctx, who, d1, zero, 1.0));
+    MAD_TRY(search_check(ctx, who, d0, c0, e, iso));
+    if (!(fabs(min_score) <= 1.7e308) || !(e_fill >= 0.0 && e_fill <= 1.7e308))
+        return mad_fail(ctx, MAD_EINVAL, "%s: e_fill %g, min_score %g (finite, e_fill 0 or more)", who, e_fill, min_score);
+    if (mode != 0 && mode != 1) return mad_fail(ctx, MAD_EINVAL, "%s: mode %d (0 un-centred, 1 centred)", who, mode);
+    if (k < 0) return mad_fail(ctx, MAD_EINVAL, "%s: k = %lld (0 or more)", who, (long long)k);
+    int longest = 0;
+    for (int a = 0; a < 3; a++) longest = std::max(longest, (int)d1[a]);
+    if (longest > FFT_MAX_N) return mad_fail(ctx, MAD_EDOM, "%s: the map's longest axis is %d voxels, more than %d", who, longest, FFT_MAX_N);
+    for (int a = 0; a < 3; a++)
+        if (e > d1[a])
+            return mad_fail(ctx, MAD_EDOM, "%s: the cube is %d voxels long, the map %d on axis %d: no offset keeps it inside", who, e, d1[a], a);
+    int N = FFT_MIN_N, logN = 3;
+    while (N < longest) { N <<= 1; logN++; }
+    if (N_out) *N_out = N;
+    if (!best) return MAD_OK;      // the size query
+    for (int32_t j = 0; j < n_r; j++)
+        if (!search_rotation_ok(rot + (size_t)9 * j))
+            return mad_fail(ctx, MAD_EINVAL, "%s: rotation %d is not finite or not orthonormal (max |R R^T - I| > 1e-6)", who, j);
+    const unsigned D[3] = {(unsigned)(d1[0] - e + 1), (unsigned)(d1[1] - e + 1), (unsigned)(d1[2] - e + 1)};
+    const size_t n1 = (size_t)d1[0] * d1[1] * d1[2], n0 = (size_t)d0[0] * d0[1] * d0[2], nD = (size_t)D[0] * D[1] * D[2];
+
+    SearchRotateArgs RA;
+    search_rotate_args(&RA, nullptr, d0, c0, e, iso, logN);
+    const int n_lat = mode ? 3 : 2;
+    const size_t bytes_Z = (size_t)16 << (3 * logN);
+    const size_t n_pb = (RA.n_runs + SEARCH_RUN - 1) / SEARCH_RUN;
+    const size_t b_best = (nD * 4 + 15) & ~(size_t)15, b_rot = (size_t)n_r * 72, b_rec = (size_t)n_r * 24, b_skip = ((size_t)n_r * 4 + 15) & ~(size_t)15;
+    const size_t b_pa = (size_t)RA.n_runs * 24, b_pb = n_pb * 24;
+    const size_t b_out = 2 * b_best + 16 + b_rot + b_rec + b_skip + b_pa + b_pb, b_list = (size_t)SCAN_CAP0 * 4;
+    const size_t grow_g = mad_sb(ctx, S_TMP_G).cap >= b_out ? 0 : b_out + b_out / 4, grow_j = mad_sb(ctx, S_TMP_J).cap >= b_list ? 0 : b_list + b_list / 4;
+    MAD_TRY(fourier_room(ctx, who, N, logN, n1, n0, (size_t)(n_lat - 1) * bytes_Z + grow_g + grow_j));
+    MAD_TRY(fourier_twiddles(ctx, N));
+    MAD_TRY(mad_reserve(ctx, mad_sb(ctx, S_TMP_H), (n1 + 4) * 4));
+    MAD_TRY(mad_reserve(ctx, mad_sb(ctx, S_TMP_I), (n0 + 4) * 4));
+    MAD_TRY(mad_reserve(ctx, mad_sb(ctx, S_TMP_G), b_out));
+    MAD_TRY(mad_reserve(ctx, mad_sb(ctx, S_TMP_J), b_list));
+    for (int l = 0; l < n_lat; l++) MAD_TRY(fourier_alloc(ctx, who, N, logN, &L->Z[l]));
+    double2 *Zm = L->Z[0], *Zt = L->Z[1], *Zq = L->Z[2];
+    const double2 *tw = (const double2 *)ctx->fft_tw.p;
+    float *d_map = scratch<float>(ctx, S_TMP_H), *d_base = scratch<float>(ctx, S_TMP_I);
+    char *blk = scratch<char>(ctx, S_TMP_G);
+    float *d_best = (float *)blk;
+    int *d_best_r = (int *)(blk + b_best);
+    unsigned *d_count = (unsigned *)(blk + 2 * b_best);
+    double *d_rot = (double *)(blk + 2 * b_best + 16), *d_rec = (double *)((char *)d_rot + b_rot);
+    int *d_skip = (int *)((char *)d_rec + b_rec);
+    double *part_a = (double *)((char *)d_skip + b_skip), *part_b = (double *)((char *)part_a + b_pa);
+    const unsigned wg_Z = fourier_blocks(ctx, (size_t)1 << (3 * logN)), wg_D = fourier_blocks(ctx, nD);
+    const int threads = std::min(N, 256);
+    const bool prune = ctx->search_prune != 0;
+    RA.g0 = d_base;
+
+    // the map, the base grid and the rotations go up once
+    MAD_HIP(hipMemcpyAsync(d_map, map, n1 * 4, hipMemcpyHostToDevice, ctx->stream));
+    MAD_HIP(hipMemcpyAsync(d_base, base, n0 * 4, hipMemcpyHostToDevice, ctx->stream));
+    MAD_HIP(hipMemcpyAsync(d_rot, rot, b_rot, hipMemcpyHostToDevice, ctx->stream));
+    mad_timer_begin(ctx, MAD_T_SCAN);
+    hipLaunchKernelGGL(k_scan_pack<false>, dim3(wg_Z), dim3(256), 0, ctx->stream, (const float *)d_map, (unsigned)d1[0], (unsigned)d1[1], (unsigned)d1[2],
+                       0.0, logN, Zm);
+    mad_timer_end(ctx, MAD_T_SCAN);
+    mad_timer_begin(ctx, MAD_T_FFT);
+    int rc = fourier_passes(ctx, Zm, logN);
+    mad_timer_end(ctx, MAD_T_FFT);
+    if (rc != MAD_OK) return rc;
+    MAD_HIP(hipGetLastError());
+
+    SearchScoreArgs SA;
+    memset(&SA, 0, sizeof(SA));
+    SA.logN = logN; SA.mode = mode; SA.D1 = D[1]; SA.D2 = D[2]; SA.nD = nD; SA.scale = ldexp(1.0, -3 * logN); SA.e_fill = e_fill;
+    // tiles of 8 that cover the cube's lines (forward) and the offsets' (inverse)
+    const int nt = N / FFT_L, te = (e + FFT_L - 1) / FFT_L, tD2 = ((int)D[2] + FFT_L - 1) / FFT_L;
+    mad_timer_begin(ctx, MAD_T_SEARCH);      // one interval around every rotation: no event, and so no wait, per rotation
+    for (int32_t j = 0; j < n_r && rc == MAD_OK; j++) {
+        double *rec = d_rec + (size_t)3 * j;
+        search_rotate_launch(ctx, RA, d_rot + (size_t)9 * j, Zt, nullptr, part_a, part_b, rec, prune ? 0u : wg_Z);
+        if (prune) {      // forward: only the cube is not zero
+            rc = fft_axis_pruned<2>(ctx, Zt, tw, logN, te, e, e);
+            if (rc == MAD_OK) rc = fft_axis_pruned<1>(ctx, Zt, tw, logN, nt, e, e);
+            if (rc == MAD_OK) rc = fft_axis_pruned<0>(ctx, Zt, tw, logN, nt, N, e);
+        } else rc = fourier_passes(ctx, Zt, logN);
+        if (rc != MAD_OK) break;
+        hipLaunchKernelGGL(k_scan_product, dim3((unsigned)N, (unsigned)(N / 2 + 1)), dim3(threads), 0, ctx->stream, (const double2 *)Zm, Zt, Zq, logN);
+        for (int l = 1; l < n_lat && rc == MAD_OK; l++) {
+            if (prune) {      // inverse: only the box of offsets is read
+                rc = fft_axis_pruned<2>(ctx, L->Z[l], tw, logN, nt, N, N);
+                if (rc == MAD_OK) rc = fft_axis_pruned<1>(ctx, L->Z[l], tw, logN, tD2, N, N);
+                if (rc == MAD_OK) rc = fft_axis_pruned<0>(ctx, L->Z[l], tw, logN, tD2, (int)D[1], N);
+            } else rc = fourier_passes(ctx, L->Z[l], logN);
+        }
+        if (rc != MAD_OK) break;
+        SA.rot = j;
+        hipLaunchKernelGGL(k_search_score, dim3(wg_D), dim3(256), 0, ctx->stream, (const double2 *)Zt, (const double2 *)Zq, SA, (const double *)rec,
+                           d_best, d_best_r, d_skip + j);
+    }
+    mad_timer_end(ctx, MAD_T_SEARCH);
+    if (rc != MAD_OK) return rc;
+    MAD_HIP(hipGetLastError());
+    std::vector<int> h_skip((size_t)n_r);
+    MAD_HIP(hipMemcpyAsync(h_skip.data(), d_skip, (size_t)n_r * 4, hipMemcpyDeviceToHost, ctx->stream));
+    MAD_HIP(hipStreamSynchronize(ctx->stream));      // the one synchronisation before the peak search
+    int32_t skipped = 0;
+    for (int32_t j = 0; j < n_r; j++) skipped += h_skip[(size_t)j] != 0;
+    MAD_TRY(scan_peaks_out(ctx, who, MAD_T_SEARCH, d_best, d_best_r, d_count, D, nD, min_score, k, best, best_r, peaks, n_peaks, n_found));
+    *n_skipped = skipped;
+    return MAD_OK;
+}
+
+extern "C" int mad_map_search(mad_ctx *ctx, const float *map, const int32_t dims1[3], const float *base, const int32_t dims0[3], const double c0[3],
+                              int32_t edge, const double *rotations, int32_t n_r, double iso, double e_fill, int32_t mode, double min_score, int64_t k,
+                              float *best, int32_t *best_r, double *peaks, int64_t *n_peaks, int64_t *n_found, int32_t *n_skipped, int32_t *N_out) {
+    if (ctx) mad_use_lane(ctx, 0);
+    if (!ctx || !dims1 || !dims0 || !c0 || (!best && !N_out) ||
+        (best && (!map || !base || !rotations || !best_r || !n_peaks || !n_found || !n_skipped || (k > 0 && !peaks))))
+        return ctx ? mad_fail(ctx, MAD_EINVAL, "mad_map_search: NULL argument") : MAD_EINVAL;
+    ScanLattices L;
+    int rc = map_search_run(ctx, map, dims1, base, dims0, c0, edge, rotations, n_r, iso, e_fill, mode, min_score, k, best, best_r, peaks, n_peaks,
+                            n_found, n_skipped, N_out, &L);
+    for (int l = 0; l < 3; l++) rc = fourier_free(ctx, L.Z[l], rc);
+    return rc;
+}
+
+extern "C" int mad_map_rotate(mad_ctx *ctx, const float *base, const int32_t dims0[3], const double c0[3], int32_t edge, const double R[9], double iso,
+                              float *out, double stats[3]) {
+    if (ctx) mad_use_lane(ctx, 0);
+    if (!ctx || !base || !dims0 || !c0 || !R || !out || !stats) return ctx ? mad_fail(ctx, MAD_EINVAL, "mad_map_rotate: NULL argument") : MAD_EINVAL;
+    const char *who = "mad_map_rotate";
+    MAD_TRY(search_check(ctx, who, dims0, c0, edge, iso));
+    if (edge > FFT_MAX_N) return mad_fail(ctx, MAD_EDOM, "%s: edge %d, more than %d", who, edge, FFT_MAX_N);
+    if (!search_rotation_ok(R)) return mad_fail(ctx, MAD_EINVAL, "%s: the rotation is not finite or not orthonormal (max |R R^T - I| > 1e-6)", who);
+    SearchRotateArgs RA;
+    search_rotate_args(&RA, nullptr, dims0, c0, edge, iso, 0);
+    const size_t n0 = (size_t)dims0[0] * dims0[1] * dims0[2], n_pb = (RA.n_runs + SEARCH_RUN - 1) / SEARCH_RUN;
+    const size_t b_pa = (size_t)RA.n_runs * 24, b_pb = n_pb * 24, b_blk = 96 + b_pa + b_pb;
+    size_t free_b = 0, total_b = 0;
+    MAD_HIP(hipMemGetInfo(&free_b, &total_b));
+    const size_t need = (RA.n_box + n0 + 8) * 5 + b_blk * 2 + ((size_t)8 << 20);
+    if (need > free_b) return mad_fail(ctx, MAD_ENOMEM, "%s: %zu MiB of device memory needed, %zu MiB are free", who, need >> 20, free_b >> 20);
+    MAD_TRY(mad_reserve(ctx, mad_sb(ctx, S_TMP_H), (RA.n_box + 4) * 4));
+    MAD_TRY(mad_reserve(ctx, mad_sb(ctx, S_TMP_I), (n0 + 4) * 4));
+    MAD_TRY(mad_reserve(ctx, mad_sb(ctx, S_TMP_G), b_blk));
+    float *d_out = scratch<float>(ctx, S_TMP_H), *d_base = scratch<float>(ctx, S_TMP_I);
+    char *blk = scratch<char>(ctx, S_TMP_G);
+    double *d_R = (double *)blk, *d_rec = (double *)(blk + 72), *part_a = (double *)(blk + 96), *part_b = (double *)(blk + 96 + b_pa);
+    RA.g0 = d_base;
+    MAD_HIP(hipMemcpyAsync(d_base, base, n0 * 4, hipMemcpyHostToDevice, ctx->stream));
+    MAD_HIP(hipMemcpyAsync(d_R, R, 72, hipMemcpyHostToDevice, ctx->stream));
+    mad_timer_begin(ctx, MAD_T_SEARCH);
+    search_rotate_launch(ctx, RA, d_R, nullptr, d_out, part_a, part_b, d_rec, 0u);
+    mad_timer_end(ctx, MAD_T_SEARCH);
+    MAD_HIP(hipGetLastError());
+    MAD_HIP(hipMemcpyAsync(out, d_out, RA.n_box * 4, hipMemcpyDeviceToHost, ctx->stream));
+    MAD_HIP(hipMemcpyAsync(stats, d_rec, 24, hipMemcpyDeviceToHost, ctx->stream));
+    MAD_HIP(hipStreamSynchronize(ctx->stream));
+    return MAD_OK;
 }

@@ -3670,6 +3670,11 @@ extern "C" int mad_set_option(mad_ctx *ctx, const char *name, double value) {
         ctx->fft_bpt = (int)value;
         return MAD_OK;
     }
+    if (!strcmp(name, "search_prune")) {      // test hook: 0 = mad_map_search transforms whole lattices; it changes speed, never numbers
+        if (value != 0 && value != 1) return mad_fail(ctx, MAD_EINVAL, "mad_set_option: search_prune = %g (0 or 1)", value);
+        ctx->search_prune = (int)value;
+        return MAD_OK;
+    }
     return mad_fail(ctx, MAD_EINVAL, "mad_set_option: unknown option '%s'", name);
 }
 

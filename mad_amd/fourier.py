@@ -1,6 +1,7 @@
 """Fourier shell correlation of two maps and radial filters in Fourier space (section 4m): the host side.
 The filters -- `filter_lattice`, `radial_gain`, the designs `gain_*` and the restatement `filter_numpy` -- have their contract
-further down, and so has the translation scan (section 4n): `scan_lattice`, the restatement `scan_numpy`, `peaks_numpy` and `Scan`.
+further down, and so have the translation scan (section 4n): `scan_lattice`, the restatement `scan_numpy`, `peaks_numpy` and `Scan`,
+and the rotational search (section 4o): `rotation_set`, the restatements `rotate_numpy`, `tree_sum` and `search_numpy`, and `Search`.
 
 `plan_box` puts two grids of one spacing onto a common cubic lattice, `fsc_numpy` restates the contract of `mad_map_fsc` with
 `numpy.fft.fftn` in float64 -- the checker of the GPU tests, and the one place the contract is spelled out in code -- and `FSC` is
@@ -395,6 +396,232 @@ class Scan(object):
         is the best score of the template whose voxel (0, 0, 0) is placed there."""
         from . import mapio
         mapio.write_volume(outname, np.ascontiguousarray(self.best, np.float32), tuple(self.origin), self.voxsp)
+
+
+# ---------------------------------------------------------------------------
+# rotational search (DESIGN.md section 4o): the contract of `mad_map_search` and `mad_map_rotate`
+#
+# A map m (float32 [x, y, z], dims d1), ONE base template g0 (float32, any dims d0), a centre c0 (float64 [3], in g0's voxel
+# coordinates, may be fractional), a cube edge e >= 1 with e <= d1 per axis, n_r >= 1 rotations R_j (row-major 3 x 3; the library
+# moves points by y = (x - c) @ R + c, so the rotated density at y is the base density at (y - c) @ R^T + c), iso, e_fill >= 0, mode,
+# min_score, k.
+# Rotated template: c2 = (e - 1) / 2; for the cube's voxel x, d = x - c2 and p_a = c0_a + ((d_0 R[a][0] + d_1 R[a][1]) + d_2 R[a][2]);
+# f = floor(p), t = p - f; the eight corners are read from g0, a corner outside g0 is 0 (a p at or beyond -1 or d0 on an axis has no
+# corner inside and gives 0); lerp(a, b, t) = a + t (b - a) along z, then y, then x; float64 in exactly this order, no fused
+# multiply-add; rounded to float32: the template voxel g_j(x).  With c0 - c2 integral the identity returns g0's bits, and a rotation
+# whose entries are 0 and +-1 permutes voxels.
+# Mask and sums: w = [g_j > iso] in float64, n_w = sum w, G = tree_sum(g^2 w), S = tree_sum(g w) over the cube in linear [x][y][z]
+# order; mode 1: gbar = S / n_w, G' = G - n_w (gbar gbar).  A rotation is skipped (scores no offset; counted, not refused) when
+# n_w = 0, G is not in (0, 1.7e308] or, in mode 1, G' <= 0.
+# Scores: section 4n's over D = d1 - e + 1 with the floor e_min_j = e_fill n_w_j; best, best_r and the peaks as there.
+# ---------------------------------------------------------------------------
+
+def rotation_set(angle):
+    """-> float64 [n, 3, 3]: rotations such that every rotation of SO(3) lies within `angle` degrees of a member.  Member 0 is the
+    identity; deterministic.  Directions on a Fibonacci spiral from pole to pole, one per hexagonal cell of side `angle`
+    (n_d = ceil(4 pi / (sqrt(3) / 2 angle^2))), each reached from +z by the shortest turn, after an in-plane turn about z by
+    multiples of 360 / ceil(360 / angle) degrees: member i n_t + k is Rz(k step) followed by the turn to direction i (matrices for
+    row vectors, x @ R).  45 / 30 / 20 / 15 degrees give 192 / 636 / 2160 / 5088 members."""
+    angle = float(angle)
+    if not (0.0 < angle <= 180.0):
+        raise ValueError("rotation_set: angle %r (in (0, 180] degrees)" % (angle,))
+    a = np.radians(angle)
+    n_d = max(int(np.ceil(4.0 * np.pi / (np.sqrt(3.0) / 2.0 * a * a))), 2)
+    n_t = int(np.ceil(360.0 / angle))
+    golden = np.pi * (3.0 - np.sqrt(5.0))
+    out = np.zeros((n_d * n_t, 3, 3))
+    for i in range(n_d):
+        z = 1.0 - 2.0 * i / (n_d - 1.0)
+        r = np.sqrt(max(0.0, 1.0 - z * z))
+        d = np.array([r * np.cos(golden * i), r * np.sin(golden * i), z])
+        if i == 0:
+            A = np.eye(3)
+        elif i == n_d - 1:
+            A = np.diag([1.0, -1.0, -1.0])      # +z to -z: half a turn about x
+        else:      # Rodrigues about z x d: the column form, +z -> d
+            ax = np.array([-d[1], d[0], 0.0]) / r
+            K = np.array([[0.0, -ax[2], ax[1]], [ax[2], 0.0, -ax[0]], [-ax[1], ax[0], 0.0]])
+            A = np.eye(3) + r * K + (1.0 - z) * (K @ K)
+        for k in range(n_t):
+            psi = 2.0 * np.pi * k / n_t
+            c, s = (1.0, 0.0) if k == 0 else (np.cos(psi), np.sin(psi))
+            Rz = np.array([[c, -s, 0.0], [s, c, 0.0], [0.0, 0.0, 1.0]])
+            M = (A @ Rz).T      # row-vector form
+            u, _, vt = np.linalg.svd(M)      # the nearest rotation: orthonormal to the last bit
+            out[i * n_t + k] = np.eye(3) if (i == 0 and k == 0) else u @ vt
+    return out
+
+
+def rotation_distance(Q, members):
+    """Degrees from the rotation `Q` [3, 3] to the nearest of `members` [n, 3, 3]."""
+    tr = np.einsum("ab,nab->n", np.asarray(Q, np.float64), np.asarray(members, np.float64))
+    return float(np.degrees(np.arccos(np.clip((tr.max() - 1.0) / 2.0, -1.0, 1.0))))
+
+
+def rotate_numpy(g0, c0, e, R):
+    """The rotated template of the contract -> float32 [e, e, e]."""
+    g0 = np.asarray(g0)
+    g64 = g0.astype(np.float64)
+    e = int(e)
+    if g0.ndim != 3 or g0.size == 0 or e < 1:
+        raise ValueError("rotate_numpy: a grid of shape %r, edge %r" % (g0.shape, e))
+    c0, R = np.asarray(c0, np.float64).reshape(3), np.asarray(R, np.float64).reshape(3, 3)
+    if not (np.isfinite(c0).all() and np.isfinite(R).all()):
+        raise ValueError("rotate_numpy: c0 or R is not finite")
+    c2 = (float(e) - 1.0) / 2.0
+    ax = np.arange(e, dtype=np.float64) - c2
+    d = [ax[:, None, None], ax[None, :, None], ax[None, None, :]]
+    p = [c0[a] + ((d[0] * R[a, 0] + d[1] * R[a, 1]) + d[2] * R[a, 2]) for a in range(3)]
+    inside = np.ones((e, e, e), bool)
+    for a in range(3):
+        inside &= (p[a] > -1.0) & (p[a] < float(g0.shape[a]))
+    p = [np.where(inside, v, 0.0) for v in p]
+    f = [np.floor(v) for v in p]
+    t = [p[a] - f[a] for a in range(3)]
+    i = [f[a].astype(np.int64) for a in range(3)]
+
+    def corner(da, db, dc):
+        x, y, z = i[0] + da, i[1] + db, i[2] + dc
+        ok = (x >= 0) & (x < g0.shape[0]) & (y >= 0) & (y < g0.shape[1]) & (z >= 0) & (z < g0.shape[2])
+        return np.where(ok, g64[np.clip(x, 0, g0.shape[0] - 1), np.clip(y, 0, g0.shape[1] - 1), np.clip(z, 0, g0.shape[2] - 1)], 0.0)
+
+    def lerp(a, b, w):
+        return a + w * (b - a)
+
+    v00, v01 = lerp(corner(0, 0, 0), corner(0, 0, 1), t[2]), lerp(corner(0, 1, 0), corner(0, 1, 1), t[2])
+    v10, v11 = lerp(corner(1, 0, 0), corner(1, 0, 1), t[2]), lerp(corner(1, 1, 0), corner(1, 1, 1), t[2])
+    v = lerp(lerp(v00, v01, t[1]), lerp(v10, v11, t[1]), t[0])
+    return np.where(inside, v, 0.0).astype(np.float32)
+
+
+def tree_sum(x):
+    """The fixed pairing of the contract's sums: runs of 256 consecutive elements (the last zero-padded), each summed by halving
+    (x[:128] + x[128:], then 64, ... 1), and the partial sums the same way until one value is left -> float."""
+    x = np.asarray(x, np.float64).reshape(-1)
+    if x.size == 0:
+        return 0.0
+    while True:
+        n = -(-x.size // 256)
+        r = np.zeros(n * 256)
+        r[:x.size] = x
+        r = r.reshape(n, 256)
+        h = 128
+        while h >= 1:
+            r = r[:, :h] + r[:, h:2 * h]
+            h //= 2
+        x = r.reshape(-1)
+        if x.size == 1:
+            return float(x[0])
+
+
+def search_stats(g, iso, mode=0):
+    """-> (n_w int, G, S, G' (G in mode 0), skipped) of one rotated template by the contract's sums."""
+    g = np.asarray(g).astype(np.float64).reshape(-1)
+    w = (g > float(iso)).astype(np.float64)
+    n_w, G, S = int(w.sum()), tree_sum(g * g * w), tree_sum(g * w)
+    skipped = n_w == 0 or not (0.0 < G <= 1.7e308)
+    Gp = G
+    if mode and not skipped:
+        gbar = S / n_w
+        Gp = G - n_w * (gbar * gbar)
+        skipped = not Gp > 0.0
+    return n_w, G, S, Gp, skipped
+
+
+def search_numpy(m, g0, c0, e, rotations, iso, e_fill, mode):
+    """The contract of `mad_map_search` through `rotate_numpy` and, per rotation, `scan_numpy` -> (best float64 [D] before the cast
+    to float32 -- the maximum is taken on the float32 values --, best_r int32 [D], n_skipped, and per rotation the tuple
+    (n_w, G, S, G', skipped))."""
+    if mode not in (0, 1):
+        raise ValueError("search_numpy: mode %r (0 un-centred, 1 centred)" % (mode,))
+    e_fill = float(e_fill)
+    if not (e_fill >= 0) or not np.isfinite(e_fill) or not np.isfinite(float(iso)):
+        raise ValueError("search_numpy: iso %r, e_fill %r (finite, e_fill 0 or more)" % (iso, e_fill))
+    rot = np.asarray(rotations, np.float64)
+    if rot.ndim != 3 or rot.shape[1:] != (3, 3) or len(rot) < 1:
+        raise ValueError("search_numpy: rotations of shape %r, not (n, 3, 3) with n >= 1" % (rot.shape,))
+    for j, R in enumerate(rot):
+        if not np.isfinite(R).all() or np.abs(R @ R.T - np.eye(3)).max() > 1e-6:
+            raise ValueError("search_numpy: rotation %d is not finite or not orthonormal" % j)
+    m, e = np.asarray(m), int(e)
+    _, D = scan_lattice(m.shape, (e, e, e))
+    best, best32, best_r = np.zeros(D), np.zeros(D, np.float32), np.full(D, -1, np.int32)
+    stats, n_skipped = [], 0
+    for j, R in enumerate(rot):
+        g = rotate_numpy(g0, c0, e, R)
+        st = search_stats(g, iso, mode)
+        stats.append(st)
+        if st[4]:
+            n_skipped += 1
+            continue
+        b, bt = scan_numpy(m, [g], iso, e_fill * st[0], mode)[:2]
+        b32 = b.astype(np.float32)
+        take = (bt >= 0) & ((best_r < 0) | (b32 > best32))
+        best[take], best32[take], best_r[take] = b[take], b32[take], j
+    return best, best_r, n_skipped, stats
+
+
+def search_edge(g0, c0, iso):
+    """The cube edge `Dmap.search` uses: the smallest odd integer >= 2 rho + 3, rho the largest distance in voxels from `c0` to a
+    voxel of `g0` above `iso` (0 where there is none): the mask of every rotation fits with a voxel to spare."""
+    g0, c0 = np.asarray(g0), np.asarray(c0, np.float64).reshape(3)
+    idx = np.argwhere(g0.astype(np.float64) > float(iso))
+    rho = float(np.sqrt(((idx - c0) ** 2).sum(axis=1).max())) if len(idx) else 0.0
+    e = int(np.ceil(2.0 * rho + 3.0))
+    return e if e % 2 else e + 1
+
+
+class Search(object):
+    """What `Dmap.search` returns.  `best` float32 [D]: the best score over the rotations at every whole-voxel offset; `best_r` int32
+    [D]: the rotation that attains it, -1 where none was scored; `peaks`: float64 [n, 5] = ux, uy, uz, score, rotation, the best
+    first; `n_found`: how many peaks there are (`peaks` holds the first k); `n_skipped`: rotations whose mask was empty (or, centred,
+    flat).  `rotations` [n, 3, 3], `centroid`, `origin`, `voxsp` and `edge` turn a peak into a placement: at offset u the centre of the
+    cube, voxel c2 = (edge - 1) / 2, carries the centroid, so a point x of the structure goes to (x - centroid) @ R + centroid + T,
+    T = origin + (u + c2) voxsp - centroid.  Peaks are whole-voxel and no finer in angle than the set's spacing."""
+
+    def __init__(self, best, best_r, peaks, n_found, n_skipped, origin, voxsp, rotations, centroid, edge, N=0, e_fill=0.0, mode=0):
+        self.best, self.best_r = best, best_r
+        self.peaks = np.asarray(peaks, np.float64).reshape(-1, 5)
+        self.n_found, self.n_skipped = int(n_found), int(n_skipped)
+        self.origin = np.asarray(origin, np.float64).reshape(3)
+        self.voxsp = float(voxsp)
+        self.rotations = np.asarray(rotations, np.float64).reshape(-1, 3, 3)
+        self.centroid = np.asarray(centroid, np.float64).reshape(3)
+        self.edge = int(edge)
+        self.N, self.e_fill, self.mode = int(N), float(e_fill), int(mode)
+
+    def pose(self, i):
+        """-> (rotation index, R [3, 3], T [3], score) of peak i."""
+        ux, uy, uz, score, j = self.peaks[i]
+        j = int(j)
+        c2 = (self.edge - 1.0) / 2.0
+        T = self.origin + (np.array([ux, uy, uz]) + c2) * self.voxsp - self.centroid
+        return j, self.rotations[j], T, float(score)
+
+    def place(self, i, pdb):
+        """The structure at peak i: a copy of `pdb` (a `PDB`: a new `PDB` with the coordinates moved; an (n, 3) array: a new array)."""
+        _, R, T, _ = self.pose(i)
+        if hasattr(pdb, "get_coords"):
+            import copy
+            out = copy.deepcopy(pdb)
+            out.set_coords((np.asarray(pdb.get_coords(), np.float64) - self.centroid) @ R + self.centroid + T)
+            return out
+        return (np.asarray(pdb, np.float64) - self.centroid) @ R + self.centroid + T
+
+    def write_peaks(self, path):
+        """Columns rank, ux, uy, uz (voxels), score, rotation, tx, ty, tz (Angstrom)."""
+        with open(path, "w") as f:
+            f.write("rank,ux,uy,uz,score,rotation,tx,ty,tz\n")
+            for i in range(len(self.peaks)):
+                j, _, T, score = self.pose(i)
+                f.write("%d,%d,%d,%d,%.9g,%d,%.6f,%.6f,%.6f\n" % ((i,) + tuple(int(v) for v in self.peaks[i][:3]) + (score, j) + tuple(T)))
+
+    def write(self, outname):
+        """The score volume as a map (.sit / .situs: Situs, anything else MRC) whose origin is the map's origin + c2 voxsp: the value
+        at a point is the best score of the structure with its centroid there."""
+        from . import mapio
+        o = self.origin + (self.edge - 1.0) / 2.0 * self.voxsp
+        mapio.write_volume(outname, np.ascontiguousarray(self.best, np.float32), tuple(o), self.voxsp)
 
 
 class FSC(object):
