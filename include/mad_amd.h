@@ -693,6 +693,36 @@ int mad_map_search(mad_ctx *ctx, const float *map, const int32_t dims1[3], const
 int mad_map_rotate(mad_ctx *ctx, const float *base, const int32_t dims0[3], const double c0[3], int32_t edge, const double R[9], double iso,
                    float *out /* float32 [e^3] */, double stats[3] /* n_w, G, S */);
 
+/*
+ * Local resolution of a map by windowed Fourier shell correlation.  DESIGN.md section 4p has the contract; mad_amd/fourier.py restates
+ * it as local_fsc_numpy.  No reference counterpart.
+ *   Placement.  As mad_map_fsc: per axis d = o2 / voxsp - o1 / voxsp, s = round(d) (half to even), delta = d - s; grid 2's voxel j
+ *     sits at grid 1's index j + s, delta goes into the phase ramp with N = box.  The dims need not be equal; a voxel outside either
+ *     grid is 0 for that grid.
+ *   Samples.  n_a = (dims1[a] - 1) / step + 1 points per axis at grid-1 voxel p_a = step m_a; the outputs are volumes [n_x][n_y][n_z]
+ *     with grid 1's origin and spacing step voxsp.  select (uint8 over that lattice, NULL: every sample): a sample whose byte is 0 gets
+ *     resolution 0.0, shell -1 and zero sums, and nothing is computed for it.
+ *   Box.  Box index n in 0 .. box - 1 stands for voxel p - box / 2 + n on every axis.  Both grids are multiplied by the periodic Hann
+ *     window (h[nx] h[ny]) h[nz], h[n] = 0.5 - 0.5 cos(2 pi n / box) (the cosine of an exactly reduced angle): it peaks at the sample.
+ *   Sums.  Z = FFT(w1 + i w2), forward, unnormalised; F1, F2, the shells 0 .. box / 2 and P1, P2, C as mad_map_fsc with N = box.
+ *   Crossing.  fsc_s = C_s / sqrt(P1_s P2_s), 0 where P1_s P2_s is not > 0; the first shell s >= 1 with fsc_s < threshold; with
+ *     a = fsc_(s-1), b = fsc_s, freq_s = s / (box voxsp): f = freq_(s-1) + (freq_s - freq_(s-1)) ((a - threshold) / (a - b)) when
+ *     a >= threshold, else f = freq_s; resolution = 1 / f, shell = s.  No such shell: resolution = 2 voxsp, shell = 0.
+ *   float64, no fused multiply-add, no atomics, every sum in an order fixed by indices: the same bits every run and after any other call.
+ * resolution == NULL: the size query -- the checks and n_out only, nothing allocated or launched.  Otherwise resolution and shell hold
+ * n_x n_y n_z entries, sums (may be NULL) n_x n_y n_z (box / 2 + 1) 3.
+ * MAD_EINVAL: NULL (other than select, sums, and resolution with shell), a box other than 8, 16 or 32, step < 1, a threshold outside
+ * (-1, 1) or not finite, voxsp <= 0 or not finite, a dimension < 1, a grid of 2^32 voxels or more, an origin that is not finite.
+ * MAD_EDOM: origins 1e15 voxels or more apart, 2^31 selected samples or more.  MAD_ENOMEM: less device memory free than the grids, the
+ * outputs and (box 32) the 32 MiB scratch buffer need, judged before anything is allocated.  Each leaves the outputs untouched,
+ * launches nothing, and the next call works.
+ */
+int mad_map_local_fsc(mad_ctx *ctx, const float *grid1, const int32_t dims1[3], const double origin1[3],
+                      const float *grid2, const int32_t dims2[3], const double origin2[3], double voxsp,
+                      int32_t box, int32_t step, double threshold, const uint8_t *select /* may be NULL: every sample */,
+                      double *resolution /* [nx][ny][nz]; NULL: size query */, int32_t *shell /* same */,
+                      double *sums /* may be NULL; [nx][ny][nz][box / 2 + 1][3] = P1, P2, C */, int32_t n_out[3]);
+
 /* ---- one subunit's pair grid sharded over GPUs by blocks of map rows (the exchange steps -- OR of the flag vectors,
  *      all-gather of the per-shard top-k -- are the caller's, mad_amd/dist.py::sharded_match, or the library's own:
  *      mad_dist_or_allreduce / mad_dist_allgather_topk below) ------------------------------------------------- */

@@ -15,7 +15,8 @@ correlation of the map against a second map or a placed model through `mad_map_f
 `lowpass`, `highpass`, `sharpen` and `filter_radial` filter the map in Fourier space through `mad_map_filter` (fourier.py; no
 counterpart in the reference).  `scan` scores every whole-voxel translation of a structure, in a handful of orientations, against the
 map through `mad_map_scan` (fourier.py; no counterpart in the reference: the exhaustive cross-check of a docked pose), and `search`
-does so over a whole set of rotations made on the device (`mad_map_search`).
+does so over a whole set of rotations made on the device (`mad_map_search`).  `local_resolution` is `fsc` per sample point, in a
+windowed cube around it, through `mad_map_local_fsc` (fourier.py; no counterpart in the reference).
 None of them has a CPU fallback.  The reference's per-voxel text writer is replaced by `mapio.write_situs`.
 """
 import os
@@ -203,31 +204,61 @@ class Dmap(object):
         list / tuple of those -- whose density is simulated at `resolution` on this map's spacing (masses as in `fit_by_group`).
         The two grids need not share a lattice: whole voxels of offset place them, the rest goes into a phase ramp.  No mask, no
         soft edge (`zone(soft=...)` or `mask_with` first); neither map is modified.  DESIGN.md section 4l has the exact contract."""
-        from . import fourier, localfit
+        from . import fourier
         voxsp = float(self.voxsp)
+        g1, g2, o2, _ = self._fsc_pair("Dmap.fsc", other, resolution, masses)
+        N, sums, count = _lib.get_lib().map_fsc(g1, (self.xi, self.yi, self.zi), g2, o2, voxsp)
+        return fourier.FSC(N, voxsp, sums, count)
+
+    def _fsc_pair(self, who, other, resolution, masses):
+        """What `fsc` and `local_resolution` compare -> (this map's grid, the second grid, its origin, whether it is a simulated
+        model), both grids C-contiguous float32."""
+        from . import localfit
+        voxsp, model = float(self.voxsp), False
         if isinstance(other, Dmap):
             if other.voxsp != self.voxsp:
-                raise ValueError("Dmap.fsc: voxsp differ (%r vs %r): bring one map onto the other's lattice with resample(like=...) first"
-                                 % (self.voxsp, other.voxsp))
+                raise ValueError("%s: voxsp differ (%r vs %r): bring one map onto the other's lattice with resample(like=...) first"
+                                 % (who, self.voxsp, other.voxsp))
             g2, o2 = other.grid3d, (other.xi, other.yi, other.zi)
         elif isinstance(other, (list, tuple)) and len(other) == 2 and np.ndim(other[0]) == 3:
             g2, o2 = other
         else:
             if resolution is None or not (float(resolution) > 0) or not np.isfinite(float(resolution)):
-                raise ValueError("Dmap.fsc: a model needs the resolution to simulate its density at (positive and finite), got %r" % (resolution,))
+                raise ValueError("%s: a model needs the resolution to simulate its density at (positive and finite), got %r" % (who, resolution))
             parts = localfit.structure_parts(other)
             m = localfit.structure_masses(parts, masses)
             if sum(len(c) for c, _, _ in parts) == 0:
-                raise ValueError("Dmap.fsc: no atoms to simulate a density from")
+                raise ValueError("%s: no atoms to simulate a density from" % who)
             coords = np.concatenate([c for c, _, _ in parts], axis=0)
             g2, x0, y0, z0 = _lib.get_lib().structure_to_density(coords, m, float(resolution), voxsp)
-            o2 = (x0, y0, z0)
+            o2, model = (x0, y0, z0), True
         g1 = np.ascontiguousarray(self.grid3d, dtype=np.float32)
         g2 = np.ascontiguousarray(g2, dtype=np.float32)
         if g2.ndim != 3:
-            raise ValueError("Dmap.fsc: the second grid has %d dimensions" % g2.ndim)
-        N, sums, count = _lib.get_lib().map_fsc(g1, (self.xi, self.yi, self.zi), g2, o2, voxsp)
-        return fourier.FSC(N, voxsp, sums, count)
+            raise ValueError("%s: the second grid has %d dimensions" % (who, g2.ndim))
+        return g1, g2, o2, model
+
+    def local_resolution(self, other, box=16, step=2, threshold=None, resolution=None, masses=None, isovalue=None, sums=False):
+        """Where does the map hold which resolution?  The Fourier shell correlation of this map against `other`, not over the whole
+        box as `fsc` takes it but in a Hann-windowed cube of `box` (8, 16 or 32) voxels around every `step`-th voxel, through
+        `mad_map_local_fsc` -> `fourier.LocalResolution` (`resolution`, `shell`, `reached`, `computed`, `curve(i, j, k)`, `median()`,
+        `to_dmap()`, `write(outname)`).  `other` as in `fsc`: a `Dmap` of the same spacing, a (grid, (x0, y0, z0)) pair, or a placed
+        model simulated at `resolution`.  `threshold=None` means 0.143 against a map (two half maps) and 0.5 against a model.
+        `isovalue=v` computes only the samples whose own voxel of this map is > v; the others hold 0.0.  `sums=True` keeps every
+        box's shell sums (`curve` needs them).  A box resolves frequencies no finer than 1 / (box voxsp) apart: a large box for a
+        trustworthy number, a small one for a sharp picture.  No mask, no soft edge (`zone(soft=...)` or `mask_with` first); neither
+        map is modified.  DESIGN.md section 4p has the exact contract."""
+        from . import fourier
+        voxsp = float(self.voxsp)
+        g1, g2, o2, model = self._fsc_pair("Dmap.local_resolution", other, resolution, masses)
+        thr = (0.5 if model else 0.143) if threshold is None else float(threshold)
+        step = int(step)
+        sel = None
+        if isovalue is not None and step >= 1:
+            sel = g1[::step, ::step, ::step] > float(isovalue)
+        o1 = (self.xi, self.yi, self.zi)
+        res, shell, sm = _lib.get_lib().map_local_fsc(g1, o1, g2, o2, voxsp, box=box, step=step, threshold=thr, select=sel, sums=sums)
+        return fourier.LocalResolution(res, shell, sm, box, step, voxsp, o1, thr)
 
     def scan(self, structure, resolution, rotations=None, mode="uncentred", isovalue=None, min_fill=0.25, min_score=0.0, k=20, masses=None):
         """Where in the map does the structure fit best?  Every whole-voxel translation of it, in each of the given orientations,

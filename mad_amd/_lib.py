@@ -39,7 +39,7 @@ SYMBOLS = [
     "mad_dist_unique_id", "mad_dist_init", "mad_dist_destroy", "mad_dist_info", "mad_dist_rehearse_flags", "mad_dist_or_allreduce", "mad_dist_allgather",
     "mad_dist_allgather_topk", "mad_dist_scratch", "mad_dist_copy",
     "mad_set_wire_bytes", "mad_set_export", "mad_set_import", "mad_set_lane", "mad_set_stream", "mad_set_bind_lane",
-    "mad_upload_density", "mad_refine", "mad_last_refine_plan", "mad_last_density_chunks", "mad_structure_to_density", "mad_ccc", "mad_map_mask", "mad_map_ccc", "mad_map_resample", "mad_map_zone", "mad_map_group_fit", "mad_map_smooth", "mad_map_segment", "mad_map_fsc", "mad_map_fft", "mad_map_filter", "mad_map_ifft", "mad_map_scan", "mad_map_search", "mad_map_rotate", "mad_density_ccc", "mad_dock_refine_score", "mad_grid_overlap", "mad_overlap_matrix",
+    "mad_upload_density", "mad_refine", "mad_last_refine_plan", "mad_last_density_chunks", "mad_structure_to_density", "mad_ccc", "mad_map_mask", "mad_map_ccc", "mad_map_resample", "mad_map_zone", "mad_map_group_fit", "mad_map_smooth", "mad_map_segment", "mad_map_fsc", "mad_map_fft", "mad_map_filter", "mad_map_ifft", "mad_map_scan", "mad_map_search", "mad_map_rotate", "mad_map_local_fsc", "mad_density_ccc", "mad_dock_refine_score", "mad_grid_overlap", "mad_overlap_matrix",
     "mad_space_create", "mad_space_destroy", "mad_space_build", "mad_space_info", "mad_space_download",
     "mad_space_peaks", "mad_space_patches", "mad_space_localize", "mad_localize_volume",
     "mad_pose_cluster_many",
@@ -1196,6 +1196,27 @@ class Lib(object):
                                        _p(sums), _p(count), C.c_int64(cap)))
         sh = n.value // 2 + 1
         return int(n.value), sums[:sh].copy(), count[:sh].copy()
+
+    def map_local_fsc(self, g1, o1, g2, o2, voxsp, box=16, step=2, threshold=0.143, select=None, sums=False):
+        """Local resolution by windowed Fourier shell correlation -> (resolution float64 [nx, ny, nz], shell int32 [nx, ny, nz],
+        sums float64 [nx, ny, nz, box / 2 + 1, 3] or None) over the samples at every `step`-th voxel of `g1` (mad_map_local_fsc;
+        DESIGN.md section 4p; `fourier.local_fsc_numpy` restates it).  `select`: an array over the sample lattice, a sample where it
+        is 0 gets 0.0 / -1 and is not computed.  Both grids C-contiguous float32 [x, y, z]; neither is modified."""
+        d1, o1, d2, o2 = self._fourier_args("map_local_fsc", g1, o1, g2, o2)
+        n = np.zeros(3, np.int32)
+        args = (self.ctx, _p(g1), _p(d1), _p(o1), _p(g2), _p(d2), _p(o2), C.c_double(voxsp), C.c_int32(int(box)), C.c_int32(int(step)),
+                C.c_double(float(threshold)))
+        self._chk(self.dll.mad_map_local_fsc(*args, None, None, None, None, _p(n)))      # the size query
+        shape = tuple(int(v) for v in n)
+        sel = None
+        if select is not None:
+            sel = np.ascontiguousarray(np.asarray(select) != 0, dtype=np.uint8)
+            if sel.shape != shape:
+                raise ValueError("map_local_fsc: select of shape %r, the sample lattice is %r" % (sel.shape, shape))
+        res, shell = np.empty(shape, np.float64), np.empty(shape, np.int32)
+        sm = np.empty(shape + (int(box) // 2 + 1, 3), np.float64) if sums else None
+        self._chk(self.dll.mad_map_local_fsc(*args, None if sel is None else _p(sel), _p(res), _p(shell), None if sm is None else _p(sm), _p(n)))
+        return res, shell, sm
 
     def map_fft(self, g1, o1, g2=None, o2=None, voxsp=1.0):
         """The transform `map_fsc` works on, for testing it alone -> complex128 [N, N, N]: the FFT of the lattice that holds `g1`

@@ -110,6 +110,7 @@ extern "C" void mad_destroy(mad_ctx *ctx) {
     for (auto &lane : ctx->dist_buf)
         for (auto &b : lane) mad_release(b);
     mad_release(ctx->fft_tw);
+    for (auto &b : ctx->lr_tab) mad_release(b);
     if (ctx->eq[0]) (void)hipFree(ctx->eq[0]);
     if (ctx->eq[1]) (void)hipFree(ctx->eq[1]);
     if (ctx->mask_off) (void)hipFree(ctx->mask_off);
@@ -186,7 +187,7 @@ void mad_timer_end(mad_ctx *ctx, int group) {
 
 static const char *k_timer_names[MAD_T_COUNT] = {"orient", "describe", "correlate", "pairs", "pose",
                                                  "topk",   "refine",   "density",   "ccc",
-                                                 "seg_parent", "seg_jump", "seg_scan", "seg_smooth", "fft", "fsc", "filter", "scan", "search"};
+                                                 "seg_parent", "seg_jump", "seg_scan", "seg_smooth", "fft", "fsc", "filter", "scan", "search", "localres"};
 
 extern "C" int mad_timing_enable(mad_ctx *ctx, int on) {
     if (!ctx) return MAD_EINVAL;

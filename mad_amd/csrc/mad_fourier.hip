@@ -44,7 +44,7 @@
 #include <algorithm>
 #include <vector>
 
-#include "mad_common.h"
+#include "mad_fft_common.h"
 
 #define FFT_L 8                 // lines per tile
 #define FFT_MIN_N 8
@@ -87,10 +87,7 @@ __global__ __launch_bounds__(256) void k_fft_pack(const PackArgs A, double2 *__r
 // 1-D transforms
 // ---------------------------------------------------------------------------
 
-__device__ __forceinline__ double2 c_add(double2 a, double2 b) { return make_double2(a.x + b.x, a.y + b.y); }
-__device__ __forceinline__ double2 c_sub(double2 a, double2 b) { return make_double2(a.x - b.x, a.y - b.y); }
-__device__ __forceinline__ double2 c_mul(double2 a, double2 b) { return make_double2(a.x * b.x - a.y * b.y, a.x * b.y + a.y * b.x); }
-__device__ __forceinline__ double2 c_muli(double2 a) { return make_double2(-a.y, a.x); }      // i a
+// (c_add, c_sub, c_mul, c_muli and the host's unit_root: mad_fft_common.h)
 
 // AXIS 0 / 1 / 2: lines along x / y / z.  One workgroup per tile, N^2 / 8 tiles; blockDim.x * BPT = max(2 N, 64) butterflies of a
 // radix-4 stage (a thread of the smallest lattices may have none).  Dynamic LDS: N * ROW * 16 bytes.
@@ -321,21 +318,6 @@ struct FourierPlan {
     int p1[3], p2[3];
     double delta[3];
 };
-
-// cos and sin of 2 pi k / N, the angle reduced exactly (in integers) to [0, pi / 4] first; N a power of two >= 8
-static void unit_root(int k, int N, double *c, double *s) {
-    const int quad = N / 4, q = (k / quad) & 3, m = k % quad;
-    double cm, sm;
-    if (m <= N / 8) { cm = cos(2.0 * M_PI * (double)m / (double)N); sm = sin(2.0 * M_PI * (double)m / (double)N); }
-    else { cm = sin(2.0 * M_PI * (double)(quad - m) / (double)N); sm = cos(2.0 * M_PI * (double)(quad - m) / (double)N); }
-    if (m == 0) { cm = 1.0; sm = 0.0; }
-    switch (q) {
-    case 0: *c = cm; *s = sm; break;
-    case 1: *c = -sm; *s = cm; break;
-    case 2: *c = -cm; *s = -sm; break;
-    default: *c = sm; *s = -cm; break;
-    }
-}
 
 static int fourier_check(mad_ctx *ctx, const char *who, const int32_t d[3], const double o[3], double voxsp) {
     for (int k = 0; k < 3; k++) {

@@ -1,7 +1,8 @@
 """Fourier shell correlation of two maps and radial filters in Fourier space (section 4m): the host side.
 The filters -- `filter_lattice`, `radial_gain`, the designs `gain_*` and the restatement `filter_numpy` -- have their contract
 further down, and so have the translation scan (section 4n): `scan_lattice`, the restatement `scan_numpy`, `peaks_numpy` and `Scan`,
-and the rotational search (section 4o): `rotation_set`, the restatements `rotate_numpy`, `tree_sum` and `search_numpy`, and `Search`.
+and the rotational search (section 4o): `rotation_set`, the restatements `rotate_numpy`, `tree_sum` and `search_numpy`, and `Search`,
+and local resolution (section 4p): `local_plan`, `hann_window`, the restatement `local_fsc_numpy` and `LocalResolution`.
 
 `plan_box` puts two grids of one spacing onto a common cubic lattice, `fsc_numpy` restates the contract of `mad_map_fsc` with
 `numpy.fft.fftn` in float64 -- the checker of the GPU tests, and the one place the contract is spelled out in code -- and `FSC` is
@@ -622,6 +623,157 @@ class Search(object):
         from . import mapio
         o = self.origin + (self.edge - 1.0) / 2.0 * self.voxsp
         mapio.write_volume(outname, np.ascontiguousarray(self.best, np.float32), tuple(o), self.voxsp)
+
+
+# ---------------------------------------------------------------------------
+# local resolution: the contract of `mad_map_local_fsc`
+#
+# Two float32 grids [x, y, z] of one spacing, placed as in section 4l: per axis d = o2 / voxsp - o1 / voxsp, s = round(d) (half to
+# even), delta = d - s; grid 2's voxel j sits at grid 1's index j + s; a voxel outside either grid is 0 for that grid.  Samples at the
+# grid-1 voxels p_a = step m_a, m_a = 0 .. n_a - 1, n_a = (dims1[a] - 1) // step + 1.  The box of a sample has edge w in {8, 16, 32}:
+# box index n stands for voxel p - w / 2 + n on every axis.  Both grids are multiplied by (h[nx] h[ny]) h[nz],
+# h[n] = 0.5 - 0.5 cos(2 pi n / w) (the cosine of the exactly reduced angle, `unit_root`): the periodic Hann window, 1 at the sample.
+# Z = FFT(w1 + i w2); F1, F2 = split_pair(Z); P1, P2, C per shell 0 .. w / 2 = shell_sums(F1, F2, delta) with N = w; the curve and its
+# crossing with the threshold are `FSC`'s and `FSC.resolution`'s: the first shell s >= 1 with fsc_s < thr, interpolated in frequency
+# against shell s - 1 where that one is at or above thr.  Not reached: 2 voxsp and shell 0.  Not selected: 0.0 and shell -1.
+# ---------------------------------------------------------------------------
+
+LOCAL_BOXES = (8, 16, 32)
+
+
+def unit_root(k, N):
+    """-> (cos, sin) of 2 pi k / N with the angle reduced exactly (in integers) to [0, pi / 4] first, as the library's host tables do;
+    N a power of two >= 8."""
+    import math
+    k, N = int(k), int(N)
+    quad = N // 4
+    q, m = (k // quad) & 3, k % quad
+    if m <= N // 8:
+        cm, sm = math.cos(2.0 * math.pi * m / N), math.sin(2.0 * math.pi * m / N)
+    else:
+        cm, sm = math.sin(2.0 * math.pi * (quad - m) / N), math.cos(2.0 * math.pi * (quad - m) / N)
+    if m == 0:
+        cm, sm = 1.0, 0.0
+    return ((cm, sm), (-sm, cm), (-cm, -sm), (sm, -cm))[q]
+
+
+def hann_window(w):
+    """float64 [w]: h[n] = 0.5 - 0.5 cos(2 pi n / w), the periodic Hann window: exactly 0 at n = 0, 0.5 at w / 4, 1 at w / 2."""
+    return np.array([0.5 - 0.5 * unit_root(n, w)[0] for n in range(int(w))])
+
+
+def shell_counts(N):
+    """int64 [N / 2 + 1]: the lattice points of every kept shell of an N^3 lattice."""
+    sh = shell_index(N).ravel()
+    return np.bincount(sh[sh <= N // 2], minlength=N // 2 + 1).astype(np.int64)
+
+
+def local_plan(dims1, o1, dims2, o2, voxsp, box, step, threshold):
+    """-> (n (int tuple: the sample lattice), s (int tuple: grid 2's voxel j sits at grid 1's index j + s), delta float64 [3]).
+    ValueError where `mad_map_local_fsc` refuses."""
+    voxsp, threshold = float(voxsp), float(threshold)
+    if box not in LOCAL_BOXES:
+        raise ValueError("local_plan: box %r (8, 16 or 32)" % (box,))
+    if int(step) != step or step < 1:
+        raise ValueError("local_plan: step %r (a whole number, 1 or more)" % (step,))
+    if not (-1.0 < threshold < 1.0):
+        raise ValueError("local_plan: threshold %r (inside (-1, 1))" % (threshold,))
+    if not (voxsp > 0) or not np.isfinite(voxsp):
+        raise ValueError("local_plan: voxsp %r (positive and finite)" % (voxsp,))
+    o1, o2 = np.asarray(o1, np.float64).reshape(3), np.asarray(o2, np.float64).reshape(3)
+    if not (np.isfinite(o1).all() and np.isfinite(o2).all()):
+        raise ValueError("local_plan: an origin is not finite")
+    if len(dims1) != 3 or len(dims2) != 3 or min(tuple(dims1) + tuple(dims2)) < 1:
+        raise ValueError("local_plan: empty grid (%r, %r)" % (tuple(dims1), tuple(dims2)))
+    s, delta = [], np.zeros(3)
+    for a in range(3):
+        d = float(o2[a]) / voxsp - float(o1[a]) / voxsp
+        if not abs(d) < 1e15:
+            raise ValueError("local_plan: origins %r voxels apart" % (d,))
+        s.append(int(round(d)))      # python's round: half to even
+        delta[a] = d - s[a]
+    return tuple((int(dims1[a]) - 1) // int(step) + 1 for a in range(3)), tuple(s), delta
+
+
+def local_box(g, lo, w):
+    """float64 [w, w, w]: the voxels lo .. lo + w - 1 (per axis) of `g`, 0 outside it."""
+    out = np.zeros((w, w, w))
+    a = [max(0, -int(lo[k])) for k in range(3)]
+    b = [min(w, g.shape[k] - int(lo[k])) for k in range(3)]
+    if all(b[k] > a[k] for k in range(3)):
+        out[a[0]:b[0], a[1]:b[1], a[2]:b[2]] = g[lo[0] + a[0]:lo[0] + b[0], lo[1] + a[1]:lo[1] + b[1], lo[2] + a[2]:lo[2] + b[2]]
+    return out
+
+
+def local_fsc_numpy(g1, o1, g2, o2, voxsp, box, step, threshold, select=None):
+    """The contract of `mad_map_local_fsc` with numpy.fft.fftn in float64 -> `LocalResolution` (with `sums`).  `select`: anything
+    that converts to a boolean array over the sample lattice, None for every sample."""
+    g1, g2 = np.asarray(g1), np.asarray(g2)
+    if g1.ndim != 3 or g2.ndim != 3:
+        raise ValueError("local_fsc_numpy: 3-D grids")
+    n, s, delta = local_plan(g1.shape, o1, g2.shape, o2, voxsp, box, step, threshold)
+    w, step, voxsp, threshold = int(box), int(step), float(voxsp), float(threshold)
+    sel = np.ones(n, bool) if select is None else np.asarray(select).astype(bool).reshape(n)
+    h = hann_window(w)
+    H = (h[:, None, None] * h[None, :, None]) * h[None, None, :]
+    count = shell_counts(w)
+    res, shell, sums = np.zeros(n), np.full(n, -1, np.int32), np.zeros(n + (w // 2 + 1, 3))
+    for m in np.argwhere(sel):
+        lo = [step * int(m[a]) - w // 2 for a in range(3)]
+        w1 = local_box(g1, lo, w) * H
+        w2 = local_box(g2, [lo[a] - s[a] for a in range(3)], w) * H
+        F1, F2 = split_pair(np.fft.fftn(w1 + 1j * w2))
+        sm, _ = shell_sums(F1, F2, delta)
+        curve = FSC(w, voxsp, sm, count)
+        r, reached = curve.resolution(threshold)
+        res[tuple(m)] = r
+        shell[tuple(m)] = int(np.nonzero(curve.fsc[1:] < threshold)[0][0]) + 1 if reached else 0
+        sums[tuple(m)] = sm
+    return LocalResolution(res, shell, sums, w, step, voxsp, o1, threshold)
+
+
+class LocalResolution(object):
+    """What `Dmap.local_resolution` returns.  `resolution` float64 [nx, ny, nz] (Angstrom): per sample the crossing of its box's FSC
+    curve with `threshold`, 2 voxsp where the curve never falls below it, 0.0 where the sample was not selected; `shell` int32: the
+    crossing shell, 0 (not reached) or -1 (not selected); `reached` = shell > 0, `computed` = shell >= 0; `sums` float64
+    [nx, ny, nz, box / 2 + 1, 3] = P1, P2, C per shell, or None.  Sample (i, j, k) sits at `origin` + step voxsp (i, j, k)."""
+
+    def __init__(self, resolution, shell, sums, box, step, voxsp, origin, threshold):
+        self.resolution = np.asarray(resolution, np.float64)
+        self.shell = np.asarray(shell, np.int32)
+        self.sums = None if sums is None else np.asarray(sums, np.float64)
+        self.box, self.step, self.voxsp, self.threshold = int(box), int(step), float(voxsp), float(threshold)
+        self.origin = np.asarray(origin, np.float64).reshape(3).copy()
+        self.reached, self.computed = self.shell > 0, self.shell >= 0
+
+    def curve(self, i, j, k):
+        """The `FSC` of the box of sample (i, j, k); needs `sums`, and a sample that was computed."""
+        if self.sums is None:
+            raise ValueError("LocalResolution.curve: made without sums (ask for sums=True)")
+        if not self.computed[i, j, k]:
+            raise ValueError("LocalResolution.curve: sample (%d, %d, %d) was not selected" % (i, j, k))
+        return FSC(self.box, self.voxsp, self.sums[i, j, k], shell_counts(self.box))
+
+    def median(self):
+        """The median resolution (Angstrom) over the samples whose curve reached the threshold; nan where none did."""
+        return float(np.median(self.resolution[self.reached])) if self.reached.any() else float("nan")
+
+    def to_dmap(self):
+        """The resolution volume as a `Dmap` of spacing step voxsp at the map's origin (float32); `resample(like=map)` brings it
+        onto the map's own lattice."""
+        from .Dmap import Dmap
+        d = Dmap.__new__(Dmap)
+        d.grid3d = np.ascontiguousarray(self.resolution, dtype=np.float32)
+        d.voxsp = self.step * self.voxsp
+        d.xi, d.yi, d.zi = (float(v) for v in self.origin)
+        d.xb, d.yb, d.zb = d.grid3d.shape
+        d.map_name, d.name = "", "local_resolution"
+        return d
+
+    def write(self, outname):
+        """The resolution volume as a map (.sit / .situs: Situs, anything else MRC) of spacing step voxsp at the map's origin."""
+        from . import mapio
+        mapio.write_volume(outname, np.ascontiguousarray(self.resolution, np.float32), tuple(self.origin), self.step * self.voxsp)
 
 
 class FSC(object):
