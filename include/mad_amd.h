@@ -723,6 +723,32 @@ int mad_map_local_fsc(mad_ctx *ctx, const float *grid1, const int32_t dims1[3], 
                       double *resolution /* [nx][ny][nz]; NULL: size query */, int32_t *shell /* same */,
                       double *sums /* may be NULL; [nx][ny][nz][box / 2 + 1][3] = P1, P2, C */, int32_t n_out[3]);
 
+/*
+ * A low-pass whose width varies from voxel to voxel: every output voxel is the map under the Gaussian of its own resolution
+ * (mad_localfilter.hip).  DESIGN.md section 4q has the contract; mad_amd/fourier.py restates it as local_sigma_numpy and
+ * local_filter_numpy.  No reference counterpart.  grid float32 [nx][ny][nz]; res float64 (Angstrom) on the sample lattice of step
+ * s >= 1, rdims m_a = (n_a - 1) / s + 1 (the lattice mad_map_local_fsc writes; s = 1: a full-size field).
+ *   Resolution at voxel (i, j, k).  Per axis j0 = min(i / s, m - 1), j1 = min(j0 + 1, m - 1), f = (i - j0 * s) / s as a float64
+ *     division, 0.0 where j1 == j0 (beyond the last sample the field is clamped, not extrapolated).  Trilinear with
+ *     lerp(a, b, f) = a + (b - a) * f along z first, then y, then x.  sigma = d / (voxsp * K) voxels, K = pi * sqrt(2) formed once on
+ *     the host in float64.  These IEEE operations in this order, none fused: sigma is the same bits on the device and in numpy.
+ *   Taps.  R = max(1, (int)(4 sigma + 0.5)) (mad_map_smooth's truncation), q = -0.5 / (sigma * sigma), w_k = exp(q * (k * k)) for
+ *     k = 0 .. R, W = w_0 + 2 * (w_R + ... + w_1), summed from R down to 1.
+ *   Output.  out = S / (W * W * W), S = sum_dx w_|dx| * (sum_dy w_|dy| * (sum_dz w_|dz| * g[i + dx, j + dy, k + dz])), each offset
+ *     from -R to R, a voxel outside the grid being 0.0.  A gather: the width is the OUTPUT voxel's.  float64 throughout, no atomics;
+ *     the order of summation depends on nothing but the inputs: two calls give the same bits.  A voxel beyond a kernel's R never
+ *     enters its sum: a voxel that is not finite spoils the outputs whose kernel covers it and no other.
+ * out = the float32 rounding of the float64 result, may be grid itself; out64 (may be NULL) = that result before rounding; sigma (may
+ * be NULL) = the per-voxel sigma in voxels.  The results do not depend on which optional outputs were asked for.
+ * MAD_EINVAL, naming the sample: a sample that is not finite or not > 0.  MAD_EDOM ("... voxels wide"): a sample whose sigma exceeds
+ * 6.0 voxels (fourier.LOCAL_FILTER_MAX_SIGMA; R <= 24) -- the interpolation is convex, so the samples alone are checked.  MAD_EINVAL:
+ * NULL (other than out64, sigma), step < 1, rdims other than the formula's, a dimension < 1, 2^31 voxels or more, voxsp not positive
+ * and finite.  Each is found on the host: nothing is allocated or launched, the outputs are untouched, and the next call works.
+ */
+int mad_map_local_filter(mad_ctx *ctx, const float *grid, const int32_t dims[3], double voxsp, const double *res,
+                         const int32_t rdims[3], int32_t step, float *out, double *out64 /* may be NULL */,
+                         double *sigma /* may be NULL */);
+
 /* ---- one subunit's pair grid sharded over GPUs by blocks of map rows (the exchange steps -- OR of the flag vectors,
  *      all-gather of the per-shard top-k -- are the caller's, mad_amd/dist.py::sharded_match, or the library's own:
  *      mad_dist_or_allreduce / mad_dist_allgather_topk below) ------------------------------------------------- */

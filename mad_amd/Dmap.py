@@ -16,7 +16,8 @@ correlation of the map against a second map or a placed model through `mad_map_f
 counterpart in the reference).  `scan` scores every whole-voxel translation of a structure, in a handful of orientations, against the
 map through `mad_map_scan` (fourier.py; no counterpart in the reference: the exhaustive cross-check of a docked pose), and `search`
 does so over a whole set of rotations made on the device (`mad_map_search`).  `local_resolution` is `fsc` per sample point, in a
-windowed cube around it, through `mad_map_local_fsc` (fourier.py; no counterpart in the reference).
+windowed cube around it, through `mad_map_local_fsc` (fourier.py; no counterpart in the reference), and `lowpass_local` low-passes
+the map by such a measurement, every voxel under the Gaussian of its own resolution, through `mad_map_local_filter`.
 None of them has a CPU fallback.  The reference's per-voxel text writer is replaced by `mapio.write_situs`.
 """
 import os
@@ -377,6 +378,72 @@ class Dmap(object):
         _lib.get_lib().map_smooth(g, sigma / self.voxsp, out=g)
         self.grid3d = g
         return self
+
+    def lowpass_local(self, local, fill=None, clip=None):
+        """A low-pass whose width varies from voxel to voxel, in place: every voxel becomes the map under the Gaussian of the
+        resolution d measured THERE, sigma = d / (pi sqrt(2)) Angstrom -- the envelope of `lowpass(kind="gaussian")` -- truncated and
+        zero-extended as `smooth` does it, through `mad_map_local_filter`.  `local`: a `fourier.LocalResolution` of this map (what
+        `local_resolution` returns; its step and `filled(fill)` are used); or a `Dmap` of resolution values whose spacing is a whole
+        multiple of this map's (within 1e-3) and whose origin is this map's (`LocalResolution.to_dmap()`, the output of
+        tools/local_resolution.py), its zeros -- samples that were not computed -- filled as `filled` does; or a pair
+        (array, step).  Between the samples the resolution is interpolated trilinearly, beyond the last one it is clamped.
+        `fill` (Angstrom; None: the largest computed value) goes where nothing was computed.  `clip=(lo, hi)` in Angstrom, by default
+        (2 voxsp, the widest the library takes: sigma just under `fourier.LOCAL_FILTER_MAX_SIGMA` = 6 voxels): values outside are
+        CLIPPED to it, not refused.  Returns self.  DESIGN.md section 4q has the exact contract."""
+        from . import fourier
+        who = "Dmap.lowpass_local"
+        voxsp = float(self.voxsp)
+        g = self.grid3d
+        if g.ndim != 3 or g.size == 0:
+            raise ValueError("%s: the grid has shape %r" % (who, g.shape))
+        if fill is not None and (not np.isfinite(float(fill)) or not (float(fill) > 0)):
+            raise ValueError("%s: fill %r (positive and finite)" % (who, fill))
+        if isinstance(local, fourier.LocalResolution):
+            if abs(local.voxsp - voxsp) > 1e-3 * voxsp or not np.allclose(local.origin, (self.xi, self.yi, self.zi), rtol=0.0, atol=1e-3 * voxsp):
+                raise ValueError("%s: the local resolution was measured on another lattice (spacing %g at %r, this map %g at %r)"
+                                 % (who, local.voxsp, tuple(local.origin), voxsp, (self.xi, self.yi, self.zi)))
+            step, field = local.step, local.filled(fill)
+        elif isinstance(local, Dmap):
+            ratio = float(local.voxsp) / voxsp
+            step = int(round(ratio))
+            if step < 1 or abs(ratio - step) > 1e-3:
+                raise ValueError("%s: the resolution map's spacing %g is no whole multiple of this map's %g" % (who, local.voxsp, voxsp))
+            if not np.allclose((local.xi, local.yi, local.zi), (self.xi, self.yi, self.zi), rtol=0.0, atol=1e-3 * voxsp):
+                raise ValueError("%s: the resolution map begins at %r, this map at %r" % (who, (local.xi, local.yi, local.zi), (self.xi, self.yi, self.zi)))
+            r = np.asarray(local.grid3d, np.float64)
+            field = fourier.LocalResolution(r, np.where(r > 0, 1, -1), None, 8, step, voxsp, (self.xi, self.yi, self.zi), 0.0).filled(fill)
+        else:
+            try:
+                field, step = local
+            except (TypeError, ValueError):
+                raise ValueError("%s: local is a LocalResolution, a Dmap of resolutions or a pair (array, step), not %r" % (who, type(local)))
+            field = np.array(field, np.float64)
+        if isinstance(step, bool) or int(step) != step or step < 1:
+            raise ValueError("%s: step %r (a whole number, 1 or more)" % (who, step))
+        step = int(step)
+        want = tuple((n - 1) // step + 1 for n in g.shape)
+        if field.shape != want:
+            raise ValueError("%s: a field of shape %r, the samples at every %d-th voxel of %r are %r" % (who, field.shape, step, g.shape, want))
+        lo, hi = self.local_clip() if clip is None else (float(clip[0]), float(clip[1]))
+        if not (0 < lo <= hi) or not np.isfinite(hi):
+            raise ValueError("%s: clip %r (0 < lo <= hi, finite)" % (who, clip))
+        if not np.isfinite(field).all():
+            raise ValueError("%s: a resolution that is not finite" % who)
+        field = np.ascontiguousarray(np.clip(field, lo, hi))
+        if g.dtype != np.float32 or not g.flags.c_contiguous or not g.flags.writeable:
+            g = np.ascontiguousarray(g, dtype=np.float32)
+            if not g.flags.writeable or g is self.grid3d:
+                g = g.copy()
+        _lib.get_lib().map_local_filter(g, field, step, voxsp, out=g)
+        self.grid3d = g
+        return self
+
+    def local_clip(self):
+        """(lo, hi) in Angstrom: the default `clip` of `lowpass_local` -- twice the spacing (Nyquist), and the resolution whose sigma
+        is just under `fourier.LOCAL_FILTER_MAX_SIGMA` voxels."""
+        from . import fourier
+        voxsp = float(self.voxsp)
+        return 2.0 * voxsp, fourier.LOCAL_FILTER_MAX_SIGMA * fourier.LOCAL_FILTER_K * voxsp * (1.0 - 1e-12)
 
     def _filter(self, who, design, pad):
         """The radial gain `design(N)(f)` (f in 1 / Angstrom) on the map through `mad_map_filter`, in place; `pad` voxels of zero

@@ -39,7 +39,7 @@ SYMBOLS = [
     "mad_dist_unique_id", "mad_dist_init", "mad_dist_destroy", "mad_dist_info", "mad_dist_rehearse_flags", "mad_dist_or_allreduce", "mad_dist_allgather",
     "mad_dist_allgather_topk", "mad_dist_scratch", "mad_dist_copy",
     "mad_set_wire_bytes", "mad_set_export", "mad_set_import", "mad_set_lane", "mad_set_stream", "mad_set_bind_lane",
-    "mad_upload_density", "mad_refine", "mad_last_refine_plan", "mad_last_density_chunks", "mad_structure_to_density", "mad_ccc", "mad_map_mask", "mad_map_ccc", "mad_map_resample", "mad_map_zone", "mad_map_group_fit", "mad_map_smooth", "mad_map_segment", "mad_map_fsc", "mad_map_fft", "mad_map_filter", "mad_map_ifft", "mad_map_scan", "mad_map_search", "mad_map_rotate", "mad_map_local_fsc", "mad_density_ccc", "mad_dock_refine_score", "mad_grid_overlap", "mad_overlap_matrix",
+    "mad_upload_density", "mad_refine", "mad_last_refine_plan", "mad_last_density_chunks", "mad_structure_to_density", "mad_ccc", "mad_map_mask", "mad_map_ccc", "mad_map_resample", "mad_map_zone", "mad_map_group_fit", "mad_map_smooth", "mad_map_segment", "mad_map_fsc", "mad_map_fft", "mad_map_filter", "mad_map_ifft", "mad_map_scan", "mad_map_search", "mad_map_rotate", "mad_map_local_fsc", "mad_map_local_filter", "mad_density_ccc", "mad_dock_refine_score", "mad_grid_overlap", "mad_overlap_matrix",
     "mad_space_create", "mad_space_destroy", "mad_space_build", "mad_space_info", "mad_space_download",
     "mad_space_peaks", "mad_space_patches", "mad_space_localize", "mad_localize_volume",
     "mad_pose_cluster_many",
@@ -1217,6 +1217,34 @@ class Lib(object):
         sm = np.empty(shape + (int(box) // 2 + 1, 3), np.float64) if sums else None
         self._chk(self.dll.mad_map_local_fsc(*args, None if sel is None else _p(sel), _p(res), _p(shell), None if sm is None else _p(sm), _p(n)))
         return res, shell, sm
+
+    def map_local_filter(self, grid, res, step, voxsp, out=None, out64=False, sigma=False):
+        """`grid` (C-contiguous float32 [x, y, z]) low-passed voxel by voxel: every output voxel is the map under the Gaussian of its
+        own resolution, sigma = d / (voxsp pi sqrt(2)) voxels, d interpolated trilinearly from `res` (float64, Angstrom) on the
+        lattice of every `step`-th voxel, shape ((n - 1) // step + 1 per axis) (mad_map_local_filter; DESIGN.md section 4q;
+        `fourier.local_filter_numpy` restates it).  -> the float32 result (a new array, or `out`, which may be `grid` itself); with
+        `out64` and / or `sigma` a tuple (out, out64 or None, sigma or None): the float64 result before rounding and the per-voxel
+        sigma in voxels.  The results do not depend on which of the two were asked for."""
+        if not isinstance(grid, np.ndarray) or grid.dtype != np.float32 or not grid.flags.c_contiguous:
+            raise ValueError("map_local_filter needs a C-contiguous float32 grid")
+        if grid.ndim != 3:
+            raise ValueError("map_local_filter needs a 3-D grid")
+        r = _c(np.asarray(res), np.float64)
+        if r.ndim != 3:
+            raise ValueError("map_local_filter needs a 3-D field of resolutions")
+        step_i = int(step)
+        if step_i != step or not -2 ** 31 <= step_i < 2 ** 31:
+            raise ValueError("map_local_filter: step %r" % (step,))
+        if out is None:
+            out = np.empty(grid.shape, np.float32)
+        elif out.dtype != np.float32 or not out.flags.c_contiguous or not out.flags.writeable or out.shape != grid.shape:
+            raise ValueError("map_local_filter: out must be a writable C-contiguous float32 array of the grid's shape")
+        d, rd = np.array(grid.shape, np.int32), np.array(r.shape, np.int32)
+        o64 = np.empty(grid.shape, np.float64) if out64 else None
+        sg = np.empty(grid.shape, np.float64) if sigma else None
+        self._chk(self.dll.mad_map_local_filter(self.ctx, _p(grid), _p(d), C.c_double(float(voxsp)), _p(r), _p(rd), C.c_int32(step_i), _p(out),
+                                                None if o64 is None else _p(o64), None if sg is None else _p(sg)))
+        return (out, o64, sg) if (out64 or sigma) else out
 
     def map_fft(self, g1, o1, g2=None, o2=None, voxsp=1.0):
         """The transform `map_fsc` works on, for testing it alone -> complex128 [N, N, N]: the FFT of the lattice that holds `g1`

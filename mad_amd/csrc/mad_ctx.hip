@@ -187,7 +187,7 @@ void mad_timer_end(mad_ctx *ctx, int group) {
 
 static const char *k_timer_names[MAD_T_COUNT] = {"orient", "describe", "correlate", "pairs", "pose",
                                                  "topk",   "refine",   "density",   "ccc",
-                                                 "seg_parent", "seg_jump", "seg_scan", "seg_smooth", "fft", "fsc", "filter", "scan", "search", "localres"};
+                                                 "seg_parent", "seg_jump", "seg_scan", "seg_smooth", "fft", "fsc", "filter", "scan", "search", "localres", "localfilter"};
 
 extern "C" int mad_timing_enable(mad_ctx *ctx, int on) {
     if (!ctx) return MAD_EINVAL;

@@ -2,7 +2,8 @@
 The filters -- `filter_lattice`, `radial_gain`, the designs `gain_*` and the restatement `filter_numpy` -- have their contract
 further down, and so have the translation scan (section 4n): `scan_lattice`, the restatement `scan_numpy`, `peaks_numpy` and `Scan`,
 and the rotational search (section 4o): `rotation_set`, the restatements `rotate_numpy`, `tree_sum` and `search_numpy`, and `Search`,
-and local resolution (section 4p): `local_plan`, `hann_window`, the restatement `local_fsc_numpy` and `LocalResolution`.
+and local resolution (section 4p): `local_plan`, `hann_window`, the restatement `local_fsc_numpy` and `LocalResolution`;
+a low-pass by local resolution (section 4q): the restatements `local_sigma_numpy` and `local_filter_numpy`.
 
 `plan_box` puts two grids of one spacing onto a common cubic lattice, `fsc_numpy` restates the contract of `mad_map_fsc` with
 `numpy.fft.fftn` in float64 -- the checker of the GPU tests, and the one place the contract is spelled out in code -- and `FSC` is
@@ -758,6 +759,17 @@ class LocalResolution(object):
         """The median resolution (Angstrom) over the samples whose curve reached the threshold; nan where none did."""
         return float(np.median(self.resolution[self.reached])) if self.reached.any() else float("nan")
 
+    def filled(self, fill=None):
+        """float64 [nx, ny, nz]: the samples with every not-computed one (shell == -1, stored as 0.0) holding `fill` (Angstrom) -- what
+        `Dmap.lowpass_local` filters by.  `fill=None`: the largest computed value: samples an isovalue left out are background, and
+        filtering them hardest is the cautious choice.  ValueError where nothing was computed."""
+        if not self.computed.any():
+            raise ValueError("LocalResolution.filled: no sample was computed")
+        v = float(self.resolution[self.computed].max()) if fill is None else float(fill)
+        out = self.resolution.copy()
+        out[~self.computed] = v
+        return out
+
     def to_dmap(self):
         """The resolution volume as a `Dmap` of spacing step voxsp at the map's origin (float32); `resample(like=map)` brings it
         onto the map's own lattice."""
@@ -774,6 +786,120 @@ class LocalResolution(object):
         """The resolution volume as a map (.sit / .situs: Situs, anything else MRC) of spacing step voxsp at the map's origin."""
         from . import mapio
         mapio.write_volume(outname, np.ascontiguousarray(self.resolution, np.float32), tuple(self.origin), self.step * self.voxsp)
+
+
+# ---------------------------------------------------------------------------
+# a low-pass by local resolution (DESIGN.md section 4q): the contract of `mad_map_local_filter`
+#
+# A float32 grid [x, y, z] of n voxels per axis and a float64 field of resolutions d (Angstrom) on the lattice of every step-th voxel,
+# m_a = (n_a - 1) // step + 1 samples per axis.  At voxel i of an axis: j0 = min(i // step, m - 1), j1 = min(j0 + 1, m - 1),
+# f = (i - j0 step) / step, 0.0 where j1 == j0 (clamped beyond the last sample).  d = trilinear, lerp(a, b, f) = a + (b - a) f along z,
+# then y, then x; sigma = d / (voxsp K) voxels, K = pi sqrt(2).  R = max(1, int(4 sigma + 0.5)) -- `Dmap.smooth`'s truncation --,
+# q = -0.5 / (sigma sigma), w_k = exp(q (k k)), W = w_0 + 2 (w_R + ... + w_1) summed from R down to 1.  out = S / (W W W) with
+# S = sum_dx w_|dx| (sum_dy w_|dy| (sum_dz w_|dz| g[i + dx, j + dy, k + dz])), each offset ascending from -R to R, 0.0 outside the
+# grid: a gather with the OUTPUT voxel's weights.  float64 throughout.
+# ---------------------------------------------------------------------------
+
+LOCAL_FILTER_MAX_SIGMA = 6.0                      # voxels: the widest Gaussian `mad_map_local_filter` takes (R <= 24)
+LOCAL_FILTER_K = np.pi * np.sqrt(2.0)             # sigma (Angstrom) = d / K: the envelope of `lowpass(kind="gaussian")`
+
+
+def local_radius(sigma):
+    """int array: R = max(1, int(4 sigma + 0.5)) for sigma in voxels."""
+    return np.maximum(1, (4.0 * np.asarray(sigma, np.float64) + 0.5).astype(np.int64))
+
+
+def _local_filter_field(dims, res, step, voxsp):
+    """-> (dims, res float64 [m0, m1, m2], step, voxsp) checked; ValueError where `mad_map_local_filter` refuses."""
+    who = "local_filter"
+    if isinstance(step, bool) or int(step) != step or step < 1:
+        raise ValueError("%s: step %r (a whole number, 1 or more)" % (who, step))
+    step, voxsp = int(step), float(voxsp)
+    dims = tuple(int(v) for v in dims)
+    if len(dims) != 3 or min(dims) < 1:
+        raise ValueError("%s: grid of %r voxels" % (who, dims))
+    if not (voxsp > 0) or not np.isfinite(voxsp):
+        raise ValueError("%s: voxsp %r (positive and finite)" % (who, voxsp))
+    res = np.asarray(res, np.float64)
+    want = tuple((n - 1) // step + 1 for n in dims)
+    if res.shape != want:
+        raise ValueError("%s: rdims %r, the samples at every %d-th voxel of %r are %r" % (who, res.shape, step, dims, want))
+    bad = ~(np.isfinite(res) & (res > 0))
+    wide = ~bad & ~(res / (voxsp * LOCAL_FILTER_K) <= LOCAL_FILTER_MAX_SIGMA)
+    for m in np.argwhere(bad | wide)[:1]:      # the first in index order, as the entry reports it
+        m = tuple(int(v) for v in m)
+        if bad[m]:
+            raise ValueError("%s: sample %r is %r A (positive and finite)" % (who, m, float(res[m])))
+        raise ValueError("%s: sample %r is %r A, a Gaussian of sigma %r voxels wide (at most %r)"
+                         % (who, m, float(res[m]), float(res[m] / (voxsp * LOCAL_FILTER_K)), LOCAL_FILTER_MAX_SIGMA))
+    return dims, res, step, voxsp
+
+
+def local_sigma_numpy(dims, res, step, voxsp):
+    """float64 [n0, n1, n2]: sigma in voxels at every voxel of a grid of `dims` from the field `res` on the lattice of every `step`-th
+    voxel -- the operations of the contract in its order, so the same bits as `mad_map_local_filter`'s `sigma`."""
+    dims, res, step, voxsp = _local_filter_field(dims, res, step, voxsp)
+    j0, j1, f = [], [], []
+    for a in range(3):
+        i, m = np.arange(dims[a]), res.shape[a]
+        lo = np.minimum(i // step, m - 1)
+        hi = np.minimum(lo + 1, m - 1)
+        j0.append(lo)
+        j1.append(hi)
+        f.append(np.where(hi == lo, 0.0, (i - lo * step).astype(np.float64) / float(step)))
+    a, b = res[:, :, j0[2]], res[:, :, j1[2]]
+    c = a + (b - a) * f[2][None, None, :]
+    a, b = c[:, j0[1], :], c[:, j1[1], :]
+    c = a + (b - a) * f[1][None, :, None]
+    a, b = c[j0[0]], c[j1[0]]
+    c = a + (b - a) * f[0][:, None, None]
+    return c / (voxsp * LOCAL_FILTER_K)
+
+
+def local_filter_numpy(grid, res, step, voxsp, with_abs=False):
+    """The contract of `mad_map_local_filter` with numpy in float64 -> (out64, sigma), both float64 of the grid's shape; with
+    `with_abs` -> (out64, sigma, A), A the same sums over |grid| (what an error bound of out64 scales with), for the price of one
+    pass.  Vectorised over the voxels of one R at a time: a loop over dx and dy, the taps along z as one window per voxel summed in
+    ascending order (a cumulative sum).  A voxel beyond a kernel's R is never touched."""
+    g = np.asarray(grid)
+    if g.ndim != 3:
+        raise ValueError("local_filter: a 3-D grid")
+    sigma = local_sigma_numpy(g.shape, res, step, voxsp)
+    R = local_radius(sigma)
+    Rm = int(R.max())
+    vols = [g.astype(np.float64)] + ([np.abs(g.astype(np.float64))] if with_abs else [])
+    pad = np.zeros((len(vols),) + tuple(n + 2 * Rm for n in g.shape))
+    for v, vol in enumerate(vols):
+        pad[v, Rm:Rm + g.shape[0], Rm:Rm + g.shape[1], Rm:Rm + g.shape[2]] = vol
+    flat = pad.reshape(len(vols), -1)
+    outs = np.zeros((len(vols),) + g.shape)
+    with np.errstate(invalid="ignore", over="ignore"):
+        for r in (int(v) for v in np.unique(R)):
+            i, j, k = np.nonzero(R == r)
+            s = sigma[i, j, k]
+            q = -0.5 / (s * s)
+            w = np.stack([np.exp(q * float(t * t)) for t in range(r + 1)])      # [t][voxel]
+            tail = np.zeros(len(s))
+            for t in range(r, 0, -1):
+                tail = tail + w[t]
+            W = w[0] + 2.0 * tail
+            wz = np.ascontiguousarray(w[np.abs(np.arange(-r, r + 1))].T)        # [voxel][dz]
+            first = ((i + Rm) * pad.shape[2] + (j + Rm)) * pad.shape[3] + (k + (Rm - r))      # of the voxel's own row: tap dz = -r
+            taps = first[:, None] + np.arange(2 * r + 1)[None, :]
+            sx = np.zeros((len(vols), len(s)))
+            for dx in range(-r, r + 1):
+                if i.max() + dx < 0 or i.min() + dx >= g.shape[0]:
+                    continue      # every tap of this plane lies outside the grid for every voxel: zeros, which change no sum
+                sy = np.zeros((len(vols), len(s)))
+                for dy in range(-r, r + 1):
+                    if j.max() + dy < 0 or j.min() + dy >= g.shape[1]:
+                        continue
+                    rows = np.take(flat, taps + (dx * pad.shape[2] + dy) * pad.shape[3], axis=1)      # [volume][voxel][dz]
+                    rows *= wz
+                    sy = sy + w[abs(dy)] * np.cumsum(rows, axis=-1, out=rows)[..., -1]
+                sx = sx + w[abs(dx)] * sy
+            outs[:, i, j, k] = sx / (W * W * W)
+    return (outs[0], sigma, outs[1]) if with_abs else (outs[0], sigma)
 
 
 class FSC(object):
