@@ -439,6 +439,18 @@ int mad_map_mask(mad_ctx *ctx, float *grid1, const int32_t dims1[3], const doubl
                  const float *mask, const int32_t dims2[3], const double origin2[3], double voxsp);
 
 /*
+ * A map times a soft mask (no counterpart in the reference).  Host pointers, synchronous.  grid1 (float32
+ * [x][y][z]) is updated IN PLACE, the mask is read only.  The mask sits at the whole-voxel offset s = round(origin2 / voxsp -
+ * origin1 / voxsp) per axis (half to even: mad_map_mask's expression), mask voxel j under grid voxel j + s; what is left of the offset
+ * is rounded away, so a soft edge lands up to half a voxel from where its origin puts it.  Under the mask's box
+ * g = (float)((double)g * (double)m), except that a voxel under m == 1 is not written (every bit stays); a voxel of grid 1 outside the
+ * mask's box becomes +0.0f.  Where the boxes do not meet the whole grid becomes +0.0f and the call returns MAD_OK.
+ * MAD_EINVAL: as mad_map_mask.
+ */
+int mad_map_multiply(mad_ctx *ctx, float *grid1, const int32_t dims1[3], const double origin1[3],
+                     const float *mask, const int32_t dims2[3], const double origin2[3], double voxsp);
+
+/*
  * Dmap.get_CCC_with_dmap (Dmap.py:260-372) of grid 1 against n second maps: grids2[j] float32 [x][y][z] with dims2[3 j ..] and
  * origins2[3 j ..].  Grid 1 is uploaded once and its voxels above the isovalue are counted once; the call with one map is the
  * n = 1 case of the same path (same bits).  No grid is modified.  With n1 / n2 = voxels of the whole grids above the isovalue and,
@@ -492,6 +504,27 @@ int mad_map_resample(mad_ctx *ctx, const float *grid, const int32_t dims[3], con
 int mad_map_zone(mad_ctx *ctx, float *grid, const int32_t dims[3], const double origin[3], double voxsp,
                  const double *atoms, int64_t n_atoms, double radius, double soft, int erase,
                  int64_t counts[2] /* may be NULL */);
+
+/*
+ * A soft mask made from the map itself: threshold, grow, raised-cosine edge (mad_envelope.hip; DESIGN.md section 4r;
+ * mad_amd/envelope.py::envelope_numpy restates the contract).  Host pointers, synchronous; grid (float32 [x][y][z]) is read only.
+ *   Seeds.  A voxel is a seed where (double)g > threshold.
+ *   Distance.  d2(v) is the squared Euclidean distance in whole voxels from v to the nearest seed, exact wherever it is at most Rv^2
+ *   with Rv = min(floor((extend + soft) / voxsp) + 1, max(dims) - 1); anything farther, and everything when there is no seed, is the
+ *   sentinel INT32_MAX.  (Where max(dims) - 1 is the smaller term, voxels farther than that from every seed hold the sentinel although
+ *   extend + soft would reach them.)
+ *   Weight.  mad_map_zone's expressions with D2 = (double)d2 * (voxsp * voxsp), r2 = extend * extend, R = extend + soft, R2 = R * R:
+ *   w = 1 where D2 <= r2, w = 0 where D2 >= R2 or d2 is the sentinel, else w = 0.5 + 0.5 * cos(pi * ((sqrt(D2) - extend) / soft)), in
+ *   float64, stored as float32.  extend = soft = 0 is legal: the mask is the seed set.
+ * mask_out: float32 [x][y][z], every voxel written.  d2_out (may be NULL): int32 [x][y][z].  counts (may be NULL): [0] seeds, [1]
+ * voxels with D2 <= r2 (seeds included), [2] voxels with r2 < D2 < R2 -- by the branch taken, as mad_map_zone counts, so they do not
+ * depend on how cos rounds.  The same call gives the same bits alone or after any other call.
+ * MAD_EINVAL, nothing launched: NULL, a dimension < 1, 2^31 voxels or more, voxsp not positive and finite, a NaN threshold, extend or
+ * soft negative or not finite.  MAD_EDOM, outputs untouched: Rv > 255 (the figure is in the message); a voxel that is not finite.
+ */
+int mad_map_envelope(mad_ctx *ctx, const float *grid, const int32_t dims[3], double voxsp,
+                     double threshold, double extend, double soft,
+                     float *mask_out, int32_t *d2_out /* may be NULL */, int64_t counts[3] /* may be NULL */);
 
 /*
  * A placed model scored per group of atoms -- residue, chain, any partition -- against a map (mad_groupfit.hip; DESIGN.md section
@@ -590,6 +623,40 @@ int mad_map_segment(mad_ctx *ctx, const float *grid, const int32_t dims[3], doub
 int mad_map_fsc(mad_ctx *ctx, const float *grid1, const int32_t dims1[3], const double origin1[3],
                 const float *grid2, const int32_t dims2[3], const double origin2[3], double voxsp,
                 int32_t *N_out, double *sums /* [N / 2 + 1][3]: P1, P2, C */, int64_t *count /* [N / 2 + 1] */, int64_t cap_shells);
+
+/*
+ * The Fourier shell correlation of two maps under a soft mask, with what it takes to correct the curve for the mask's own
+ * contribution (Chen et al. 2013; mad_fourier.hip; restated with numpy as fourier.fsc_masked_numpy).  Host
+ * pointers, synchronous, nothing modified but the outputs.  Lattice, placement, delta and phase ramp are mad_map_fsc's, from grid 1 and
+ * grid 2 alone.  The mask (float32 [x][y][z] with dimsm, originm) is placed against grid 1 by whole voxels, its voxel j at lattice index
+ * p1 + round(originm / voxsp - origin1 / voxsp) + j (half to even; no wrap-around); it multiplies both parts of the packed lattice at
+ * the same lattice index, lattice points outside its box become 0.  What is left of its offset to either grid is rounded away: a soft
+ * edge moves by at most half a voxel.
+ *   1. Z = FFT(g1 + i g2); its shell sums are sums_unmasked (= mad_map_fsc's, bit for bit).
+ *   2. shell_r >= 0 is taken as given.  shell_r < 0: the lowest shell s >= 1 whose unmasked C / sqrt(P1 P2) (0 where P1 P2 is not
+ *      positive) is below t_r, N / 2 + 1 when there is none; found on the host.  *shell_r_out (may be NULL) receives it.
+ *   3. k_fsc_randomize, in place on Z, one thread per lattice point L = (a N + b) N + c, acting where L < L', the index of -k; a
+ *      self-conjugate point is never touched.  F1, F2 as above; where shell(k) >= shell_r (corners beyond N / 2 included) each becomes
+ *      |F| (cos t + i sin t), |F| = sqrt(re*re + im*im), t = 6.283185307179586 * u, u = (z >> 11) * 2^-53, z = seed +
+ *      0x9E3779B97F4A7C15 * (2 L + which + 1) (which: 0 for F1, 1 for F2) put through z ^= z >> 30; z *= 0xBF58476D1CE4E5B9;
+ *      z ^= z >> 27; z *= 0x94D049BB133111EB; z ^= z >> 31 (mod 2^64).  Z(k) = F1' + i F2', Z(-k) = conj(F1') + i conj(F2').
+ *   4. The inverse transform (mad_map_ifft's passes); the mask times real and imaginary part, with the 1 / N^3; forward; the shell sums
+ *      are sums_random.
+ *   5. The lattice packed again, times the mask, forward; the shell sums are sums_masked.
+ * Each table is [N / 2 + 1][3] = P1, P2, C, count [N / 2 + 1] as mad_map_fsc's (mad_map_fft's size query gives N beforehand).  No
+ * floating-point atomics: the same call with the same seed gives the same bits.  MAD_EINVAL / MAD_EDOM / MAD_ENOMEM as mad_map_fsc, the
+ * mask's dims and origin judged like a grid's; MAD_EINVAL also for shell_r < 0 with a NaN t_r.
+ * mad_map_phase_randomize is step 3 alone on a spectrum the caller brings (complex128 [N][N][N] on the host, interleaved, N a power
+ * of two in 8 .. 1024, updated IN PLACE), the sibling of mad_map_ifft: F1 is the spectrum itself, F2 is absent, Z(-k) = conj(F1').
+ * MAD_EINVAL: NULL, such an N, shell_r < 0.
+ */
+int mad_map_fsc_masked(mad_ctx *ctx, const float *grid1, const int32_t dims1[3], const double origin1[3],
+                       const float *grid2, const int32_t dims2[3], const double origin2[3], double voxsp,
+                       const float *mask, const int32_t dimsm[3], const double originm[3],
+                       int32_t shell_r /* < 0: from t_r */, double t_r, uint64_t seed,
+                       double *sums_unmasked, double *sums_masked, double *sums_random /* each [N / 2 + 1][3] */,
+                       int64_t *count, int32_t *N_out, int32_t *shell_r_out);
+int mad_map_phase_randomize(mad_ctx *ctx, double *spectrum, int32_t N, int32_t shell_r, uint64_t seed);
 int mad_map_fft(mad_ctx *ctx, const float *grid1, const int32_t dims1[3], const double origin1[3],
                 const float *grid2 /* may be NULL */, const int32_t dims2[3], const double origin2[3], double voxsp,
                 int32_t *N_out, double *spectrum /* N^3 complex128, interleaved; NULL: size query */);

@@ -18,6 +18,9 @@ map through `mad_map_scan` (fourier.py; no counterpart in the reference: the exh
 does so over a whole set of rotations made on the device (`mad_map_search`).  `local_resolution` is `fsc` per sample point, in a
 windowed cube around it, through `mad_map_local_fsc` (fourier.py; no counterpart in the reference), and `lowpass_local` low-passes
 the map by such a measurement, every voxel under the Gaussian of its own resolution, through `mad_map_local_filter`.
+`envelope` makes a soft mask from the map itself (threshold, grow, raised-cosine edge) through `mad_map_envelope`, `apply_mask`
+multiplies a map by one through `mad_map_multiply`, and `fsc(mask=...)` is the masked curve corrected for the mask by phase
+randomisation through `mad_map_fsc_masked` (envelope.py, fourier.py; no counterpart in the reference).
 None of them has a CPU fallback.  The reference's per-voxel text writer is replaced by `mapio.write_situs`.
 """
 import os
@@ -186,6 +189,52 @@ class Dmap(object):
             self.grid3d = g
         return _lib.get_lib().map_zone(g, (self.xi, self.yi, self.zi), self.voxsp, atoms, radius, soft, erase)
 
+    def envelope(self, threshold, extend=3.0, soft=6.0):
+        """A soft mask made from this map itself, as a new `Dmap` with the same dims, origin and spacing (`self` is untouched):
+        1 on every voxel within `extend` Angstrom of a voxel above `threshold`, a raised-cosine edge over the next `soft`
+        Angstrom, 0 beyond, through `mad_map_envelope`.  The result carries `n_seeds` (voxels above the threshold), `n_core` (weight
+        1, seeds included) and `n_edge` (voxels in the edge).  `apply_mask` multiplies a map by it.  A binary mask such as
+        `Segmentation.mask(ids)` gets a soft edge the same way: put it into a `Dmap` and call `envelope(0.5, ...)`.  Dust -- stray
+        voxels above the threshold far from the particle -- grows an envelope of its own: remove it beforehand with `lowpass`, or
+        by choosing segments; connected components are not looked for here.  The distances are exact Euclidean ones in whole
+        voxels; (extend + soft) / voxsp has to stay below 255 voxels.  DESIGN.md section 4r has the exact contract."""
+        threshold, extend, soft = float(threshold), float(extend), float(soft)
+        if threshold != threshold:
+            raise ValueError("Dmap.envelope: the threshold is not a number")
+        if not (extend >= 0 and soft >= 0) or not np.isfinite(extend + soft):
+            raise ValueError("Dmap.envelope: extend %r, soft %r (finite, neither negative)" % (extend, soft))
+        g = np.ascontiguousarray(self.grid3d, dtype=np.float32)
+        if g.ndim != 3 or g.size == 0:
+            raise ValueError("Dmap.envelope: the grid has shape %r" % (g.shape,))
+        out = Dmap.__new__(Dmap)
+        out.grid3d, _, (out.n_seeds, out.n_core, out.n_edge) = _lib.get_lib().map_envelope(g, float(self.voxsp), threshold, extend, soft)
+        out.voxsp = self.voxsp
+        out.xi, out.yi, out.zi = self.xi, self.yi, self.zi
+        out.xb, out.yb, out.zb = out.grid3d.shape
+        for k in ("map_name", "name"):
+            if hasattr(self, k):
+                setattr(out, k, getattr(self, k))
+        return out
+
+    def apply_mask(self, mask):
+        """This map times the soft mask `mask` (a `Dmap` of the same spacing, such as `envelope` returns), in place, through
+        `mad_map_multiply`: a voxel under a mask value of 1 keeps its bits, one outside the mask's box becomes 0.  The mask is
+        placed by whole voxels, round((mask origin - map origin) / voxsp); what is left of the offset is rounded away, so an edge
+        lands up to half a voxel from where the mask's origin puts it (`resample(like=...)` first where that matters).  Returns
+        self."""
+        if not np.isclose(self.voxsp, mask.voxsp):
+            raise ValueError("Dmap.apply_mask: voxsp differ (%r vs %r): bring the mask onto the map's lattice with resample(like=...) first"
+                             % (self.voxsp, mask.voxsp))
+        g = self.grid3d
+        if g.dtype != np.float32 or not g.flags.c_contiguous or not g.flags.writeable:
+            g = np.ascontiguousarray(g, dtype=np.float32)
+            if not g.flags.writeable or g is self.grid3d:
+                g = g.copy()
+            self.grid3d = g
+        m = np.ascontiguousarray(mask.grid3d, dtype=np.float32)
+        _lib.get_lib().map_multiply(g, (self.xi, self.yi, self.zi), m, (mask.xi, mask.yi, mask.zi), float(self.voxsp))
+        return self
+
     def fit_by_group(self, structure, resolution, by="residue", radius=None, isovalue=0, model=None, masses=None):
         """Which part of a placed model sits in density: the un-centred score of this map against the model's density per group of
         atoms, over the voxels within `radius` Angstrom of the group -> `localfit.GroupFit` (labels, n_voxels, sums, ccc, and
@@ -198,18 +247,39 @@ class Dmap(object):
         from . import localfit
         return localfit.fit_by_group(self, structure, resolution, by=by, radius=radius, isovalue=isovalue, model=model, masses=masses)
 
-    def fsc(self, other, resolution=None, masses=None):
+    def fsc(self, other, resolution=None, masses=None, mask=None, randomize_from=None, seed=0):
         """Fourier shell correlation of this map against `other` -> `fourier.FSC` (freq, fsc, n, power1, power2, `resolution()`,
         `write_csv()`).  `other`: a `Dmap` of the same spacing (half map against half map; `resample(like=...)` first where the
         spacings differ), a (grid, (x0, y0, z0)) pair on this map's spacing, or a placed model -- a `PDB`, an (n, 3) array, or a
         list / tuple of those -- whose density is simulated at `resolution` on this map's spacing (masses as in `fit_by_group`).
-        The two grids need not share a lattice: whole voxels of offset place them, the rest goes into a phase ramp.  No mask, no
-        soft edge (`zone(soft=...)` or `mask_with` first); neither map is modified.  DESIGN.md section 4l has the exact contract."""
+        The two grids need not share a lattice: whole voxels of offset place them, the rest goes into a phase ramp.  Neither map
+        is modified.  DESIGN.md section 4l has the exact contract.
+        `mask=None`: no mask, no soft edge -- the whole box, solvent noise included.  `mask`: a soft mask as a `Dmap` of the same
+        spacing (`envelope` makes one from the map itself), applied to both maps -> `fourier.MaskedFSC`, whose `fsc` is the masked
+        curve corrected for what the mask alone contributes (Chen et al. 2013): the phases of both maps are randomised beyond a
+        shell, the result is masked, and the correlation that survives is taken out; `fsc_unmasked`, `fsc_masked` and `fsc_random`
+        are kept.  `randomize_from` (Angstrom) is where the randomisation begins, taken to the nearest shell; None: the lowest
+        shell whose unmasked curve is below 0.8 (RELION's convention).  `seed` fixes the random phases: the same seed gives the
+        same bits.  The mask is placed by whole voxels against this map (its edge moves by at most half a voxel).  Section 4s."""
         from . import fourier
         voxsp = float(self.voxsp)
         g1, g2, o2, _ = self._fsc_pair("Dmap.fsc", other, resolution, masses)
-        N, sums, count = _lib.get_lib().map_fsc(g1, (self.xi, self.yi, self.zi), g2, o2, voxsp)
-        return fourier.FSC(N, voxsp, sums, count)
+        if mask is None:
+            N, sums, count = _lib.get_lib().map_fsc(g1, (self.xi, self.yi, self.zi), g2, o2, voxsp)
+            return fourier.FSC(N, voxsp, sums, count)
+        if not np.isclose(self.voxsp, mask.voxsp):
+            raise ValueError("Dmap.fsc: the mask's voxsp differs (%r vs %r): resample(like=...) first" % (self.voxsp, mask.voxsp))
+        m = np.ascontiguousarray(mask.grid3d, dtype=np.float32)
+        shell_r = None
+        if randomize_from is not None:
+            r = float(randomize_from)
+            if not (r > 0) or not np.isfinite(r):
+                raise ValueError("Dmap.fsc: randomize_from %r Angstrom (positive and finite)" % (randomize_from,))
+            N = fourier.plan_box(g1.shape, (self.xi, self.yi, self.zi), g2.shape, o2, voxsp)[0]
+            shell_r = max(0, min(int(round(N * voxsp / r)), 2 ** 31 - 1))      # freq of shell s is s / (N voxsp)
+        N, su, sm, sr, count, shell_r = _lib.get_lib().map_fsc_masked(g1, (self.xi, self.yi, self.zi), g2, o2, voxsp, m,
+                                                                       (mask.xi, mask.yi, mask.zi), shell_r=shell_r, t_r=0.8, seed=seed)
+        return fourier.MaskedFSC(N, voxsp, su, sm, sr, count, shell_r, seed)
 
     def _fsc_pair(self, who, other, resolution, masses):
         """What `fsc` and `local_resolution` compare -> (this map's grid, the second grid, its origin, whether it is a simulated

@@ -39,7 +39,7 @@ SYMBOLS = [
     "mad_dist_unique_id", "mad_dist_init", "mad_dist_destroy", "mad_dist_info", "mad_dist_rehearse_flags", "mad_dist_or_allreduce", "mad_dist_allgather",
     "mad_dist_allgather_topk", "mad_dist_scratch", "mad_dist_copy",
     "mad_set_wire_bytes", "mad_set_export", "mad_set_import", "mad_set_lane", "mad_set_stream", "mad_set_bind_lane",
-    "mad_upload_density", "mad_refine", "mad_last_refine_plan", "mad_last_density_chunks", "mad_structure_to_density", "mad_ccc", "mad_map_mask", "mad_map_ccc", "mad_map_resample", "mad_map_zone", "mad_map_group_fit", "mad_map_smooth", "mad_map_segment", "mad_map_fsc", "mad_map_fft", "mad_map_filter", "mad_map_ifft", "mad_map_scan", "mad_map_search", "mad_map_rotate", "mad_map_local_fsc", "mad_map_local_filter", "mad_density_ccc", "mad_dock_refine_score", "mad_grid_overlap", "mad_overlap_matrix",
+    "mad_upload_density", "mad_refine", "mad_last_refine_plan", "mad_last_density_chunks", "mad_structure_to_density", "mad_ccc", "mad_map_mask", "mad_map_multiply", "mad_map_ccc", "mad_map_resample", "mad_map_zone", "mad_map_envelope", "mad_map_group_fit", "mad_map_smooth", "mad_map_segment", "mad_map_fsc", "mad_map_fsc_masked", "mad_map_phase_randomize", "mad_map_fft", "mad_map_filter", "mad_map_ifft", "mad_map_scan", "mad_map_search", "mad_map_rotate", "mad_map_local_fsc", "mad_map_local_filter", "mad_density_ccc", "mad_dock_refine_score", "mad_grid_overlap", "mad_overlap_matrix",
     "mad_space_create", "mad_space_destroy", "mad_space_build", "mad_space_info", "mad_space_download",
     "mad_space_peaks", "mad_space_patches", "mad_space_localize", "mad_localize_volume",
     "mad_pose_cluster_many",
@@ -1128,6 +1128,41 @@ class Lib(object):
         o1, o2 = _c(o1, np.float64), _c(o2, np.float64)
         self._chk(self.dll.mad_map_mask(self.ctx, _p(g1), _p(d1), _p(o1), _p(mask), _p(d2), _p(o2), C.c_double(voxsp)))
 
+    def map_multiply(self, g1, o1, mask, o2, voxsp):
+        """g1 (writable C-contiguous float32) times the soft mask (C-contiguous float32, only read) in place: the mask sits at the
+        whole-voxel offset round(o2 / voxsp - o1 / voxsp), a voxel under a mask value of 1 keeps its bits, one outside the mask's
+        box becomes +0 (mad_map_multiply)."""
+        if g1.dtype != np.float32 or not g1.flags.c_contiguous or not g1.flags.writeable:
+            raise ValueError("map_multiply needs a writable C-contiguous float32 grid")
+        if mask.dtype != np.float32 or not mask.flags.c_contiguous:
+            raise ValueError("map_multiply needs a C-contiguous float32 mask")
+        if g1.ndim != 3 or mask.ndim != 3:
+            raise ValueError("map_multiply needs 3-D grids")
+        d1, d2 = np.array(g1.shape, np.int32), np.array(mask.shape, np.int32)
+        o1, o2 = _c(np.asarray(o1, np.float64).reshape(3), np.float64), _c(np.asarray(o2, np.float64).reshape(3), np.float64)
+        self._chk(self.dll.mad_map_multiply(self.ctx, _p(g1), _p(d1), _p(o1), _p(mask), _p(d2), _p(o2), C.c_double(voxsp)))
+
+    def map_envelope(self, g, voxsp, threshold, extend, soft, want_d2=False, out=None):
+        """A soft mask from the map `g` (C-contiguous float32 [x, y, z], not modified) itself: 1 within `extend` Angstrom of a voxel
+        above `threshold`, a raised cosine over the next `soft` Angstrom, 0 beyond -> (mask float32, d2 int32 or None, (seeds,
+        core, edge)); d2, with `want_d2`, is the squared distance in voxels to the nearest seed, 2^31 - 1 beyond the window
+        (mad_map_envelope).  `out`: a float32 array to take the mask instead of a new one; it stays as it is
+        when the call is refused."""
+        if g.dtype != np.float32 or not g.flags.c_contiguous:
+            raise ValueError("map_envelope needs a C-contiguous float32 grid")
+        if g.ndim != 3:
+            raise ValueError("map_envelope needs a 3-D grid")
+        d = np.array(g.shape, np.int32)
+        if out is None:
+            out = np.empty(g.shape, np.float32)
+        elif out.dtype != np.float32 or out.shape != g.shape or not out.flags.c_contiguous or not out.flags.writeable:
+            raise ValueError("map_envelope: out must be a writable C-contiguous float32 array of the grid's shape")
+        d2 = np.empty(g.shape, np.int32) if want_d2 else None
+        counts = np.zeros(3, np.int64)
+        self._chk(self.dll.mad_map_envelope(self.ctx, _p(g), _p(d), C.c_double(voxsp), C.c_double(threshold), C.c_double(extend),
+                                            C.c_double(soft), _p(out), _p(d2), _p(counts)))
+        return out, d2, (int(counts[0]), int(counts[1]), int(counts[2]))
+
     def map_ccc(self, g1, o1, seconds, voxsp, isovalue=0.0):
         """Dmap.get_CCC_with_dmap of g1 against every (grid, origin) of `seconds` in one call -> float64 array.
         All grids C-contiguous float32; none is modified."""
@@ -1196,6 +1231,42 @@ class Lib(object):
                                        _p(sums), _p(count), C.c_int64(cap)))
         sh = n.value // 2 + 1
         return int(n.value), sums[:sh].copy(), count[:sh].copy()
+
+    def map_fsc_masked(self, g1, o1, g2, o2, voxsp, mask, om, shell_r=None, t_r=0.8, seed=0):
+        """The Fourier shell correlation of two maps under a soft mask and what corrects it for the mask -> (N, sums_unmasked,
+        sums_masked, sums_random -- each float64 [N / 2 + 1, 3] = P1, P2, C --, count int64 [N / 2 + 1], shell_r): the phases are
+        randomised from shell `shell_r` on, or with None from the lowest shell whose unmasked curve is below `t_r`
+        (mad_map_fsc_masked; `fourier.fsc_masked_numpy` restates it, `fourier.MaskedFSC` makes the curves).
+        All three grids C-contiguous float32 [x, y, z]; none is modified."""
+        d1, o1, d2, o2 = self._fourier_args("map_fsc_masked", g1, o1, g2, o2)
+        dm, om, _, _ = self._fourier_args("map_fsc_masked", mask, om, None, None)
+        seed = int(seed)
+        if not 0 <= seed < 2 ** 64:
+            raise ValueError("map_fsc_masked: seed %r (0 .. 2^64 - 1)" % (seed,))
+        sr = -1 if shell_r is None else int(shell_r)
+        if shell_r is not None and not 0 <= sr < 2 ** 31:
+            raise ValueError("map_fsc_masked: shell_r %r (0 or more, or None)" % (shell_r,))
+        n = C.c_int32(0)
+        self._chk(self.dll.mad_map_fft(self.ctx, _p(g1), _p(d1), _p(o1), _p(g2), _p(d2), _p(o2), C.c_double(voxsp), C.byref(n), None))
+        sh = n.value // 2 + 1
+        su, sm, sr_sums, count = np.zeros((sh, 3)), np.zeros((sh, 3)), np.zeros((sh, 3)), np.zeros(sh, np.int64)
+        got = C.c_int32(0)
+        self._chk(self.dll.mad_map_fsc_masked(self.ctx, _p(g1), _p(d1), _p(o1), _p(g2), _p(d2), _p(o2), C.c_double(voxsp), _p(mask), _p(dm), _p(om),
+                                              C.c_int32(sr), C.c_double(float(t_r)), C.c_uint64(seed), _p(su), _p(sm), _p(sr_sums), _p(count),
+                                              C.byref(n), C.byref(got)))
+        return int(n.value), su, sm, sr_sums, count, int(got.value)
+
+    def map_phase_randomize(self, spectrum, shell_r, seed=0):
+        """A copy of `spectrum` (complex128 [N, N, N], N a power of two from 8 to 1024) with new phases from shell `shell_r` on and
+        F(-k) = conj F(k) there (mad_map_phase_randomize; `fourier.randomize_numpy` restates it)."""
+        s = np.array(spectrum, np.complex128, order="C")
+        if s.ndim != 3 or s.shape[0] != s.shape[1] or s.shape[0] != s.shape[2]:
+            raise ValueError("map_phase_randomize needs a cubic 3-D spectrum, got %r" % (s.shape,))
+        seed = int(seed)
+        if not 0 <= seed < 2 ** 64:
+            raise ValueError("map_phase_randomize: seed %r (0 .. 2^64 - 1)" % (seed,))
+        self._chk(self.dll.mad_map_phase_randomize(self.ctx, _p(s), C.c_int32(s.shape[0]), C.c_int32(int(shell_r)), C.c_uint64(seed)))
+        return s
 
     def map_local_fsc(self, g1, o1, g2, o2, voxsp, box=16, step=2, threshold=0.143, select=None, sums=False):
         """Local resolution by windowed Fourier shell correlation -> (resolution float64 [nx, ny, nz], shell int32 [nx, ny, nz],

@@ -310,6 +310,89 @@ __global__ __launch_bounds__(256) void k_fsc_sum(int n_part, int SH, const doubl
 }
 
 // ---------------------------------------------------------------------------
+// phase randomisation and the mask on the lattice
+// ---------------------------------------------------------------------------
+
+// u in [0, 1) for draw n of a seed: splitmix64's finaliser on seed + golden * n, the top 53 bits (fourier.splitmix_u)
+__device__ __forceinline__ double fsc_splitmix_u(unsigned long long seed, unsigned long long n) {
+    unsigned long long z = seed + 0x9E3779B97F4A7C15ull * n;
+    z ^= z >> 30; z *= 0xBF58476D1CE4E5B9ull;
+    z ^= z >> 27; z *= 0x94D049BB133111EBull;
+    z ^= z >> 31;
+    return (double)(z >> 11) * 0x1.0p-53;
+}
+
+// |f| (cos theta + i sin theta), theta = 2 pi u
+__device__ __forceinline__ double2 fsc_rephase(double2 f, double u) {
+    const double mag = sqrt(f.x * f.x + f.y * f.y), th = 6.283185307179586 * u;
+    double s, c;
+    sincos(th, &s, &c);
+    return make_double2(mag * c, mag * s);
+}
+
+// In place on Z, one thread per lattice point L, acting only where L < L', the index of -k: a pair (k, -k) belongs to one thread, a
+// self-conjugate point (L == L') to none.  Where shell(k) >= shell_r -- the corners beyond N / 2 included -- the spectra get new
+// phases: draw 2 L + 1 for F1, 2 L + 2 for F2.  PAIR: Z = FFT(g1 + i g2), F1 and F2 as k_fsc_shells separates them, written back as
+// Z(k) = F1' + i F2' and Z(-k) = conj(F1') + i conj(F2').  Not PAIR: Z is one spectrum, F1 = Z(k), Z(-k) = conj(F1').
+template <bool PAIR>
+__global__ __launch_bounds__(256) void k_fsc_randomize(double2 *Z, int logN, int shell_r, unsigned long long seed) {
+    const int N = 1 << logN;
+    const unsigned m = (unsigned)N - 1u;
+    const size_t n = (size_t)1 << (3 * logN);
+    for (size_t L = (size_t)blockIdx.x * 256 + threadIdx.x; L < n; L += (size_t)gridDim.x * 256) {
+        const unsigned c = (unsigned)L & m, b = (unsigned)(L >> logN) & m, a = (unsigned)(L >> (2 * logN));
+        const unsigned ma = (N - a) & m, mb = (N - b) & m, mc = (N - c) & m;
+        const size_t Lm = (((((size_t)ma) << logN) + mb) << logN) + mc;
+        if (L >= Lm) continue;
+        const int fi = (int)a < (N >> 1) ? (int)a : (int)a - N, fj = (int)b < (N >> 1) ? (int)b : (int)b - N, fk = (int)c < (N >> 1) ? (int)c : (int)c - N;
+        const int r2 = fi * fi + fj * fj + fk * fk;
+        int sh = (int)(sqrt((double)r2) + 0.5);      // k_fsc_shells' shell
+        while (sh * sh + sh < r2) sh++;
+        while (sh > 0 && sh * sh - sh >= r2) sh--;
+        if (sh < shell_r) continue;
+        const double2 z = Z[L];
+        if (PAIR) {
+            const double2 zm = Z[Lm];
+            const double2 f1 = make_double2((z.x + zm.x) * 0.5, (z.y - zm.y) * 0.5), f2 = make_double2((z.y + zm.y) * 0.5, (zm.x - z.x) * 0.5);
+            const double2 g1 = fsc_rephase(f1, fsc_splitmix_u(seed, 2ull * L + 1ull)), g2 = fsc_rephase(f2, fsc_splitmix_u(seed, 2ull * L + 2ull));
+            Z[L] = make_double2(g1.x - g2.y, g1.y + g2.x);
+            Z[Lm] = make_double2(g1.x + g2.y, g2.x - g1.y);
+        } else {
+            const double2 g1 = fsc_rephase(z, fsc_splitmix_u(seed, 2ull * L + 1ull));
+            Z[L] = g1;
+            Z[Lm] = make_double2(g1.x, -g1.y);
+        }
+    }
+}
+
+struct LatMask {
+    const float *mask;
+    int d[3];
+    int p[3];                   // lattice index of the mask's voxel (0, 0, 0); may be negative, or N where the mask misses the lattice
+    int logN;
+};
+
+// Z(L) = (Re Z scale m, +-(Im Z) scale m) with m the mask's voxel at lattice point L, (+0, +0) outside the mask's box.  CONJ: the
+// conjugate that ends an inverse transform (ifft(X) = conj(FFT(conj X)) / N^3), with scale = 1 / N^3.
+template <bool CONJ>
+__global__ __launch_bounds__(256) void k_fft_mask(double2 *__restrict__ Z, const LatMask A, double scale) {
+    const int logN = A.logN;
+    const unsigned m = (1u << logN) - 1u;
+    const size_t n = (size_t)1 << (3 * logN);
+    for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (size_t)gridDim.x * 256) {
+        const unsigned c = (unsigned)i & m, b = (unsigned)(i >> logN) & m, a = (unsigned)(i >> (2 * logN));
+        const unsigned x = a - (unsigned)A.p[0], y = b - (unsigned)A.p[1], z = c - (unsigned)A.p[2];      // below the start: wraps past any extent
+        double2 v = make_double2(0.0, 0.0);
+        if (x < (unsigned)A.d[0] && y < (unsigned)A.d[1] && z < (unsigned)A.d[2]) {
+            const double w = (double)A.mask[((size_t)x * A.d[1] + y) * A.d[2] + z];
+            const double2 t = Z[i];
+            v = make_double2((t.x * scale) * w, ((CONJ ? -t.y : t.y) * scale) * w);
+        }
+        Z[i] = v;
+    }
+}
+
+// ---------------------------------------------------------------------------
 // host
 // ---------------------------------------------------------------------------
 
@@ -519,6 +602,8 @@ extern "C" int mad_map_fft(mad_ctx *ctx, const float *grid1, const int32_t dims1
     return fourier_free(ctx, Z, rc);
 }
 
+static int fsc_shell_tables(mad_ctx *ctx, const double2 *Z, const FourierPlan &P, double *sums, int64_t *count);
+
 static int map_fsc_run(mad_ctx *ctx, const float *g1, const int32_t *d1, const double *o1, const float *g2, const int32_t *d2,
                        const double *o2, double voxsp, int32_t *N_out, double *sums, int64_t *count, int64_t cap_shells, double2 **Z) {
     // the partial tables of the largest lattice: 1024 x 513 x 32 bytes
@@ -535,6 +620,11 @@ static int map_fsc_run(mad_ctx *ctx, const float *g1, const int32_t *d1, const d
             return mad_fail(ctx, MAD_ENOSPC, "mad_map_fsc: room for %lld shells, the %d^3 lattice has %d", (long long)cap_shells, Q.N, Q.N / 2 + 1);
     }
     MAD_TRY(fourier_transform(ctx, "mad_map_fsc", g1, d1, o1, g2, d2, o2, voxsp, extra, &P, Z));
+    return fsc_shell_tables(ctx, *Z, P, sums, count);
+}
+
+// the shell sums of the transformed lattice Z under the plan's phase ramp -> sums [N / 2 + 1][3], count [N / 2 + 1] (may be NULL)
+static int fsc_shell_tables(mad_ctx *ctx, const double2 *Z, const FourierPlan &P, double *sums, int64_t *count) {
     const int N = P.N, logN = P.logN, SH = N / 2 + 1;
     const int64_t n_brick = (int64_t)1 << (3 * logN - 6);
     const int wgs = (int)std::min<int64_t>(std::max<int64_t>(n_brick / 4, 1), FSC_MAX_WGS);
@@ -558,7 +648,7 @@ static int map_fsc_run(mad_ctx *ctx, const float *g1, const int32_t *d1, const d
     static bool attr = false;
     if (!attr) { MAD_HIP(hipFuncSetAttribute((const void *)k_fsc_shells, hipFuncAttributeMaxDynamicSharedMemorySize, 4 * (FFT_MAX_N / 2 + 1) * 28 + 16)); attr = true; }
     mad_timer_begin(ctx, MAD_T_FSC);
-    hipLaunchKernelGGL(k_fsc_shells, dim3(wgs), dim3(FSC_THREADS), lds, ctx->stream, (const double2 *)*Z, (const double2 *)phi, logN, part_f, part_i);
+    hipLaunchKernelGGL(k_fsc_shells, dim3(wgs), dim3(FSC_THREADS), lds, ctx->stream, Z, (const double2 *)phi, logN, part_f, part_i);
     hipLaunchKernelGGL(k_fsc_sum, dim3((unsigned)mad_ceil_div(SH * 4, 256)), dim3(256), 0, ctx->stream, wgs, SH, (const double *)part_f,
                        (const long long *)part_i, out_f, out_i);
     mad_timer_end(ctx, MAD_T_FSC);
@@ -567,7 +657,8 @@ static int map_fsc_run(mad_ctx *ctx, const float *g1, const int32_t *d1, const d
     MAD_HIP(hipMemcpyAsync(sums, out_f, (size_t)SH * 24, hipMemcpyDeviceToHost, ctx->stream));
     MAD_HIP(hipMemcpyAsync(h_cnt.data(), out_i, (size_t)SH * 8, hipMemcpyDeviceToHost, ctx->stream));
     MAD_HIP(hipStreamSynchronize(ctx->stream));
-    for (int s = 0; s < SH; s++) count[s] = (int64_t)h_cnt[s];
+    if (count)
+        for (int s = 0; s < SH; s++) count[s] = (int64_t)h_cnt[s];
     return MAD_OK;
 }
 
@@ -579,6 +670,135 @@ extern "C" int mad_map_fsc(mad_ctx *ctx, const float *grid1, const int32_t dims1
         return ctx ? mad_fail(ctx, MAD_EINVAL, "mad_map_fsc: NULL argument") : MAD_EINVAL;
     double2 *Z = nullptr;
     const int rc = map_fsc_run(ctx, grid1, dims1, origin1, grid2, dims2, origin2, voxsp, N_out, sums, count, cap_shells, &Z);
+    return fourier_free(ctx, Z, rc);
+}
+
+// ---------------------------------------------------------------------------
+// the masked curve and its phase-randomised correction
+// ---------------------------------------------------------------------------
+
+static int filter_gain_launch(mad_ctx *ctx, double2 *Z, const double *gain, double scale, int logN);
+
+// FSC's convention for one shell of a sums table: C / sqrt(P1 P2), 0 where P1 P2 is not positive
+static double fsc_value(const double *sums, int s) {
+    const double pp = sums[3 * s] * sums[3 * s + 1];
+    return pp > 0 ? sums[3 * s + 2] / sqrt(pp) : 0.0;
+}
+
+static int map_fsc_masked_run(mad_ctx *ctx, const float *g1, const int32_t *d1, const double *o1, const float *g2, const int32_t *d2,
+                              const double *o2, double voxsp, const float *mask, const int32_t *dm, const double *om, int32_t shell_r, double t_r,
+                              uint64_t seed, double *sums_u, double *sums_m, double *sums_r, int64_t *count, int32_t *N_out,
+                              int32_t *shell_r_out, double2 **Z) {
+    const char *who = "mad_map_fsc_masked";
+    if (!(voxsp > 0) || !(voxsp < 1e15)) return mad_fail(ctx, MAD_EINVAL, "%s: voxsp %g", who, voxsp);
+    MAD_TRY(fourier_check(ctx, who, dm, om, voxsp));
+    if (shell_r < 0 && !(t_r == t_r)) return mad_fail(ctx, MAD_EINVAL, "%s: no shell and a threshold that is not a number", who);
+    const size_t n_m = (size_t)dm[0] * dm[1] * dm[2];
+    const size_t grow_m = mad_sb(ctx, S_TMP_J).cap >= (n_m + 4) * 4 ? 0 : (n_m + 4) * 5;
+    const size_t extra = (size_t)FSC_MAX_WGS * (FFT_MAX_N / 2 + 1) * 32 + ((size_t)1 << 20) + grow_m;
+    FourierPlan P;
+    MAD_TRY(fourier_transform(ctx, who, g1, d1, o1, g2, d2, o2, voxsp, extra, &P, Z));      // (the other checks are mad_map_fsc's)
+    const int N = P.N, logN = P.logN, SH = N / 2 + 1;
+    if (N_out) *N_out = N;
+    // the mask against grid 1 by whole voxels (mad_map_multiply's placement); what is left of its offset is rounded away
+    LatMask M;
+    memset(&M, 0, sizeof(M));
+    M.logN = logN;
+    bool meets = true;
+    long pm[3];
+    for (int k = 0; k < 3; k++) {
+        pm[k] = (long)P.p1[k] + py_round(om[k] / voxsp - o1[k] / voxsp);
+        if (pm[k] >= N || pm[k] + (long)dm[k] <= 0) meets = false;
+    }
+    for (int k = 0; k < 3; k++) { M.d[k] = dm[k]; M.p[k] = meets ? (int)pm[k] : N; }      // -2^31 < -dm < pm < N where they meet
+    MAD_TRY(mad_reserve(ctx, mad_sb(ctx, S_TMP_J), (n_m + 4) * 4));
+    M.mask = scratch<float>(ctx, S_TMP_J);
+    MAD_HIP(hipMemcpyAsync((void *)M.mask, mask, n_m * 4, hipMemcpyHostToDevice, ctx->stream));
+    // 1. the curve without the mask, and from it the shell the randomisation begins at
+    MAD_TRY(fsc_shell_tables(ctx, *Z, P, sums_u, count));
+    int sr = shell_r;
+    if (sr < 0) {
+        sr = SH;
+        for (int s = 1; s < SH; s++)
+            if (fsc_value(sums_u, s) < t_r) { sr = s; break; }
+    }
+    if (shell_r_out) *shell_r_out = sr;
+    // 2. new phases from that shell on, back to real space, times the mask, forward again
+    const unsigned blocks = fourier_blocks(ctx, (size_t)1 << (3 * logN));
+    mad_timer_begin(ctx, MAD_T_FSC);
+    hipLaunchKernelGGL(k_fsc_randomize<true>, dim3(blocks), dim3(256), 0, ctx->stream, *Z, logN, sr, (unsigned long long)seed);
+    filter_gain_launch(ctx, *Z, nullptr, 1.0, logN);      // conj(X)
+    mad_timer_end(ctx, MAD_T_FSC);
+    mad_timer_begin(ctx, MAD_T_FFT);
+    int rc = fourier_passes(ctx, *Z, logN);
+    mad_timer_end(ctx, MAD_T_FFT);
+    if (rc != MAD_OK) return rc;
+    mad_timer_begin(ctx, MAD_T_FSC);
+    hipLaunchKernelGGL(k_fft_mask<true>, dim3(blocks), dim3(256), 0, ctx->stream, *Z, M, ldexp(1.0, -3 * logN));
+    mad_timer_end(ctx, MAD_T_FSC);
+    mad_timer_begin(ctx, MAD_T_FFT);
+    rc = fourier_passes(ctx, *Z, logN);
+    mad_timer_end(ctx, MAD_T_FFT);
+    if (rc != MAD_OK) return rc;
+    MAD_HIP(hipGetLastError());
+    MAD_TRY(fsc_shell_tables(ctx, *Z, P, sums_r, nullptr));
+    // 3. the two grids again (they are still in their buffers: the lattice is packed anew, not kept), times the mask, forward
+    PackArgs A;
+    memset(&A, 0, sizeof(A));
+    A.g1 = scratch<float>(ctx, S_TMP_H);
+    A.g2 = scratch<float>(ctx, S_TMP_I);
+    A.logN = logN;
+    for (int k = 0; k < 3; k++) { A.d1[k] = d1[k]; A.p1[k] = P.p1[k]; A.d2[k] = d2[k]; A.p2[k] = P.p2[k]; }
+    mad_timer_begin(ctx, MAD_T_FFT);
+    hipLaunchKernelGGL(k_fft_pack, dim3(blocks), dim3(256), 0, ctx->stream, A, *Z);
+    hipLaunchKernelGGL(k_fft_mask<false>, dim3(blocks), dim3(256), 0, ctx->stream, *Z, M, 1.0);
+    rc = fourier_passes(ctx, *Z, logN);
+    mad_timer_end(ctx, MAD_T_FFT);
+    if (rc != MAD_OK) return rc;
+    MAD_HIP(hipGetLastError());
+    return fsc_shell_tables(ctx, *Z, P, sums_m, nullptr);
+}
+
+extern "C" int mad_map_fsc_masked(mad_ctx *ctx, const float *grid1, const int32_t dims1[3], const double origin1[3], const float *grid2,
+                                  const int32_t dims2[3], const double origin2[3], double voxsp, const float *mask, const int32_t dimsm[3],
+                                  const double originm[3], int32_t shell_r, double t_r, uint64_t seed, double *sums_unmasked,
+                                  double *sums_masked, double *sums_random, int64_t *count, int32_t *N_out, int32_t *shell_r_out) {
+    if (ctx) mad_use_lane(ctx, 0);
+    if (!ctx || !grid1 || !dims1 || !origin1 || !grid2 || !dims2 || !origin2 || !mask || !dimsm || !originm || !sums_unmasked || !sums_masked ||
+        !sums_random || !count)
+        return ctx ? mad_fail(ctx, MAD_EINVAL, "mad_map_fsc_masked: NULL argument") : MAD_EINVAL;
+    double2 *Z = nullptr;
+    const int rc = map_fsc_masked_run(ctx, grid1, dims1, origin1, grid2, dims2, origin2, voxsp, mask, dimsm, originm, shell_r, t_r, seed,
+                                      sums_unmasked, sums_masked, sums_random, count, N_out, shell_r_out, &Z);
+    return fourier_free(ctx, Z, rc);
+}
+
+static int map_phase_randomize_run(mad_ctx *ctx, double *spectrum, int32_t N, int32_t shell_r, uint64_t seed, double2 **Z) {
+    const char *who = "mad_map_phase_randomize";
+    int logN = 0;
+    while ((1 << logN) < N && logN < 11) logN++;
+    if (N < FFT_MIN_N || N > FFT_MAX_N || (1 << logN) != N)
+        return mad_fail(ctx, MAD_EINVAL, "%s: N = %d (a power of two from %d to %d)", who, N, FFT_MIN_N, FFT_MAX_N);
+    if (shell_r < 0) return mad_fail(ctx, MAD_EINVAL, "%s: shell %d (0 or more)", who, shell_r);
+    MAD_TRY(fourier_room(ctx, who, N, logN, 0, 0, 0));
+    MAD_TRY(fourier_alloc(ctx, who, N, logN, Z));
+    const size_t bytes_Z = (size_t)16 << (3 * logN);
+    MAD_HIP(hipMemcpyAsync(*Z, spectrum, bytes_Z, hipMemcpyHostToDevice, ctx->stream));
+    mad_timer_begin(ctx, MAD_T_FSC);
+    hipLaunchKernelGGL(k_fsc_randomize<false>, dim3(fourier_blocks(ctx, (size_t)1 << (3 * logN))), dim3(256), 0, ctx->stream, *Z, logN, shell_r,
+                       (unsigned long long)seed);
+    mad_timer_end(ctx, MAD_T_FSC);
+    MAD_HIP(hipGetLastError());
+    MAD_HIP(hipMemcpyAsync(spectrum, *Z, bytes_Z, hipMemcpyDeviceToHost, ctx->stream));
+    MAD_HIP(hipStreamSynchronize(ctx->stream));
+    return MAD_OK;
+}
+
+extern "C" int mad_map_phase_randomize(mad_ctx *ctx, double *spectrum, int32_t N, int32_t shell_r, uint64_t seed) {
+    if (ctx) mad_use_lane(ctx, 0);
+    if (!ctx || !spectrum) return ctx ? mad_fail(ctx, MAD_EINVAL, "mad_map_phase_randomize: NULL argument") : MAD_EINVAL;
+    double2 *Z = nullptr;
+    const int rc = map_phase_randomize_run(ctx, spectrum, N, shell_r, seed, &Z);
     return fourier_free(ctx, Z, rc);
 }
 

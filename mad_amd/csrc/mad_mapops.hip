@@ -138,6 +138,93 @@ extern "C" int mad_map_mask(mad_ctx *ctx, float *grid1, const int32_t d1[3], con
 }
 
 // ---------------------------------------------------------------------------
+// multiply by a soft mask
+// ---------------------------------------------------------------------------
+
+struct MulArgs {
+    float *g;                   // grid 1, edited in place
+    const float *mask;          // grid 2
+    unsigned long long n;       // voxels of grid 1
+    int ny, nz;                 // grid 1
+    int my, mz;                 // grid 2
+    int lo[3], hi[3];           // the mask's box in grid 1: lo <= i < hi (empty on an axis: the boxes do not meet)
+    int sh[3];                  // mask index = grid index - sh
+};
+
+// g = (float)((double)g * (double)m) under the mask's box, +0 outside it; a voxel under m == 1 is not written (every bit stays).
+// The walk over chunks of four voxels is k_map_mask's.
+__global__ __launch_bounds__(MAPOP_THREADS) void k_map_multiply(const MulArgs A) {
+    const size_t n_chunk = (size_t)((A.n + 3) >> 2);
+    for (size_t c = (size_t)blockIdx.x * MAPOP_THREADS + threadIdx.x; c < n_chunk; c += (size_t)gridDim.x * MAPOP_THREADS) {
+        const size_t i0 = c << 2;
+        const bool full = i0 + 4 <= A.n;
+        float v[4] = {0.f, 0.f, 0.f, 0.f};
+        if (full) {
+            const float4 q = *(const float4 *)(A.g + i0);
+            v[0] = q.x; v[1] = q.y; v[2] = q.z; v[3] = q.w;
+        } else {
+            for (int k = 0; k < 4; k++)
+                if (i0 + k < A.n) v[k] = A.g[i0 + k];
+        }
+        const unsigned t = (unsigned)i0 / (unsigned)A.nz;
+        int z = (int)((unsigned)i0 - t * (unsigned)A.nz), y = (int)(t % (unsigned)A.ny), x = (int)(t / (unsigned)A.ny);
+        bool changed = false;
+#pragma unroll
+        for (int k = 0; k < 4; k++) {
+            if (full || i0 + k < A.n) {
+                const bool in = x >= A.lo[0] && x < A.hi[0] && y >= A.lo[1] && y < A.hi[1] && z >= A.lo[2] && z < A.hi[2];
+                if (in) {
+                    const float m = A.mask[((size_t)(x - A.sh[0]) * A.my + (y - A.sh[1])) * A.mz + (z - A.sh[2])];
+                    if (m != 1.f) { v[k] = (float)((double)v[k] * (double)m); changed = true; }
+                } else if (__float_as_uint(v[k]) != 0u) { v[k] = 0.f; changed = true; }
+            }
+            if (++z == A.nz) { z = 0; if (++y == A.ny) { y = 0; x++; } }
+        }
+        if (!changed) continue;
+        if (full) *(float4 *)(A.g + i0) = make_float4(v[0], v[1], v[2], v[3]);
+        else
+            for (int k = 0; k < 4; k++)
+                if (i0 + k < A.n) A.g[i0 + k] = v[k];
+    }
+}
+
+extern "C" int mad_map_multiply(mad_ctx *ctx, float *grid1, const int32_t d1[3], const double o1[3], const float *mask, const int32_t d2[3],
+                                const double o2[3], double voxsp) {
+    const char *who = "mad_map_multiply";
+    if (ctx) mad_use_lane(ctx, 0);
+    if (!ctx || !grid1 || !mask || !d1 || !d2 || !o1 || !o2) return ctx ? mad_fail(ctx, MAD_EINVAL, "%s: NULL argument", who) : MAD_EINVAL;
+    if (!(voxsp > 0) || !(voxsp < 1e15)) return mad_fail(ctx, MAD_EINVAL, "%s: voxsp %g", who, voxsp);
+    size_t n1 = 0, n2 = 0;
+    MAD_TRY(map_check(ctx, who, d1, o1, voxsp, &n1));
+    MAD_TRY(map_check(ctx, who, d2, o2, voxsp, &n2));
+    MulArgs A;
+    memset(&A, 0, sizeof(A));
+    A.n = n1; A.ny = d1[1]; A.nz = d1[2]; A.my = d2[1]; A.mz = d2[2];
+    bool meet = true;
+    for (int k = 0; k < 3; k++) {
+        const long s = py_round(o2[k] / voxsp - o1[k] / voxsp);      // mad_map_mask's offset (mask_axis)
+        const long lo = s > 0 ? s : 0, hi = (long)d1[k] < (long)d2[k] + s ? (long)d1[k] : (long)d2[k] + s;
+        if (hi <= lo) { meet = false; continue; }      // (s itself may be far outside an int)
+        A.lo[k] = (int)lo; A.hi[k] = (int)hi; A.sh[k] = (int)s;      // 0 <= lo - s and hi - s <= d2: every mask index is inside grid 2
+    }
+    if (!meet)
+        for (int k = 0; k < 3; k++) { A.lo[k] = 0; A.hi[k] = 0; A.sh[k] = 0; }
+    MAD_TRY(mad_reserve(ctx, mad_sb(ctx, S_TMP_H), (n1 + 4) * 4));
+    MAD_TRY(mad_reserve(ctx, mad_sb(ctx, S_TMP_I), (n2 + 4) * 4));
+    A.g = scratch<float>(ctx, S_TMP_H);
+    float *d_mask = scratch<float>(ctx, S_TMP_I);
+    A.mask = d_mask;
+    MAD_HIP(hipMemcpyAsync(A.g, grid1, n1 * 4, hipMemcpyHostToDevice, ctx->stream));
+    if (meet) MAD_HIP(hipMemcpyAsync(d_mask, mask, n2 * 4, hipMemcpyHostToDevice, ctx->stream));
+    const int blocks = (int)std::min<int64_t>(mad_ceil_div((int64_t)((n1 + 3) >> 2), MAPOP_THREADS), (int64_t)ctx->n_cu * 8);
+    hipLaunchKernelGGL(k_map_multiply, dim3(blocks), dim3(MAPOP_THREADS), 0, ctx->stream, A);
+    MAD_HIP(hipGetLastError());
+    MAD_HIP(hipMemcpyAsync(grid1, A.g, n1 * 4, hipMemcpyDeviceToHost, ctx->stream));
+    MAD_HIP(hipStreamSynchronize(ctx->stream));
+    return MAD_OK;
+}
+
+// ---------------------------------------------------------------------------
 // get_CCC_with_dmap
 // ---------------------------------------------------------------------------
 

@@ -3,7 +3,9 @@ The filters -- `filter_lattice`, `radial_gain`, the designs `gain_*` and the res
 further down, and so have the translation scan (section 4n): `scan_lattice`, the restatement `scan_numpy`, `peaks_numpy` and `Scan`,
 and the rotational search (section 4o): `rotation_set`, the restatements `rotate_numpy`, `tree_sum` and `search_numpy`, and `Search`,
 and local resolution (section 4p): `local_plan`, `hann_window`, the restatement `local_fsc_numpy` and `LocalResolution`;
-a low-pass by local resolution (section 4q): the restatements `local_sigma_numpy` and `local_filter_numpy`.
+a low-pass by local resolution (section 4q): the restatements `local_sigma_numpy` and `local_filter_numpy`;
+the masked curve and its phase-randomised correction (section 4s): `splitmix_u`, the restatements `randomize_numpy` and
+`fsc_masked_numpy`, and `MaskedFSC`.
 
 `plan_box` puts two grids of one spacing onto a common cubic lattice, `fsc_numpy` restates the contract of `mad_map_fsc` with
 `numpy.fft.fftn` in float64 -- the checker of the GPU tests, and the one place the contract is spelled out in code -- and `FSC` is
@@ -937,3 +939,139 @@ class FSC(object):
             for s in range(len(self.fsc)):
                 res = "inf" if s == 0 else "%.6f" % (1.0 / self.freq[s])
                 f.write("%d,%.9g,%s,%d,%.9g\n" % (s, self.freq[s], res, self.n[s], self.fsc[s]))
+
+
+# ---------------------------------------------------------------------------
+# the masked curve and its phase-randomised correction: the contract of `mad_map_fsc_masked`
+#
+# Lattice, placement, delta and the phase ramp are `plan_box`'s, from the two grids alone.  The mask is placed against grid 1 by whole
+# voxels, round(om / voxsp - o1 / voxsp) per axis (half to even); what is left of its offset is rounded away, so a soft edge moves by
+# at most half a voxel.  It multiplies both parts of the packed lattice; lattice points outside its box become 0.
+#   1. Z = FFT(g1 + i g2): the unmasked shell sums.
+#   2. shell_r: given, or the lowest shell s >= 1 whose unmasked fsc (FSC's convention) is below t_r; N / 2 + 1 when there is none.
+#   3. `randomize_numpy` on F1 (which = 0) and F2 (which = 1), Z = F1' + i F2'.
+#   4. inverse transform, times the mask, forward: the random shell sums.
+#   5. the packed lattice times the mask, forward: the masked shell sums.
+# ---------------------------------------------------------------------------
+
+_MASK64 = (1 << 64) - 1
+
+
+def splitmix_u(seed, n):
+    """-> (u, z): u = (z >> 11) * 2^-53 in [0, 1) and the 64-bit z itself, z = splitmix64's finaliser on
+    seed + 0x9E3779B97F4A7C15 * n (mod 2^64).  `n`: an integer or an array of them; the results are float64 / uint64 arrays."""
+    with np.errstate(over="ignore"):
+        z = np.uint64(int(seed) & _MASK64) + np.uint64(0x9E3779B97F4A7C15) * np.asarray(n).astype(np.uint64)
+        z = z ^ (z >> np.uint64(30))
+        z = z * np.uint64(0xBF58476D1CE4E5B9)
+        z = z ^ (z >> np.uint64(27))
+        z = z * np.uint64(0x94D049BB133111EB)
+        z = z ^ (z >> np.uint64(31))
+    return (z >> np.uint64(11)).astype(np.float64) * 2.0 ** -53, z
+
+
+def mirror_index(N):
+    """int64 [N, N, N]: the flat index L' of -k for every lattice point L = (a N + b) N + c."""
+    m = (N - np.arange(N)) % N
+    return ((m[:, None, None] * N + m[None, :, None]) * N + m[None, None, :]).astype(np.int64)
+
+
+def randomize_numpy(F, shell_r, seed, which=0):
+    """The spectrum F (complex128 [N, N, N]) with new phases from shell `shell_r` on, as k_fsc_randomize makes them: where L < L'
+    (the index of -k) and shell(k) >= shell_r, F(k) = |F(k)| (cos t + i sin t), t = 6.283185307179586 * u,
+    u = splitmix_u(seed, 2 L + which + 1), and F(-k) = conj F(k).  Everything else -- lower shells, self-conjugate points -- is
+    returned as it came."""
+    F = np.array(F, np.complex128)
+    N = F.shape[0]
+    L = np.arange(N ** 3, dtype=np.int64).reshape(N, N, N)
+    Lm = mirror_index(N)
+    act = (L < Lm) & (shell_index(N) >= int(shell_r))
+    la, lm = L[act], Lm[act]
+    flat = F.reshape(-1)
+    f = flat[la]
+    mag = np.sqrt(f.real * f.real + f.imag * f.imag)
+    t = 6.283185307179586 * splitmix_u(seed, 2 * la + int(which) + 1)[0]
+    new = mag * np.cos(t) + 1j * (mag * np.sin(t))
+    flat[la] = new
+    flat[lm] = np.conj(new)
+    return F
+
+
+def mask_lattice(N, p1, o1, mask, om, voxsp):
+    """float64 [N, N, N]: the mask on the lattice whose index p1 holds grid 1's voxel (0, 0, 0); 0 outside the mask's box (no
+    wrap-around)."""
+    mask = np.asarray(mask)
+    M = np.zeros((N, N, N))
+    lo, hi, src = [], [], []
+    for a in range(3):
+        p = p1[a] + int(round(float(om[a]) / float(voxsp) - float(o1[a]) / float(voxsp)))
+        l, h = max(p, 0), min(p + mask.shape[a], N)
+        if h <= l:
+            return M
+        lo.append(l); hi.append(h); src.append(l - p)
+    M[lo[0]:hi[0], lo[1]:hi[1], lo[2]:hi[2]] = mask[src[0]:src[0] + hi[0] - lo[0], src[1]:src[1] + hi[1] - lo[1],
+                                                     src[2]:src[2] + hi[2] - lo[2]].astype(np.float64)
+    return M
+
+
+def randomize_shell(sums, t_r):
+    """The shell the 0.8 rule picks: the lowest s >= 1 whose C / sqrt(P1 P2) (0 where P1 P2 is not positive) is below t_r, else
+    N / 2 + 1 (= len(sums))."""
+    sums = np.asarray(sums, np.float64)
+    for s in range(1, len(sums)):
+        pp = sums[s, 0] * sums[s, 1]
+        if (sums[s, 2] / np.sqrt(pp) if pp > 0 else 0.0) < t_r:
+            return s
+    return len(sums)
+
+
+def fsc_masked_numpy(g1, o1, g2, o2, voxsp, mask, om, shell_r=None, t_r=0.8, seed=0):
+    """The contract of `mad_map_fsc_masked` with numpy.fft in float64 -> `MaskedFSC`."""
+    Z0, delta = pack_lattice(g1, o1, g2, o2, voxsp)
+    N = Z0.shape[0]
+    _, p1, _, _ = plan_box(np.asarray(g1).shape, o1, np.asarray(g2).shape, o2, voxsp)
+    M = mask_lattice(N, p1, o1, mask, om, voxsp)
+    F1, F2 = split_pair(np.fft.fftn(Z0))
+    su, count = shell_sums(F1, F2, delta)
+    sr = randomize_shell(su, t_r) if shell_r is None or shell_r < 0 else int(shell_r)
+    Zr = randomize_numpy(F1, sr, seed, 0) + 1j * randomize_numpy(F2, sr, seed, 1)
+    sr_sums, _ = shell_sums(*split_pair(np.fft.fftn(np.fft.ifftn(Zr) * M)), delta)
+    sm, _ = shell_sums(*split_pair(np.fft.fftn(Z0 * M)), delta)
+    return MaskedFSC(N, voxsp, su, sm, sr_sums, count, sr, seed)
+
+
+class MaskedFSC(FSC):
+    """What `Dmap.fsc(mask=...)` returns: an `FSC` whose `fsc` is the masked curve corrected for the mask's own contribution (Chen et
+    al. 2013).  `fsc_unmasked`, `fsc_masked` and `fsc_random` are the three measured curves (each an `FSC`'s: 0 where a power is 0),
+    `shell_r` the shell the phases were randomised from, `seed` the seed.  fsc = fsc_masked for s < shell_r + 2 and
+    (fsc_masked - fsc_random) / (1 - fsc_random) from there on; where 1 - fsc_random is 0 the masked value stands.  `power1`,
+    `power2`, `cross` and `n` are the masked sums."""
+
+    def __init__(self, N, voxsp, sums_unmasked, sums_masked, sums_random, count, shell_r, seed=0):
+        FSC.__init__(self, N, voxsp, sums_masked, count)
+        self.sums_unmasked, self.sums_masked, self.sums_random = (np.array(s, np.float64).reshape(self.N // 2 + 1, 3)
+                                                                  for s in (sums_unmasked, sums_masked, sums_random))
+        self.fsc_masked = self.fsc
+        self.fsc_unmasked = FSC(N, voxsp, sums_unmasked, count).fsc
+        self.fsc_random = FSC(N, voxsp, sums_random, count).fsc
+        self.shell_r, self.seed = int(shell_r), int(seed)
+        self.fsc = self.corrected(self.fsc_masked, self.fsc_random, self.shell_r)
+
+    @staticmethod
+    def corrected(masked, random, shell_r):
+        masked, random = np.asarray(masked, np.float64), np.asarray(random, np.float64)
+        out = masked.copy()
+        den = 1.0 - random
+        use = (np.arange(len(masked)) >= shell_r + 2) & (den != 0) & np.isfinite(den) & np.isfinite(masked)
+        out[use] = (masked[use] - random[use]) / den[use]
+        return out
+
+    def write_csv(self, path):
+        """Columns shell, freq (1 / Angstrom), resolution (Angstrom; inf for shell 0), n, fsc (corrected), fsc_unmasked, fsc_masked,
+        fsc_random."""
+        with open(path, "w") as f:
+            f.write("shell,freq,resolution,n,fsc,fsc_unmasked,fsc_masked,fsc_random\n")
+            for s in range(len(self.fsc)):
+                res = "inf" if s == 0 else "%.6f" % (1.0 / self.freq[s])
+                f.write("%d,%.9g,%s,%d,%.9g,%.9g,%.9g,%.9g\n" % (s, self.freq[s], res, self.n[s], self.fsc[s], self.fsc_unmasked[s],
+                                                              self.fsc_masked[s], self.fsc_random[s]))
