@@ -331,6 +331,33 @@ class Dmap(object):
         res, shell, sm = _lib.get_lib().map_local_fsc(g1, o1, g2, o2, voxsp, box=box, step=step, threshold=thr, select=sel, sums=sums)
         return fourier.LocalResolution(res, shell, sm, box, step, voxsp, o1, thr)
 
+    def _correlation_args(self, who, structure, resolution, rotations, default_rotations, mode, isovalue, min_fill, masses):
+        """What `scan` and `search` check and derive alike, before any library call -> (coords, mass, centroid, rot, g1, iso,
+        min_fill, spread, md): the atoms, their masses and centroid, the rotations (`default_rotations()` where `rotations` is
+        None), the map as C-contiguous float32, and for the floor mean(m^2) ("uncentred", md 0) or var(m) ("centred", md 1)."""
+        from . import localfit
+        if mode not in ("uncentred", "centred"):
+            raise ValueError("%s: mode %r ('uncentred' or 'centred')" % (who, mode))
+        if resolution is None or not (float(resolution) > 0) or not np.isfinite(float(resolution)):
+            raise ValueError("%s: resolution %r (positive and finite)" % (who, resolution))
+        iso, min_fill = (0.0 if isovalue is None else float(isovalue)), float(min_fill)
+        if not np.isfinite(iso) or not (min_fill >= 0) or not np.isfinite(min_fill):
+            raise ValueError("%s: isovalue %r, min_fill %r (finite, min_fill 0 or more)" % (who, isovalue, min_fill))
+        parts = localfit.structure_parts(structure)
+        mass = localfit.structure_masses(parts, masses)
+        if sum(len(c) for c, _, _ in parts) == 0:
+            raise ValueError("%s: no atoms to simulate a density from" % who)
+        coords = np.concatenate([c for c, _, _ in parts], axis=0)
+        rot = default_rotations() if rotations is None else np.asarray(rotations, np.float64)
+        if rot.ndim != 3 or rot.shape[1:] != (3, 3) or len(rot) == 0 or not np.isfinite(rot).all():
+            raise ValueError("%s: rotations of shape %r, not (n, 3, 3) with n >= 1" % (who, rot.shape))
+        g1 = np.ascontiguousarray(self.grid3d, dtype=np.float32)
+        if g1.ndim != 3 or g1.size == 0:
+            raise ValueError("%s: the grid has shape %r" % (who, g1.shape))
+        m64 = g1.astype(np.float64)
+        spread = float(np.mean(m64 * m64)) if mode == "uncentred" else float(np.var(m64))
+        return coords, mass, coords.mean(axis=0), rot, g1, iso, min_fill, spread, (0 if mode == "uncentred" else 1)
+
     def scan(self, structure, resolution, rotations=None, mode="uncentred", isovalue=None, min_fill=0.25, min_score=0.0, k=20, masses=None):
         """Where in the map does the structure fit best?  Every whole-voxel translation of it, in each of the given orientations,
         scored by fast local correlation (Roseman's scheme) through `mad_map_scan` -> `fourier.Scan` (`best`, `best_t`, `peaks`,
@@ -345,26 +372,10 @@ class Dmap(object):
         rotations -- a convention: it keeps round-off over round-off in empty regions from being reported as a score.  The first
         `k` peaks of at least `min_score` come back, each with its rotation index and, through `Scan.pose(i)`, the translation
         T = (map origin + u voxsp) - the rotated copy's grid origin.  The map is not modified.  DESIGN.md section 4n."""
-        from . import fourier, localfit
-        if mode not in ("uncentred", "centred"):
-            raise ValueError("Dmap.scan: mode %r ('uncentred' or 'centred')" % (mode,))
-        if resolution is None or not (float(resolution) > 0) or not np.isfinite(float(resolution)):
-            raise ValueError("Dmap.scan: resolution %r (positive and finite)" % (resolution,))
-        iso, min_fill = (0.0 if isovalue is None else float(isovalue)), float(min_fill)
-        if not np.isfinite(iso) or not (min_fill >= 0) or not np.isfinite(min_fill):
-            raise ValueError("Dmap.scan: isovalue %r, min_fill %r (finite, min_fill 0 or more)" % (isovalue, min_fill))
-        parts = localfit.structure_parts(structure)
-        mass = localfit.structure_masses(parts, masses)
-        if sum(len(c) for c, _, _ in parts) == 0:
-            raise ValueError("Dmap.scan: no atoms to simulate a density from")
-        coords = np.concatenate([c for c, _, _ in parts], axis=0)
-        rot = np.eye(3)[None] if rotations is None else np.asarray(rotations, np.float64)
-        if rot.ndim != 3 or rot.shape[1:] != (3, 3) or len(rot) == 0 or not np.isfinite(rot).all():
-            raise ValueError("Dmap.scan: rotations of shape %r, not (n, 3, 3) with n >= 1" % (rot.shape,))
-        g1 = np.ascontiguousarray(self.grid3d, dtype=np.float32)
-        if g1.ndim != 3 or g1.size == 0:
-            raise ValueError("Dmap.scan: the grid has shape %r" % (g1.shape,))
-        lib, voxsp, centroid = _lib.get_lib(), float(self.voxsp), coords.mean(axis=0)
+        from . import fourier
+        coords, mass, centroid, rot, g1, iso, min_fill, spread, md = self._correlation_args(
+            "Dmap.scan", structure, resolution, rotations, lambda: np.eye(3)[None], mode, isovalue, min_fill, masses)
+        lib, voxsp = _lib.get_lib(), float(self.voxsp)
         grids, origins = [], []
         for R in rot:
             g, x0, y0, z0 = lib.structure_to_density((coords - centroid) @ R + centroid, mass, float(resolution), voxsp)
@@ -378,10 +389,7 @@ class Dmap(object):
             t[:g.shape[0], :g.shape[1], :g.shape[2]] = g
             templates.append(t)
         n_w = min(int((t.astype(np.float64) > iso).sum()) for t in templates)      # in float64, as the device compares
-        m64 = g1.astype(np.float64)
-        spread = float(np.mean(m64 * m64)) if mode == "uncentred" else float(np.var(m64))
         e_min = min_fill * n_w * spread
-        md = 0 if mode == "uncentred" else 1
         best, best_t, peaks, n_found, N = lib.map_scan(g1, templates, iso, e_min, md, float(min_score), int(k))
         return fourier.Scan(best, best_t, peaks, n_found, (self.xi, self.yi, self.zi), voxsp, rot, centroid, origins, N=N, e_min=e_min, mode=md)
 
@@ -398,26 +406,10 @@ class Dmap(object):
         on every axis (`pad_grid` first where it does not).  An offset is scored by a rotation where the map's energy under its mask
         exceeds min_fill n_w mean(m^2) (centred: var(m)).  Peaks are whole-voxel and no finer in angle than the set's spacing: the
         rigid refinement is the step after this, and is not called here.  The map is not modified.  DESIGN.md section 4o."""
-        from . import fourier, localfit
-        if mode not in ("uncentred", "centred"):
-            raise ValueError("Dmap.search: mode %r ('uncentred' or 'centred')" % (mode,))
-        if resolution is None or not (float(resolution) > 0) or not np.isfinite(float(resolution)):
-            raise ValueError("Dmap.search: resolution %r (positive and finite)" % (resolution,))
-        iso, min_fill = (0.0 if isovalue is None else float(isovalue)), float(min_fill)
-        if not np.isfinite(iso) or not (min_fill >= 0) or not np.isfinite(min_fill):
-            raise ValueError("Dmap.search: isovalue %r, min_fill %r (finite, min_fill 0 or more)" % (isovalue, min_fill))
-        parts = localfit.structure_parts(structure)
-        mass = localfit.structure_masses(parts, masses)
-        if sum(len(c) for c, _, _ in parts) == 0:
-            raise ValueError("Dmap.search: no atoms to simulate a density from")
-        coords = np.concatenate([c for c, _, _ in parts], axis=0)
-        rot = fourier.rotation_set(angle) if rotations is None else np.asarray(rotations, np.float64)
-        if rot.ndim != 3 or rot.shape[1:] != (3, 3) or len(rot) == 0 or not np.isfinite(rot).all():
-            raise ValueError("Dmap.search: rotations of shape %r, not (n, 3, 3) with n >= 1" % (rot.shape,))
-        g1 = np.ascontiguousarray(self.grid3d, dtype=np.float32)
-        if g1.ndim != 3 or g1.size == 0:
-            raise ValueError("Dmap.search: the grid has shape %r" % (g1.shape,))
-        lib, voxsp, centroid = _lib.get_lib(), float(self.voxsp), coords.mean(axis=0)
+        from . import fourier
+        coords, mass, centroid, rot, g1, iso, min_fill, spread, md = self._correlation_args(
+            "Dmap.search", structure, resolution, rotations, lambda: fourier.rotation_set(angle), mode, isovalue, min_fill, masses)
+        lib, voxsp = _lib.get_lib(), float(self.voxsp)
         g0, x0, y0, z0 = lib.structure_to_density(coords, mass, float(resolution), voxsp)
         g0 = np.ascontiguousarray(g0, np.float32)
         c0 = (centroid - np.array([x0, y0, z0], np.float64)) / voxsp
@@ -426,10 +418,7 @@ class Dmap(object):
             if e > g1.shape[a]:
                 raise ValueError("Dmap.search: the cube that holds every rotation is %d voxels long, the map %d on axis %d (pad_grid first)"
                                  % (e, g1.shape[a], a))
-        m64 = g1.astype(np.float64)
-        spread = float(np.mean(m64 * m64)) if mode == "uncentred" else float(np.var(m64))
         e_fill = min_fill * spread
-        md = 0 if mode == "uncentred" else 1
         best, best_r, peaks, n_found, n_skipped, N = lib.map_search(g1, g0, c0, e, rot, iso, e_fill, md, float(min_score), int(k))
         return fourier.Search(best, best_r, peaks, n_found, n_skipped, (self.xi, self.yi, self.zi), voxsp, rot, centroid, e, N=N, e_fill=e_fill,
                               mode=md)

@@ -1361,6 +1361,14 @@ class Lib(object):
                                         C.c_double(0.0), C.c_int64(0), None, None, None, None, None, C.byref(n)))
         return int(n.value)
 
+    def _corr_outputs(self, who, k, shape, ext):
+        """What `map_scan` / `map_search` fill, over the offsets D = shape - ext + 1 -> (k, best, best_i, peaks, n_peaks, n_found, n_skipped, n)."""
+        k = int(k)
+        if k < 0:
+            raise ValueError("%s: k = %d (0 or more)" % (who, k))
+        D = tuple(max(int(a) - int(b) + 1, 1) for a, b in zip(shape, ext))
+        return k, np.zeros(D, np.float32), np.full(D, -1, np.int32), np.zeros((max(k, 1), 5), np.float64), C.c_int64(0), C.c_int64(0), C.c_int32(0), C.c_int32(0)
+
     def map_scan(self, m, templates, iso=0.0, e_min=0.0, mode=0, min_score=0.0, k=20):
         """Every whole-voxel translation of the templates inside the map `m`, scored by fast local correlation -> (best float32 [D],
         best_t int32 [D], peaks float64 [min(k, n_found), 5] = ux, uy, uz, score, template; n_found, N) (mad_map_scan; DESIGN.md
@@ -1375,13 +1383,8 @@ class Lib(object):
             if g.shape != templates[0].shape:
                 raise ValueError("map_scan needs templates of one shape, got %r and %r" % (templates[0].shape, g.shape))
         d1, d2 = np.array(m.shape, np.int32), np.array(templates[0].shape, np.int32)
-        k = int(k)
-        if k < 0:
-            raise ValueError("map_scan: k = %d (0 or more)" % k)
-        D = tuple(max(int(a) - int(b) + 1, 1) for a, b in zip(m.shape, templates[0].shape))
+        k, best, best_t, peaks, n_peaks, n_found, _, n = self._corr_outputs("map_scan", k, m.shape, templates[0].shape)
         ptrs = (C.c_void_p * len(templates))(*[g.ctypes.data for g in templates])
-        best, best_t, peaks = np.zeros(D, np.float32), np.full(D, -1, np.int32), np.zeros((max(k, 1), 5), np.float64)
-        n_peaks, n_found, n = C.c_int64(0), C.c_int64(0), C.c_int32(0)
         self._chk(self.dll.mad_map_scan(self.ctx, _p(m), _p(d1), C.c_int32(len(templates)), ptrs, _p(d2), C.c_double(float(iso)),
                                         C.c_double(float(e_min)), C.c_int32(int(mode)), C.c_double(float(min_score)), C.c_int64(k), _p(best),
                                         _p(best_t), _p(peaks), C.byref(n_peaks), C.byref(n_found), C.byref(n)))
@@ -1410,14 +1413,10 @@ class Lib(object):
         rot = _c(np.asarray(rotations, np.float64), np.float64)
         if rot.ndim != 3 or rot.shape[1:] != (3, 3) or len(rot) < 1:
             raise ValueError("map_search: rotations of shape %r, not (n, 3, 3) with n >= 1" % (rot.shape,))
-        k, e = int(k), int(edge)
-        if k < 0:
-            raise ValueError("map_search: k = %d (0 or more)" % k)
+        e = int(edge)
+        k, best, best_r, peaks, n_peaks, n_found, n_skipped, n = self._corr_outputs("map_search", k, m.shape, (e, e, e))
         d1, d0 = np.array(m.shape, np.int32), np.array(base.shape, np.int32)
         c0 = _c(np.asarray(c0, np.float64).reshape(3), np.float64)
-        D = tuple(max(int(a) - e + 1, 1) for a in m.shape)
-        best, best_r, peaks = np.zeros(D, np.float32), np.full(D, -1, np.int32), np.zeros((max(k, 1), 5), np.float64)
-        n_peaks, n_found, n_skipped, n = C.c_int64(0), C.c_int64(0), C.c_int32(0), C.c_int32(0)
         self._chk(self.dll.mad_map_search(self.ctx, _p(m), _p(d1), _p(base), _p(d0), _p(c0), C.c_int32(e), _p(rot), C.c_int32(len(rot)),
                                           C.c_double(float(iso)), C.c_double(float(e_fill)), C.c_int32(int(mode)), C.c_double(float(min_score)),
                                           C.c_int64(k), _p(best), _p(best_r), _p(peaks), C.byref(n_peaks), C.byref(n_found), C.byref(n_skipped),

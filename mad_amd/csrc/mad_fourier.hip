@@ -38,9 +38,13 @@
 // three k_fft_lines passes follow (ifft(X) = conj(FFT(conj X)) / N^3), and k_fft_unpack writes Re Z / N^3 over grid 1's box and
 // -(Im Z) / N^3 over grid 2's as float32.  A gain that depends on r2 alone is real and even, so the two maps stay apart.
 //
-// The translation scan (mad_map_scan: k_scan_pack, k_scan_product, k_scan_score, k_scan_peaks) is at the end of the file: DESIGN.md
-// section 4n.  The rotational search (mad_map_search: k_search_rotate, k_search_stats, k_search_score and the pruned form of
-// k_fft_lines) follows it: section 4o.
+// The translation scan (mad_map_scan: k_scan_pack, k_scan_product, k_scan_score, k_scan_peaks) and the
+// rotational search (mad_map_search: k_search_rotate, k_search_stats, k_search_score and the pruned form of k_fft_lines; section 4o)
+// are at the end of the file.  They are one correlation: the score of an offset and the rule that keeps the best one are stated once
+// (scan_score_at, scan_keep), and so is the host's set-up (CorrPlan and the corr_ functions); the scan adds its templates' statistics
+// from the host, the search its rotations, their records on the device and the pruned passes.
+//
+// On the host every entry point owns its lattices through a `Lattices`, which waits for the stream and frees them on every way out.
 #include <algorithm>
 #include <vector>
 
@@ -402,6 +406,8 @@ struct FourierPlan {
     double delta[3];
 };
 
+static const double fourier_zero[3] = {0.0, 0.0, 0.0};      // the origin of a grid that has none, with voxsp 1
+
 static int fourier_check(mad_ctx *ctx, const char *who, const int32_t d[3], const double o[3], double voxsp) {
     for (int k = 0; k < 3; k++) {
         if (d[k] <= 0) return mad_fail(ctx, MAD_EINVAL, "%s: empty grid (%d x %d x %d)", who, d[0], d[1], d[2]);
@@ -438,38 +444,24 @@ static int fourier_plan(mad_ctx *ctx, const char *who, const int32_t d1[3], cons
     return MAD_OK;
 }
 
-template <int AXIS, int BPT> static int fft_launch(mad_ctx *ctx, double2 *Z, const double2 *tw, int logN, int threads) {
-    const int N = 1 << logN;
-    const size_t lds = (size_t)N * (AXIS == 2 ? FFT_L + 1 : FFT_L) * sizeof(double2);
+// One pass of k_fft_lines.  `grid` and `arg` select the form: every tile, dim3(N^2 / 8) with arg = logN, or (PRUNE, section 4o) the
+// tiles_x x planes tiles at the low corner of the tile grid, dim3(tiles_x, planes) with arg = live << 8 | logN.  The limit on dynamic
+// LDS is raised once per process for each instantiation.
+template <int AXIS, int BPT, bool PRUNE> static int fft_launch(mad_ctx *ctx, double2 *Z, const double2 *tw, int logN, int threads, dim3 grid, int arg) {
+    const size_t lds = ((size_t)(AXIS == 2 ? FFT_L + 1 : FFT_L) << logN) * sizeof(double2);
     static bool attr = false;
-    if (!attr) { MAD_HIP(hipFuncSetAttribute((const void *)k_fft_lines<AXIS, BPT>, hipFuncAttributeMaxDynamicSharedMemorySize, FFT_MAX_N * (FFT_L + 1) * 16)); attr = true; }
-    hipLaunchKernelGGL((k_fft_lines<AXIS, BPT>), dim3((unsigned)(N * N / FFT_L)), dim3(threads), lds, ctx->stream, Z, tw, logN);
+    if (!attr) { MAD_HIP(hipFuncSetAttribute((const void *)k_fft_lines<AXIS, BPT, PRUNE>, hipFuncAttributeMaxDynamicSharedMemorySize, FFT_MAX_N * (FFT_L + 1) * 16)); attr = true; }
+    hipLaunchKernelGGL((k_fft_lines<AXIS, BPT, PRUNE>), grid, dim3(threads), lds, ctx->stream, Z, tw, arg);
     return MAD_OK;
 }
-template <int AXIS> static int fft_axis(mad_ctx *ctx, double2 *Z, const double2 *tw, int logN) {
+template <int AXIS, bool PRUNE> static int fft_axis(mad_ctx *ctx, double2 *Z, int logN, dim3 grid, int arg) {
     // butterflies per thread: as few as 512 threads allow, or what the test hook asks for where that still fits
     const int N = 1 << logN, least = N <= 256 ? 1 : (N == 512 ? 2 : 4), bpt = std::max(ctx->fft_bpt, least);
     const int threads = std::max(2 * N / bpt, MAD_WAVE);
-    if (bpt == 1) return fft_launch<AXIS, 1>(ctx, Z, tw, logN, threads);
-    if (bpt == 2) return fft_launch<AXIS, 2>(ctx, Z, tw, logN, threads);
-    return fft_launch<AXIS, 4>(ctx, Z, tw, logN, threads);
-}
-
-// The pruned form (section 4o): tiles_x x planes tiles from the low corner of the tile grid, lines of live length `live`.
-template <int AXIS, int BPT> static int fft_launch_pruned(mad_ctx *ctx, double2 *Z, const double2 *tw, int logN, int threads, int tiles_x, int planes, int live) {
-    const int N = 1 << logN;
-    const size_t lds = (size_t)N * (AXIS == 2 ? FFT_L + 1 : FFT_L) * sizeof(double2);
-    static bool attr = false;
-    if (!attr) { MAD_HIP(hipFuncSetAttribute((const void *)k_fft_lines<AXIS, BPT, true>, hipFuncAttributeMaxDynamicSharedMemorySize, FFT_MAX_N * (FFT_L + 1) * 16)); attr = true; }
-    hipLaunchKernelGGL((k_fft_lines<AXIS, BPT, true>), dim3((unsigned)tiles_x, (unsigned)planes), dim3(threads), lds, ctx->stream, Z, tw, (live << 8) | logN);
-    return MAD_OK;
-}
-template <int AXIS> static int fft_axis_pruned(mad_ctx *ctx, double2 *Z, const double2 *tw, int logN, int tiles_x, int planes, int live) {
-    const int N = 1 << logN, least = N <= 256 ? 1 : (N == 512 ? 2 : 4), bpt = std::max(ctx->fft_bpt, least);
-    const int threads = std::max(2 * N / bpt, MAD_WAVE);
-    if (bpt == 1) return fft_launch_pruned<AXIS, 1>(ctx, Z, tw, logN, threads, tiles_x, planes, live);
-    if (bpt == 2) return fft_launch_pruned<AXIS, 2>(ctx, Z, tw, logN, threads, tiles_x, planes, live);
-    return fft_launch_pruned<AXIS, 4>(ctx, Z, tw, logN, threads, tiles_x, planes, live);
+    const double2 *tw = (const double2 *)ctx->fft_tw.p;
+    if (bpt == 1) return fft_launch<AXIS, 1, PRUNE>(ctx, Z, tw, logN, threads, grid, arg);
+    if (bpt == 2) return fft_launch<AXIS, 2, PRUNE>(ctx, Z, tw, logN, threads, grid, arg);
+    return fft_launch<AXIS, 4, PRUNE>(ctx, Z, tw, logN, threads, grid, arg);
 }
 
 // the twiddles exp(-2 pi i k / N) of the lattice edge N on the device, uploaded when N changes
@@ -512,12 +504,25 @@ static int fourier_alloc(mad_ctx *ctx, const char *who, int N, int logN, double2
     return MAD_OK;
 }
 
-// the three passes of k_fft_lines along z, y, x
-static int fourier_passes(mad_ctx *ctx, double2 *Z, int logN) {
-    const double2 *tw = (const double2 *)ctx->fft_tw.p;
-    MAD_TRY(fft_axis<2>(ctx, Z, tw, logN));
-    MAD_TRY(fft_axis<1>(ctx, Z, tw, logN));
-    return fft_axis<0>(ctx, Z, tw, logN);
+// The three passes of k_fft_lines along z, y, x over every tile.  With P (section 4o) pass a transforms only the P[a].tiles_x x
+// P[a].planes tiles at the low corner of the tile grid and takes its lines as P[a].live elements long.
+struct PrunedPass { int tiles_x, planes, live; };
+template <int AXIS> static int fft_pass(mad_ctx *ctx, double2 *Z, int logN, const PrunedPass *P) {
+    if (!P) return fft_axis<AXIS, false>(ctx, Z, logN, dim3(1u << (2 * logN - 3)), logN);      // N^2 / 8 tiles
+    return fft_axis<AXIS, true>(ctx, Z, logN, dim3((unsigned)P->tiles_x, (unsigned)P->planes), (P->live << 8) | logN);
+}
+static int fourier_passes(mad_ctx *ctx, double2 *Z, int logN, const PrunedPass *P = nullptr) {
+    MAD_TRY(fft_pass<2>(ctx, Z, logN, P));
+    MAD_TRY(fft_pass<1>(ctx, Z, logN, P ? P + 1 : P));
+    return fft_pass<0>(ctx, Z, logN, P ? P + 2 : P);
+}
+
+// the full passes inside an interval of the "fft" timer of their own
+static int fourier_passes_timed(mad_ctx *ctx, double2 *Z, int logN) {
+    mad_timer_begin(ctx, MAD_T_FFT);
+    const int rc = fourier_passes(ctx, Z, logN);
+    mad_timer_end(ctx, MAD_T_FFT);
+    return rc;
 }
 
 // workgroups of 256 for a streaming kernel over n elements (grid-stride beyond 16 per CU)
@@ -525,70 +530,72 @@ static unsigned fourier_blocks(mad_ctx *ctx, size_t n) {
     return (unsigned)std::min<int64_t>(mad_ceil_div((int64_t)n, 256), (int64_t)ctx->n_cu * 16);
 }
 
-// The lattice of a plan: judges the memory, allocates (*Zout, the caller frees it), uploads, packs and transforms.  The grids stay
-// in S_TMP_H and S_TMP_I.
+// The lattices of one call, at most three.  Constructed empty and filled by fourier_alloc alone, so that a refusal allocates nothing.
+// On every way out of the entry point each lattice is freed after a wait for the stream: kernels may still be running on it, and
+// copies from pageable host memory may still be reading their source.
+struct Lattices {
+    mad_ctx *ctx;
+    double2 *Z[3] = {nullptr, nullptr, nullptr};
+    explicit Lattices(mad_ctx *c) : ctx(c) {}
+    Lattices(const Lattices &) = delete;
+    Lattices &operator=(const Lattices &) = delete;
+    ~Lattices() {
+        for (double2 *z : Z)
+            if (z) {
+                (void)hipStreamSynchronize(ctx->stream);
+                (void)hipFree(z);
+            }
+    }
+};
+
+// *logN of a lattice edge N that the caller hands in; refuses an N that is no power of two from FFT_MIN_N to FFT_MAX_N
+static int fourier_log2(mad_ctx *ctx, const char *who, int N, int *logN) {
+    for (*logN = 0; (1 << *logN) < N && *logN < 11;) ++*logN;
+    if (N < FFT_MIN_N || N > FFT_MAX_N || (1 << *logN) != N)
+        return mad_fail(ctx, MAD_EINVAL, "%s: N = %d (a power of two from %d to %d)", who, N, FFT_MIN_N, FFT_MAX_N);
+    return MAD_OK;
+}
+
+// what every entry point with origins checks before it plans: the spacing, either grid (g2 false: grid 1 alone), then the plan
+static int fourier_plan_checked(mad_ctx *ctx, const char *who, const int32_t *d1, const double *o1, bool g2, const int32_t *d2, const double *o2,
+                                double voxsp, FourierPlan *P) {
+    if (!(voxsp > 0) || !(voxsp < 1e15)) return mad_fail(ctx, MAD_EINVAL, "%s: voxsp %g", who, voxsp);
+    MAD_TRY(fourier_check(ctx, who, d1, o1, voxsp));
+    if (g2) MAD_TRY(fourier_check(ctx, who, d2, o2, voxsp));
+    return fourier_plan(ctx, who, d1, o1, g2 ? d2 : nullptr, g2 ? o2 : nullptr, voxsp, P);
+}
+
+// k_fft_pack's arguments for the grids in S_TMP_H and S_TMP_I (d2 NULL: grid 1 alone) under a plan
+static PackArgs fourier_pack_args(mad_ctx *ctx, const FourierPlan &P, const int32_t *d1, const int32_t *d2) {
+    PackArgs A;
+    memset(&A, 0, sizeof(A));
+    A.g1 = scratch<float>(ctx, S_TMP_H);
+    A.g2 = d2 ? scratch<float>(ctx, S_TMP_I) : nullptr;
+    A.logN = P.logN;
+    for (int k = 0; k < 3; k++) { A.d1[k] = d1[k]; A.p1[k] = P.p1[k]; A.d2[k] = d2 ? d2[k] : 0; A.p2[k] = P.p2[k]; }
+    return A;
+}
+
+// The lattice of a plan: judges the memory, allocates *Zout (a slot of the caller's Lattices), uploads, packs and transforms.  The
+// grids stay in S_TMP_H and S_TMP_I.
 static int fourier_forward(mad_ctx *ctx, const char *who, const float *g1, const int32_t *d1, const float *g2, const int32_t *d2,
-                           size_t extra_bytes, const FourierPlan *P, double2 **Zout) {
-    *Zout = nullptr;
-    const int N = P->N, logN = P->logN;
+                           size_t extra_bytes, const FourierPlan &P, double2 **Zout) {
+    const int N = P.N, logN = P.logN;
     const size_t n1 = (size_t)d1[0] * d1[1] * d1[2], n2 = g2 ? (size_t)d2[0] * d2[1] * d2[2] : 0;
     MAD_TRY(fourier_room(ctx, who, N, logN, n1, n2, extra_bytes));
     MAD_TRY(fourier_twiddles(ctx, N));
     MAD_TRY(mad_reserve(ctx, mad_sb(ctx, S_TMP_H), (n1 + 4) * 4));
     MAD_TRY(mad_reserve(ctx, mad_sb(ctx, S_TMP_I), (n2 + 4) * 4));
     MAD_TRY(fourier_alloc(ctx, who, N, logN, Zout));
-    double2 *Z = *Zout;
-    PackArgs A;
-    memset(&A, 0, sizeof(A));
-    A.g1 = scratch<float>(ctx, S_TMP_H);
-    A.g2 = g2 ? scratch<float>(ctx, S_TMP_I) : nullptr;
-    A.logN = logN;
-    for (int k = 0; k < 3; k++) { A.d1[k] = d1[k]; A.p1[k] = P->p1[k]; A.d2[k] = g2 ? d2[k] : 0; A.p2[k] = P->p2[k]; }
+    const PackArgs A = fourier_pack_args(ctx, P, d1, g2 ? d2 : nullptr);
     MAD_HIP(hipMemcpyAsync((void *)A.g1, g1, n1 * 4, hipMemcpyHostToDevice, ctx->stream));
     if (g2) MAD_HIP(hipMemcpyAsync((void *)A.g2, g2, n2 * 4, hipMemcpyHostToDevice, ctx->stream));
     mad_timer_begin(ctx, MAD_T_FFT);
-    hipLaunchKernelGGL(k_fft_pack, dim3(fourier_blocks(ctx, (size_t)1 << (3 * logN))), dim3(256), 0, ctx->stream, A, Z);
-    const int rc = fourier_passes(ctx, Z, logN);
+    hipLaunchKernelGGL(k_fft_pack, dim3(fourier_blocks(ctx, (size_t)1 << (3 * logN))), dim3(256), 0, ctx->stream, A, *Zout);
+    const int rc = fourier_passes(ctx, *Zout, logN);
     mad_timer_end(ctx, MAD_T_FFT);
     if (rc != MAD_OK) return rc;
     MAD_HIP(hipGetLastError());
-    return MAD_OK;
-}
-
-// Validates, plans, allocates the lattice (*Zout, the caller frees it), uploads and transforms.  Nothing is allocated on a refusal.
-static int fourier_transform(mad_ctx *ctx, const char *who, const float *g1, const int32_t *d1, const double *o1, const float *g2,
-                             const int32_t *d2, const double *o2, double voxsp, size_t extra_bytes, FourierPlan *P, double2 **Zout) {
-    *Zout = nullptr;
-    if (!(voxsp > 0) || !(voxsp < 1e15)) return mad_fail(ctx, MAD_EINVAL, "%s: voxsp %g", who, voxsp);
-    MAD_TRY(fourier_check(ctx, who, d1, o1, voxsp));
-    if (g2) MAD_TRY(fourier_check(ctx, who, d2, o2, voxsp));
-    MAD_TRY(fourier_plan(ctx, who, d1, o1, g2 ? d2 : nullptr, g2 ? o2 : nullptr, voxsp, P));
-    return fourier_forward(ctx, who, g1, d1, g2, d2, extra_bytes, P, Zout);
-}
-
-static int fourier_free(mad_ctx *ctx, double2 *Z, int rc) {
-    if (Z) {
-        (void)hipStreamSynchronize(ctx->stream);
-        (void)hipFree(Z);
-    }
-    return rc;
-}
-
-static int map_fft_run(mad_ctx *ctx, const float *g1, const int32_t *d1, const double *o1, const float *g2, const int32_t *d2,
-                       const double *o2, double voxsp, int32_t *N_out, double *spectrum, double2 **Z) {
-    FourierPlan P;
-    if (!spectrum) {      // the size query: the checks and the plan, nothing allocated or launched
-        if (!(voxsp > 0) || !(voxsp < 1e15)) return mad_fail(ctx, MAD_EINVAL, "mad_map_fft: voxsp %g", voxsp);
-        MAD_TRY(fourier_check(ctx, "mad_map_fft", d1, o1, voxsp));
-        if (g2) MAD_TRY(fourier_check(ctx, "mad_map_fft", d2, o2, voxsp));
-        MAD_TRY(fourier_plan(ctx, "mad_map_fft", d1, o1, g2 ? d2 : nullptr, g2 ? o2 : nullptr, voxsp, &P));
-        *N_out = P.N;
-        return MAD_OK;
-    }
-    MAD_TRY(fourier_transform(ctx, "mad_map_fft", g1, d1, o1, g2, d2, o2, voxsp, 0, &P, Z));
-    if (N_out) *N_out = P.N;
-    MAD_HIP(hipMemcpyAsync(spectrum, *Z, (size_t)16 << (3 * P.logN), hipMemcpyDeviceToHost, ctx->stream));
-    MAD_HIP(hipStreamSynchronize(ctx->stream));
     return MAD_OK;
 }
 
@@ -597,30 +604,18 @@ extern "C" int mad_map_fft(mad_ctx *ctx, const float *grid1, const int32_t dims1
     if (ctx) mad_use_lane(ctx, 0);
     if (!ctx || !grid1 || !dims1 || !origin1 || (grid2 && (!dims2 || !origin2)) || (!N_out && !spectrum))
         return ctx ? mad_fail(ctx, MAD_EINVAL, "mad_map_fft: NULL argument") : MAD_EINVAL;
-    double2 *Z = nullptr;
-    const int rc = map_fft_run(ctx, grid1, dims1, origin1, grid2, dims2, origin2, voxsp, N_out, spectrum, &Z);
-    return fourier_free(ctx, Z, rc);
-}
-
-static int fsc_shell_tables(mad_ctx *ctx, const double2 *Z, const FourierPlan &P, double *sums, int64_t *count);
-
-static int map_fsc_run(mad_ctx *ctx, const float *g1, const int32_t *d1, const double *o1, const float *g2, const int32_t *d2,
-                       const double *o2, double voxsp, int32_t *N_out, double *sums, int64_t *count, int64_t cap_shells, double2 **Z) {
-    // the partial tables of the largest lattice: 1024 x 513 x 32 bytes
-    const size_t extra = (size_t)FSC_MAX_WGS * (FFT_MAX_N / 2 + 1) * 32 + ((size_t)1 << 20);
     FourierPlan P;
-    {      // the capacity is judged before anything is allocated or launched
-        FourierPlan Q;
-        if (!(voxsp > 0) || !(voxsp < 1e15)) return mad_fail(ctx, MAD_EINVAL, "mad_map_fsc: voxsp %g", voxsp);
-        MAD_TRY(fourier_check(ctx, "mad_map_fsc", d1, o1, voxsp));
-        MAD_TRY(fourier_check(ctx, "mad_map_fsc", d2, o2, voxsp));
-        MAD_TRY(fourier_plan(ctx, "mad_map_fsc", d1, o1, d2, o2, voxsp, &Q));
-        if (N_out) *N_out = Q.N;
-        if (cap_shells < Q.N / 2 + 1)
-            return mad_fail(ctx, MAD_ENOSPC, "mad_map_fsc: room for %lld shells, the %d^3 lattice has %d", (long long)cap_shells, Q.N, Q.N / 2 + 1);
+    MAD_TRY(fourier_plan_checked(ctx, "mad_map_fft", dims1, origin1, grid2 != nullptr, dims2, origin2, voxsp, &P));
+    if (!spectrum) {      // the size query: the checks and the plan, nothing allocated or launched
+        *N_out = P.N;
+        return MAD_OK;
     }
-    MAD_TRY(fourier_transform(ctx, "mad_map_fsc", g1, d1, o1, g2, d2, o2, voxsp, extra, &P, Z));
-    return fsc_shell_tables(ctx, *Z, P, sums, count);
+    Lattices L(ctx);
+    MAD_TRY(fourier_forward(ctx, "mad_map_fft", grid1, dims1, grid2, dims2, 0, P, &L.Z[0]));
+    if (N_out) *N_out = P.N;
+    MAD_HIP(hipMemcpyAsync(spectrum, L.Z[0], (size_t)16 << (3 * P.logN), hipMemcpyDeviceToHost, ctx->stream));
+    MAD_HIP(hipStreamSynchronize(ctx->stream));
+    return MAD_OK;
 }
 
 // the shell sums of the transformed lattice Z under the plan's phase ramp -> sums [N / 2 + 1][3], count [N / 2 + 1] (may be NULL)
@@ -662,15 +657,23 @@ static int fsc_shell_tables(mad_ctx *ctx, const double2 *Z, const FourierPlan &P
     return MAD_OK;
 }
 
+// what the shell tables of the largest lattice need beside the lattice: 1024 x 513 x 32 bytes of partial tables
+static const size_t FSC_EXTRA_BYTES = (size_t)FSC_MAX_WGS * (FFT_MAX_N / 2 + 1) * 32 + ((size_t)1 << 20);
+
 extern "C" int mad_map_fsc(mad_ctx *ctx, const float *grid1, const int32_t dims1[3], const double origin1[3], const float *grid2,
                            const int32_t dims2[3], const double origin2[3], double voxsp, int32_t *N_out, double *sums, int64_t *count,
                            int64_t cap_shells) {
     if (ctx) mad_use_lane(ctx, 0);
     if (!ctx || !grid1 || !dims1 || !origin1 || !grid2 || !dims2 || !origin2 || !sums || !count)
         return ctx ? mad_fail(ctx, MAD_EINVAL, "mad_map_fsc: NULL argument") : MAD_EINVAL;
-    double2 *Z = nullptr;
-    const int rc = map_fsc_run(ctx, grid1, dims1, origin1, grid2, dims2, origin2, voxsp, N_out, sums, count, cap_shells, &Z);
-    return fourier_free(ctx, Z, rc);
+    FourierPlan P;
+    MAD_TRY(fourier_plan_checked(ctx, "mad_map_fsc", dims1, origin1, true, dims2, origin2, voxsp, &P));
+    if (N_out) *N_out = P.N;
+    if (cap_shells < P.N / 2 + 1)      // the capacity is judged before anything is allocated or launched
+        return mad_fail(ctx, MAD_ENOSPC, "mad_map_fsc: room for %lld shells, the %d^3 lattice has %d", (long long)cap_shells, P.N, P.N / 2 + 1);
+    Lattices L(ctx);
+    MAD_TRY(fourier_forward(ctx, "mad_map_fsc", grid1, dims1, grid2, dims2, FSC_EXTRA_BYTES, P, &L.Z[0]));
+    return fsc_shell_tables(ctx, L.Z[0], P, sums, count);
 }
 
 // ---------------------------------------------------------------------------
@@ -685,19 +688,25 @@ static double fsc_value(const double *sums, int s) {
     return pp > 0 ? sums[3 * s + 2] / sqrt(pp) : 0.0;
 }
 
-static int map_fsc_masked_run(mad_ctx *ctx, const float *g1, const int32_t *d1, const double *o1, const float *g2, const int32_t *d2,
-                              const double *o2, double voxsp, const float *mask, const int32_t *dm, const double *om, int32_t shell_r, double t_r,
-                              uint64_t seed, double *sums_u, double *sums_m, double *sums_r, int64_t *count, int32_t *N_out,
-                              int32_t *shell_r_out, double2 **Z) {
+extern "C" int mad_map_fsc_masked(mad_ctx *ctx, const float *grid1, const int32_t dims1[3], const double origin1[3], const float *grid2,
+                                  const int32_t dims2[3], const double origin2[3], double voxsp, const float *mask, const int32_t dimsm[3],
+                                  const double originm[3], int32_t shell_r, double t_r, uint64_t seed, double *sums_unmasked,
+                                  double *sums_masked, double *sums_random, int64_t *count, int32_t *N_out, int32_t *shell_r_out) {
     const char *who = "mad_map_fsc_masked";
+    if (ctx) mad_use_lane(ctx, 0);
+    if (!ctx || !grid1 || !dims1 || !origin1 || !grid2 || !dims2 || !origin2 || !mask || !dimsm || !originm || !sums_unmasked || !sums_masked ||
+        !sums_random || !count)
+        return ctx ? mad_fail(ctx, MAD_EINVAL, "%s: NULL argument", who) : MAD_EINVAL;
     if (!(voxsp > 0) || !(voxsp < 1e15)) return mad_fail(ctx, MAD_EINVAL, "%s: voxsp %g", who, voxsp);
-    MAD_TRY(fourier_check(ctx, who, dm, om, voxsp));
+    MAD_TRY(fourier_check(ctx, who, dimsm, originm, voxsp));
     if (shell_r < 0 && !(t_r == t_r)) return mad_fail(ctx, MAD_EINVAL, "%s: no shell and a threshold that is not a number", who);
-    const size_t n_m = (size_t)dm[0] * dm[1] * dm[2];
+    const size_t n_m = (size_t)dimsm[0] * dimsm[1] * dimsm[2];
     const size_t grow_m = mad_sb(ctx, S_TMP_J).cap >= (n_m + 4) * 4 ? 0 : (n_m + 4) * 5;
-    const size_t extra = (size_t)FSC_MAX_WGS * (FFT_MAX_N / 2 + 1) * 32 + ((size_t)1 << 20) + grow_m;
     FourierPlan P;
-    MAD_TRY(fourier_transform(ctx, who, g1, d1, o1, g2, d2, o2, voxsp, extra, &P, Z));      // (the other checks are mad_map_fsc's)
+    MAD_TRY(fourier_plan_checked(ctx, who, dims1, origin1, true, dims2, origin2, voxsp, &P));      // the mask first, then the grids
+    Lattices L(ctx);
+    MAD_TRY(fourier_forward(ctx, who, grid1, dims1, grid2, dims2, FSC_EXTRA_BYTES + grow_m, P, &L.Z[0]));
+    double2 *Z = L.Z[0];
     const int N = P.N, logN = P.logN, SH = N / 2 + 1;
     if (N_out) *N_out = N;
     // the mask against grid 1 by whole voxels (mad_map_multiply's placement); what is left of its offset is rounded away
@@ -707,99 +716,66 @@ static int map_fsc_masked_run(mad_ctx *ctx, const float *g1, const int32_t *d1, 
     bool meets = true;
     long pm[3];
     for (int k = 0; k < 3; k++) {
-        pm[k] = (long)P.p1[k] + py_round(om[k] / voxsp - o1[k] / voxsp);
-        if (pm[k] >= N || pm[k] + (long)dm[k] <= 0) meets = false;
+        pm[k] = (long)P.p1[k] + py_round(originm[k] / voxsp - origin1[k] / voxsp);
+        if (pm[k] >= N || pm[k] + (long)dimsm[k] <= 0) meets = false;
     }
-    for (int k = 0; k < 3; k++) { M.d[k] = dm[k]; M.p[k] = meets ? (int)pm[k] : N; }      // -2^31 < -dm < pm < N where they meet
+    for (int k = 0; k < 3; k++) { M.d[k] = dimsm[k]; M.p[k] = meets ? (int)pm[k] : N; }      // -2^31 < -dm < pm < N where they meet
     MAD_TRY(mad_reserve(ctx, mad_sb(ctx, S_TMP_J), (n_m + 4) * 4));
     M.mask = scratch<float>(ctx, S_TMP_J);
     MAD_HIP(hipMemcpyAsync((void *)M.mask, mask, n_m * 4, hipMemcpyHostToDevice, ctx->stream));
     // 1. the curve without the mask, and from it the shell the randomisation begins at
-    MAD_TRY(fsc_shell_tables(ctx, *Z, P, sums_u, count));
+    MAD_TRY(fsc_shell_tables(ctx, Z, P, sums_unmasked, count));
     int sr = shell_r;
     if (sr < 0) {
         sr = SH;
         for (int s = 1; s < SH; s++)
-            if (fsc_value(sums_u, s) < t_r) { sr = s; break; }
+            if (fsc_value(sums_unmasked, s) < t_r) { sr = s; break; }
     }
     if (shell_r_out) *shell_r_out = sr;
     // 2. new phases from that shell on, back to real space, times the mask, forward again
     const unsigned blocks = fourier_blocks(ctx, (size_t)1 << (3 * logN));
     mad_timer_begin(ctx, MAD_T_FSC);
-    hipLaunchKernelGGL(k_fsc_randomize<true>, dim3(blocks), dim3(256), 0, ctx->stream, *Z, logN, sr, (unsigned long long)seed);
-    filter_gain_launch(ctx, *Z, nullptr, 1.0, logN);      // conj(X)
+    hipLaunchKernelGGL(k_fsc_randomize<true>, dim3(blocks), dim3(256), 0, ctx->stream, Z, logN, sr, (unsigned long long)seed);
+    filter_gain_launch(ctx, Z, nullptr, 1.0, logN);      // conj(X)
     mad_timer_end(ctx, MAD_T_FSC);
-    mad_timer_begin(ctx, MAD_T_FFT);
-    int rc = fourier_passes(ctx, *Z, logN);
-    mad_timer_end(ctx, MAD_T_FFT);
-    if (rc != MAD_OK) return rc;
+    MAD_TRY(fourier_passes_timed(ctx, Z, logN));
     mad_timer_begin(ctx, MAD_T_FSC);
-    hipLaunchKernelGGL(k_fft_mask<true>, dim3(blocks), dim3(256), 0, ctx->stream, *Z, M, ldexp(1.0, -3 * logN));
+    hipLaunchKernelGGL(k_fft_mask<true>, dim3(blocks), dim3(256), 0, ctx->stream, Z, M, ldexp(1.0, -3 * logN));
     mad_timer_end(ctx, MAD_T_FSC);
-    mad_timer_begin(ctx, MAD_T_FFT);
-    rc = fourier_passes(ctx, *Z, logN);
-    mad_timer_end(ctx, MAD_T_FFT);
-    if (rc != MAD_OK) return rc;
+    MAD_TRY(fourier_passes_timed(ctx, Z, logN));
     MAD_HIP(hipGetLastError());
-    MAD_TRY(fsc_shell_tables(ctx, *Z, P, sums_r, nullptr));
+    MAD_TRY(fsc_shell_tables(ctx, Z, P, sums_random, nullptr));
     // 3. the two grids again (they are still in their buffers: the lattice is packed anew, not kept), times the mask, forward
-    PackArgs A;
-    memset(&A, 0, sizeof(A));
-    A.g1 = scratch<float>(ctx, S_TMP_H);
-    A.g2 = scratch<float>(ctx, S_TMP_I);
-    A.logN = logN;
-    for (int k = 0; k < 3; k++) { A.d1[k] = d1[k]; A.p1[k] = P.p1[k]; A.d2[k] = d2[k]; A.p2[k] = P.p2[k]; }
     mad_timer_begin(ctx, MAD_T_FFT);
-    hipLaunchKernelGGL(k_fft_pack, dim3(blocks), dim3(256), 0, ctx->stream, A, *Z);
-    hipLaunchKernelGGL(k_fft_mask<false>, dim3(blocks), dim3(256), 0, ctx->stream, *Z, M, 1.0);
-    rc = fourier_passes(ctx, *Z, logN);
+    hipLaunchKernelGGL(k_fft_pack, dim3(blocks), dim3(256), 0, ctx->stream, fourier_pack_args(ctx, P, dims1, dims2), Z);
+    hipLaunchKernelGGL(k_fft_mask<false>, dim3(blocks), dim3(256), 0, ctx->stream, Z, M, 1.0);
+    const int rc = fourier_passes(ctx, Z, logN);
     mad_timer_end(ctx, MAD_T_FFT);
     if (rc != MAD_OK) return rc;
     MAD_HIP(hipGetLastError());
-    return fsc_shell_tables(ctx, *Z, P, sums_m, nullptr);
-}
-
-extern "C" int mad_map_fsc_masked(mad_ctx *ctx, const float *grid1, const int32_t dims1[3], const double origin1[3], const float *grid2,
-                                  const int32_t dims2[3], const double origin2[3], double voxsp, const float *mask, const int32_t dimsm[3],
-                                  const double originm[3], int32_t shell_r, double t_r, uint64_t seed, double *sums_unmasked,
-                                  double *sums_masked, double *sums_random, int64_t *count, int32_t *N_out, int32_t *shell_r_out) {
-    if (ctx) mad_use_lane(ctx, 0);
-    if (!ctx || !grid1 || !dims1 || !origin1 || !grid2 || !dims2 || !origin2 || !mask || !dimsm || !originm || !sums_unmasked || !sums_masked ||
-        !sums_random || !count)
-        return ctx ? mad_fail(ctx, MAD_EINVAL, "mad_map_fsc_masked: NULL argument") : MAD_EINVAL;
-    double2 *Z = nullptr;
-    const int rc = map_fsc_masked_run(ctx, grid1, dims1, origin1, grid2, dims2, origin2, voxsp, mask, dimsm, originm, shell_r, t_r, seed,
-                                      sums_unmasked, sums_masked, sums_random, count, N_out, shell_r_out, &Z);
-    return fourier_free(ctx, Z, rc);
-}
-
-static int map_phase_randomize_run(mad_ctx *ctx, double *spectrum, int32_t N, int32_t shell_r, uint64_t seed, double2 **Z) {
-    const char *who = "mad_map_phase_randomize";
-    int logN = 0;
-    while ((1 << logN) < N && logN < 11) logN++;
-    if (N < FFT_MIN_N || N > FFT_MAX_N || (1 << logN) != N)
-        return mad_fail(ctx, MAD_EINVAL, "%s: N = %d (a power of two from %d to %d)", who, N, FFT_MIN_N, FFT_MAX_N);
-    if (shell_r < 0) return mad_fail(ctx, MAD_EINVAL, "%s: shell %d (0 or more)", who, shell_r);
-    MAD_TRY(fourier_room(ctx, who, N, logN, 0, 0, 0));
-    MAD_TRY(fourier_alloc(ctx, who, N, logN, Z));
-    const size_t bytes_Z = (size_t)16 << (3 * logN);
-    MAD_HIP(hipMemcpyAsync(*Z, spectrum, bytes_Z, hipMemcpyHostToDevice, ctx->stream));
-    mad_timer_begin(ctx, MAD_T_FSC);
-    hipLaunchKernelGGL(k_fsc_randomize<false>, dim3(fourier_blocks(ctx, (size_t)1 << (3 * logN))), dim3(256), 0, ctx->stream, *Z, logN, shell_r,
-                       (unsigned long long)seed);
-    mad_timer_end(ctx, MAD_T_FSC);
-    MAD_HIP(hipGetLastError());
-    MAD_HIP(hipMemcpyAsync(spectrum, *Z, bytes_Z, hipMemcpyDeviceToHost, ctx->stream));
-    MAD_HIP(hipStreamSynchronize(ctx->stream));
-    return MAD_OK;
+    return fsc_shell_tables(ctx, Z, P, sums_masked, nullptr);
 }
 
 extern "C" int mad_map_phase_randomize(mad_ctx *ctx, double *spectrum, int32_t N, int32_t shell_r, uint64_t seed) {
+    const char *who = "mad_map_phase_randomize";
     if (ctx) mad_use_lane(ctx, 0);
-    if (!ctx || !spectrum) return ctx ? mad_fail(ctx, MAD_EINVAL, "mad_map_phase_randomize: NULL argument") : MAD_EINVAL;
-    double2 *Z = nullptr;
-    const int rc = map_phase_randomize_run(ctx, spectrum, N, shell_r, seed, &Z);
-    return fourier_free(ctx, Z, rc);
+    if (!ctx || !spectrum) return ctx ? mad_fail(ctx, MAD_EINVAL, "%s: NULL argument", who) : MAD_EINVAL;
+    int logN;
+    MAD_TRY(fourier_log2(ctx, who, N, &logN));
+    if (shell_r < 0) return mad_fail(ctx, MAD_EINVAL, "%s: shell %d (0 or more)", who, shell_r);
+    MAD_TRY(fourier_room(ctx, who, N, logN, 0, 0, 0));
+    Lattices L(ctx);
+    MAD_TRY(fourier_alloc(ctx, who, N, logN, &L.Z[0]));
+    const size_t bytes_Z = (size_t)16 << (3 * logN);
+    MAD_HIP(hipMemcpyAsync(L.Z[0], spectrum, bytes_Z, hipMemcpyHostToDevice, ctx->stream));
+    mad_timer_begin(ctx, MAD_T_FSC);
+    hipLaunchKernelGGL(k_fsc_randomize<false>, dim3(fourier_blocks(ctx, (size_t)1 << (3 * logN))), dim3(256), 0, ctx->stream, L.Z[0], logN, shell_r,
+                       (unsigned long long)seed);
+    mad_timer_end(ctx, MAD_T_FSC);
+    MAD_HIP(hipGetLastError());
+    MAD_HIP(hipMemcpyAsync(spectrum, L.Z[0], bytes_Z, hipMemcpyDeviceToHost, ctx->stream));
+    MAD_HIP(hipStreamSynchronize(ctx->stream));
+    return MAD_OK;
 }
 
 // ---------------------------------------------------------------------------
@@ -814,14 +790,18 @@ static int filter_gain_launch(mad_ctx *ctx, double2 *Z, const double *gain, doub
     return MAD_OK;
 }
 
-static int map_filter_run(mad_ctx *ctx, const float *g1, const int32_t *d1, const float *g2, const int32_t *d2, int32_t pad,
-                          const double *gain, int64_t n_gain, int32_t *N_out, float *out1, float *out2, double2 **Z) {
-    static const double zero[3] = {0.0, 0.0, 0.0};
-    MAD_TRY(fourier_check(ctx, "mad_map_filter", d1, zero, 1.0));
-    if (g2) MAD_TRY(fourier_check(ctx, "mad_map_filter", d2, zero, 1.0));
+extern "C" int mad_map_filter(mad_ctx *ctx, const float *grid1, const int32_t dims1[3], const float *grid2, const int32_t dims2[3],
+                              int32_t pad, const double *gain, int64_t n_gain, int32_t *N_out, float *out1, float *out2) {
+    if (ctx) mad_use_lane(ctx, 0);
+    if (!ctx || !grid1 || !dims1 || (grid2 && !dims2) || (!gain && !N_out) || (gain && !out1))
+        return ctx ? mad_fail(ctx, MAD_EINVAL, "mad_map_filter: NULL argument") : MAD_EINVAL;
+    if (gain && (grid2 != nullptr) != (out2 != nullptr))
+        return mad_fail(ctx, MAD_EINVAL, "mad_map_filter: grid2 and out2 go together (%s is NULL)", grid2 ? "out2" : "grid2");
+    MAD_TRY(fourier_check(ctx, "mad_map_filter", dims1, fourier_zero, 1.0));
+    if (grid2) MAD_TRY(fourier_check(ctx, "mad_map_filter", dims2, fourier_zero, 1.0));
     if (pad < 0) return mad_fail(ctx, MAD_EINVAL, "mad_map_filter: pad %d (0 or more)", pad);
     int64_t longest = 0;
-    for (int k = 0; k < 3; k++) longest = std::max<int64_t>(longest, std::max<int64_t>(d1[k], g2 ? d2[k] : 0));
+    for (int k = 0; k < 3; k++) longest = std::max<int64_t>(longest, std::max<int64_t>(dims1[k], grid2 ? dims2[k] : 0));
     if (longest + pad > FFT_MAX_N)
         return mad_fail(ctx, MAD_EDOM, "mad_map_filter: the longest axis and the pad are %lld + %d voxels, more than %d", (long long)longest, pad, FFT_MAX_N);
     FourierPlan P;
@@ -837,69 +817,30 @@ static int map_filter_run(mad_ctx *ctx, const float *g1, const int32_t *d1, cons
     for (int64_t i = 0; i < n_gain; i++)
         if (!(fabs(gain[i]) <= 1.7976931348623157e308)) return mad_fail(ctx, MAD_EINVAL, "mad_map_filter: gain[%lld] is not finite", (long long)i);
     const size_t b_gain = (size_t)n_gain * 8, grow_g = mad_sb(ctx, S_TMP_G).cap >= b_gain ? 0 : b_gain + b_gain / 4;
-    MAD_TRY(fourier_forward(ctx, "mad_map_filter", g1, d1, g2, d2, grow_g, &P, Z));
+    Lattices L(ctx);
+    MAD_TRY(fourier_forward(ctx, "mad_map_filter", grid1, dims1, grid2, dims2, grow_g, P, &L.Z[0]));
+    double2 *Z = L.Z[0];
     MAD_TRY(mad_reserve(ctx, mad_sb(ctx, S_TMP_G), b_gain));
     double *d_gain = scratch<double>(ctx, S_TMP_G);
     MAD_HIP(hipMemcpyAsync(d_gain, gain, b_gain, hipMemcpyHostToDevice, ctx->stream));
     mad_timer_begin(ctx, MAD_T_FILTER);
-    filter_gain_launch(ctx, *Z, d_gain, 1.0, logN);
+    filter_gain_launch(ctx, Z, d_gain, 1.0, logN);
     mad_timer_end(ctx, MAD_T_FILTER);
-    mad_timer_begin(ctx, MAD_T_FFT);
-    const int rc = fourier_passes(ctx, *Z, logN);
-    mad_timer_end(ctx, MAD_T_FFT);
-    if (rc != MAD_OK) return rc;
+    MAD_TRY(fourier_passes_timed(ctx, Z, logN));
     // the grids were consumed by k_fft_pack: their buffers take the outputs
-    const size_t n1 = (size_t)d1[0] * d1[1] * d1[2], n2 = g2 ? (size_t)d2[0] * d2[1] * d2[2] : 0;
+    const size_t n1 = (size_t)dims1[0] * dims1[1] * dims1[2], n2 = grid2 ? (size_t)dims2[0] * dims2[1] * dims2[2] : 0;
     const double scale = ldexp(1.0, -3 * logN);
     float *o1 = scratch<float>(ctx, S_TMP_H), *o2 = scratch<float>(ctx, S_TMP_I);
     mad_timer_begin(ctx, MAD_T_FILTER);
-    hipLaunchKernelGGL(k_fft_unpack<false>, dim3(fourier_blocks(ctx, n1)), dim3(256), 0, ctx->stream, (const double2 *)*Z, logN, scale, o1,
-                       (unsigned)d1[1], (unsigned)d1[2], n1);
-    if (g2)
-        hipLaunchKernelGGL(k_fft_unpack<true>, dim3(fourier_blocks(ctx, n2)), dim3(256), 0, ctx->stream, (const double2 *)*Z, logN, scale, o2,
-                           (unsigned)d2[1], (unsigned)d2[2], n2);
+    hipLaunchKernelGGL(k_fft_unpack<false>, dim3(fourier_blocks(ctx, n1)), dim3(256), 0, ctx->stream, (const double2 *)Z, logN, scale, o1,
+                       (unsigned)dims1[1], (unsigned)dims1[2], n1);
+    if (grid2)
+        hipLaunchKernelGGL(k_fft_unpack<true>, dim3(fourier_blocks(ctx, n2)), dim3(256), 0, ctx->stream, (const double2 *)Z, logN, scale, o2,
+                           (unsigned)dims2[1], (unsigned)dims2[2], n2);
     mad_timer_end(ctx, MAD_T_FILTER);
     MAD_HIP(hipGetLastError());
     MAD_HIP(hipMemcpyAsync(out1, o1, n1 * 4, hipMemcpyDeviceToHost, ctx->stream));
-    if (g2) MAD_HIP(hipMemcpyAsync(out2, o2, n2 * 4, hipMemcpyDeviceToHost, ctx->stream));
-    MAD_HIP(hipStreamSynchronize(ctx->stream));
-    return MAD_OK;
-}
-
-extern "C" int mad_map_filter(mad_ctx *ctx, const float *grid1, const int32_t dims1[3], const float *grid2, const int32_t dims2[3],
-                              int32_t pad, const double *gain, int64_t n_gain, int32_t *N_out, float *out1, float *out2) {
-    if (ctx) mad_use_lane(ctx, 0);
-    if (!ctx || !grid1 || !dims1 || (grid2 && !dims2) || (!gain && !N_out) || (gain && !out1))
-        return ctx ? mad_fail(ctx, MAD_EINVAL, "mad_map_filter: NULL argument") : MAD_EINVAL;
-    if (gain && (grid2 != nullptr) != (out2 != nullptr))
-        return mad_fail(ctx, MAD_EINVAL, "mad_map_filter: grid2 and out2 go together (%s is NULL)", grid2 ? "out2" : "grid2");
-    double2 *Z = nullptr;
-    const int rc = map_filter_run(ctx, grid1, dims1, grid2, dims2, pad, gain, n_gain, N_out, out1, out2, &Z);
-    return fourier_free(ctx, Z, rc);
-}
-
-static int map_ifft_run(mad_ctx *ctx, const double *spectrum, int32_t N, double *out, double2 **Z) {
-    int logN = 0;
-    while ((1 << logN) < N && logN < 11) logN++;
-    if (N < FFT_MIN_N || N > FFT_MAX_N || (1 << logN) != N)
-        return mad_fail(ctx, MAD_EINVAL, "mad_map_ifft: N = %d (a power of two from %d to %d)", N, FFT_MIN_N, FFT_MAX_N);
-    MAD_TRY(fourier_room(ctx, "mad_map_ifft", N, logN, 0, 0, 0));
-    MAD_TRY(fourier_twiddles(ctx, N));
-    MAD_TRY(fourier_alloc(ctx, "mad_map_ifft", N, logN, Z));
-    const size_t bytes_Z = (size_t)16 << (3 * logN);
-    MAD_HIP(hipMemcpyAsync(*Z, spectrum, bytes_Z, hipMemcpyHostToDevice, ctx->stream));
-    mad_timer_begin(ctx, MAD_T_FILTER);
-    filter_gain_launch(ctx, *Z, nullptr, 1.0, logN);      // conj(X)
-    mad_timer_end(ctx, MAD_T_FILTER);
-    mad_timer_begin(ctx, MAD_T_FFT);
-    const int rc = fourier_passes(ctx, *Z, logN);
-    mad_timer_end(ctx, MAD_T_FFT);
-    if (rc != MAD_OK) return rc;
-    mad_timer_begin(ctx, MAD_T_FILTER);
-    filter_gain_launch(ctx, *Z, nullptr, ldexp(1.0, -3 * logN), logN);      // conj(.) / N^3: a power of two, exact
-    mad_timer_end(ctx, MAD_T_FILTER);
-    MAD_HIP(hipGetLastError());
-    MAD_HIP(hipMemcpyAsync(out, *Z, bytes_Z, hipMemcpyDeviceToHost, ctx->stream));
+    if (grid2) MAD_HIP(hipMemcpyAsync(out2, o2, n2 * 4, hipMemcpyDeviceToHost, ctx->stream));
     MAD_HIP(hipStreamSynchronize(ctx->stream));
     return MAD_OK;
 }
@@ -907,9 +848,26 @@ static int map_ifft_run(mad_ctx *ctx, const double *spectrum, int32_t N, double 
 extern "C" int mad_map_ifft(mad_ctx *ctx, const double *spectrum, int32_t N, double *out) {
     if (ctx) mad_use_lane(ctx, 0);
     if (!ctx || !spectrum || !out) return ctx ? mad_fail(ctx, MAD_EINVAL, "mad_map_ifft: NULL argument") : MAD_EINVAL;
-    double2 *Z = nullptr;
-    const int rc = map_ifft_run(ctx, spectrum, N, out, &Z);
-    return fourier_free(ctx, Z, rc);
+    int logN;
+    MAD_TRY(fourier_log2(ctx, "mad_map_ifft", N, &logN));
+    MAD_TRY(fourier_room(ctx, "mad_map_ifft", N, logN, 0, 0, 0));
+    MAD_TRY(fourier_twiddles(ctx, N));
+    Lattices L(ctx);
+    MAD_TRY(fourier_alloc(ctx, "mad_map_ifft", N, logN, &L.Z[0]));
+    double2 *Z = L.Z[0];
+    const size_t bytes_Z = (size_t)16 << (3 * logN);
+    MAD_HIP(hipMemcpyAsync(Z, spectrum, bytes_Z, hipMemcpyHostToDevice, ctx->stream));
+    mad_timer_begin(ctx, MAD_T_FILTER);
+    filter_gain_launch(ctx, Z, nullptr, 1.0, logN);      // conj(X)
+    mad_timer_end(ctx, MAD_T_FILTER);
+    MAD_TRY(fourier_passes_timed(ctx, Z, logN));
+    mad_timer_begin(ctx, MAD_T_FILTER);
+    filter_gain_launch(ctx, Z, nullptr, ldexp(1.0, -3 * logN), logN);      // conj(.) / N^3: a power of two, exact
+    mad_timer_end(ctx, MAD_T_FILTER);
+    MAD_HIP(hipGetLastError());
+    MAD_HIP(hipMemcpyAsync(out, Z, bytes_Z, hipMemcpyDeviceToHost, ctx->stream));
+    MAD_HIP(hipStreamSynchronize(ctx->stream));
+    return MAD_OK;
 }
 
 // ---------------------------------------------------------------------------
@@ -981,38 +939,65 @@ __global__ __launch_bounds__(256) void k_scan_product(const double2 *__restrict_
     }
 }
 
-struct ScanScoreArgs {
-    int logN, mode, tpl;         // tpl: the template's index; template 0 initialises best / best_t
+struct ScoreStat { double n_w, G, gbar; };      // of one template or rotation; G: G' in mode 1
+
+struct ScoreArgs {
+    int logN, mode, idx;         // idx: the template's or rotation's index; index 0 initialises best / best_i
     unsigned D1, D2;             // the offset box [D0][D1][D2]
     size_t nD;
     double scale;                // 1 / N^3
-    double e_min, G, gbar, n_w;  // G: G' in mode 1
+    double floor;                // mad_map_scan: e_min; mad_map_search: e_fill, the floor is e_fill n_w
+    ScoreStat st;                // mad_map_scan: the template's, from the host; mad_map_search reads the rotation's record instead
 };
 
-// Over the box of offsets alone.  Zt holds N^3 conj(C + i E), Zq (mode 1) N^3 conj(A).  An offset is scored where E > e_min
-// (E' in mode 1); best / best_t take a strictly greater float32 score only, so the lowest template index keeps a tie.
-__global__ __launch_bounds__(256) void k_scan_score(const double2 *__restrict__ Zt, const double2 *__restrict__ Zq, const ScanScoreArgs A,
-                                                    float *__restrict__ best, int *__restrict__ best_t) {
-    for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < A.nD; i += (size_t)gridDim.x * 256) {
-        const unsigned q = (unsigned)i, t = q / A.D2, z = q - t * A.D2, x = t / A.D1, y = t - x * A.D1;
-        const size_t at = (((((size_t)x) << A.logN) + y) << A.logN) + z;
-        const double2 v = Zt[at];
-        double c = v.x * A.scale, e = -(v.y * A.scale);
-        if (A.mode) {
-            const double a = Zq[at].x * A.scale;
-            c = c - a * A.gbar;
-            e = e - (a * a) / A.n_w;
-        }
-        const bool scored = e > A.e_min;
-        const float s = scored ? (float)(c / sqrt(e * A.G)) : 0.0f;
-        if (A.tpl == 0) {
-            best[i] = s;
-            best_t[i] = scored ? 0 : -1;
-        } else if (scored && (best_t[i] < 0 || s > best[i])) {
-            best[i] = s;
-            best_t[i] = A.tpl;
-        }
+// offset q of the box [D0][D1][D2] in linear order -> (x, y, z)
+__device__ __forceinline__ void scan_offset(unsigned q, unsigned D1, unsigned D2, unsigned &x, unsigned &y, unsigned &z) {
+    const unsigned t = q / D2;
+    z = q - t * D2; x = t / D1; y = t - x * D1;
+}
+
+// The score of the offset at lattice index `at`.  Zt holds N^3 conj(C + i E), Zq (mode 1) N^3 conj(A).  The offset is scored where
+// E > e_min (E' in mode 1): -> whether it is, *s its float32 score (0 where it is not).
+__device__ __forceinline__ bool scan_score_at(const double2 *__restrict__ Zt, const double2 *__restrict__ Zq, size_t at, int mode, double scale,
+                                              const ScoreStat &st, double e_min, float *s) {
+    const double2 v = Zt[at];
+    double c = v.x * scale, e = -(v.y * scale);
+    if (mode) {
+        const double a = Zq[at].x * scale;
+        c = c - a * st.gbar;
+        e = e - (a * a) / st.n_w;
     }
+    const bool scored = e > e_min;
+    *s = scored ? (float)(c / sqrt(e * st.G)) : 0.0f;
+    return scored;
+}
+
+// best / best_i take what index 0 gives, whatever it is, and after it a strictly greater float32 score only, so the lowest index
+// keeps a tie; best_i is -1 where nothing has scored the offset.
+__device__ __forceinline__ void scan_keep(float *__restrict__ best, int *__restrict__ best_i, size_t i, int idx, bool scored, float s) {
+    if (idx == 0) { best[i] = s; best_i[i] = scored ? 0 : -1; }
+    else if (scored && (best_i[i] < 0 || s > best[i])) { best[i] = s; best_i[i] = idx; }
+}
+
+// Over the box of offsets alone, grid-stride in workgroups of 256: every offset scored (skip: none is) and kept.
+__device__ __forceinline__ void scan_score_box(const double2 *__restrict__ Zt, const double2 *__restrict__ Zq, const ScoreArgs &A, const ScoreStat &st,
+                                               double e_min, bool skip, float *__restrict__ best, int *__restrict__ best_i) {
+    for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < A.nD; i += (size_t)gridDim.x * 256) {
+        bool scored = false;
+        float s = 0.0f;
+        if (!skip) {
+            unsigned x, y, z;
+            scan_offset((unsigned)i, A.D1, A.D2, x, y, z);
+            scored = scan_score_at(Zt, Zq, (((((size_t)x) << A.logN) + y) << A.logN) + z, A.mode, A.scale, st, e_min, &s);
+        }
+        scan_keep(best, best_i, i, A.idx, scored, s);
+    }
+}
+
+// mad_map_scan: the template's statistics and the floor come with the arguments
+__global__ __launch_bounds__(256) void k_scan_score(const double2 *__restrict__ Zt, const double2 *__restrict__ Zq, const ScoreArgs A,
+                                                    float *__restrict__ best, int *__restrict__ best_t) {
+    scan_score_box(Zt, Zq, A, A.st, A.floor, false, best, best_t);
 }
 
 // An offset is a peak when a template scored it, its score is at least min_score and every neighbour of the 26 inside the box is
@@ -1025,7 +1010,9 @@ __global__ __launch_bounds__(256) void k_scan_peaks(const float *__restrict__ be
         if (best_t[i] < 0) continue;
         const float s = best[i];
         if (!((double)s >= min_score)) continue;
-        const unsigned q = (unsigned)i, t = q / D2, z = q - t * D2, x = t / D1, y = t - x * D1;
+        const unsigned q = (unsigned)i;
+        unsigned x, y, z;
+        scan_offset(q, D1, D2, x, y, z);
         bool peak = true;
         for (int dx = -1; dx <= 1 && peak; dx++)
             for (int dy = -1; dy <= 1 && peak; dy++)
@@ -1043,16 +1030,36 @@ __global__ __launch_bounds__(256) void k_scan_peaks(const float *__restrict__ be
     }
 }
 
-struct ScanLattices {
-    double2 *Z[3] = {nullptr, nullptr, nullptr};      // the map's, the template's, mode 1: the third
+// ---------------------------------------------------------------------------
+// the correlation set-up mad_map_scan and mad_map_search share
+// ---------------------------------------------------------------------------
+
+struct CorrPlan {
+    int N, logN;
+    int n_lat;                   // lattices: the map's and the template's, mode 1: a third
+    unsigned D[3];               // the box of offsets
+    size_t n1, nD;               // voxels of the map, offsets
+    unsigned wg_Z, wg_D;         // workgroups of 256 over the lattice and over the box
+    int threads;                 // of k_scan_product
+    // the output block, S_TMP_G once corr_setup has run: best | best_i (b_best bytes each) | count (16 bytes) | the caller's tail
+    size_t b_best;
+    char *blk;
+    float *best() const { return (float *)blk; }
+    int *best_i() const { return (int *)(blk + b_best); }
+    unsigned *count() const { return (unsigned *)(blk + 2 * b_best); }
+    char *tail() const { return blk + 2 * b_best + 16; }
 };
 
-// The peaks of the score volume on the device (d_best, d_best_t over the box D; d_count: 16 bytes) and the volume itself, to the
-// host.  The list in S_TMP_J holds `cap` candidates; where more were found and some are wanted it grows to the count and the kernel
-// runs again, while best is still on the device.
-static int scan_peaks_out(mad_ctx *ctx, const char *who, int timer, const float *d_best, const int *d_best_t, unsigned *d_count, const unsigned D[3],
-                          size_t nD, double min_score, int64_t k, float *best, int32_t *best_t, double *peaks, int64_t *n_peaks, int64_t *n_found) {
-    const unsigned wg_D = fourier_blocks(ctx, nD);
+// The peaks of the score volume on the device (C.best(), C.best_i() over the box C.D) and the volume itself, to the host.  The list
+// in S_TMP_J holds `cap` candidates; where more were found and some are wanted it grows to the count and the kernel runs again, while
+// best is still on the device.
+static int scan_peaks_out(mad_ctx *ctx, const char *who, int timer, const CorrPlan &C, double min_score, int64_t k, float *best, int32_t *best_t,
+                          double *peaks, int64_t *n_peaks, int64_t *n_found) {
+    const float *d_best = C.best();
+    const int *d_best_t = C.best_i();
+    unsigned *d_count = C.count();
+    const unsigned *D = C.D, wg_D = C.wg_D;
+    const size_t nD = C.nD;
     unsigned cap = SCAN_CAP0, found = 0;
     for (int pass = 0; pass < 2; pass++) {
         MAD_HIP(hipMemsetAsync(d_count, 0, 16, ctx->stream));
@@ -1092,123 +1099,131 @@ static int scan_peaks_out(mad_ctx *ctx, const char *who, int timer, const float 
     return MAD_OK;
 }
 
-struct ScanStat { double n_w, G, gbar; };      // G: G' in mode 1
-
-static int map_scan_run(mad_ctx *ctx, const float *map, const int32_t *d1, int32_t n_t, const float *const *tpl, const int32_t *d2, double iso,
-                        double e_min, int32_t mode, double min_score, int64_t k, float *best, int32_t *best_t, double *peaks, int64_t *n_peaks,
-                        int64_t *n_found, int32_t *N_out, ScanLattices *L) {
-    static const double zero[3] = {0.0, 0.0, 0.0};
-    if (n_t < 1) return mad_fail(ctx, MAD_EINVAL, "mad_map_scan: %d templates (1 or more)", n_t);
-    MAD_TRY(fourier_check(ctx, "mad_map_scan", d1, zero, 1.0));
-    MAD_TRY(fourier_check(ctx, "mad_map_scan", d2, zero, 1.0));
-    if (!(fabs(iso) <= 1.7e308) || !(fabs(min_score) <= 1.7e308) || !(e_min >= 0.0 && e_min <= 1.7e308))
-        return mad_fail(ctx, MAD_EINVAL, "mad_map_scan: iso %g, e_min %g, min_score %g (finite, e_min 0 or more)", iso, e_min, min_score);
-    if (mode != 0 && mode != 1) return mad_fail(ctx, MAD_EINVAL, "mad_map_scan: mode %d (0 un-centred, 1 centred)", mode);
-    if (k < 0) return mad_fail(ctx, MAD_EINVAL, "mad_map_scan: k = %lld (0 or more)", (long long)k);
+// What both refuse after their own checks, in this order: mode, k, a map longer than FFT_MAX_N, and `ext` voxels (`what`: "the
+// templates are", "the cube is") that do not fit into the map.  -> N, logN, the box of offsets, and the answer to the size query.
+static int corr_plan(mad_ctx *ctx, const char *who, const char *what, const int32_t *d1, const int32_t *ext, int32_t mode, int64_t k, int32_t *N_out,
+                     CorrPlan *C) {
+    if (mode != 0 && mode != 1) return mad_fail(ctx, MAD_EINVAL, "%s: mode %d (0 un-centred, 1 centred)", who, mode);
+    if (k < 0) return mad_fail(ctx, MAD_EINVAL, "%s: k = %lld (0 or more)", who, (long long)k);
     int longest = 0;
     for (int a = 0; a < 3; a++) longest = std::max(longest, (int)d1[a]);
-    if (longest > FFT_MAX_N) return mad_fail(ctx, MAD_EDOM, "mad_map_scan: the map's longest axis is %d voxels, more than %d", longest, FFT_MAX_N);
+    if (longest > FFT_MAX_N) return mad_fail(ctx, MAD_EDOM, "%s: the map's longest axis is %d voxels, more than %d", who, longest, FFT_MAX_N);
     for (int a = 0; a < 3; a++)
-        if (d2[a] > d1[a])
-            return mad_fail(ctx, MAD_EDOM, "mad_map_scan: the templates are %d voxels long on axis %d, the map %d: no offset keeps them inside", d2[a], a, d1[a]);
-    int N = FFT_MIN_N, logN = 3;
-    while (N < longest) { N <<= 1; logN++; }
-    if (N_out) *N_out = N;
-    if (!best) return MAD_OK;      // the size query
-    const unsigned D[3] = {(unsigned)(d1[0] - d2[0] + 1), (unsigned)(d1[1] - d2[1] + 1), (unsigned)(d1[2] - d2[2] + 1)};
-    const size_t n1 = (size_t)d1[0] * d1[1] * d1[2], n2 = (size_t)d2[0] * d2[1] * d2[2], nD = (size_t)D[0] * D[1] * D[2];
+        if (ext[a] > d1[a])
+            return mad_fail(ctx, MAD_EDOM, "%s: %s %d voxels long on axis %d, the map %d: no offset keeps that inside", who, what, ext[a], a, d1[a]);
+    C->N = FFT_MIN_N; C->logN = 3;
+    while (C->N < longest) { C->N <<= 1; C->logN++; }
+    C->n_lat = mode ? 3 : 2;
+    for (int a = 0; a < 3; a++) C->D[a] = (unsigned)(d1[a] - ext[a] + 1);
+    C->n1 = (size_t)d1[0] * d1[1] * d1[2];
+    C->nD = (size_t)C->D[0] * C->D[1] * C->D[2];
+    if (N_out) *N_out = C->N;
+    return MAD_OK;
+}
 
-    // n_w, G and the sum of every template, in voxel order in float64, before anything is allocated
-    std::vector<ScanStat> st((size_t)n_t);
-    for (int32_t j = 0; j < n_t; j++) {
-        if (!tpl[j]) return mad_fail(ctx, MAD_EINVAL, "mad_map_scan: template %d is NULL", j);
-        double n_w = 0.0, G = 0.0, S = 0.0;
-        for (size_t i = 0; i < n2; i++) {
-            const double x = (double)tpl[j][i];
-            if (x > iso) { n_w += 1.0; G += x * x; S += x; }
-        }
-        if (!(n_w > 0.0)) return mad_fail(ctx, MAD_EINVAL, "mad_map_scan: template %d has no voxel above iso = %g", j, iso);
-        st[j].n_w = n_w; st[j].G = G; st[j].gbar = 0.0;
-        if (!(G > 0.0 && G <= 1.7e308)) return mad_fail(ctx, MAD_EINVAL, "mad_map_scan: template %d has G = %g under its mask", j, G);
-        if (mode) {
-            st[j].gbar = S / n_w;
-            st[j].G = G - n_w * (st[j].gbar * st[j].gbar);
-            if (!(st[j].G > 0.0)) return mad_fail(ctx, MAD_EINVAL, "mad_map_scan: template %d is constant under its mask (G' = %g)", j, st[j].G);
-        }
-    }
-
-    const int n_lat = mode ? 3 : 2;
-    const size_t bytes_Z = (size_t)16 << (3 * logN);
-    const size_t b_best = (nD * 4 + 15) & ~(size_t)15, b_out = 2 * b_best + 16, b_list = (size_t)SCAN_CAP0 * 4;
+// Everything up to the map's transform.  The memory is judged before anything is allocated: n2 voxels go into S_TMP_I beside the map
+// in S_TMP_H, `tail` bytes of the caller's behind the output block in S_TMP_G.  Then the twiddles, the four scratch buffers, the
+// lattices, and Zm = L->Z[0] = FFT(m + i m^2).
+static int corr_setup(mad_ctx *ctx, const char *who, const float *map, const int32_t *d1, size_t n2, size_t tail, CorrPlan *C, Lattices *L) {
+    const int N = C->N, logN = C->logN;
+    C->b_best = (C->nD * 4 + 15) & ~(size_t)15;
+    const size_t b_out = 2 * C->b_best + 16 + tail, b_list = (size_t)SCAN_CAP0 * 4;
     const size_t grow_g = mad_sb(ctx, S_TMP_G).cap >= b_out ? 0 : b_out + b_out / 4, grow_j = mad_sb(ctx, S_TMP_J).cap >= b_list ? 0 : b_list + b_list / 4;
-    MAD_TRY(fourier_room(ctx, "mad_map_scan", N, logN, n1, n2, (size_t)(n_lat - 1) * bytes_Z + grow_g + grow_j));
+    MAD_TRY(fourier_room(ctx, who, N, logN, C->n1, n2, (size_t)(C->n_lat - 1) * ((size_t)16 << (3 * logN)) + grow_g + grow_j));
     MAD_TRY(fourier_twiddles(ctx, N));
-    MAD_TRY(mad_reserve(ctx, mad_sb(ctx, S_TMP_H), (n1 + 4) * 4));
+    MAD_TRY(mad_reserve(ctx, mad_sb(ctx, S_TMP_H), (C->n1 + 4) * 4));
     MAD_TRY(mad_reserve(ctx, mad_sb(ctx, S_TMP_I), (n2 + 4) * 4));
     MAD_TRY(mad_reserve(ctx, mad_sb(ctx, S_TMP_G), b_out));
     MAD_TRY(mad_reserve(ctx, mad_sb(ctx, S_TMP_J), b_list));
-    for (int l = 0; l < n_lat; l++) MAD_TRY(fourier_alloc(ctx, "mad_map_scan", N, logN, &L->Z[l]));
-    double2 *Zm = L->Z[0], *Zt = L->Z[1], *Zq = L->Z[2];
-    float *d_map = scratch<float>(ctx, S_TMP_H), *d_tpl = scratch<float>(ctx, S_TMP_I);
-    char *blk = scratch<char>(ctx, S_TMP_G);
-    float *d_best = (float *)blk;
-    int *d_best_t = (int *)(blk + b_best);
-    unsigned *d_count = (unsigned *)(blk + 2 * b_best);
-    const unsigned wg_Z = fourier_blocks(ctx, (size_t)1 << (3 * logN)), wg_D = fourier_blocks(ctx, nD);
-    const int threads = std::min(N, 256);
-
-    MAD_HIP(hipMemcpyAsync(d_map, map, n1 * 4, hipMemcpyHostToDevice, ctx->stream));
+    for (int l = 0; l < C->n_lat; l++) MAD_TRY(fourier_alloc(ctx, who, N, logN, &L->Z[l]));
+    C->blk = scratch<char>(ctx, S_TMP_G);
+    C->wg_Z = fourier_blocks(ctx, (size_t)1 << (3 * logN));
+    C->wg_D = fourier_blocks(ctx, C->nD);
+    C->threads = std::min(N, 256);
+    float *d_map = scratch<float>(ctx, S_TMP_H);
+    MAD_HIP(hipMemcpyAsync(d_map, map, C->n1 * 4, hipMemcpyHostToDevice, ctx->stream));
     mad_timer_begin(ctx, MAD_T_SCAN);
-    hipLaunchKernelGGL(k_scan_pack<false>, dim3(wg_Z), dim3(256), 0, ctx->stream, (const float *)d_map, (unsigned)d1[0], (unsigned)d1[1], (unsigned)d1[2],
-                       0.0, logN, Zm);
+    hipLaunchKernelGGL(k_scan_pack<false>, dim3(C->wg_Z), dim3(256), 0, ctx->stream, (const float *)d_map, (unsigned)d1[0], (unsigned)d1[1], (unsigned)d1[2],
+                       0.0, logN, L->Z[0]);
     mad_timer_end(ctx, MAD_T_SCAN);
-    mad_timer_begin(ctx, MAD_T_FFT);
-    int rc = fourier_passes(ctx, Zm, logN);
-    mad_timer_end(ctx, MAD_T_FFT);
-    if (rc != MAD_OK) return rc;
+    MAD_TRY(fourier_passes_timed(ctx, L->Z[0], logN));
     MAD_HIP(hipGetLastError());
+    return MAD_OK;
+}
 
-    ScanScoreArgs A;
+// k_scan_score's and k_search_score's arguments but for what changes from launch to launch: the index and, in the scan, the statistics
+static ScoreArgs corr_score_args(const CorrPlan &C, int mode, double floor) {
+    ScoreArgs A;
     memset(&A, 0, sizeof(A));
-    A.logN = logN; A.mode = mode; A.D1 = D[1]; A.D2 = D[2]; A.nD = nD; A.scale = ldexp(1.0, -3 * logN); A.e_min = e_min;
-    for (int32_t j = 0; j < n_t; j++) {
-        MAD_HIP(hipMemcpyAsync(d_tpl, tpl[j], n2 * 4, hipMemcpyHostToDevice, ctx->stream));
-        mad_timer_begin(ctx, MAD_T_SCAN);
-        hipLaunchKernelGGL(k_scan_pack<true>, dim3(wg_Z), dim3(256), 0, ctx->stream, (const float *)d_tpl, (unsigned)d2[0], (unsigned)d2[1],
-                           (unsigned)d2[2], iso, logN, Zt);
-        mad_timer_end(ctx, MAD_T_SCAN);
-        mad_timer_begin(ctx, MAD_T_FFT);
-        rc = fourier_passes(ctx, Zt, logN);
-        mad_timer_end(ctx, MAD_T_FFT);
-        if (rc != MAD_OK) return rc;
-        mad_timer_begin(ctx, MAD_T_SCAN);
-        hipLaunchKernelGGL(k_scan_product, dim3((unsigned)N, (unsigned)(N / 2 + 1)), dim3(threads), 0, ctx->stream, (const double2 *)Zm, Zt, Zq, logN);
-        mad_timer_end(ctx, MAD_T_SCAN);
-        mad_timer_begin(ctx, MAD_T_FFT);
-        rc = fourier_passes(ctx, Zt, logN);
-        if (rc == MAD_OK && mode) rc = fourier_passes(ctx, Zq, logN);
-        mad_timer_end(ctx, MAD_T_FFT);
-        if (rc != MAD_OK) return rc;
-        A.tpl = j; A.G = st[j].G; A.gbar = st[j].gbar; A.n_w = st[j].n_w;
-        mad_timer_begin(ctx, MAD_T_SCAN);
-        hipLaunchKernelGGL(k_scan_score, dim3(wg_D), dim3(256), 0, ctx->stream, (const double2 *)Zt, (const double2 *)Zq, A, d_best, d_best_t);
-        mad_timer_end(ctx, MAD_T_SCAN);
-        MAD_HIP(hipGetLastError());
-    }
-
-    return scan_peaks_out(ctx, "mad_map_scan", MAD_T_SCAN, d_best, d_best_t, d_count, D, nD, min_score, k, best, best_t, peaks, n_peaks, n_found);
+    A.logN = C.logN; A.mode = mode; A.D1 = C.D[1]; A.D2 = C.D[2]; A.nD = C.nD; A.scale = ldexp(1.0, -3 * C.logN); A.floor = floor;
+    return A;
 }
 
 extern "C" int mad_map_scan(mad_ctx *ctx, const float *map, const int32_t dims1[3], int32_t n_t, const float *const *templates,
                             const int32_t dims2[3], double iso, double e_min, int32_t mode, double min_score, int64_t k, float *best,
                             int32_t *best_t, double *peaks, int64_t *n_peaks, int64_t *n_found, int32_t *N_out) {
+    const char *who = "mad_map_scan";
     if (ctx) mad_use_lane(ctx, 0);
     if (!ctx || !dims1 || !dims2 || (!best && !N_out) || (best && (!map || !templates || !best_t || !n_peaks || !n_found || (k > 0 && !peaks))))
-        return ctx ? mad_fail(ctx, MAD_EINVAL, "mad_map_scan: NULL argument") : MAD_EINVAL;
-    ScanLattices L;
-    int rc = map_scan_run(ctx, map, dims1, n_t, templates, dims2, iso, e_min, mode, min_score, k, best, best_t, peaks, n_peaks, n_found, N_out, &L);
-    for (int l = 0; l < 3; l++) rc = fourier_free(ctx, L.Z[l], rc);
-    return rc;
+        return ctx ? mad_fail(ctx, MAD_EINVAL, "%s: NULL argument", who) : MAD_EINVAL;
+    if (n_t < 1) return mad_fail(ctx, MAD_EINVAL, "%s: %d templates (1 or more)", who, n_t);
+    MAD_TRY(fourier_check(ctx, who, dims1, fourier_zero, 1.0));
+    MAD_TRY(fourier_check(ctx, who, dims2, fourier_zero, 1.0));
+    if (!(fabs(iso) <= 1.7e308) || !(fabs(min_score) <= 1.7e308) || !(e_min >= 0.0 && e_min <= 1.7e308))
+        return mad_fail(ctx, MAD_EINVAL, "%s: iso %g, e_min %g, min_score %g (finite, e_min 0 or more)", who, iso, e_min, min_score);
+    CorrPlan C;
+    MAD_TRY(corr_plan(ctx, who, "the templates are", dims1, dims2, mode, k, N_out, &C));
+    if (!best) return MAD_OK;      // the size query
+    const size_t n2 = (size_t)dims2[0] * dims2[1] * dims2[2];
+
+    // n_w, G and the sum of every template, in voxel order in float64, before anything is allocated
+    std::vector<ScoreStat> st((size_t)n_t);
+    for (int32_t j = 0; j < n_t; j++) {
+        if (!templates[j]) return mad_fail(ctx, MAD_EINVAL, "%s: template %d is NULL", who, j);
+        double n_w = 0.0, G = 0.0, S = 0.0;
+        for (size_t i = 0; i < n2; i++) {
+            const double x = (double)templates[j][i];
+            if (x > iso) { n_w += 1.0; G += x * x; S += x; }
+        }
+        if (!(n_w > 0.0)) return mad_fail(ctx, MAD_EINVAL, "%s: template %d has no voxel above iso = %g", who, j, iso);
+        st[j].n_w = n_w; st[j].G = G; st[j].gbar = 0.0;
+        if (!(G > 0.0 && G <= 1.7e308)) return mad_fail(ctx, MAD_EINVAL, "%s: template %d has G = %g under its mask", who, j, G);
+        if (mode) {
+            st[j].gbar = S / n_w;
+            st[j].G = G - n_w * (st[j].gbar * st[j].gbar);
+            if (!(st[j].G > 0.0)) return mad_fail(ctx, MAD_EINVAL, "%s: template %d is constant under its mask (G' = %g)", who, j, st[j].G);
+        }
+    }
+
+    Lattices L(ctx);
+    MAD_TRY(corr_setup(ctx, who, map, dims1, n2, 0, &C, &L));
+    double2 *Zm = L.Z[0], *Zt = L.Z[1], *Zq = L.Z[2];
+    float *d_tpl = scratch<float>(ctx, S_TMP_I);
+    const int N = C.N, logN = C.logN;
+
+    ScoreArgs A = corr_score_args(C, mode, e_min);
+    for (int32_t j = 0; j < n_t; j++) {
+        MAD_HIP(hipMemcpyAsync(d_tpl, templates[j], n2 * 4, hipMemcpyHostToDevice, ctx->stream));
+        mad_timer_begin(ctx, MAD_T_SCAN);
+        hipLaunchKernelGGL(k_scan_pack<true>, dim3(C.wg_Z), dim3(256), 0, ctx->stream, (const float *)d_tpl, (unsigned)dims2[0], (unsigned)dims2[1],
+                           (unsigned)dims2[2], iso, logN, Zt);
+        mad_timer_end(ctx, MAD_T_SCAN);
+        MAD_TRY(fourier_passes_timed(ctx, Zt, logN));
+        mad_timer_begin(ctx, MAD_T_SCAN);
+        hipLaunchKernelGGL(k_scan_product, dim3((unsigned)N, (unsigned)(N / 2 + 1)), dim3(C.threads), 0, ctx->stream, (const double2 *)Zm, Zt, Zq, logN);
+        mad_timer_end(ctx, MAD_T_SCAN);
+        mad_timer_begin(ctx, MAD_T_FFT);      // one interval for both inverse transforms
+        int rc = fourier_passes(ctx, Zt, logN);
+        if (rc == MAD_OK && mode) rc = fourier_passes(ctx, Zq, logN);
+        mad_timer_end(ctx, MAD_T_FFT);
+        if (rc != MAD_OK) return rc;
+        A.idx = j; A.st = st[j];
+        mad_timer_begin(ctx, MAD_T_SCAN);
+        hipLaunchKernelGGL(k_scan_score, dim3(C.wg_D), dim3(256), 0, ctx->stream, (const double2 *)Zt, (const double2 *)Zq, A, C.best(), C.best_i());
+        mad_timer_end(ctx, MAD_T_SCAN);
+        MAD_HIP(hipGetLastError());
+    }
+    return scan_peaks_out(ctx, who, MAD_T_SCAN, C, min_score, k, best, best_t, peaks, n_peaks, n_found);
 }
 
 // ---------------------------------------------------------------------------
@@ -1314,53 +1329,22 @@ __global__ __launch_bounds__(SEARCH_RUN) void k_search_stats(const double *__res
     if (t < 3) out[(size_t)blockIdx.x * 3 + t] = s[t][0];
 }
 
-struct SearchScoreArgs {
-    int logN, mode, rot;         // rot: the rotation's index; rotation 0 initialises best / best_r
-    unsigned D1, D2;
-    size_t nD;
-    double scale, e_fill;        // 1 / N^3; the floor is e_fill n_w
-};
-
-// k_scan_score with n_w, G and S read from the rotation's record rec[3]: gbar, G' and the floor are formed here in the contract's
+// mad_map_search: n_w, G and S come from the rotation's record rec[3]; gbar, G' and the floor are formed here in the contract's
 // order.  A rotation with n_w = 0, G outside (0, 1.7e308] or (mode 1) G' <= 0 is skipped: it scores no offset, and *skipped is 1.
-__global__ __launch_bounds__(256) void k_search_score(const double2 *__restrict__ Zt, const double2 *__restrict__ Zq, const SearchScoreArgs A,
+__global__ __launch_bounds__(256) void k_search_score(const double2 *__restrict__ Zt, const double2 *__restrict__ Zq, const ScoreArgs A,
                                                       const double *__restrict__ rec, float *__restrict__ best, int *__restrict__ best_r,
                                                       int *__restrict__ skipped) {
-    const double n_w = rec[0], S = rec[2];
-    double G = rec[1], gbar = 0.0;
-    bool skip = !(n_w > 0.0) || !(G > 0.0 && G <= 1.7e308);
+    const double S = rec[2];
+    ScoreStat st = {rec[0], rec[1], 0.0};
+    bool skip = !(st.n_w > 0.0) || !(st.G > 0.0 && st.G <= 1.7e308);
     if (!skip && A.mode) {
-        gbar = S / n_w;
-        G = G - n_w * (gbar * gbar);
-        skip = !(G > 0.0);
+        st.gbar = S / st.n_w;
+        st.G = st.G - st.n_w * (st.gbar * st.gbar);
+        skip = !(st.G > 0.0);
     }
-    const double e_min = A.e_fill * n_w;
     if (blockIdx.x == 0 && threadIdx.x == 0) *skipped = skip ? 1 : 0;
-    if (skip && A.rot != 0) return;
-    for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < A.nD; i += (size_t)gridDim.x * 256) {
-        bool scored = false;
-        float s = 0.0f;
-        if (!skip) {
-            const unsigned q = (unsigned)i, t = q / A.D2, z = q - t * A.D2, x = t / A.D1, y = t - x * A.D1;
-            const size_t at = (((((size_t)x) << A.logN) + y) << A.logN) + z;
-            const double2 v = Zt[at];
-            double c = v.x * A.scale, e = -(v.y * A.scale);
-            if (A.mode) {
-                const double a = Zq[at].x * A.scale;
-                c = c - a * gbar;
-                e = e - (a * a) / n_w;
-            }
-            scored = e > e_min;
-            if (scored) s = (float)(c / sqrt(e * G));
-        }
-        if (A.rot == 0) {
-            best[i] = s;
-            best_r[i] = scored ? 0 : -1;
-        } else if (scored && (best_r[i] < 0 || s > best[i])) {
-            best[i] = s;
-            best_r[i] = A.rot;
-        }
-    }
+    if (skip && A.idx != 0) return;      // rotation 0 still initialises best / best_r
+    scan_score_box(Zt, Zq, A, st, A.floor * st.n_w, skip, best, best_r);
 }
 
 // k_search_rotate and the levels of k_search_stats of one rotation; the record ends in rec.  part_a holds n_runs records, part_b
@@ -1391,8 +1375,7 @@ static bool search_rotation_ok(const double *R) {
 
 // what mad_map_search and mad_map_rotate refuse about the base template, the cube and the mask
 static int search_check(mad_ctx *ctx, const char *who, const int32_t *d0, const double *c0, int32_t e, double iso) {
-    static const double zero[3] = {0.0, 0.0, 0.0};
-    MAD_TRY(fourier_check(ctx, who, d0, zero, 1.0));
+    MAD_TRY(fourier_check(ctx, who, d0, fourier_zero, 1.0));
     if (e < 1) return mad_fail(ctx, MAD_EINVAL, "%s: edge %d (1 or more)", who, e);
     for (int a = 0; a < 3; a++)
         if (!(fabs(c0[a]) <= 1.7e308)) return mad_fail(ctx, MAD_EINVAL, "%s: centre c0[%d] = %g is not finite", who, a, c0[a]);
@@ -1412,106 +1395,66 @@ static void search_rotate_args(SearchRotateArgs *A, const float *d_base, const i
     A->iso = iso;
 }
 
-static int map_search_run(mad_ctx *ctx, const float *map, const int32_t *d1, const float *base, const int32_t *d0, const double *c0, int32_t e,
-                          const double *rot, int32_t n_r, double iso, double e_fill, int32_t mode, double min_score, int64_t k, float *best,
-                          int32_t *best_r, double *peaks, int64_t *n_peaks, int64_t *n_found, int32_t *n_skipped, int32_t *N_out, ScanLattices *L) {
-    static const double zero[3] = {0.0, 0.0, 0.0};
+extern "C" int mad_map_search(mad_ctx *ctx, const float *map, const int32_t dims1[3], const float *base, const int32_t dims0[3], const double c0[3],
+                              int32_t edge, const double *rotations, int32_t n_r, double iso, double e_fill, int32_t mode, double min_score, int64_t k,
+                              float *best, int32_t *best_r, double *peaks, int64_t *n_peaks, int64_t *n_found, int32_t *n_skipped, int32_t *N_out) {
     const char *who = "mad_map_search";
+    if (ctx) mad_use_lane(ctx, 0);
+    if (!ctx || !dims1 || !dims0 || !c0 || (!best && !N_out) ||
+        (best && (!map || !base || !rotations || !best_r || !n_peaks || !n_found || !n_skipped || (k > 0 && !peaks))))
+        return ctx ? mad_fail(ctx, MAD_EINVAL, "%s: NULL argument", who) : MAD_EINVAL;
     if (n_r < 1) return mad_fail(ctx, MAD_EINVAL, "%s: %d rotations (1 or more)", who, n_r);
-    MAD_TRY(fourier_check(ctx, who, d1, zero, 1.0));
-    MAD_TRY(search_check(ctx, who, d0, c0, e, iso));
+    MAD_TRY(fourier_check(ctx, who, dims1, fourier_zero, 1.0));
+    MAD_TRY(search_check(ctx, who, dims0, c0, edge, iso));
     if (!(fabs(min_score) <= 1.7e308) || !(e_fill >= 0.0 && e_fill <= 1.7e308))
         return mad_fail(ctx, MAD_EINVAL, "%s: e_fill %g, min_score %g (finite, e_fill 0 or more)", who, e_fill, min_score);
-    if (mode != 0 && mode != 1) return mad_fail(ctx, MAD_EINVAL, "%s: mode %d (0 un-centred, 1 centred)", who, mode);
-    if (k < 0) return mad_fail(ctx, MAD_EINVAL, "%s: k = %lld (0 or more)", who, (long long)k);
-    int longest = 0;
-    for (int a = 0; a < 3; a++) longest = std::max(longest, (int)d1[a]);
-    if (longest > FFT_MAX_N) return mad_fail(ctx, MAD_EDOM, "%s: the map's longest axis is %d voxels, more than %d", who, longest, FFT_MAX_N);
-    for (int a = 0; a < 3; a++)
-        if (e > d1[a])
-            return mad_fail(ctx, MAD_EDOM, "%s: the cube is %d voxels long, the map %d on axis %d: no offset keeps it inside", who, e, d1[a], a);
-    int N = FFT_MIN_N, logN = 3;
-    while (N < longest) { N <<= 1; logN++; }
-    if (N_out) *N_out = N;
+    CorrPlan C;
+    const int32_t cube[3] = {edge, edge, edge};
+    MAD_TRY(corr_plan(ctx, who, "the cube is", dims1, cube, mode, k, N_out, &C));
     if (!best) return MAD_OK;      // the size query
     for (int32_t j = 0; j < n_r; j++)
-        if (!search_rotation_ok(rot + (size_t)9 * j))
+        if (!search_rotation_ok(rotations + (size_t)9 * j))
             return mad_fail(ctx, MAD_EINVAL, "%s: rotation %d is not finite or not orthonormal (max |R R^T - I| > 1e-6)", who, j);
-    const unsigned D[3] = {(unsigned)(d1[0] - e + 1), (unsigned)(d1[1] - e + 1), (unsigned)(d1[2] - e + 1)};
-    const size_t n1 = (size_t)d1[0] * d1[1] * d1[2], n0 = (size_t)d0[0] * d0[1] * d0[2], nD = (size_t)D[0] * D[1] * D[2];
+    const int N = C.N, logN = C.logN, e = edge;
+    const size_t n0 = (size_t)dims0[0] * dims0[1] * dims0[2];
 
+    // behind the output block: the rotations, their records and skip flags, and the partial sums of k_search_rotate / k_search_stats
     SearchRotateArgs RA;
-    search_rotate_args(&RA, nullptr, d0, c0, e, iso, logN);
-    const int n_lat = mode ? 3 : 2;
-    const size_t bytes_Z = (size_t)16 << (3 * logN);
+    search_rotate_args(&RA, nullptr, dims0, c0, e, iso, logN);
     const size_t n_pb = (RA.n_runs + SEARCH_RUN - 1) / SEARCH_RUN;
-    const size_t b_best = (nD * 4 + 15) & ~(size_t)15, b_rot = (size_t)n_r * 72, b_rec = (size_t)n_r * 24, b_skip = ((size_t)n_r * 4 + 15) & ~(size_t)15;
+    const size_t b_rot = (size_t)n_r * 72, b_rec = (size_t)n_r * 24, b_skip = ((size_t)n_r * 4 + 15) & ~(size_t)15;
     const size_t b_pa = (size_t)RA.n_runs * 24, b_pb = n_pb * 24;
-    const size_t b_out = 2 * b_best + 16 + b_rot + b_rec + b_skip + b_pa + b_pb, b_list = (size_t)SCAN_CAP0 * 4;
-    const size_t grow_g = mad_sb(ctx, S_TMP_G).cap >= b_out ? 0 : b_out + b_out / 4, grow_j = mad_sb(ctx, S_TMP_J).cap >= b_list ? 0 : b_list + b_list / 4;
-    MAD_TRY(fourier_room(ctx, who, N, logN, n1, n0, (size_t)(n_lat - 1) * bytes_Z + grow_g + grow_j));
-    MAD_TRY(fourier_twiddles(ctx, N));
-    MAD_TRY(mad_reserve(ctx, mad_sb(ctx, S_TMP_H), (n1 + 4) * 4));
-    MAD_TRY(mad_reserve(ctx, mad_sb(ctx, S_TMP_I), (n0 + 4) * 4));
-    MAD_TRY(mad_reserve(ctx, mad_sb(ctx, S_TMP_G), b_out));
-    MAD_TRY(mad_reserve(ctx, mad_sb(ctx, S_TMP_J), b_list));
-    for (int l = 0; l < n_lat; l++) MAD_TRY(fourier_alloc(ctx, who, N, logN, &L->Z[l]));
-    double2 *Zm = L->Z[0], *Zt = L->Z[1], *Zq = L->Z[2];
-    const double2 *tw = (const double2 *)ctx->fft_tw.p;
-    float *d_map = scratch<float>(ctx, S_TMP_H), *d_base = scratch<float>(ctx, S_TMP_I);
-    char *blk = scratch<char>(ctx, S_TMP_G);
-    float *d_best = (float *)blk;
-    int *d_best_r = (int *)(blk + b_best);
-    unsigned *d_count = (unsigned *)(blk + 2 * b_best);
-    double *d_rot = (double *)(blk + 2 * b_best + 16), *d_rec = (double *)((char *)d_rot + b_rot);
+    Lattices L(ctx);
+    MAD_TRY(corr_setup(ctx, who, map, dims1, n0, b_rot + b_rec + b_skip + b_pa + b_pb, &C, &L));
+    double2 *Zm = L.Z[0], *Zt = L.Z[1], *Zq = L.Z[2];
+    float *d_base = scratch<float>(ctx, S_TMP_I);
+    double *d_rot = (double *)C.tail(), *d_rec = (double *)(C.tail() + b_rot);
     int *d_skip = (int *)((char *)d_rec + b_rec);
     double *part_a = (double *)((char *)d_skip + b_skip), *part_b = (double *)((char *)part_a + b_pa);
-    const unsigned wg_Z = fourier_blocks(ctx, (size_t)1 << (3 * logN)), wg_D = fourier_blocks(ctx, nD);
-    const int threads = std::min(N, 256);
     const bool prune = ctx->search_prune != 0;
     RA.g0 = d_base;
 
-    // the map, the base grid and the rotations go up once
-    MAD_HIP(hipMemcpyAsync(d_map, map, n1 * 4, hipMemcpyHostToDevice, ctx->stream));
+    // the base grid and the rotations go up once, as the map has
     MAD_HIP(hipMemcpyAsync(d_base, base, n0 * 4, hipMemcpyHostToDevice, ctx->stream));
-    MAD_HIP(hipMemcpyAsync(d_rot, rot, b_rot, hipMemcpyHostToDevice, ctx->stream));
-    mad_timer_begin(ctx, MAD_T_SCAN);
-    hipLaunchKernelGGL(k_scan_pack<false>, dim3(wg_Z), dim3(256), 0, ctx->stream, (const float *)d_map, (unsigned)d1[0], (unsigned)d1[1], (unsigned)d1[2],
-                       0.0, logN, Zm);
-    mad_timer_end(ctx, MAD_T_SCAN);
-    mad_timer_begin(ctx, MAD_T_FFT);
-    int rc = fourier_passes(ctx, Zm, logN);
-    mad_timer_end(ctx, MAD_T_FFT);
-    if (rc != MAD_OK) return rc;
-    MAD_HIP(hipGetLastError());
+    MAD_HIP(hipMemcpyAsync(d_rot, rotations, b_rot, hipMemcpyHostToDevice, ctx->stream));
 
-    SearchScoreArgs SA;
-    memset(&SA, 0, sizeof(SA));
-    SA.logN = logN; SA.mode = mode; SA.D1 = D[1]; SA.D2 = D[2]; SA.nD = nD; SA.scale = ldexp(1.0, -3 * logN); SA.e_fill = e_fill;
-    // tiles of 8 that cover the cube's lines (forward) and the offsets' (inverse)
-    const int nt = N / FFT_L, te = (e + FFT_L - 1) / FFT_L, tD2 = ((int)D[2] + FFT_L - 1) / FFT_L;
+    ScoreArgs SA = corr_score_args(C, mode, e_fill);
+    // tiles of 8 that cover the cube's lines (forward: only the cube is not zero) and the offsets' (inverse: only the box is read)
+    const int nt = N / FFT_L, te = (e + FFT_L - 1) / FFT_L, tD2 = ((int)C.D[2] + FFT_L - 1) / FFT_L;
+    const PrunedPass fwd[3] = {{te, e, e}, {nt, e, e}, {nt, N, e}}, inv[3] = {{nt, N, N}, {tD2, N, N}, {tD2, (int)C.D[1], N}};
+    int rc = MAD_OK;
     mad_timer_begin(ctx, MAD_T_SEARCH);      // one interval around every rotation: no event, and so no wait, per rotation
     for (int32_t j = 0; j < n_r && rc == MAD_OK; j++) {
         double *rec = d_rec + (size_t)3 * j;
-        search_rotate_launch(ctx, RA, d_rot + (size_t)9 * j, Zt, nullptr, part_a, part_b, rec, prune ? 0u : wg_Z);
-        if (prune) {      // forward: only the cube is not zero
-            rc = fft_axis_pruned<2>(ctx, Zt, tw, logN, te, e, e);
-            if (rc == MAD_OK) rc = fft_axis_pruned<1>(ctx, Zt, tw, logN, nt, e, e);
-            if (rc == MAD_OK) rc = fft_axis_pruned<0>(ctx, Zt, tw, logN, nt, N, e);
-        } else rc = fourier_passes(ctx, Zt, logN);
+        search_rotate_launch(ctx, RA, d_rot + (size_t)9 * j, Zt, nullptr, part_a, part_b, rec, prune ? 0u : C.wg_Z);
+        rc = fourier_passes(ctx, Zt, logN, prune ? fwd : nullptr);
         if (rc != MAD_OK) break;
-        hipLaunchKernelGGL(k_scan_product, dim3((unsigned)N, (unsigned)(N / 2 + 1)), dim3(threads), 0, ctx->stream, (const double2 *)Zm, Zt, Zq, logN);
-        for (int l = 1; l < n_lat && rc == MAD_OK; l++) {
-            if (prune) {      // inverse: only the box of offsets is read
-                rc = fft_axis_pruned<2>(ctx, L->Z[l], tw, logN, nt, N, N);
-                if (rc == MAD_OK) rc = fft_axis_pruned<1>(ctx, L->Z[l], tw, logN, tD2, N, N);
-                if (rc == MAD_OK) rc = fft_axis_pruned<0>(ctx, L->Z[l], tw, logN, tD2, (int)D[1], N);
-            } else rc = fourier_passes(ctx, L->Z[l], logN);
-        }
+        hipLaunchKernelGGL(k_scan_product, dim3((unsigned)N, (unsigned)(N / 2 + 1)), dim3(C.threads), 0, ctx->stream, (const double2 *)Zm, Zt, Zq, logN);
+        for (int l = 1; l < C.n_lat && rc == MAD_OK; l++) rc = fourier_passes(ctx, L.Z[l], logN, prune ? inv : nullptr);
         if (rc != MAD_OK) break;
-        SA.rot = j;
-        hipLaunchKernelGGL(k_search_score, dim3(wg_D), dim3(256), 0, ctx->stream, (const double2 *)Zt, (const double2 *)Zq, SA, (const double *)rec,
-                           d_best, d_best_r, d_skip + j);
+        SA.idx = j;
+        hipLaunchKernelGGL(k_search_score, dim3(C.wg_D), dim3(256), 0, ctx->stream, (const double2 *)Zt, (const double2 *)Zq, SA, (const double *)rec,
+                           C.best(), C.best_i(), d_skip + j);
     }
     mad_timer_end(ctx, MAD_T_SEARCH);
     if (rc != MAD_OK) return rc;
@@ -1521,23 +1464,9 @@ static int map_search_run(mad_ctx *ctx, const float *map, const int32_t *d1, con
     MAD_HIP(hipStreamSynchronize(ctx->stream));      // the one synchronisation before the peak search
     int32_t skipped = 0;
     for (int32_t j = 0; j < n_r; j++) skipped += h_skip[(size_t)j] != 0;
-    MAD_TRY(scan_peaks_out(ctx, who, MAD_T_SEARCH, d_best, d_best_r, d_count, D, nD, min_score, k, best, best_r, peaks, n_peaks, n_found));
+    MAD_TRY(scan_peaks_out(ctx, who, MAD_T_SEARCH, C, min_score, k, best, best_r, peaks, n_peaks, n_found));
     *n_skipped = skipped;
     return MAD_OK;
-}
-
-extern "C" int mad_map_search(mad_ctx *ctx, const float *map, const int32_t dims1[3], const float *base, const int32_t dims0[3], const double c0[3],
-                              int32_t edge, const double *rotations, int32_t n_r, double iso, double e_fill, int32_t mode, double min_score, int64_t k,
-                              float *best, int32_t *best_r, double *peaks, int64_t *n_peaks, int64_t *n_found, int32_t *n_skipped, int32_t *N_out) {
-    if (ctx) mad_use_lane(ctx, 0);
-    if (!ctx || !dims1 || !dims0 || !c0 || (!best && !N_out) ||
-        (best && (!map || !base || !rotations || !best_r || !n_peaks || !n_found || !n_skipped || (k > 0 && !peaks))))
-        return ctx ? mad_fail(ctx, MAD_EINVAL, "mad_map_search: NULL argument") : MAD_EINVAL;
-    ScanLattices L;
-    int rc = map_search_run(ctx, map, dims1, base, dims0, c0, edge, rotations, n_r, iso, e_fill, mode, min_score, k, best, best_r, peaks, n_peaks,
-                            n_found, n_skipped, N_out, &L);
-    for (int l = 0; l < 3; l++) rc = fourier_free(ctx, L.Z[l], rc);
-    return rc;
 }
 
 extern "C" int mad_map_rotate(mad_ctx *ctx, const float *base, const int32_t dims0[3], const double c0[3], int32_t edge, const double R[9], double iso,

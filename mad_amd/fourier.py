@@ -351,31 +351,27 @@ def peaks_numpy(best, best_t, min_score, k):
     return out, int(ok.sum())
 
 
-class Scan(object):
-    """What `Dmap.scan` returns.  `best` float32 [D]: the best score over the rotations at every whole-voxel offset; `best_t` int32
-    [D]: the rotation that attains it, -1 where none was scored; `peaks`: float64 [n, 5] = ux, uy, uz, score, rotation, the best
-    first; `n_found`: how many peaks there are (`peaks` holds the first k).  `origin`, `voxsp`: where offset (0, 0, 0) puts the
-    template's voxel (0, 0, 0), i.e. the map's origin and spacing.  `rotations` [n, 3, 3], `centroid` and `template_origins` [n, 3]
-    (the grid origin of every rotated copy's box before it is moved) turn a peak into a placement: a point x of the structure goes to
-    (x - centroid) @ R + centroid + T, T = origin + u voxsp - template_origins[rotation]."""
+class _Peaks(object):
+    """What `Scan` and `Search` share: `peaks` float64 [n, 5] = ux, uy, uz, score, rotation, the best first; `n_found`: how many
+    peaks there are (`peaks` holds the first k); `origin`, `voxsp`: the map's; `rotations` [n, 3, 3] and `centroid`: a point x of the
+    structure goes to (x - centroid) @ R + centroid + T at a peak.  A subclass says what T is (`_shift`) and where its score volume
+    `best` has its origin (`_write_origin`)."""
 
-    def __init__(self, best, best_t, peaks, n_found, origin, voxsp, rotations, centroid, template_origins, N=0, e_min=0.0, mode=0):
-        self.best, self.best_t = best, best_t
+    def __init__(self, best, peaks, n_found, origin, voxsp, rotations, centroid, N, mode):
+        self.best = best
         self.peaks = np.asarray(peaks, np.float64).reshape(-1, 5)
         self.n_found = int(n_found)
         self.origin = np.asarray(origin, np.float64).reshape(3)
         self.voxsp = float(voxsp)
         self.rotations = np.asarray(rotations, np.float64).reshape(-1, 3, 3)
         self.centroid = np.asarray(centroid, np.float64).reshape(3)
-        self.template_origins = np.asarray(template_origins, np.float64).reshape(-1, 3)
-        self.N, self.e_min, self.mode = int(N), float(e_min), int(mode)
+        self.N, self.mode = int(N), int(mode)
 
     def pose(self, i):
         """-> (rotation index, R [3, 3], T [3], score) of peak i."""
         ux, uy, uz, score, j = self.peaks[i]
         j = int(j)
-        T = self.origin + np.array([ux, uy, uz]) * self.voxsp - self.template_origins[j]
-        return j, self.rotations[j], T, float(score)
+        return j, self.rotations[j], self._shift(np.array([ux, uy, uz]), j), float(score)
 
     def place(self, i, pdb):
         """The structure at peak i: a copy of `pdb` (a `PDB`: a new `PDB` with the coordinates moved; an (n, 3) array: a new array)."""
@@ -396,10 +392,30 @@ class Scan(object):
                 f.write("%d,%d,%d,%d,%.9g,%d,%.6f,%.6f,%.6f\n" % ((i,) + tuple(int(v) for v in self.peaks[i][:3]) + (score, j) + tuple(T)))
 
     def write(self, outname):
-        """The score volume as a map whose origin is the map's origin (.sit / .situs: Situs, anything else MRC): the value at a voxel
-        is the best score of the template whose voxel (0, 0, 0) is placed there."""
+        """The score volume as a map (.sit / .situs: Situs, anything else MRC)."""
         from . import mapio
-        mapio.write_volume(outname, np.ascontiguousarray(self.best, np.float32), tuple(self.origin), self.voxsp)
+        mapio.write_volume(outname, np.ascontiguousarray(self.best, np.float32), tuple(self._write_origin()), self.voxsp)
+
+
+class Scan(_Peaks):
+    """What `Dmap.scan` returns.  `best` float32 [D]: the best score over the rotations at every whole-voxel offset; `best_t` int32
+    [D]: the rotation that attains it, -1 where none was scored; `peaks`: float64 [n, 5] = ux, uy, uz, score, rotation, the best
+    first; `n_found`: how many peaks there are (`peaks` holds the first k).  `origin`, `voxsp`: where offset (0, 0, 0) puts the
+    template's voxel (0, 0, 0), i.e. the map's origin and spacing.  `rotations` [n, 3, 3], `centroid` and `template_origins` [n, 3]
+    (the grid origin of every rotated copy's box before it is moved) turn a peak into a placement: a point x of the structure goes to
+    (x - centroid) @ R + centroid + T, T = origin + u voxsp - template_origins[rotation].  `write(outname)`: the score volume as a
+    map whose origin is the map's origin: the value at a voxel is the best score of the template whose voxel (0, 0, 0) is placed there."""
+
+    def __init__(self, best, best_t, peaks, n_found, origin, voxsp, rotations, centroid, template_origins, N=0, e_min=0.0, mode=0):
+        _Peaks.__init__(self, best, peaks, n_found, origin, voxsp, rotations, centroid, N, mode)
+        self.best_t, self.e_min = best_t, float(e_min)
+        self.template_origins = np.asarray(template_origins, np.float64).reshape(-1, 3)
+
+    def _shift(self, u, j):
+        return self.origin + u * self.voxsp - self.template_origins[j]
+
+    def _write_origin(self):
+        return self.origin
 
 
 # ---------------------------------------------------------------------------
@@ -575,57 +591,25 @@ def search_edge(g0, c0, iso):
     return e if e % 2 else e + 1
 
 
-class Search(object):
+class Search(_Peaks):
     """What `Dmap.search` returns.  `best` float32 [D]: the best score over the rotations at every whole-voxel offset; `best_r` int32
     [D]: the rotation that attains it, -1 where none was scored; `peaks`: float64 [n, 5] = ux, uy, uz, score, rotation, the best
     first; `n_found`: how many peaks there are (`peaks` holds the first k); `n_skipped`: rotations whose mask was empty (or, centred,
     flat).  `rotations` [n, 3, 3], `centroid`, `origin`, `voxsp` and `edge` turn a peak into a placement: at offset u the centre of the
     cube, voxel c2 = (edge - 1) / 2, carries the centroid, so a point x of the structure goes to (x - centroid) @ R + centroid + T,
-    T = origin + (u + c2) voxsp - centroid.  Peaks are whole-voxel and no finer in angle than the set's spacing."""
+    T = origin + (u + c2) voxsp - centroid.  Peaks are whole-voxel and no finer in angle than the set's spacing.  `write(outname)`:
+    the score volume as a map whose origin is the map's origin + c2 voxsp: the value at a point is the best score of the structure
+    with its centroid there."""
 
     def __init__(self, best, best_r, peaks, n_found, n_skipped, origin, voxsp, rotations, centroid, edge, N=0, e_fill=0.0, mode=0):
-        self.best, self.best_r = best, best_r
-        self.peaks = np.asarray(peaks, np.float64).reshape(-1, 5)
-        self.n_found, self.n_skipped = int(n_found), int(n_skipped)
-        self.origin = np.asarray(origin, np.float64).reshape(3)
-        self.voxsp = float(voxsp)
-        self.rotations = np.asarray(rotations, np.float64).reshape(-1, 3, 3)
-        self.centroid = np.asarray(centroid, np.float64).reshape(3)
-        self.edge = int(edge)
-        self.N, self.e_fill, self.mode = int(N), float(e_fill), int(mode)
+        _Peaks.__init__(self, best, peaks, n_found, origin, voxsp, rotations, centroid, N, mode)
+        self.best_r, self.n_skipped, self.edge, self.e_fill = best_r, int(n_skipped), int(edge), float(e_fill)
 
-    def pose(self, i):
-        """-> (rotation index, R [3, 3], T [3], score) of peak i."""
-        ux, uy, uz, score, j = self.peaks[i]
-        j = int(j)
-        c2 = (self.edge - 1.0) / 2.0
-        T = self.origin + (np.array([ux, uy, uz]) + c2) * self.voxsp - self.centroid
-        return j, self.rotations[j], T, float(score)
+    def _shift(self, u, j):
+        return self.origin + (u + (self.edge - 1.0) / 2.0) * self.voxsp - self.centroid
 
-    def place(self, i, pdb):
-        """The structure at peak i: a copy of `pdb` (a `PDB`: a new `PDB` with the coordinates moved; an (n, 3) array: a new array)."""
-        _, R, T, _ = self.pose(i)
-        if hasattr(pdb, "get_coords"):
-            import copy
-            out = copy.deepcopy(pdb)
-            out.set_coords((np.asarray(pdb.get_coords(), np.float64) - self.centroid) @ R + self.centroid + T)
-            return out
-        return (np.asarray(pdb, np.float64) - self.centroid) @ R + self.centroid + T
-
-    def write_peaks(self, path):
-        """Columns rank, ux, uy, uz (voxels), score, rotation, tx, ty, tz (Angstrom)."""
-        with open(path, "w") as f:
-            f.write("rank,ux,uy,uz,score,rotation,tx,ty,tz\n")
-            for i in range(len(self.peaks)):
-                j, _, T, score = self.pose(i)
-                f.write("%d,%d,%d,%d,%.9g,%d,%.6f,%.6f,%.6f\n" % ((i,) + tuple(int(v) for v in self.peaks[i][:3]) + (score, j) + tuple(T)))
-
-    def write(self, outname):
-        """The score volume as a map (.sit / .situs: Situs, anything else MRC) whose origin is the map's origin + c2 voxsp: the value
-        at a point is the best score of the structure with its centroid there."""
-        from . import mapio
-        o = self.origin + (self.edge - 1.0) / 2.0 * self.voxsp
-        mapio.write_volume(outname, np.ascontiguousarray(self.best, np.float32), tuple(o), self.voxsp)
+    def _write_origin(self):
+        return self.origin + (self.edge - 1.0) / 2.0 * self.voxsp
 
 
 # ---------------------------------------------------------------------------
