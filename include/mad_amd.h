@@ -594,6 +594,37 @@ int mad_map_segment(mad_ctx *ctx, const float *grid, const int32_t dims[3], doub
                     int64_t *n_regions, int64_t *history, int32_t *steps_done);
 
 /*
+ * The connected components of a map above a threshold, and the map with its small components ("dust") replaced by a fill value
+ * (mad_components.hip; mad_amd/components.py::components_numpy / dust_numpy restate the contract).  Host
+ * pointers, synchronous.  Both work in voxels: grid is float32 [x][y][z] with dims, read only, the linear index of a voxel is
+ * L = (x * ny + y) * nz + z as in mad_map_segment, neither origin nor spacing enters.
+ *   Foreground.  A voxel is foreground iff (double)v > threshold (strict, as mad_map_segment and mad_map_envelope; threshold = -inf is
+ *     allowed: every voxel).
+ *   Neighbours.  connectivity 6, 18 or 26: the offsets in {-1, 0, 1}^3 with 1, at most 2, or at most 3 components that are not 0.  Only
+ *     neighbours inside the grid count: no wrap-around.
+ *   Components.  A component is a class of the transitive closure of "foreground voxels that are neighbours".  Its root is its member
+ *     with the smallest L.  The components are numbered 1 .. n by ascending root; a background voxel has label 0.
+ * mad_map_components writes labels (int32 [x][y][z]), per component c (0-based, component c + 1) root[c] int64 = L of its root and
+ * size[c] int64 = its voxels -- either table may be NULL --, and *n_components = n.  cap = entries each table holds: with n > cap the
+ * call returns MAD_ENOSPC with *n_components = n (the capacity needed), the tables untouched and labels as valid as otherwise.
+ * mad_map_dust ranks the components by size descending, root ascending (a strict order); a component is kept iff size >= min_size and
+ * (keep == 0 or its rank, from 0, is < keep).  out (float32 [x][y][z]; may be grid): a background voxel keeps its bits, a voxel of a
+ * kept component keeps its bits, a foreground voxel of a component that is not kept becomes fill.  counts (may be NULL) = {components,
+ * kept components, foreground voxels, kept voxels}.
+ * The same call gives the same bits alone or after any other call (labels by comparisons and integer atomics whose order cannot
+ * show; ids by a scan; sizes are integer sums).
+ * MAD_EINVAL, nothing launched or written: NULL (other than a table or counts), a dimension < 1, 2^31 voxels or more, a NaN threshold,
+ * a connectivity other than 6, 18 or 26, cap < 0, min_size < 1, keep < 0, fill not finite or (double)fill > threshold (a fill above
+ * the threshold would turn dust back into foreground).
+ * MAD_EDOM, nothing written: a voxel that is not finite (found by the first pass over the map on the device).
+ */
+int mad_map_components(mad_ctx *ctx, const float *grid, const int32_t dims[3], double threshold, int32_t connectivity,
+                       int32_t *labels, int64_t *root /* may be NULL */, int64_t *size /* may be NULL */,
+                       int64_t cap, int64_t *n_components);
+int mad_map_dust(mad_ctx *ctx, const float *grid, const int32_t dims[3], double threshold, int32_t connectivity,
+                 int64_t min_size, int64_t keep, float fill, float *out /* may be grid */, int64_t counts[4] /* may be NULL */);
+
+/*
  * Fourier shell correlation of two maps, and the 3-D transform under it (mad_fourier.hip; restated with numpy
  * in mad_amd/fourier.py).  Host pointers, synchronous, nothing modified but the outputs.  grid1, grid2: float32 [x][y][z] with
  * their dims and origins (Angstrom, centre of voxel (0,0,0)) and the common spacing voxsp.

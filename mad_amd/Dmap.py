@@ -21,6 +21,9 @@ the map by such a measurement, every voxel under the Gaussian of its own resolut
 `envelope` makes a soft mask from the map itself (threshold, grow, raised-cosine edge) through `mad_map_envelope`, `apply_mask`
 multiplies a map by one through `mad_map_multiply`, and `fsc(mask=...)` is the masked curve corrected for the mask by phase
 randomisation through `mad_map_fsc_masked` (envelope.py, fourier.py; no counterpart in the reference).
+`components` labels the connected components of the voxels above a threshold through `mad_map_components`, `remove_dust` replaces
+the small ones through `mad_map_dust`, and `envelope(min_size=..., keep=...)` seeds the mask from the components that are kept
+(components.py; no counterpart in the reference).
 None of them has a CPU fallback.  The reference's per-voxel text writer is replaced by `mapio.write_situs`.
 """
 import os
@@ -189,15 +192,17 @@ class Dmap(object):
             self.grid3d = g
         return _lib.get_lib().map_zone(g, (self.xi, self.yi, self.zi), self.voxsp, atoms, radius, soft, erase)
 
-    def envelope(self, threshold, extend=3.0, soft=6.0):
+    def envelope(self, threshold, extend=3.0, soft=6.0, min_size=1, keep=0, connectivity=26):
         """A soft mask made from this map itself, as a new `Dmap` with the same dims, origin and spacing (`self` is untouched):
         1 on every voxel within `extend` Angstrom of a voxel above `threshold`, a raised-cosine edge over the next `soft`
         Angstrom, 0 beyond, through `mad_map_envelope`.  The result carries `n_seeds` (voxels above the threshold), `n_core` (weight
         1, seeds included) and `n_edge` (voxels in the edge).  `apply_mask` multiplies a map by it.  A binary mask such as
         `Segmentation.mask(ids)` gets a soft edge the same way: put it into a `Dmap` and call `envelope(0.5, ...)`.  Dust -- stray
-        voxels above the threshold far from the particle -- grows an envelope of its own: remove it beforehand with `lowpass`, or
-        by choosing segments; connected components are not looked for here.  The distances are exact Euclidean ones in whole
-        voxels; (extend + soft) / voxsp has to stay below 255 voxels.  DESIGN.md section 4r has the exact contract."""
+        voxels above the threshold far from the particle -- grows an envelope of its own: `min_size` (voxels) and `keep` (the
+        largest so many; 0: all) leave it out, as `remove_dust` ranks and keeps the components under `connectivity`.  Then the seeds
+        are the voxels of the kept components only, `n_seeds` counts those, and the result also carries `n_components` and `n_kept`.
+        With the defaults no component is looked for.  The distances are exact Euclidean ones in whole voxels; (extend + soft) /
+        voxsp has to stay below 255 voxels.  DESIGN.md sections 4r and 4t have the exact contract."""
         threshold, extend, soft = float(threshold), float(extend), float(soft)
         if threshold != threshold:
             raise ValueError("Dmap.envelope: the threshold is not a number")
@@ -206,7 +211,11 @@ class Dmap(object):
         g = np.ascontiguousarray(self.grid3d, dtype=np.float32)
         if g.ndim != 3 or g.size == 0:
             raise ValueError("Dmap.envelope: the grid has shape %r" % (g.shape,))
+        if int(min_size) != min_size or min_size < 1 or int(keep) != keep or keep < 0:
+            raise ValueError("Dmap.envelope: min_size %r, keep %r (whole numbers; 1 or more, 0 or more)" % (min_size, keep))
         out = Dmap.__new__(Dmap)
+        if int(min_size) > 1 or int(keep) > 0:
+            g, (out.n_components, out.n_kept, _, _) = _lib.get_lib().map_dust(g, threshold, connectivity, int(min_size), int(keep))
         out.grid3d, _, (out.n_seeds, out.n_core, out.n_edge) = _lib.get_lib().map_envelope(g, float(self.voxsp), threshold, extend, soft)
         out.voxsp = self.voxsp
         out.xi, out.yi, out.zi = self.xi, self.yi, self.zi
@@ -611,6 +620,45 @@ class Dmap(object):
         r = _lib.get_lib().map_segment(g, threshold, int(steps), step_f, int(stop_at))
         return Segmentation(r["labels"], (self.xi, self.yi, self.zi), self.voxsp,
                             dict((k, r[k]) for k in ("root", "peak", "size", "group")), r["history"], r["n_regions"])
+
+    def components(self, threshold, connectivity=26):
+        """The connected components of the voxels above `threshold` -> `components.Components` (`labels`, `root`, `size`, `n`,
+        `order()`, `largest(k)`, `mask(ids)`, `write(outname)`); the map is untouched.  Two voxels above the threshold belong together
+        where a chain of neighbours above it joins them; `connectivity` 6, 18 or 26 says which of the 26 voxels around one are its
+        neighbours (faces; faces and edges; all).  The box does not wrap around.  Where `segment` splits a body at every saddle, this
+        says what hangs together.  DESIGN.md section 4t has the exact contract."""
+        threshold = float(threshold)
+        if threshold != threshold:
+            raise ValueError("Dmap.components: the threshold is not a number")
+        g = np.ascontiguousarray(self.grid3d, dtype=np.float32)
+        if g.ndim != 3 or g.size == 0:
+            raise ValueError("Dmap.components: the grid has shape %r" % (g.shape,))
+        from .components import Components
+        r = _lib.get_lib().map_components(g, threshold, connectivity)
+        return Components(r["labels"], (self.xi, self.yi, self.zi), self.voxsp, r["root"], r["size"])
+
+    def remove_dust(self, threshold, min_size=1, keep=0, connectivity=26, fill=None):
+        """Hide the dust, in place: of the connected components of the voxels above `threshold` (`components`), ranked by size
+        descending (equal sizes: the one that begins first in the file's order), those of `min_size` voxels or more are kept, and with
+        `keep` > 0 only the first `keep` of the ranking; every voxel above the threshold of any other component becomes `fill`, every
+        other voxel keeps its bits.  `fill=None`: 0.0 for a threshold of 0 or more, else the largest float32 not above the threshold
+        (a fill above the threshold would be foreground again and is refused).  A size in cubic Angstrom is `min_size` times
+        voxsp^3.  Returns (components, kept components, voxels above the threshold, kept voxels)."""
+        threshold = float(threshold)
+        if threshold != threshold:
+            raise ValueError("Dmap.remove_dust: the threshold is not a number")
+        if int(min_size) != min_size or min_size < 1 or int(keep) != keep or keep < 0:
+            raise ValueError("Dmap.remove_dust: min_size %r, keep %r (whole numbers; 1 or more, 0 or more)" % (min_size, keep))
+        g = self.grid3d
+        if g.ndim != 3 or g.size == 0:
+            raise ValueError("Dmap.remove_dust: the grid has shape %r" % (g.shape,))
+        if g.dtype != np.float32 or not g.flags.c_contiguous or not g.flags.writeable:
+            g = np.ascontiguousarray(g, dtype=np.float32)
+            if not g.flags.writeable or g is self.grid3d:
+                g = g.copy()
+        _, counts = _lib.get_lib().map_dust(g, threshold, connectivity, int(min_size), int(keep), fill, out=g)
+        self.grid3d = g
+        return counts
 
     def write_to_mrc(self, outname):
         mapio.write_mrc(outname, self.grid3d, (self.xi, self.yi, self.zi), self.voxsp)

@@ -39,7 +39,7 @@ SYMBOLS = [
     "mad_dist_unique_id", "mad_dist_init", "mad_dist_destroy", "mad_dist_info", "mad_dist_rehearse_flags", "mad_dist_or_allreduce", "mad_dist_allgather",
     "mad_dist_allgather_topk", "mad_dist_scratch", "mad_dist_copy",
     "mad_set_wire_bytes", "mad_set_export", "mad_set_import", "mad_set_lane", "mad_set_stream", "mad_set_bind_lane",
-    "mad_upload_density", "mad_refine", "mad_last_refine_plan", "mad_last_density_chunks", "mad_structure_to_density", "mad_ccc", "mad_map_mask", "mad_map_multiply", "mad_map_ccc", "mad_map_resample", "mad_map_zone", "mad_map_envelope", "mad_map_group_fit", "mad_map_smooth", "mad_map_segment", "mad_map_fsc", "mad_map_fsc_masked", "mad_map_phase_randomize", "mad_map_fft", "mad_map_filter", "mad_map_ifft", "mad_map_scan", "mad_map_search", "mad_map_rotate", "mad_map_local_fsc", "mad_map_local_filter", "mad_density_ccc", "mad_dock_refine_score", "mad_grid_overlap", "mad_overlap_matrix",
+    "mad_upload_density", "mad_refine", "mad_last_refine_plan", "mad_last_density_chunks", "mad_structure_to_density", "mad_ccc", "mad_map_mask", "mad_map_multiply", "mad_map_ccc", "mad_map_resample", "mad_map_zone", "mad_map_envelope", "mad_map_group_fit", "mad_map_smooth", "mad_map_segment", "mad_map_components", "mad_map_dust", "mad_map_fsc", "mad_map_fsc_masked", "mad_map_phase_randomize", "mad_map_fft", "mad_map_filter", "mad_map_ifft", "mad_map_scan", "mad_map_search", "mad_map_rotate", "mad_map_local_fsc", "mad_map_local_filter", "mad_density_ccc", "mad_dock_refine_score", "mad_grid_overlap", "mad_overlap_matrix",
     "mad_space_create", "mad_space_destroy", "mad_space_build", "mad_space_info", "mad_space_download",
     "mad_space_peaks", "mad_space_patches", "mad_space_localize", "mad_localize_volume",
     "mad_pose_cluster_many",
@@ -1534,6 +1534,69 @@ class Lib(object):
         for k, name in enumerate(("root", "peak", "size", "group")):
             out[name] = None if tabs is None else tabs[k][:n].copy()
         return out
+
+    def map_components(self, g, threshold, connectivity=26, cap=None):
+        """The connected components of the voxels of `g` (C-contiguous float32 [x, y, z], not modified) above `threshold` (strict),
+        neighbours by `connectivity` 6, 18 or 26, no wrap-around (mad_map_components).  -> dict: `labels` int32
+        (the component of every voxel, 1 .. n by ascending smallest linear index, 0 for background), per component `root` (int64, that
+        index) and `size` (int64, its voxels), and `n`.  `cap`: the capacity of the two tables; by default it grows until they fit,
+        with a given one that is too small they come back as None and `n` says what is needed."""
+        if g.dtype != np.float32 or not g.flags.c_contiguous:
+            raise ValueError("map_components needs a C-contiguous float32 grid")
+        if g.ndim != 3:
+            raise ValueError("map_components needs a 3-D grid")
+        conn = int(connectivity)
+        if conn != connectivity or not -2 ** 31 <= conn < 2 ** 31:
+            raise ValueError("map_components: connectivity %r" % (connectivity,))
+        d = np.array(g.shape, np.int32)
+        labels = np.zeros(g.shape, np.int32)
+        try_cap = int(cap) if cap is not None else max(1, min(g.size, self.SEGMENT_CAP0))
+        while True:
+            tabs = (np.zeros(max(try_cap, 0), np.int64), np.zeros(max(try_cap, 0), np.int64))
+            n = C.c_int64(0)
+            rc = self.dll.mad_map_components(self.ctx, _p(g), _p(d), C.c_double(threshold), C.c_int32(conn), _p(labels), _p(tabs[0]),
+                                             _p(tabs[1]), C.c_int64(try_cap), C.byref(n))
+            if rc == -28 and n.value > try_cap:      # MAD_ENOSPC: n holds the capacity needed; labels are valid
+                if cap is not None:
+                    tabs = None
+                    break
+                try_cap = n.value
+                continue
+            self._chk(rc)
+            break
+        n = int(n.value)
+        return dict(labels=labels, n=n, root=None if tabs is None else tabs[0][:n].copy(), size=None if tabs is None else tabs[1][:n].copy())
+
+    def map_dust(self, g, threshold, connectivity=26, min_size=1, keep=0, fill=None, out=None):
+        """`g` (C-contiguous float32 [x, y, z]) without its dust: the components of `map_components` are ranked by size descending,
+        root ascending, one is kept where its size is `min_size` or more and (`keep` == 0 or its rank < `keep`), and every foreground
+        voxel of one that is not kept becomes `fill` (None: 0.0 for a threshold of 0 or more, else the largest float32 not above the
+        threshold); every other voxel keeps its bits (mad_map_dust).  -> (out float32, (components, kept
+        components, foreground voxels, kept voxels)).  `out`: a float32 array to take the result instead of a new one; it may be `g`,
+        and stays as it is when the call is refused."""
+        from .components import default_fill
+        if g.dtype != np.float32 or not g.flags.c_contiguous:
+            raise ValueError("map_dust needs a C-contiguous float32 grid")
+        if g.ndim != 3:
+            raise ValueError("map_dust needs a 3-D grid")
+        ints = []
+        for name, v in (("connectivity", connectivity), ("min_size", min_size), ("keep", keep)):
+            i = int(v)
+            if i != v or not -2 ** 31 <= i < 2 ** 63:
+                raise ValueError("map_dust: %s %r" % (name, v))
+            ints.append(i)
+        if not -2 ** 31 <= ints[0] < 2 ** 31:
+            raise ValueError("map_dust: connectivity %r" % (connectivity,))
+        if out is None:
+            out = np.empty(g.shape, np.float32)
+        elif out.dtype != np.float32 or out.shape != g.shape or not out.flags.c_contiguous or not out.flags.writeable:
+            raise ValueError("map_dust: out must be a writable C-contiguous float32 array of the grid's shape")
+        fill = default_fill(threshold) if fill is None else np.float32(fill)
+        d = np.array(g.shape, np.int32)
+        counts = np.zeros(4, np.int64)
+        self._chk(self.dll.mad_map_dust(self.ctx, _p(g), _p(d), C.c_double(threshold), C.c_int32(ints[0]), C.c_int64(ints[1]),
+                                        C.c_int64(ints[2]), C.c_float(float(fill)), _p(out), _p(counts)))
+        return out, tuple(int(v) for v in counts)
 
 
 _default = None

@@ -20,21 +20,17 @@
 #include <vector>
 
 #include "mad_common.h"
+#include "mad_segment_scan.h"      // SG_THREADS, and the jumping and numbering kernels with their constants
 
-#define SG_THREADS 256
 #define SG_TX 8                  // a workgroup's tile: 8 x 8 x 64 voxels, a wavefront per z row of 64 (lanes along z: loads coalesce)
 #define SG_TY 8
 #define SG_TZ 64
 #define SG_HX (SG_TX + 2)
 #define SG_HY (SG_TY + 2)
 #define SG_HZ (SG_TZ + 2)
-#define SG_JUMP_HOPS 4           // pointers one lane follows per pass of k_seg_jump
-#define SG_SCAN_PER 2048         // voxels of one workgroup of k_seg_count / k_seg_assign (8 rounds of SG_THREADS)
-#define SG_SCAN_THREADS 1024     // k_seg_scan_blocks
 #define SG_MAX_R (1 << 20)       // taps of one side at most (sigma up to 2^18 voxels)
 static_assert(SG_TZ == MAD_WAVE, "a wavefront per z row of the tile");
 static_assert(SG_HX * SG_HY * SG_HZ * 4 < 30 * 1024, "the staged tile leaves room for two workgroups and more per CU");
-static_assert(SG_SCAN_PER % SG_THREADS == 0, "whole rounds");
 
 struct SegDims {
     int n[3];
@@ -123,77 +119,7 @@ __global__ __launch_bounds__(SG_THREADS) void k_seg_parent(const float *__restri
     }
 }
 
-// One pass: p[i] moves up to SG_JUMP_HOPS ancestors up.  Other lanes move the same pointers meanwhile; whatever a lane reads is an
-// ancestor of what it started from, so the pass is safe in place.  *changed is raised by every lane that stored: a pass that stores
-// nothing has found p[p[i]] == p[i] everywhere.
-__global__ __launch_bounds__(SG_THREADS) void k_seg_jump(int *__restrict__ p, unsigned n_vox, int *__restrict__ changed) {
-    const unsigned i = blockIdx.x * SG_THREADS + threadIdx.x;
-    if (i >= n_vox) return;
-    const int p0 = p[i];
-    if (p0 < 0) return;
-    int r = p0;
-#pragma unroll 1
-    for (int h = 0; h < SG_JUMP_HOPS; h++) {
-        const int up = p[r];
-        if (up == r) break;
-        r = up;
-    }
-    if (r != p0) {
-        p[i] = r;
-        *changed = 1;
-    }
-}
-
-// roots (p[i] == i) among the workgroup's SG_SCAN_PER voxels
-__global__ __launch_bounds__(SG_THREADS) void k_seg_count(const int *__restrict__ p, unsigned n_vox, int *__restrict__ blk_cnt) {
-    __shared__ int warp_tot[SG_THREADS / MAD_WAVE + 1];
-    int c = 0;
-    for (int j = 0; j < SG_SCAN_PER / SG_THREADS; j++) {
-        const unsigned long long i = (unsigned long long)blockIdx.x * SG_SCAN_PER + (unsigned)j * SG_THREADS + threadIdx.x;
-        c += (i < n_vox && p[i] == (int)i) ? 1 : 0;
-    }
-    int total = 0;
-    (void)block_excl_scan(c, warp_tot, &total);
-    if (threadIdx.x == 0) blk_cnt[blockIdx.x] = total;
-}
-
-// One workgroup: off[b] = roots in the workgroups before b, off[n_blocks] = all of them.
-__global__ __launch_bounds__(SG_SCAN_THREADS) void k_seg_scan_blocks(const int *__restrict__ cnt, int n_blocks, int *__restrict__ off) {
-    __shared__ int warp_tot[SG_SCAN_THREADS / MAD_WAVE + 1];
-    const int per = (n_blocks + SG_SCAN_THREADS - 1) / SG_SCAN_THREADS;
-    const long long c0l = (long long)threadIdx.x * per;
-    const int c0 = c0l < n_blocks ? (int)c0l : n_blocks, c1 = c0l + per < n_blocks ? (int)(c0l + per) : n_blocks;
-    int s = 0;
-    for (int c = c0; c < c1; c++) s += cnt[c];
-    int total = 0;
-    int run = block_excl_scan(s, warp_tot, &total);
-    for (int c = c0; c < c1; c++) {
-        off[c] = run;
-        run += cnt[c];
-    }
-    if (threadIdx.x == 0) off[n_blocks] = total;
-}
-
-// The k-th root in ascending L is region k + 1: lab[root] = k + 1, root_tab[k] = root, peak_tab[k] = its value.
-__global__ __launch_bounds__(SG_THREADS) void k_seg_assign(const int *__restrict__ p, const float *__restrict__ g, unsigned n_vox,
-                                                           const int *__restrict__ blk_off, int *__restrict__ lab, long long *__restrict__ root_tab,
-                                                           float *__restrict__ peak_tab) {
-    __shared__ int warp_tot[SG_THREADS / MAD_WAVE + 1];
-    int base = blk_off[blockIdx.x];
-    for (int j = 0; j < SG_SCAN_PER / SG_THREADS; j++) {      // (every lane takes every round: the scan has barriers)
-        const unsigned long long i = (unsigned long long)blockIdx.x * SG_SCAN_PER + (unsigned)j * SG_THREADS + threadIdx.x;
-        const int flag = (i < n_vox && p[i] == (int)i) ? 1 : 0;
-        int total = 0;
-        const int ex = block_excl_scan(flag, warp_tot, &total);
-        if (flag) {
-            const int k = base + ex;
-            lab[i] = k + 1;
-            root_tab[k] = (long long)i;
-            peak_tab[k] = g[i];
-        }
-        base += total;
-    }
-}
+// k_seg_jump, k_seg_count, k_seg_scan_blocks, k_seg_assign: mad_segment_scan.h (shared with mad_components.hip)
 
 // lab[i] = lab[root of i], 0 for background, in place: a root reads and writes its own id, nobody else's slot is read.  A wavefront
 // whose 64 voxels share one region adds 64 to its size once.
