@@ -553,6 +553,39 @@ int mad_map_group_fit(mad_ctx *ctx, const float *grid1, const int32_t dims1[3], 
                       int64_t *n_vox /* [n_groups] */, double *sums /* [n_groups][5] */);
 
 /*
+ * The Q-score of Pintilie et al. 2020 per atom of a placed model (mad_qscore.hip; DESIGN.md section 4u;
+ * mad_amd/localfit.py::qscore_numpy restates the contract).  Host pointers, synchronous, nothing modified but the outputs.  grid:
+ * float32 [x][y][z] with dims, origin and voxsp; atoms: n_atoms x 3 float64, the environment (every atom counts as "another atom");
+ * index: the n_index atoms to score, or NULL to score all (then n_index is ignored); radii, ref: n_r shells, the radii strictly
+ * ascending from a first >= 0, and the reference profile per shell; dirs: unit vectors (|d|^2 <= 1 + 2^-20), the sets t = 1 ..
+ * n_tries one after the other, set t with 8 t of them: 4 n_tries (n_tries + 1) x 3 float64.  All arithmetic is float64 without
+ * fused multiply-adds.
+ *   Points of a shell R > 0: a candidate is p_a = x_a + R * dir_a; it is kept iff every other atom b (other by index) has
+ *     D2 = (dx*dx + dy*dy) + dz*dz > R * R with dx = p_x - b_x.  The sets are tried in order; the first with 8 kept candidates or
+ *     more gives the shell its points, the first 8 kept in table order; if none does, the shell takes the kept candidates of the
+ *     last set (0 .. 7).  A shell with R = 0 is 8 copies of the sample at the atom's centre.
+ *   Sampling: f_a = (p_a - origin_a) / voxsp; a point with any f_a outside [-1, n_a] is 0; else i_a = floor(f_a), t_a = f_a - i_a, the
+ *     eight corners (0 outside the grid) blended along z, then y, then x as c0 + t * (c1 - c0).
+ *   Score: over the slots [shell][point] (a slot without a point adds 0 to every sum): lane l = 0 .. 63 adds the slots l, l + 64, ...
+ *     in this order, then the 64 partial sums are folded as s_l += s_(l xor 32), then xor 16, 8, 4, 2, 1.  So the sums of the
+ *     samples u and of their shells' ref values v, the means (divided by the number n of points), and, the same way, the sums of du
+ *     dv, du du and dv dv; q = S_uv / (sqrt(S_uu) * sqrt(S_vv)), NaN when n < 2 or either sum of squares is 0.
+ * Outputs per scored atom, in the order of index: q float64, n_samples int32, and where the pointer is not NULL tries_used int32
+ * [n_r] (the set that gave the shell its points, 0 for R = 0), picked int32 [n_r][8] (the row of dirs, -1 for no point and in a shell
+ * with R = 0), values float64 [n_r][8] (0 for no point).  The same call gives the same bits alone or after any other call.
+ * n_atoms == 0, or nothing to score, returns MAD_OK and writes nothing.
+ * MAD_EINVAL, with nothing launched and the outputs untouched: NULL (atoms only when n_atoms == 0; index and the last three
+ * outputs may be), a dimension < 1, 2^32 voxels or more, voxsp <= 0, a number that is not finite (origin, spacing, coordinates,
+ * radii, ref, dirs), radii that do not ascend or a negative one, n_r outside 1 .. 64, n_tries outside 1 .. 64, a direction longer
+ * than a unit vector, an index outside [0, n_atoms), 2^31 atoms or indices or more.
+ */
+int mad_map_qscore(mad_ctx *ctx, const float *grid, const int32_t dims[3], const double origin[3], double voxsp,
+                   const double *atoms, int64_t n_atoms, const int64_t *index /* may be NULL */, int64_t n_index,
+                   const double *radii, const double *ref, int32_t n_r, const double *dirs, int32_t n_tries,
+                   double *q, int32_t *n_samples, int32_t *tries_used /* may be NULL */, int32_t *picked /* may be NULL */,
+                   double *values /* may be NULL */);
+
+/*
  * A Gaussian on a map, and a map cut into segments (mad_segment.hip).  Host pointers, synchronous.  Both work
  * in voxels: grid is float32 [x][y][z] with dims, the linear index of a voxel is L = (x * ny + y) * nz + z, neither origin nor
  * spacing enters.

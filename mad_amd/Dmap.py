@@ -256,6 +256,21 @@ class Dmap(object):
         from . import localfit
         return localfit.fit_by_group(self, structure, resolution, by=by, radius=radius, isovalue=isovalue, model=model, masses=masses)
 
+    def qscore(self, structure, sigma=0.6, rmax=2.0, step=0.1, tries=50, select=None, details=False):
+        """The Q-score of Pintilie et al. 2020 (MapQ) per atom of a placed model -> `localfit.QScore` (q, n_samples, index, `mean()`,
+        `by("residue" | "chain")`, `write_csv`, `write_pdb` with Q in the B-factor column).  Around every atom the map is sampled
+        on shells of radius 0, `step`, ... `rmax`, 8 points per shell that are closer to this atom than to any other atom of
+        `structure`, and the samples are correlated with exp(-(R / sigma)^2 / 2): near 1 for an atom that is resolved, near 0 for
+        one in flat density, nan where the samples or too few points leave it undefined.  The point sets are fixed spirals of
+        8, 16, ... 8 `tries` directions, not MapQ's random ones, so the same call gives the same bits; neither a resolution nor a
+        threshold enters.  `structure`: a `PDB`, an (n, 3) array, or a list / tuple of those; all of its atoms shadow each other,
+        hydrogens and alternate locations included (leave out what should not count).  `select`: the atoms to score, a boolean
+        mask or integer indices (None: all).  `details=True` keeps, per shell, the set used, the directions picked and the
+        samples.  Two atoms at the same position empty each other's shells: both get nan.  `self` is not modified.  DESIGN.md
+        section 4u has the exact contract."""
+        from . import localfit
+        return localfit.qscore(self, structure, sigma=sigma, rmax=rmax, step=step, tries=tries, select=select, details=details)
+
     def fsc(self, other, resolution=None, masses=None, mask=None, randomize_from=None, seed=0):
         """Fourier shell correlation of this map against `other` -> `fourier.FSC` (freq, fsc, n, power1, power2, `resolution()`,
         `write_csv()`).  `other`: a `Dmap` of the same spacing (half map against half map; `resample(like=...)` first where the

@@ -25,6 +25,9 @@ WIDE_FROM_R = 11
 WIDE_C = 108
 WIDE_MAX = WIDE_C + 127
 
+QSCORE_CHUNK = 256          # QS_CHUNK of csrc/mad_qscore_plan.h: neighbours of one LDS chunk of k_qscore
+QSCORE_MAX_SHELLS, QSCORE_MAX_TRIES = 64, 64      # QS_MAX_R, QS_MAX_TRIES
+
 ERRORS = {-22: "EINVAL", -12: "ENOMEM", -28: "ENOSPC", -19: "ENODEV", -33: "EDOM", -5: "EHIP"}
 
 # every symbol include/mad_amd.h declares (tests check the library exports all of them)
@@ -39,7 +42,7 @@ SYMBOLS = [
     "mad_dist_unique_id", "mad_dist_init", "mad_dist_destroy", "mad_dist_info", "mad_dist_rehearse_flags", "mad_dist_or_allreduce", "mad_dist_allgather",
     "mad_dist_allgather_topk", "mad_dist_scratch", "mad_dist_copy",
     "mad_set_wire_bytes", "mad_set_export", "mad_set_import", "mad_set_lane", "mad_set_stream", "mad_set_bind_lane",
-    "mad_upload_density", "mad_refine", "mad_last_refine_plan", "mad_last_density_chunks", "mad_structure_to_density", "mad_ccc", "mad_map_mask", "mad_map_multiply", "mad_map_ccc", "mad_map_resample", "mad_map_zone", "mad_map_envelope", "mad_map_group_fit", "mad_map_smooth", "mad_map_segment", "mad_map_components", "mad_map_dust", "mad_map_fsc", "mad_map_fsc_masked", "mad_map_phase_randomize", "mad_map_fft", "mad_map_filter", "mad_map_ifft", "mad_map_scan", "mad_map_search", "mad_map_rotate", "mad_map_local_fsc", "mad_map_local_filter", "mad_density_ccc", "mad_dock_refine_score", "mad_grid_overlap", "mad_overlap_matrix",
+    "mad_upload_density", "mad_refine", "mad_last_refine_plan", "mad_last_density_chunks", "mad_structure_to_density", "mad_ccc", "mad_map_mask", "mad_map_multiply", "mad_map_ccc", "mad_map_resample", "mad_map_zone", "mad_map_envelope", "mad_map_group_fit", "mad_map_qscore", "mad_map_smooth", "mad_map_segment", "mad_map_components", "mad_map_dust", "mad_map_fsc", "mad_map_fsc_masked", "mad_map_phase_randomize", "mad_map_fft", "mad_map_filter", "mad_map_ifft", "mad_map_scan", "mad_map_search", "mad_map_rotate", "mad_map_local_fsc", "mad_map_local_filter", "mad_density_ccc", "mad_dock_refine_score", "mad_grid_overlap", "mad_overlap_matrix",
     "mad_space_create", "mad_space_destroy", "mad_space_build", "mad_space_info", "mad_space_download",
     "mad_space_peaks", "mad_space_patches", "mad_space_localize", "mad_localize_volume",
     "mad_pose_cluster_many",
@@ -1474,6 +1477,41 @@ class Lib(object):
                                              _p(a) if len(a) else None, _p(first), C.c_int32(n_groups), C.c_double(radius),
                                              C.c_double(isovalue), _p(n_vox), _p(sums)))
         return n_vox, sums
+
+    def map_qscore(self, g, origin, voxsp, atoms, radii, ref, dirs, tries, index=None, details=False):
+        """The Q-score per atom: `g` (C-contiguous float32 [x, y, z] with `origin` and `voxsp`) sampled around `atoms` (n x 3, the
+        environment) on the shells `radii` and correlated with `ref`; `dirs`: the point sets 1 .. `tries`, set t with 8 t unit
+        vectors (`localfit.qscore_tables` makes the three).  `index`: the atoms to score (int64; None: all).
+        -> (q float64 [m], n_samples int32 [m]), with `details` also (tries_used int32 [m, n_r], picked int32 [m, n_r, 8], values
+        float64 [m, n_r, 8]) (mad_map_qscore).  Nothing is modified."""
+        if g.dtype != np.float32 or not g.flags.c_contiguous:
+            raise ValueError("map_qscore needs a C-contiguous float32 grid")
+        if g.ndim != 3:
+            raise ValueError("map_qscore needs a 3-D grid")
+        d = np.array(g.shape, np.int32)
+        o = _c(np.asarray(origin, np.float64).reshape(3), np.float64)
+        a = _c(np.asarray(atoms, np.float64).reshape(-1, 3), np.float64)
+        radii = _c(np.asarray(radii, np.float64).reshape(-1), np.float64)
+        ref = _c(np.asarray(ref, np.float64).reshape(-1), np.float64)
+        dirs = _c(np.asarray(dirs, np.float64).reshape(-1, 3), np.float64)
+        tries, n_r = int(tries), len(radii)
+        if len(ref) != n_r:
+            raise ValueError("map_qscore: %d ref values for %d radii" % (len(ref), n_r))
+        if not 1 <= n_r <= QSCORE_MAX_SHELLS or not 1 <= tries <= QSCORE_MAX_TRIES:
+            raise ValueError("map_qscore: %d shells, %d point sets (1 .. %d, 1 .. %d)" % (n_r, tries, QSCORE_MAX_SHELLS, QSCORE_MAX_TRIES))
+        if len(dirs) != 4 * tries * (tries + 1):
+            raise ValueError("map_qscore: %d directions, %d point sets need %d" % (len(dirs), tries, 4 * tries * (tries + 1)))
+        if index is not None:
+            index = _c(np.asarray(index).reshape(-1), np.int64)
+            if len(index) and (index.min() < 0 or index.max() >= len(a)):
+                raise ValueError("map_qscore: index holds an atom outside 0 .. %d" % (len(a) - 1))
+        m = len(a) if index is None else len(index)
+        q, n_samples = np.full(m, np.nan), np.zeros(m, np.int32)
+        det = (np.zeros((m, n_r), np.int32), np.full((m, n_r, 8), -1, np.int32), np.zeros((m, n_r, 8), np.float64)) if details else (None, None, None)
+        self._chk(self.dll.mad_map_qscore(self.ctx, _p(g), _p(d), _p(o), C.c_double(voxsp), _p(a) if len(a) else None, C.c_int64(len(a)),
+                                          _p(index) if index is not None else None, C.c_int64(m if index is not None else 0), _p(radii), _p(ref),
+                                          C.c_int32(n_r), _p(dirs), C.c_int32(tries), _p(q), _p(n_samples), _p(det[0]), _p(det[1]), _p(det[2])))
+        return (q, n_samples) + (det if details else ())
 
     def map_smooth(self, g, sigma_vox, out=None):
         """`g` (C-contiguous float32 [x, y, z]) smoothed with a Gaussian of `sigma_vox` voxels, zero beyond the grid, float64 inside
