@@ -855,6 +855,34 @@ int mad_map_local_fsc(mad_ctx *ctx, const float *grid1, const int32_t dims1[3], 
                       double *sums /* may be NULL; [nx][ny][nz][box / 2 + 1][3] = P1, P2, C */, int32_t n_out[3]);
 
 /*
+ * A map's amplitudes scaled to a reference, box by box: every sample gets the value, at its own voxel, of its box of grid 1 after
+ * each shell of that box's spectrum has been given the power the same box of grid 2 holds there; grid 1 keeps its phases (the local
+ * amplitude scaling of Jakobi, Wilmanns and Sachse 2017).  DESIGN.md section 4v has the contract; mad_amd/fourier.py restates it as
+ * local_scale_numpy.  No reference counterpart.
+ *   Placement, samples, select, box and window.  As mad_map_local_fsc, whose front end this call shares: s = round(d) places grid 2 by
+ *     whole voxels; the rest delta is NOT used -- amplitudes do not see a phase ramp.  Box index box / 2 on every axis is the sample's
+ *     own voxel, and the window is exactly 1 there.
+ *   Sums.  Z = FFT(w1 + i w2), F1 and F2 as mad_map_fsc with N = box.  Shells sh = min(shell index, box / 2): the corner points
+ *     beyond shell box / 2 ride with shell box / 2 (unlike mad_map_local_fsc, which drops them), so that a map scaled against itself
+ *     comes back unchanged.  P1_s = sum |F1|^2, P2_s = sum |F2|^2, D_s = sum Re F1(k) (-1)^(a + b + c) over the points (a, b, c) of
+ *     shell s.
+ *   Gain and value.  gain_s = sqrt(P2_s / P1_s) where P1_s > 0 and the quotient is finite, else 0.0.
+ *     out = (gain_0 D_0 + ... + gain_(box/2) D_(box/2)) / box^3, added in shell order: the real part of the inverse transform of
+ *     gain[sh] F1 at the centre of the box.
+ *   float64, no fused multiply-add, no atomics, every sum in an order fixed by indices: the same bits every run and after any other call.
+ * out == NULL: the size query -- the checks and n_out only, nothing allocated or launched.  Otherwise out holds n_x n_y n_z entries
+ * (0.0 where select is 0) and gains (may be NULL) n_x n_y n_z (box / 2 + 1) (zeros where select is 0).  The values do not depend on
+ * whether gains was asked for.
+ * MAD_EINVAL, MAD_EDOM, MAD_ENOMEM: those of mad_map_local_fsc, without the threshold's.  Each leaves the outputs untouched, launches
+ * nothing, and the next call works.
+ */
+int mad_map_local_scale(mad_ctx *ctx, const float *grid1, const int32_t dims1[3], const double origin1[3],
+                        const float *grid2, const int32_t dims2[3], const double origin2[3], double voxsp,
+                        int32_t box, int32_t step, const uint8_t *select /* may be NULL: every sample */,
+                        double *out /* float64 [nx][ny][nz]; NULL: size query */,
+                        double *gains /* may be NULL; float64 [nx][ny][nz][box / 2 + 1] */, int32_t n_out[3]);
+
+/*
  * A low-pass whose width varies from voxel to voxel: every output voxel is the map under the Gaussian of its own resolution
  * (mad_localfilter.hip).  DESIGN.md section 4q has the contract; mad_amd/fourier.py restates it as local_sigma_numpy and
  * local_filter_numpy.  No reference counterpart.  grid float32 [nx][ny][nz]; res float64 (Angstrom) on the sample lattice of step

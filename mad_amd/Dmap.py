@@ -18,6 +18,8 @@ map through `mad_map_scan` (fourier.py; no counterpart in the reference: the exh
 does so over a whole set of rotations made on the device (`mad_map_search`).  `local_resolution` is `fsc` per sample point, in a
 windowed cube around it, through `mad_map_local_fsc` (fourier.py; no counterpart in the reference), and `lowpass_local` low-passes
 the map by such a measurement, every voxel under the Gaussian of its own resolution, through `mad_map_local_filter`.
+`scale_local` gives every such cube of the map the radial amplitude profile of a reference and keeps the map's phases, through
+`mad_map_local_scale`; `scale_to` does it once for the whole map with the curve of `fsc` and the filter of `filter_radial`.
 `envelope` makes a soft mask from the map itself (threshold, grow, raised-cosine edge) through `mad_map_envelope`, `apply_mask`
 multiplies a map by one through `mad_map_multiply`, and `fsc(mask=...)` is the masked curve corrected for the mask by phase
 randomisation through `mad_map_fsc_masked` (envelope.py, fourier.py; no counterpart in the reference).
@@ -354,6 +356,43 @@ class Dmap(object):
         o1 = (self.xi, self.yi, self.zi)
         res, shell, sm = _lib.get_lib().map_local_fsc(g1, o1, g2, o2, voxsp, box=box, step=step, threshold=thr, select=sel, sums=sums)
         return fourier.LocalResolution(res, shell, sm, box, step, voxsp, o1, thr)
+
+    def scale_local(self, reference, box=16, step=1, resolution=None, masses=None, isovalue=None, gains=False):
+        """The map's amplitudes scaled to a reference region by region (the local amplitude scaling of Jakobi, Wilmanns and Sachse
+        2017): in a Hann-windowed cube of `box` (8, 16 or 32) voxels around every `step`-th voxel each shell of the map's spectrum is
+        given the power the reference holds there, the map keeps its phases, and the sample takes the rescaled cube's value at its
+        own voxel, through `mad_map_local_scale` -> `fourier.LocalScale` (`value`, `computed`, `gains`, `gain(i, j, k)`, `to_dmap()`,
+        `write(outname)`).  Where `sharpen` applies one B-factor the user has to bring, this takes every region's fall-off from the
+        reference.  `reference` as `other` in `local_resolution`: a `Dmap` of the same spacing, a (grid, (x0, y0, z0)) pair, or a
+        placed model -- a `PDB`, an (n, 3) array, or a list / tuple of those -- simulated at `resolution`.  The reference is placed
+        by whole voxels; amplitudes do not see the rest.  `isovalue=v` computes only the samples whose own voxel of this map is
+        > v; the others hold 0.0.  `gains=True` keeps every box's gain per shell.  The map is left untouched: at step 1
+        `to_dmap()` is the scaled map on this map's lattice, at a larger step the coarser volume that `resample(like=map)` brings
+        back.  No cap on the gain: a shell in which the map holds next to nothing is raised to the reference all the same.
+        DESIGN.md section 4v has the exact contract."""
+        from . import fourier
+        voxsp = float(self.voxsp)
+        g1, g2, o2, _ = self._fsc_pair("Dmap.scale_local", reference, resolution, masses)
+        step = int(step)
+        sel = None
+        if isovalue is not None and step >= 1:
+            sel = g1[::step, ::step, ::step] > float(isovalue)
+        o1 = (self.xi, self.yi, self.zi)
+        value, computed, gn = _lib.get_lib().map_local_scale(g1, o1, g2, o2, voxsp, box=box, step=step, select=sel, gains=gains)
+        return fourier.LocalScale(value, computed, gn, box, step, voxsp, o1)
+
+    def scale_to(self, reference, resolution=None, masses=None, pad=None):
+        """The global counterpart of `scale_local`, in place: every shell of the map's spectrum is given the power the reference
+        holds there.  -> (freq, gain): the curve applied, sqrt(power2 / power1) of `fsc(reference)` per shell, 0.0 where power1
+        is 0.  The curve `fsc` measures goes to the filter `filter_radial` runs (`mad_map_filter`), as a staircase: a lattice point
+        takes the gain of the shell it was counted in (`fourier.gain_shells`), not a value interpolated between two shells, so that
+        a shell's power lands on the reference's.  `reference` as in `fsc`; pad=None: 8 voxels, as in `filter_radial`.  Where the
+        filter's lattice is larger than the one `fsc` measured on (the pad, or a smaller reference), a point takes the nearest
+        measured shell."""
+        from . import fourier
+        freq, gain = fourier.scale_curve(self.fsc(reference, resolution=resolution, masses=masses))
+        self._filter("scale_to", lambda N: lambda f: fourier.gain_shells(f, freq, gain), 8 if pad is None else pad)
+        return freq, gain
 
     def _correlation_args(self, who, structure, resolution, rotations, default_rotations, mode, isovalue, min_fill, masses):
         """What `scan` and `search` check and derive alike, before any library call -> (coords, mass, centroid, rot, g1, iso,

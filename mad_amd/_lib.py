@@ -42,7 +42,7 @@ SYMBOLS = [
     "mad_dist_unique_id", "mad_dist_init", "mad_dist_destroy", "mad_dist_info", "mad_dist_rehearse_flags", "mad_dist_or_allreduce", "mad_dist_allgather",
     "mad_dist_allgather_topk", "mad_dist_scratch", "mad_dist_copy",
     "mad_set_wire_bytes", "mad_set_export", "mad_set_import", "mad_set_lane", "mad_set_stream", "mad_set_bind_lane",
-    "mad_upload_density", "mad_refine", "mad_last_refine_plan", "mad_last_density_chunks", "mad_structure_to_density", "mad_ccc", "mad_map_mask", "mad_map_multiply", "mad_map_ccc", "mad_map_resample", "mad_map_zone", "mad_map_envelope", "mad_map_group_fit", "mad_map_qscore", "mad_map_smooth", "mad_map_segment", "mad_map_components", "mad_map_dust", "mad_map_fsc", "mad_map_fsc_masked", "mad_map_phase_randomize", "mad_map_fft", "mad_map_filter", "mad_map_ifft", "mad_map_scan", "mad_map_search", "mad_map_rotate", "mad_map_local_fsc", "mad_map_local_filter", "mad_density_ccc", "mad_dock_refine_score", "mad_grid_overlap", "mad_overlap_matrix",
+    "mad_upload_density", "mad_refine", "mad_last_refine_plan", "mad_last_density_chunks", "mad_structure_to_density", "mad_ccc", "mad_map_mask", "mad_map_multiply", "mad_map_ccc", "mad_map_resample", "mad_map_zone", "mad_map_envelope", "mad_map_group_fit", "mad_map_qscore", "mad_map_smooth", "mad_map_segment", "mad_map_components", "mad_map_dust", "mad_map_fsc", "mad_map_fsc_masked", "mad_map_phase_randomize", "mad_map_fft", "mad_map_filter", "mad_map_ifft", "mad_map_scan", "mad_map_search", "mad_map_rotate", "mad_map_local_fsc", "mad_map_local_scale", "mad_map_local_filter", "mad_density_ccc", "mad_dock_refine_score", "mad_grid_overlap", "mad_overlap_matrix",
     "mad_space_create", "mad_space_destroy", "mad_space_build", "mad_space_info", "mad_space_download",
     "mad_space_peaks", "mad_space_patches", "mad_space_localize", "mad_localize_volume",
     "mad_pose_cluster_many",
@@ -1291,6 +1291,26 @@ class Lib(object):
         sm = np.empty(shape + (int(box) // 2 + 1, 3), np.float64) if sums else None
         self._chk(self.dll.mad_map_local_fsc(*args, None if sel is None else _p(sel), _p(res), _p(shell), None if sm is None else _p(sm), _p(n)))
         return res, shell, sm
+
+    def map_local_scale(self, g1, o1, g2, o2, voxsp, box=16, step=1, select=None, gains=False):
+        """The amplitudes of `g1` scaled to those of `g2` box by box -> (value float64 [nx, ny, nz], computed bool [nx, ny, nz],
+        gains float64 [nx, ny, nz, box / 2 + 1] or None) over the samples at every `step`-th voxel of `g1` (mad_map_local_scale;
+        DESIGN.md section 4v; `fourier.local_scale_numpy` restates it).  `select`: an array over the sample lattice, a sample where
+        it is 0 gets 0.0 and is not computed.  Both grids C-contiguous float32 [x, y, z]; neither is modified."""
+        d1, o1, d2, o2 = self._fourier_args("map_local_scale", g1, o1, g2, o2)
+        n = np.zeros(3, np.int32)
+        args = (self.ctx, _p(g1), _p(d1), _p(o1), _p(g2), _p(d2), _p(o2), C.c_double(voxsp), C.c_int32(int(box)), C.c_int32(int(step)))
+        self._chk(self.dll.mad_map_local_scale(*args, None, None, None, _p(n)))      # the size query
+        shape = tuple(int(v) for v in n)
+        sel = None
+        if select is not None:
+            sel = np.ascontiguousarray(np.asarray(select) != 0, dtype=np.uint8)
+            if sel.shape != shape:
+                raise ValueError("map_local_scale: select of shape %r, the sample lattice is %r" % (sel.shape, shape))
+        value = np.empty(shape, np.float64)
+        gn = np.empty(shape + (int(box) // 2 + 1,), np.float64) if gains else None
+        self._chk(self.dll.mad_map_local_scale(*args, None if sel is None else _p(sel), _p(value), None if gn is None else _p(gn), _p(n)))
+        return value, (np.ones(shape, bool) if sel is None else sel.astype(bool)), gn
 
     def map_local_filter(self, grid, res, step, voxsp, out=None, out64=False, sigma=False):
         """`grid` (C-contiguous float32 [x, y, z]) low-passed voxel by voxel: every output voxel is the map under the Gaussian of its

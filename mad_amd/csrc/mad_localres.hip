@@ -1,5 +1,7 @@
-// mad_localres.hip -- local resolution of a map by windowed Fourier shell correlation (mad_map_local_fsc).
-// DESIGN.md section 4p has the contract; mad_amd/fourier.py restates it as local_fsc_numpy.
+// mad_localres.hip -- local resolution of a map by windowed Fourier shell correlation (mad_map_local_fsc), and a map's amplitudes
+// scaled to a reference box by box (mad_map_local_scale): one front end, one forward transform, two tails.
+// DESIGN.md section 4p has the contract of the first and mad_amd/fourier.py restates it as local_fsc_numpy; section 4v and
+// local_scale_numpy are the second's.
 //
 // Per sample point of a lattice over grid 1 a cubic box of edge w = 8, 16 or 32 voxels is cut out of both grids (zero outside either),
 // multiplied by a separable periodic Hann window and transformed as Z = FFT(w1 + i w2); the two spectra are separated, summed per
@@ -29,10 +31,16 @@
 // w = 32: the box is 512 KiB and goes through a scratch buffer in batches of LR32_BATCH boxes (32 MiB: inside the Infinity Cache):
 //   k_lr32_planes packs, windows and transforms two y-z planes per workgroup in LDS, k_lr32_xlines transforms the x lines in place
 //   from registers (lanes over z: every access of a wave is 1 KiB contiguous), k_lr32_shells is the tail of k_lr_box on global memory.
+// mad_map_local_scale runs the same fill and line passes (k_lr_box<W, true>; k_lr32_planes and k_lr32_xlines as they are) and ends in
+//   ls_tail: its list holds every point of the box, the corners beyond shell w / 2 in the last shell's bucket, and a point gives P1, P2
+//   and D = Re F1 (-1)^(a + b + c) where the other tail gives P1, P2 and C.  The chunk, piece and shell sums are lr_reduce's, shared;
+//   a lane per shell forms the gain, one lane adds gain_s D_s in shell order and divides by w^3: the centre of the rescaled box.
+//   No ramp (amplitudes do not see one), so no phi in LDS.
 #include <algorithm>
 #include <vector>
 
 #include "mad_fft_common.h"
+#include "mad_localscale_plan.h"
 
 #define LR32_BATCH 64
 
@@ -57,6 +65,8 @@ struct LrArgs {
     double *res;                   // [samples]
     int *shell;                    // [samples]
     double *sums;                  // [samples][w / 2 + 1][3] or NULL
+    double *out;                   // mad_map_local_scale: [samples] the centre of the rescaled box
+    double *gains;                 // [samples][w / 2 + 1] or NULL
 };
 
 template <int W> __device__ __forceinline__ constexpr int lr_brev(int i) {
@@ -143,11 +153,37 @@ __device__ __forceinline__ void lr_crossing(const double *fsc, int W, double vox
 // contiguous pieces, each in chunk order; the pieces in order.
 template <int W> constexpr int LR_T() { return W == 32 ? 512 : W * W; }
 template <int W> constexpr int LR_G() { return LR_T<W>() / (3 * (W / 2 + 1)) >= 8 ? 8 : 4; }
+
+// part [n_chunks][3], the three sums of every chunk, written by the callers' threads before the call -> tab [W / 2 + 1][3], the three
+// sums of every shell, and `keep` (global, may be NULL) the same.  Begins and ends with a barrier.
+template <int W>
+__device__ __forceinline__ void lr_reduce(const LrTab &Tb, const double *part, double *part2, double *tab, double *keep) {
+    constexpr int SH = W / 2 + 1, G = LR_G<W>();
+    static_assert(G * 3 * SH <= LR_T<W>(), "one thread per piece");
+    const int t = (int)threadIdx.x;
+    __syncthreads();
+    if (t < G * 3 * SH) {
+        const int g = t / (3 * SH), j = t - g * (3 * SH), s = j / 3, q = j - 3 * s;
+        const int lo = Tb.shell_c0[s], n = Tb.shell_c0[s + 1] - lo;
+        double v = 0.0;
+        for (int c = lo + n * g / G; c < lo + n * (g + 1) / G; c++) v += part[3 * c + q];
+        part2[t] = v;
+    }
+    __syncthreads();
+    if (t < 3 * SH) {
+        double v = part2[t];
+#pragma unroll
+        for (int g = 1; g < G; g++) v += part2[g * 3 * SH + t];
+        tab[t] = v;
+        if (keep) keep[t] = v;
+    }
+    __syncthreads();
+}
+
 template <int W, int PZ, class P>
 __device__ __forceinline__ void lr_tail(P Z, const double2 *phi, const LrArgs &A, const LrTab &Tb, unsigned smp, double *part, double *part2,
                                         double *tab) {
-    constexpr int SH = W / 2 + 1, T = LR_T<W>(), G = LR_G<W>();
-    static_assert(G * 3 * SH <= T, "one thread per piece");
+    constexpr int SH = W / 2 + 1, T = LR_T<W>();
     const int t = (int)threadIdx.x;
     for (int c = t; c < Tb.n_chunks; c += T) {
         const int2 ch = Tb.chunk[c];
@@ -168,24 +204,8 @@ __device__ __forceinline__ void lr_tail(P Z, const double2 *phi, const LrArgs &A
         }
         part[3 * c] = p1; part[3 * c + 1] = p2; part[3 * c + 2] = cr;
     }
-    __syncthreads();
-    if (t < G * 3 * SH) {
-        const int g = t / (3 * SH), j = t - g * (3 * SH), s = j / 3, q = j - 3 * s;
-        const int lo = Tb.shell_c0[s], n = Tb.shell_c0[s + 1] - lo;
-        double v = 0.0;
-        for (int c = lo + n * g / G; c < lo + n * (g + 1) / G; c++) v += part[3 * c + q];
-        part2[t] = v;
-    }
-    __syncthreads();
-    if (t < 3 * SH) {
-        double v = part2[t];
-#pragma unroll
-        for (int g = 1; g < G; g++) v += part2[g * 3 * SH + t];
-        tab[t] = v;
-        if (A.sums) A.sums[(size_t)smp * (3 * SH) + t] = v;
-    }
-    __syncthreads();
-    if (t < SH) part2[t] = lr_fsc(tab + 3 * t);      // (part2 has been read: the barrier above)
+    lr_reduce<W>(Tb, part, part2, tab, A.sums ? A.sums + (size_t)smp * (3 * SH) : nullptr);
+    if (t < SH) part2[t] = lr_fsc(tab + 3 * t);      // (part2 has been read: the barrier that ends lr_reduce)
     __syncthreads();
     if (t == 0) {
         double r;
@@ -196,17 +216,63 @@ __device__ __forceinline__ void lr_tail(P Z, const double2 *phi, const LrArgs &A
     }
 }
 
-// dynamic LDS (lr_box_lds): the image W^2 (W + 1) complex128, the ramp 3 W complex128, then the doubles of lr_tail
-template <int W> static size_t lr_box_lds(int n_chunks) {
-    return ((size_t)W * W * (W + 1) + 3 * W) * 16 + ((size_t)3 * n_chunks + (LR_G<W>() + 1) * 3 * (W / 2 + 1)) * 8;
+// The tail of mad_map_local_scale: split, shell sums, gains and the centre of the rescaled box, Z and the LDS as lr_tail has them
+// (no ramp).  Tb lists every point of the box, the corners in shell W / 2's bucket.  Per point P1 += |F1|^2, P2 += |F2|^2 and
+// D += Re F1 (-1)^(a + b + c): exp(2 pi i k . (W / 2, W / 2, W / 2) / W) is that sign, and F1(-k) = conj F1(k) makes the imaginary
+// parts cancel over a shell, so (1 / W^3) sum_s gain_s D_s is the real part of the inverse transform of gain F1 at the box's centre.
+// The order of every sum is lr_tail's; one lane adds the W / 2 + 1 products in shell order.
+template <int W, int PZ, class P>
+__device__ __forceinline__ void ls_tail(P Z, const LrArgs &A, const LrTab &Tb, unsigned smp, double *part, double *part2, double *tab) {
+    constexpr int SH = W / 2 + 1, T = LR_T<W>();
+    const int t = (int)threadIdx.x;
+    for (int c = t; c < Tb.n_chunks; c += T) {
+        const int2 ch = Tb.chunk[c];
+        double p1 = 0.0, p2 = 0.0, d = 0.0;
+#pragma unroll 4
+        for (int e = ch.x; e < ch.y; e++) {
+            const unsigned pt = Tb.pts[e];
+            const int a = (int)(pt >> 10), b = (int)((pt >> 5) & 31u), cc = (int)(pt & 31u);
+            const int ma = (W - a) & (W - 1), mb = (W - b) & (W - 1), mc = (W - cc) & (W - 1);
+            const double2 z = Z[(a * W + b) * PZ + cc], zm = Z[(ma * W + mb) * PZ + mc];
+            const double f1x = (z.x + zm.x) * 0.5, f1y = (z.y - zm.y) * 0.5;      // (Z(k) + conj Z(-k)) / 2
+            const double f2x = (z.y + zm.y) * 0.5, f2y = (zm.x - z.x) * 0.5;      // (Z(k) - conj Z(-k)) / (2i)
+            p1 += f1x * f1x + f1y * f1y;
+            p2 += f2x * f2x + f2y * f2y;
+            d += ((a + b + cc) & 1) ? -f1x : f1x;
+        }
+        part[3 * c] = p1; part[3 * c + 1] = p2; part[3 * c + 2] = d;
+    }
+    lr_reduce<W>(Tb, part, part2, tab, nullptr);
+    if (t < SH) {      // (part2 has been read: the barrier that ends lr_reduce)
+        const double p1 = tab[3 * t], p2 = tab[3 * t + 1];
+        double g = 0.0;
+        if (p1 > 0.0) {
+            g = sqrt(p2 / p1);
+            if (!(g <= 1.7976931348623157e308)) g = 0.0;      // a quotient that is not finite: no gain
+        }
+        part2[t] = g;
+        if (A.gains) A.gains[(size_t)smp * SH + t] = g;
+    }
+    __syncthreads();
+    if (t == 0) {
+        double v = 0.0;
+        for (int s = 0; s < SH; s++) v += part2[s] * tab[3 * s + 2];
+        A.out[smp] = v / (double)(W * W * W);
+    }
 }
-template <int W>
+
+// k_lr_box's dynamic LDS is lsp_box_lds(W, n_chunks, !SCALE): the image W^2 (W + 1) complex128, the ramp 3 W complex128 (not SCALE),
+// then the doubles of the tail; the plan header's thread and piece counts are the kernels'
+static_assert(LR_T<8>() == 64 && LR_T<16>() == 256 && LR_T<32>() == 512 && LR_G<8>() == 4 && LR_G<16>() == 8 && LR_G<32>() == 8, "mad_localscale_plan.h");
+
+// SCALE: mad_map_local_scale -- the same fill and passes, no ramp, ls_tail
+template <int W, bool SCALE>
 __global__ __launch_bounds__(W * W) void k_lr_box(const LrArgs A, const LrTab Tb, unsigned first) {
     extern __shared__ __attribute__((aligned(16))) double2 lr_img[];
     constexpr int PZ = W + 1, SH = W / 2 + 1;
     double2 *phi = lr_img + W * W * PZ;
-    double *part = (double *)(phi + 3 * W), *part2 = part + 3 * Tb.n_chunks, *tab = part2 + LR_G<W>() * 3 * SH;
-    if (threadIdx.x < 3 * W) phi[threadIdx.x] = A.phi[threadIdx.x];
+    double *part = (double *)(phi + (SCALE ? 0 : 3 * W)), *part2 = part + 3 * Tb.n_chunks, *tab = part2 + LR_G<W>() * 3 * SH;
+    if (!SCALE && threadIdx.x < 3 * W) phi[threadIdx.x] = A.phi[threadIdx.x];
     const unsigned smp = A.list[first + blockIdx.x];
     int lo[3];
     lr_corner<W>(A, smp, lo);
@@ -228,7 +294,8 @@ __global__ __launch_bounds__(W * W) void k_lr_box(const LrArgs A, const LrTab Tb
     __syncthreads();
     lr_line<W>(lr_img + u * PZ + v, W * PZ, Tb.tw);                  // along x: (y, z) = (u, v)
     __syncthreads();
-    lr_tail<W, PZ>((const double2 *)lr_img, (const double2 *)phi, A, Tb, smp, part, part2, tab);
+    if constexpr (SCALE) ls_tail<W, PZ>((const double2 *)lr_img, A, Tb, smp, part, part2, tab);
+    else lr_tail<W, PZ>((const double2 *)lr_img, (const double2 *)phi, A, Tb, smp, part, part2, tab);
 }
 
 // ---------------------------------------------------------------------------
@@ -288,13 +355,18 @@ __global__ __launch_bounds__(LR32_TAIL_THREADS) void k_lr32_shells(const LrArgs 
     lr_tail<W, W>(Zb + (size_t)blockIdx.x * W * W * W, (const double2 *)phi, A, Tb, A.list[first + blockIdx.x], part, part2, tab);
 }
 
+__global__ __launch_bounds__(LR32_TAIL_THREADS) void k_ls32_shells(const LrArgs A, const LrTab Tb, unsigned first, const double2 *__restrict__ Zb) {
+    constexpr int W = 32;
+    __shared__ double part[3 * LR32_TAIL_THREADS], part2[LR_G<W>() * 3 * (W / 2 + 1)], tab[3 * (W / 2 + 1)];
+    ls_tail<W, W>(Zb + (size_t)blockIdx.x * W * W * W, A, Tb, A.list[first + blockIdx.x], part, part2, tab);
+}
+
 // ---------------------------------------------------------------------------
 // host
 // ---------------------------------------------------------------------------
 
 static int lr_slot(int W) { return W == 8 ? 0 : (W == 16 ? 1 : 2); }
-static int lr_tail_threads(int W) { return W == 32 ? LR_T<32>() : W * W; }
-static_assert(LR_T<32>() == LR32_TAIL_THREADS, "k_lr32_shells");
+static_assert(LR_T<32>() == LR32_TAIL_THREADS, "k_lr32_shells, k_ls32_shells");
 
 // byte offsets of the table's parts
 struct LrLayout { size_t h, tw, chunk, c0, pts, bytes; };
@@ -309,52 +381,29 @@ static LrLayout lr_layout(int W, int n_chunks, int n_pts) {
     return L;
 }
 
-// the window, the twiddles and the shell-ordered point list of edge W on the device, built when first asked for
-static int lr_tables(mad_ctx *ctx, int W, LrTab *Tb) {
-    const int slot = lr_slot(W), SH = W / 2 + 1;
+// the window, the twiddles and the shell-ordered point list of edge W on the device, built when first asked for; `corners`: the list
+// of mad_map_local_scale (every point, the corners in the last shell's bucket), a table of its own
+static int lr_tables(mad_ctx *ctx, int W, bool corners, LrTab *Tb) {
+    const int slot = lr_slot(W) + (corners ? 3 : 0);
     if (!ctx->lr_n[slot][0]) {
-        std::vector<std::vector<unsigned short>> by((size_t)SH);
-        for (int a = 0; a < W; a++)
-            for (int b = 0; b < W; b++)
-                for (int c = 0; c < W; c++) {
-                    const int fi = a < W / 2 ? a : a - W, fj = b < W / 2 ? b : b - W, fk = c < W / 2 ? c : c - W, r2 = fi * fi + fj * fj + fk * fk;
-                    int sh = (int)(sqrt((double)r2) + 0.5);      // floor(sqrt(r2) + 0.5) = the t with t^2 - t < r2 <= t^2 + t, fixed up in integers
-                    while (sh * sh + sh < r2) sh++;
-                    while (sh > 0 && sh * sh - sh >= r2) sh--;
-                    if (sh < SH) by[(size_t)sh].push_back((unsigned short)(a << 10 | b << 5 | c));
-                }
-        // the shortest chunks that leave at most one per thread of the tail
-        const int T = lr_tail_threads(W);
-        int per = 1, n_chunks = 0, n_pts = 0;
-        for (;; per++) {
-            n_chunks = 0;
-            for (const auto &v : by) n_chunks += (int)mad_ceil_div((int64_t)v.size(), per);
-            if (n_chunks <= T) break;
-        }
-        for (const auto &v : by) n_pts += (int)v.size();
+        LsPlan P;
+        lsp_plan(W, corners, P);
+        const int n_chunks = P.n_chunks(), n_pts = P.n_pts();
         const LrLayout L = lr_layout(W, n_chunks, n_pts);
         std::vector<char> blob(L.bytes, 0);
         double *h = (double *)(blob.data() + L.h), *tw = (double *)(blob.data() + L.tw);
-        int *chunk = (int *)(blob.data() + L.chunk), *c0 = (int *)(blob.data() + L.c0);
-        unsigned short *pts = (unsigned short *)(blob.data() + L.pts);
         for (int n = 0; n < W; n++) {
             double c, s;
             unit_root(n, W, &c, &s);
             h[n] = 0.5 - 0.5 * c;
             tw[2 * n] = c; tw[2 * n + 1] = -s;
         }
-        int nc = 0, np = 0;
-        for (int s = 0; s < SH; s++) {
-            c0[s] = nc;
-            const int n = (int)by[(size_t)s].size();
-            for (int e = 0; e < n; e += per) { chunk[2 * nc] = np + e; chunk[2 * nc + 1] = np + std::min(e + per, n); nc++; }
-            std::copy(by[(size_t)s].begin(), by[(size_t)s].end(), pts + np);
-            np += n;
-        }
-        c0[SH] = nc;
+        std::copy(P.chunk.begin(), P.chunk.end(), (int *)(blob.data() + L.chunk));
+        std::copy(P.c0.begin(), P.c0.end(), (int *)(blob.data() + L.c0));
+        std::copy(P.pts.begin(), P.pts.end(), (unsigned short *)(blob.data() + L.pts));
         MAD_TRY(mad_reserve(ctx, ctx->lr_tab[slot], L.bytes));
         MAD_HIP(hipMemcpy(ctx->lr_tab[slot].p, blob.data(), L.bytes, hipMemcpyHostToDevice));
-        ctx->lr_n[slot][0] = n_chunks; ctx->lr_n[slot][1] = n_pts; ctx->lr_n[slot][2] = per;
+        ctx->lr_n[slot][0] = n_chunks; ctx->lr_n[slot][1] = n_pts; ctx->lr_n[slot][2] = P.per;
     }
     const LrLayout L = lr_layout(W, ctx->lr_n[slot][0], ctx->lr_n[slot][1]);
     const char *p = (const char *)ctx->lr_tab[slot].p;
@@ -363,14 +412,14 @@ static int lr_tables(mad_ctx *ctx, int W, LrTab *Tb) {
     return MAD_OK;
 }
 
-static int lr_check_grid(mad_ctx *ctx, const int32_t d[3], const double o[3], double voxsp) {
+static int lr_check_grid(mad_ctx *ctx, const char *who, const int32_t d[3], const double o[3], double voxsp) {
     for (int k = 0; k < 3; k++) {
-        if (d[k] <= 0) return mad_fail(ctx, MAD_EINVAL, "mad_map_local_fsc: empty grid (%d x %d x %d)", d[0], d[1], d[2]);
-        if (!(fabs(o[k]) <= 1.7e308)) return mad_fail(ctx, MAD_EINVAL, "mad_map_local_fsc: origin %g", o[k]);
+        if (d[k] <= 0) return mad_fail(ctx, MAD_EINVAL, "%s: empty grid (%d x %d x %d)", who, d[0], d[1], d[2]);
+        if (!(fabs(o[k]) <= 1.7e308)) return mad_fail(ctx, MAD_EINVAL, "%s: origin %g", who, o[k]);
     }
     const unsigned long long v = (unsigned long long)d[0] * (unsigned long long)d[1];
     if (v >= (1ull << 32) || v * (unsigned long long)d[2] >= (1ull << 32))
-        return mad_fail(ctx, MAD_EINVAL, "mad_map_local_fsc: %d x %d x %d voxels: grids of 2^32 voxels or more are not supported", d[0], d[1], d[2]);
+        return mad_fail(ctx, MAD_EINVAL, "%s: %d x %d x %d voxels: grids of 2^32 voxels or more are not supported", who, d[0], d[1], d[2]);
     return MAD_OK;
 }
 
@@ -378,11 +427,11 @@ static int lr_check_grid(mad_ctx *ctx, const int32_t d[3], const double o[3], do
 // other on the stream, each with its offset into the list.  The attribute is set on every call: it belongs to the device the call
 // runs on, and setting it costs nothing.
 #define LR_ROUND ((size_t)1 << 22)
-template <int W> static int lr_launch_box(mad_ctx *ctx, const LrArgs &A, const LrTab &Tb, size_t n_sel) {
-    const size_t lds = lr_box_lds<W>(Tb.n_chunks);
-    MAD_HIP(hipFuncSetAttribute((const void *)k_lr_box<W>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+template <int W, bool SCALE> static int lr_launch_box(mad_ctx *ctx, const LrArgs &A, const LrTab &Tb, size_t n_sel) {
+    const size_t lds = lsp_box_lds(W, Tb.n_chunks, !SCALE);
+    MAD_HIP(hipFuncSetAttribute((const void *)k_lr_box<W, SCALE>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
     for (size_t first = 0; first < n_sel; first += LR_ROUND)
-        hipLaunchKernelGGL((k_lr_box<W>), dim3((unsigned)std::min(LR_ROUND, n_sel - first)), dim3(W * W), lds, ctx->stream, A, Tb, (unsigned)first);
+        hipLaunchKernelGGL((k_lr_box<W, SCALE>), dim3((unsigned)std::min(LR_ROUND, n_sel - first)), dim3(W * W), lds, ctx->stream, A, Tb, (unsigned)first);
     return MAD_OK;
 }
 static_assert(LR_ROUND * 16 * 16 < ((size_t)1 << 32), "threads of a round of k_lr_box<16>");
@@ -390,16 +439,18 @@ static_assert(LR_ROUND * 16 * 16 < ((size_t)1 << 32), "threads of a round of k_l
 // what mad_reserve would allocate to bring a buffer to `need` bytes (its 25 % slack included), 0 where the buffer holds them already
 static size_t lr_growth(const DevBuf &b, size_t need) { return b.cap >= need ? 0 : need + need / 4 + 512; }
 
-static int map_local_fsc_run(mad_ctx *ctx, const float *g1, const int32_t *d1, const double *o1, const float *g2, const int32_t *d2,
-                             const double *o2, double voxsp, int32_t W, int32_t step, double thr, const uint8_t *select, double *resolution,
-                             int32_t *shell, double *sums, int32_t *n_out) {
-    const char *who = "mad_map_local_fsc";
+// The front end of both calls.  scale == false: mad_map_local_fsc, `resolution`, `shell` and `sums` ([samples][SH][3]) its outputs.
+// scale == true: mad_map_local_scale, `resolution` is its `out`, `sums` its `gains` ([samples][SH]), `shell` and `thr` are not used.
+static int map_local_run(mad_ctx *ctx, bool scale, const float *g1, const int32_t *d1, const double *o1, const float *g2, const int32_t *d2,
+                         const double *o2, double voxsp, int32_t W, int32_t step, double thr, const uint8_t *select, double *resolution,
+                         int32_t *shell, double *sums, int32_t *n_out) {
+    const char *who = scale ? "mad_map_local_scale" : "mad_map_local_fsc";
     if (W != 8 && W != 16 && W != 32) return mad_fail(ctx, MAD_EINVAL, "%s: box %d (8, 16 or 32)", who, W);
     if (step < 1) return mad_fail(ctx, MAD_EINVAL, "%s: step %d (1 or more)", who, step);
-    if (!(thr > -1.0 && thr < 1.0)) return mad_fail(ctx, MAD_EINVAL, "%s: threshold %g (inside (-1, 1))", who, thr);
+    if (!scale && !(thr > -1.0 && thr < 1.0)) return mad_fail(ctx, MAD_EINVAL, "%s: threshold %g (inside (-1, 1))", who, thr);
     if (!(voxsp > 0) || !(voxsp < 1e15)) return mad_fail(ctx, MAD_EINVAL, "%s: voxsp %g", who, voxsp);
-    MAD_TRY(lr_check_grid(ctx, d1, o1, voxsp));
-    MAD_TRY(lr_check_grid(ctx, d2, o2, voxsp));
+    MAD_TRY(lr_check_grid(ctx, who, d1, o1, voxsp));
+    MAD_TRY(lr_check_grid(ctx, who, d2, o2, voxsp));
     LrArgs A;
     memset(&A, 0, sizeof(A));
     double delta[3];
@@ -423,14 +474,14 @@ static int map_local_fsc_run(mad_ctx *ctx, const float *g1, const int32_t *d1, c
     const size_t n_sel = list.size();
     if (n_sel >= ((size_t)1 << 31)) return mad_fail(ctx, MAD_EDOM, "%s: %zu samples selected (2^31 or more)", who, n_sel);
     // device memory, judged before anything is allocated: the grids, the list and the ramp, the outputs, the scratch of w = 32
-    const size_t b_list = ((n_sel + 4) * 4 + 15) & ~(size_t)15, b_phi = (size_t)3 * W * 16;
-    const size_t b_res = n * 8, b_shell = (n * 4 + 15) & ~(size_t)15, b_sums = sums ? n * SH * 24 : 0;
+    const size_t b_list = ((n_sel + 4) * 4 + 15) & ~(size_t)15, b_phi = scale ? 0 : (size_t)3 * W * 16, n_per = (size_t)SH * (scale ? 1 : 3);
+    const size_t b_res = n * 8, b_shell = scale ? 0 : (n * 4 + 15) & ~(size_t)15, b_sums = sums ? n * n_per * 8 : 0;
     const size_t b_scratch = W == 32 ? (size_t)std::min<size_t>(std::max<size_t>(n_sel, 1), LR32_BATCH) * W * W * W * 16 : 0;
     const size_t need_h = (n1 + 4) * 4, need_i = (n2 + 4) * 4, need_g = b_list + b_phi + b_scratch, need_j = b_res + b_shell + b_sums;
     if (n_sel == 0) {      // nothing to compute: nothing allocated or launched
         std::fill(resolution, resolution + n, 0.0);
-        std::fill(shell, shell + n, -1);
-        if (sums) std::fill(sums, sums + n * SH * 3, 0.0);
+        if (!scale) std::fill(shell, shell + n, -1);
+        if (sums) std::fill(sums, sums + n * n_per, 0.0);
         return MAD_OK;
     }
     {      // buffer by buffer: what each would have to grow by (a buffer that is released to grow gives its bytes back first)
@@ -445,7 +496,7 @@ static int map_local_fsc_run(mad_ctx *ctx, const float *g1, const int32_t *d1, c
             return mad_fail(ctx, MAD_ENOMEM, "%s: %zu samples of box %d need %zu MiB more device memory, %zu MiB are free", who, n, W, (grow - back) >> 20, free_b >> 20);
     }
     LrTab Tb;
-    MAD_TRY(lr_tables(ctx, W, &Tb));
+    MAD_TRY(lr_tables(ctx, W, scale, &Tb));
     MAD_TRY(mad_reserve(ctx, mad_sb(ctx, S_TMP_H), need_h));
     MAD_TRY(mad_reserve(ctx, mad_sb(ctx, S_TMP_I), need_i));
     MAD_TRY(mad_reserve(ctx, mad_sb(ctx, S_TMP_G), need_g));
@@ -455,7 +506,9 @@ static int map_local_fsc_run(mad_ctx *ctx, const float *g1, const int32_t *d1, c
     A.g1 = scratch<float>(ctx, S_TMP_H); A.g2 = scratch<float>(ctx, S_TMP_I);
     A.step = step; A.voxsp = voxsp; A.thr = thr;
     A.list = (const unsigned *)blk; A.phi = (const double2 *)(blk + b_list);
-    A.res = (double *)out; A.shell = (int *)(out + b_res); A.sums = sums ? (double *)(out + b_res + b_shell) : nullptr;
+    double *const d_res = (double *)out, *const d_sums = sums ? (double *)(out + b_res + b_shell) : nullptr;
+    if (scale) { A.out = d_res; A.gains = d_sums; }
+    else { A.res = d_res; A.shell = (int *)(out + b_res); A.sums = d_sums; }
     std::vector<double> h_phi((size_t)6 * W);
     for (int ax = 0; ax < 3; ax++)
         for (int a = 0; a < W; a++) {
@@ -470,30 +523,32 @@ static int map_local_fsc_run(mad_ctx *ctx, const float *g1, const int32_t *d1, c
         MAD_HIP(hipMemcpyAsync((void *)A.g1, g1, n1 * 4, hipMemcpyHostToDevice, ctx->stream));
         MAD_HIP(hipMemcpyAsync((void *)A.g2, g2, n2 * 4, hipMemcpyHostToDevice, ctx->stream));
         MAD_HIP(hipMemcpyAsync((void *)A.list, list.data(), n_sel * 4, hipMemcpyHostToDevice, ctx->stream));
-        MAD_HIP(hipMemcpyAsync((void *)A.phi, h_phi.data(), b_phi, hipMemcpyHostToDevice, ctx->stream));
-        if (n_sel < n) {      // what no box writes: 0.0, -1 and zero sums
-            MAD_HIP(hipMemsetAsync(A.res, 0, b_res, ctx->stream));
-            MAD_HIP(hipMemsetAsync(A.shell, 0xff, n * 4, ctx->stream));
-            if (sums) MAD_HIP(hipMemsetAsync(A.sums, 0, b_sums, ctx->stream));
+        if (!scale) MAD_HIP(hipMemcpyAsync((void *)A.phi, h_phi.data(), b_phi, hipMemcpyHostToDevice, ctx->stream));      // (amplitudes see no ramp)
+        if (n_sel < n) {      // what no box writes: 0.0, -1 and zero sums (or gains)
+            MAD_HIP(hipMemsetAsync(d_res, 0, b_res, ctx->stream));
+            if (!scale) MAD_HIP(hipMemsetAsync(A.shell, 0xff, n * 4, ctx->stream));
+            if (sums) MAD_HIP(hipMemsetAsync(d_sums, 0, b_sums, ctx->stream));
         }
-        mad_timer_begin(ctx, MAD_T_LOCALRES);
+        const int timer = scale ? MAD_T_LOCALSCALE : MAD_T_LOCALRES;
+        mad_timer_begin(ctx, timer);
         int rc = MAD_OK;
-        if (W == 8) rc = lr_launch_box<8>(ctx, A, Tb, n_sel);
-        else if (W == 16) rc = lr_launch_box<16>(ctx, A, Tb, n_sel);
+        if (W == 8) rc = scale ? lr_launch_box<8, true>(ctx, A, Tb, n_sel) : lr_launch_box<8, false>(ctx, A, Tb, n_sel);
+        else if (W == 16) rc = scale ? lr_launch_box<16, true>(ctx, A, Tb, n_sel) : lr_launch_box<16, false>(ctx, A, Tb, n_sel);
         else {
             for (size_t first = 0; first < n_sel; first += LR32_BATCH) {      // batch after batch on the stream, no host synchronisation
                 const unsigned nb = (unsigned)std::min<size_t>(LR32_BATCH, n_sel - first);
                 hipLaunchKernelGGL(k_lr32_planes, dim3(16, nb), dim3(64), 0, ctx->stream, A, Tb, (unsigned)first, Zb);
                 hipLaunchKernelGGL(k_lr32_xlines, dim3(16, nb), dim3(64), 0, ctx->stream, Tb, Zb);
-                hipLaunchKernelGGL(k_lr32_shells, dim3(nb), dim3(LR32_TAIL_THREADS), 0, ctx->stream, A, Tb, (unsigned)first, (const double2 *)Zb);
+                if (scale) hipLaunchKernelGGL(k_ls32_shells, dim3(nb), dim3(LR32_TAIL_THREADS), 0, ctx->stream, A, Tb, (unsigned)first, (const double2 *)Zb);
+                else hipLaunchKernelGGL(k_lr32_shells, dim3(nb), dim3(LR32_TAIL_THREADS), 0, ctx->stream, A, Tb, (unsigned)first, (const double2 *)Zb);
             }
         }
-        mad_timer_end(ctx, MAD_T_LOCALRES);
+        mad_timer_end(ctx, timer);
         if (rc != MAD_OK) return rc;
         MAD_HIP(hipGetLastError());
-        MAD_HIP(hipMemcpyAsync(resolution, A.res, n * 8, hipMemcpyDeviceToHost, ctx->stream));
-        MAD_HIP(hipMemcpyAsync(shell, A.shell, n * 4, hipMemcpyDeviceToHost, ctx->stream));
-        if (sums) MAD_HIP(hipMemcpyAsync(sums, A.sums, b_sums, hipMemcpyDeviceToHost, ctx->stream));
+        MAD_HIP(hipMemcpyAsync(resolution, d_res, n * 8, hipMemcpyDeviceToHost, ctx->stream));
+        if (!scale) MAD_HIP(hipMemcpyAsync(shell, A.shell, n * 4, hipMemcpyDeviceToHost, ctx->stream));
+        if (sums) MAD_HIP(hipMemcpyAsync(sums, d_sums, b_sums, hipMemcpyDeviceToHost, ctx->stream));
         MAD_HIP(hipStreamSynchronize(ctx->stream));
         return MAD_OK;
     };
@@ -508,7 +563,16 @@ extern "C" int mad_map_local_fsc(mad_ctx *ctx, const float *grid1, const int32_t
     if (ctx) mad_use_lane(ctx, 0);
     if (!ctx || !grid1 || !dims1 || !origin1 || !grid2 || !dims2 || !origin2 || !n_out || (resolution && !shell))
         return ctx ? mad_fail(ctx, MAD_EINVAL, "mad_map_local_fsc: NULL argument") : MAD_EINVAL;
-    const int rc = map_local_fsc_run(ctx, grid1, dims1, origin1, grid2, dims2, origin2, voxsp, box, step, threshold, select, resolution, shell,
-                                     sums, n_out);
+    const int rc = map_local_run(ctx, false, grid1, dims1, origin1, grid2, dims2, origin2, voxsp, box, step, threshold, select, resolution, shell,
+                                 sums, n_out);
     return rc;
+}
+
+extern "C" int mad_map_local_scale(mad_ctx *ctx, const float *grid1, const int32_t dims1[3], const double origin1[3], const float *grid2,
+                                   const int32_t dims2[3], const double origin2[3], double voxsp, int32_t box, int32_t step,
+                                   const uint8_t *select, double *out, double *gains, int32_t n_out[3]) {
+    if (ctx) mad_use_lane(ctx, 0);
+    if (!ctx || !grid1 || !dims1 || !origin1 || !grid2 || !dims2 || !origin2 || !n_out)
+        return ctx ? mad_fail(ctx, MAD_EINVAL, "mad_map_local_scale: NULL argument") : MAD_EINVAL;
+    return map_local_run(ctx, true, grid1, dims1, origin1, grid2, dims2, origin2, voxsp, box, step, 0.0, select, out, nullptr, gains, n_out);
 }

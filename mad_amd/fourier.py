@@ -3,6 +3,8 @@ The filters -- `filter_lattice`, `radial_gain`, the designs `gain_*` and the res
 further down, and so have the translation scan (section 4n): `scan_lattice`, the restatement `scan_numpy`, `peaks_numpy` and `Scan`,
 and the rotational search (section 4o): `rotation_set`, the restatements `rotate_numpy`, `tree_sum` and `search_numpy`, and `Search`,
 and local resolution (section 4p): `local_plan`, `hann_window`, the restatement `local_fsc_numpy` and `LocalResolution`;
+local amplitude scaling (section 4v): the restatement `local_scale_numpy`, `LocalScale`, and `scale_curve` / `gain_shells` of
+`Dmap.scale_to`;
 a low-pass by local resolution (section 4q): the restatements `local_sigma_numpy` and `local_filter_numpy`;
 the masked curve and its phase-randomised correction (section 4s): `splitmix_u`, the restatements `randomize_numpy` and
 `fsc_masked_numpy`, and `MaskedFSC`.
@@ -772,6 +774,132 @@ class LocalResolution(object):
         """The resolution volume as a map (.sit / .situs: Situs, anything else MRC) of spacing step voxsp at the map's origin."""
         from . import mapio
         mapio.write_volume(outname, np.ascontiguousarray(self.resolution, np.float32), tuple(self.origin), self.step * self.voxsp)
+
+
+# ---------------------------------------------------------------------------
+# local amplitude scaling (DESIGN.md section 4v): the contract of `mad_map_local_scale`
+#
+# Sample lattice, whole-voxel shift s, boxes and window are those of local resolution above: the corner of a sample's box is
+# step m - w / 2, so box index w / 2 on every axis is the sample's own voxel, and the window is exactly 1 there.  F1, F2 =
+# split_pair(fftn(w1 + 1j w2)).  Shells sh = min(shell_index(w), w / 2): the corner points beyond shell w / 2 ride with shell w / 2
+# (local resolution drops them), so that a map scaled against itself comes back unchanged.  P1_s, P2_s = the sums of |F1|^2, |F2|^2
+# over that binning; gain_s = sqrt(P2_s / P1_s) where P1_s > 0 and the quotient is finite, else 0.0;
+# out = Re ifftn(gain[sh] F1)[w / 2, w / 2, w / 2] = (1 / w^3) sum_s gain_s D_s, D_s = sum_{k in s} Re F1(k) (-1)^(a + b + c).
+# ---------------------------------------------------------------------------
+
+def scale_shells(w):
+    """int64 [w, w, w]: min(shell_index(w), w / 2), the binning of local amplitude scaling -- the corners ride with the last shell."""
+    return np.minimum(shell_index(w), w // 2)
+
+
+def centre_signs(w):
+    """float64 [w, w, w]: (-1)^(a + b + c) = exp(2 pi i k . (w / 2, w / 2, w / 2) / w), what the inverse transform multiplies the
+    point (a, b, c) by at the centre of the box."""
+    p = 1.0 - 2.0 * (np.arange(w) % 2)
+    return (p[:, None, None] * p[None, :, None]) * p[None, None, :]
+
+
+def scale_gains(P1, P2):
+    """gain = sqrt(P2 / P1) where P1 > 0 and the quotient is finite, else 0.0 (float64, any shape)."""
+    P1, P2 = np.asarray(P1, np.float64), np.asarray(P2, np.float64)
+    with np.errstate(divide="ignore", invalid="ignore", over="ignore"):
+        q = P2 / P1
+        ok = (P1 > 0) & np.isfinite(q)
+        return np.where(ok, np.sqrt(np.where(ok, q, 0.0)), 0.0)
+
+
+def local_scale_box(w1, w2):
+    """One box of local amplitude scaling: the windowed sub-cubes w1, w2 (float64 [w, w, w]) -> (out, gains [w / 2 + 1],
+    sums [w / 2 + 1, 3] = P1, P2, D per shell)."""
+    w = w1.shape[0]
+    F1, F2 = split_pair(np.fft.fftn(w1 + 1j * w2))
+    sh, n = scale_shells(w).ravel(), w // 2 + 1
+    sums = np.zeros((n, 3))
+    sums[:, 0] = np.bincount(sh, (F1.real ** 2 + F1.imag ** 2).ravel(), n)
+    sums[:, 1] = np.bincount(sh, (F2.real ** 2 + F2.imag ** 2).ravel(), n)
+    sums[:, 2] = np.bincount(sh, (F1.real * centre_signs(w)).ravel(), n)
+    gains = scale_gains(sums[:, 0], sums[:, 1])
+    return float((gains * sums[:, 2]).sum() / float(w) ** 3), gains, sums
+
+
+def local_scale_numpy(g1, o1, g2, o2, voxsp, box, step, select=None):
+    """The contract of `mad_map_local_scale` with numpy.fft.fftn in float64 -> `LocalScale` (with `gains` and `sums`).  The lattice,
+    the whole-voxel shift, the boxes and the window are `local_fsc_numpy`'s.  The sub-voxel rest `delta` of grid 2's placement is
+    NOT used: it is a phase ramp on F2, and amplitudes do not see a phase ramp -- a reference placed a whole voxel plus a fraction
+    off gives the bits of the whole-voxel placement.  `select`: anything that converts to a boolean array over the sample lattice,
+    None for every sample."""
+    g1, g2 = np.asarray(g1), np.asarray(g2)
+    if g1.ndim != 3 or g2.ndim != 3:
+        raise ValueError("local_scale_numpy: 3-D grids")
+    n, s, _ = local_plan(g1.shape, o1, g2.shape, o2, voxsp, box, step, 0.0)
+    w, step, voxsp = int(box), int(step), float(voxsp)
+    sel = np.ones(n, bool) if select is None else np.asarray(select).astype(bool).reshape(n)
+    h = hann_window(w)
+    H = (h[:, None, None] * h[None, :, None]) * h[None, None, :]
+    value, gains, sums = np.zeros(n), np.zeros(n + (w // 2 + 1,)), np.zeros(n + (w // 2 + 1, 3))
+    for m in np.argwhere(sel):
+        lo = [step * int(m[a]) - w // 2 for a in range(3)]
+        w1 = local_box(g1, lo, w) * H
+        w2 = local_box(g2, [lo[a] - s[a] for a in range(3)], w) * H
+        value[tuple(m)], gains[tuple(m)], sums[tuple(m)] = local_scale_box(w1, w2)
+    return LocalScale(value, sel, gains, w, step, voxsp, o1, sums=sums)
+
+
+class LocalScale(object):
+    """What `Dmap.scale_local` returns.  `value` float64 [nx, ny, nz]: per sample the map's density there after the sample's box
+    has been given the reference's power shell by shell, 0.0 where the sample was not selected; `computed` bool; `gains` float64
+    [nx, ny, nz, box / 2 + 1] (the factor every shell of the box's spectrum was multiplied by) or None; `sums` (the restatement
+    alone) float64 [nx, ny, nz, box / 2 + 1, 3] = P1, P2, D per shell, or None.  Sample (i, j, k) sits at `origin` +
+    step voxsp (i, j, k)."""
+
+    def __init__(self, value, computed, gains, box, step, voxsp, origin, sums=None):
+        self.value = np.asarray(value, np.float64)
+        self.computed = np.asarray(computed, bool).reshape(self.value.shape)
+        self.gains = None if gains is None else np.asarray(gains, np.float64)
+        self.sums = None if sums is None else np.asarray(sums, np.float64)
+        self.box, self.step, self.voxsp = int(box), int(step), float(voxsp)
+        self.origin = np.asarray(origin, np.float64).reshape(3).copy()
+
+    def gain(self, i, j, k):
+        """-> (freq [box / 2 + 1] in 1 / Angstrom: s / (box voxsp), gain [box / 2 + 1]) of the box of sample (i, j, k); needs
+        `gains`, and a sample that was computed."""
+        if self.gains is None:
+            raise ValueError("LocalScale.gain: made without gains (ask for gains=True)")
+        if not self.computed[i, j, k]:
+            raise ValueError("LocalScale.gain: sample (%d, %d, %d) was not selected" % (i, j, k))
+        return np.arange(self.box // 2 + 1) / (self.box * self.voxsp), self.gains[i, j, k].copy()
+
+    def to_dmap(self):
+        """The scaled values as a `Dmap` of spacing step voxsp at the map's origin (float32).  At step 1 that is the scaled map on
+        the map's own lattice; at a larger step `resample(like=map)` brings the coarser volume back onto it."""
+        from .Dmap import Dmap
+        d = Dmap.__new__(Dmap)
+        d.grid3d = np.ascontiguousarray(self.value, dtype=np.float32)
+        d.voxsp = self.step * self.voxsp
+        d.xi, d.yi, d.zi = (float(v) for v in self.origin)
+        d.xb, d.yb, d.zb = d.grid3d.shape
+        d.map_name, d.name = "", "local_scale"
+        return d
+
+    def write(self, outname):
+        """The scaled values as a map (.sit / .situs: Situs, anything else MRC) of spacing step voxsp at the map's origin."""
+        from . import mapio
+        mapio.write_volume(outname, np.ascontiguousarray(self.value, np.float32), tuple(self.origin), self.step * self.voxsp)
+
+
+def scale_curve(curve):
+    """-> (freq, gain) that brings the first map of an `FSC` to the second's power shell by shell: sqrt(power2 / power1), 0.0 where
+    power1 is 0 (`scale_gains`)."""
+    return curve.freq.copy(), scale_gains(curve.power1, curve.power2)
+
+
+def gain_shells(f, freq, gain):
+    """A per-shell curve `gain` over the equally spaced `freq` (1 / Angstrom, from 0) as a staircase: the value of the shell
+    nearest to f, floor(f / freq[1] + 0.5) -- the shell `shell_index` puts a lattice point of that frequency in --, the last
+    shell's beyond the curve's end."""
+    f, freq, gain = np.asarray(f, np.float64), np.asarray(freq, np.float64), np.asarray(gain, np.float64)
+    s = np.floor(f / freq[1] + 0.5).astype(np.int64)
+    return gain[np.clip(s, 0, len(gain) - 1)]
 
 
 # ---------------------------------------------------------------------------
