@@ -658,6 +658,43 @@ int mad_map_dust(mad_ctx *ctx, const float *grid, const int32_t dims[3], double 
                  int64_t min_size, int64_t keep, float fill, float *out /* may be grid */, int64_t counts[4] /* may be NULL */);
 
 /*
+ * A map's voxels sorted, its order statistics, and its confidence map: thresholds that control the false discovery rate (Beckers,
+ * Jakobi and Sachse, IUCrJ 2019) (mad_confidence.hip; mad_amd/confidence.py::sort_numpy / kth_numpy /
+ * confidence_numpy restate the contract).  Host pointers, synchronous, lane 0; grid is float32, read only; neither origin nor spacing
+ * enters.
+ *   Order.  The n values descending.  -0.0 counts as, and comes back as, +0.0: the output is a function of the values alone.  (A radix
+ *     sort of the keys only, 8 bits x 4 passes, stable; integer work throughout.)
+ * mad_map_sort writes out_desc[0 .. n) = the values in that order.  mad_map_kth writes out[i] = the k[i]-th largest value, 1-based:
+ * out_desc[k[i] - 1].
+ * mad_map_confidence, with N = the voxels of dims and s[0 .. N) = the values in that order:
+ *   Noise.  boxes[b] = {x, y, z, edge}: the cube of edge^3 voxels whose corner of least indices is (x, y, z), inside the grid.  The
+ *     samples are the voxels of box 0 in linear [x][y][z] order, then box 1, ... (a voxel in two boxes counts twice), n of them, as
+ *     float64.  mean = tree_sum(samples) / n, var = tree_sum((samples - mean)^2) / (n - 1), sd = sqrt(var); tree_sum is the fixed
+ *     pairing of mad_map_search (runs of 256 by halving, the partial sums the same way).  stats = {mean, var, n}.
+ *   p and q.  In float64, without fused multiply-add: t = ((double)s[j] - mean) / sd, p[j] = 0.5 erfc(t / sqrt 2),
+ *     r[j] = (p[j] (N c)) / (j + 1), q_sorted[j] = min(1, min over j' >= j of r[j']) -- the step-up rule of Benjamini and Hochberg
+ *     with c = 1 and of Benjamini and Yekutieli with c = 1 + 1/2 + ... + 1/N, which the caller passes.  q_sorted ascends with j, and
+ *     equal values have equal q.  Everything but erfc is correctly rounded arithmetic and minima: only the device's erfc can differ from
+ *     another library's.
+ *   Outputs.  out_q [x][y][z] (may be NULL) = q_sorted at a j with s[j] equal to the voxel; out_confidence [x][y][z] = (float)(1 - q);
+ *     out_sorted (may be NULL) = s; out_q_sorted (may be NULL).  Per level l < n_levels: out_level_count[l] = the number of j with
+ *     q_sorted[j] <= levels[l], out_level_value[l] = s[count - 1], the least density at which the rate is met, NaN where count is 0.
+ * The same call gives the same bits alone or after any other call.
+ * MAD_EINVAL, nothing launched or written: NULL (other than those named), n < 1 or a dimension < 1, 2^31 voxels or more, n_k < 1 or
+ * above 2^20, a rank below 1 or above n, n_boxes < 1 or above 4096, a box with edge < 1 or not inside the grid, fewer than 2 or 2^31
+ * and more samples, c not finite or below 1, n_levels < 0 or above 256, a level outside 0 .. 1.
+ * MAD_EDOM, nothing written: a voxel that is not finite (counted by the first pass over the map on the device); for
+ * mad_map_confidence also a variance of the samples that is not positive -- a map already masked to a constant has no noise in its
+ * corners: the caller must name boxes that lie in the solvent.
+ */
+int mad_map_sort(mad_ctx *ctx, const float *grid, int64_t n, float *out_desc);
+int mad_map_kth(mad_ctx *ctx, const float *grid, int64_t n, int64_t n_k, const int64_t *k, float *out);
+int mad_map_confidence(mad_ctx *ctx, const float *grid, const int32_t dims[3], int32_t n_boxes, const int32_t *boxes, double c,
+                       int32_t n_levels, const double *levels, float *out_confidence, double *out_q /* may be NULL */,
+                       float *out_sorted /* may be NULL */, double *out_q_sorted /* may be NULL */, int64_t *out_level_count,
+                       float *out_level_value, double stats[3] /* mean, var, n */);
+
+/*
  * Fourier shell correlation of two maps, and the 3-D transform under it (mad_fourier.hip; restated with numpy
  * in mad_amd/fourier.py).  Host pointers, synchronous, nothing modified but the outputs.  grid1, grid2: float32 [x][y][z] with
  * their dims and origins (Angstrom, centre of voxel (0,0,0)) and the common spacing voxsp.

@@ -714,6 +714,58 @@ class Dmap(object):
         self.grid3d = g
         return counts
 
+    def confidence(self, window=None, boxes=None, method="BY", fdr=(0.01,), details=False):
+        """The confidence map of Beckers, Jakobi and Sachse (IUCrJ 2019) -> `confidence.Confidence`; the map is untouched.  The noise
+        (mean and standard deviation) is measured in cubes of solvent: `boxes` (rows x, y, z of the corner and the edge, in voxels), or
+        by default four cubes of edge `window` at the middle of the low and high faces along x and along y
+        (`confidence.default_boxes`: window=None is a tenth of the shortest side -- a convention).  Every voxel becomes the one-sided
+        p-value of its density under that noise, and the p-values of all voxels become q-values that control the false discovery
+        rate: `method` "BY" (Benjamini-Yekutieli, valid under any dependence between voxels) or "BH" (Benjamini-Hochberg).  The
+        result holds `confidence` = 1 - q per voxel and `thresholds` = {rate: (density, voxels)} for every rate of `fdr`: the least
+        density whose q is at or below the rate -- a threshold for `envelope`, `components`, `segment`, ... that depends neither on
+        the map's scaling nor on the eye.  details=True keeps the sorted densities and their q-values.  DESIGN.md section 4w has the
+        exact contract."""
+        from . import confidence as CF
+        g = np.ascontiguousarray(self.grid3d, dtype=np.float32)
+        if g.ndim != 3 or g.size == 0:
+            raise ValueError("Dmap.confidence: the grid has shape %r" % (g.shape,))
+        if boxes is not None and window is not None:
+            raise ValueError("Dmap.confidence: give window= or boxes=, not both")
+        b = CF.default_boxes(g.shape, window) if boxes is None else CF.check_boxes("Dmap.confidence", g.shape, boxes)
+        rates = tuple(float(a) for a in np.atleast_1d(np.asarray(fdr, np.float64)))
+        if any(not 0.0 <= a <= 1.0 for a in rates):
+            raise ValueError("Dmap.confidence: fdr %r (false discovery rates, 0 .. 1)" % (fdr,))
+        r = _lib.get_lib().map_confidence(g, b, CF.method_constant(method, g.size), rates, want_q=True, details=details)
+        thresholds = dict((a, (float(v), int(n))) for a, v, n in zip(rates, r["value"], r["count"]))
+        return CF.Confidence(g, r["confidence"], r["q"], (self.xi, self.yi, self.zi), self.voxsp, r["mean"], r["var"], r["n"], b, method, thresholds,
+                             r.get("sorted"), r.get("q_sorted"))
+
+    def threshold_for(self, volume=None, mass=None, n_voxels=None, da_per_A3=0.81):
+        """The density above or at which the map holds a given amount -> float: the k-th largest voxel, with k = `n_voxels`, or
+        round(`volume` / voxsp^3) for a volume in cubic Angstrom, or that of the volume `mass` / `da_per_A3` for a molecular mass in
+        Dalton ("contour at the level that encloses the mass").  Exactly one of the three.  0.81 Da per cubic Angstrom (1.23 cubic
+        Angstrom per Dalton) is the usual figure for protein, a convention.  k below 1 or above the voxels of the map is refused."""
+        given = [v is not None for v in (volume, mass, n_voxels)]
+        if sum(given) != 1:
+            raise ValueError("Dmap.threshold_for: give exactly one of volume=, mass=, n_voxels=")
+        g = np.ascontiguousarray(self.grid3d, dtype=np.float32)
+        if n_voxels is not None:
+            if int(n_voxels) != n_voxels:
+                raise ValueError("Dmap.threshold_for: n_voxels %r (a whole number)" % (n_voxels,))
+            k = int(n_voxels)
+        else:
+            if mass is not None:
+                if not (float(da_per_A3) > 0) or not np.isfinite(float(da_per_A3)):
+                    raise ValueError("Dmap.threshold_for: da_per_A3 %r (positive and finite)" % (da_per_A3,))
+                volume = float(mass) / float(da_per_A3)
+            volume = float(volume)
+            if not np.isfinite(volume):
+                raise ValueError("Dmap.threshold_for: a volume of %r cubic Angstrom" % (volume,))
+            k = int(round(volume / float(self.voxsp) ** 3))
+        if k < 1 or k > g.size:
+            raise ValueError("Dmap.threshold_for: that is %d voxels of a map of %d (1 or more, and no more than the map holds)" % (k, g.size))
+        return float(_lib.get_lib().map_kth(g, [k])[0])
+
     def write_to_mrc(self, outname):
         mapio.write_mrc(outname, self.grid3d, (self.xi, self.yi, self.zi), self.voxsp)
 

@@ -42,7 +42,7 @@ SYMBOLS = [
     "mad_dist_unique_id", "mad_dist_init", "mad_dist_destroy", "mad_dist_info", "mad_dist_rehearse_flags", "mad_dist_or_allreduce", "mad_dist_allgather",
     "mad_dist_allgather_topk", "mad_dist_scratch", "mad_dist_copy",
     "mad_set_wire_bytes", "mad_set_export", "mad_set_import", "mad_set_lane", "mad_set_stream", "mad_set_bind_lane",
-    "mad_upload_density", "mad_refine", "mad_last_refine_plan", "mad_last_density_chunks", "mad_structure_to_density", "mad_ccc", "mad_map_mask", "mad_map_multiply", "mad_map_ccc", "mad_map_resample", "mad_map_zone", "mad_map_envelope", "mad_map_group_fit", "mad_map_qscore", "mad_map_smooth", "mad_map_segment", "mad_map_components", "mad_map_dust", "mad_map_fsc", "mad_map_fsc_masked", "mad_map_phase_randomize", "mad_map_fft", "mad_map_filter", "mad_map_ifft", "mad_map_scan", "mad_map_search", "mad_map_rotate", "mad_map_local_fsc", "mad_map_local_scale", "mad_map_local_filter", "mad_density_ccc", "mad_dock_refine_score", "mad_grid_overlap", "mad_overlap_matrix",
+    "mad_upload_density", "mad_refine", "mad_last_refine_plan", "mad_last_density_chunks", "mad_structure_to_density", "mad_ccc", "mad_map_mask", "mad_map_multiply", "mad_map_ccc", "mad_map_resample", "mad_map_zone", "mad_map_envelope", "mad_map_group_fit", "mad_map_qscore", "mad_map_smooth", "mad_map_segment", "mad_map_components", "mad_map_dust", "mad_map_sort", "mad_map_kth", "mad_map_confidence", "mad_map_fsc", "mad_map_fsc_masked", "mad_map_phase_randomize", "mad_map_fft", "mad_map_filter", "mad_map_ifft", "mad_map_scan", "mad_map_search", "mad_map_rotate", "mad_map_local_fsc", "mad_map_local_scale", "mad_map_local_filter", "mad_density_ccc", "mad_dock_refine_score", "mad_grid_overlap", "mad_overlap_matrix",
     "mad_space_create", "mad_space_destroy", "mad_space_build", "mad_space_info", "mad_space_download",
     "mad_space_peaks", "mad_space_patches", "mad_space_localize", "mad_localize_volume",
     "mad_pose_cluster_many",
@@ -1655,6 +1655,77 @@ class Lib(object):
         self._chk(self.dll.mad_map_dust(self.ctx, _p(g), _p(d), C.c_double(threshold), C.c_int32(ints[0]), C.c_int64(ints[1]),
                                         C.c_int64(ints[2]), C.c_float(float(fill)), _p(out), _p(counts)))
         return out, tuple(int(v) for v in counts)
+
+    @staticmethod
+    def _map_arg(who, g, ndim=None):
+        if not isinstance(g, np.ndarray) or g.dtype != np.float32 or not g.flags.c_contiguous:
+            raise ValueError("%s needs a C-contiguous float32 array" % who)
+        if ndim is not None and g.ndim != ndim:
+            raise ValueError("%s needs a %d-D grid" % (who, ndim))
+        if g.size < 1 or g.size >= 2 ** 31:
+            raise ValueError("%s: %d voxels (1 .. 2^31 - 1)" % (who, g.size))
+
+    def map_sort(self, g, out=None):
+        """The values of `g` (C-contiguous float32 of any shape, not modified) in descending order, -0.0 as +0.0 -> float32 [g.size]
+        (mad_map_sort; DESIGN.md section 4w: a radix sort of the keys on the device).  A voxel that is not finite is refused, and `out`
+        (a float32 array to take the result) then stays as it is."""
+        self._map_arg("map_sort", g)
+        if out is None:
+            out = np.empty(g.size, np.float32)
+        elif out.dtype != np.float32 or out.shape != (g.size,) or not out.flags.c_contiguous or not out.flags.writeable:
+            raise ValueError("map_sort: out must be a writable C-contiguous float32 array of g.size values")
+        self._chk(self.dll.mad_map_sort(self.ctx, _p(g), C.c_int64(g.size), _p(out)))
+        return out
+
+    def map_kth(self, g, k, out=None):
+        """The `k`-th largest values of `g` (C-contiguous float32 of any shape), 1-based: k = 1 the maximum, k = g.size the minimum; `k`
+        a whole number or several -> float32 [len(k)] (mad_map_kth)."""
+        self._map_arg("map_kth", g)
+        ka = np.atleast_1d(np.asarray(k))
+        if ka.ndim != 1 or len(ka) < 1 or not np.issubdtype(ka.dtype, np.integer):
+            raise ValueError("map_kth: ranks must be whole numbers, got %s %s" % (ka.dtype, ka.shape))
+        ka = _c(ka, np.int64)
+        if ka.min() < 1 or ka.max() > g.size:
+            raise ValueError("map_kth: ranks %d .. %d of %d voxels (1 is the largest)" % (ka.min(), ka.max(), g.size))
+        if out is None:
+            out = np.empty(len(ka), np.float32)
+        elif out.dtype != np.float32 or out.shape != (len(ka),) or not out.flags.c_contiguous or not out.flags.writeable:
+            raise ValueError("map_kth: out must be a writable C-contiguous float32 array of len(k) values")
+        self._chk(self.dll.mad_map_kth(self.ctx, _p(g), C.c_int64(g.size), C.c_int64(len(ka)), _p(ka), _p(out)))
+        return out
+
+    def map_confidence(self, g, boxes, c, levels=(0.01,), want_q=True, details=False, out=None):
+        """The confidence map of `g` (C-contiguous float32 [x, y, z], not modified): noise from the cubes `boxes` (whole numbers (n, 4):
+        x, y, z of the corner, edge; inside the grid), one-sided p-values under normal noise, q-values by the step-up rule with the
+        constant `c` (1: Benjamini-Hochberg; `confidence.harmonic(g.size)`: Benjamini-Yekutieli), and per false discovery rate of
+        `levels` the voxels whose q is at or below it and the least density among them (mad_map_confidence) ->
+        dict: `confidence` float32 (1 - q), `q` float64 (None unless want_q), `mean`, `var`, `n` of the noise, `count` int64 and `value`
+        float32 per level (NaN where count is 0), and with details=True `sorted` (float32, the densities descending) and `q_sorted`.
+        `out`: a float32 array of the grid's shape to take the confidence; it stays as it is when the call is refused."""
+        from .confidence import check_boxes
+        self._map_arg("map_confidence", g, 3)
+        b = _c(check_boxes("map_confidence", g.shape, boxes), np.int32)
+        c = float(c)
+        if not (c >= 1.0) or not np.isfinite(c):
+            raise ValueError("map_confidence: c = %r (1, or the harmonic number of the voxels)" % (c,))
+        lv = _c(np.atleast_1d(np.asarray(levels, np.float64)), np.float64)
+        if lv.ndim != 1 or len(lv) > 256 or not ((lv >= 0) & (lv <= 1)).all():
+            raise ValueError("map_confidence: levels %r (at most 256 false discovery rates, 0 .. 1)" % (levels,))
+        if out is None:
+            out = np.empty(g.shape, np.float32)
+        elif out.dtype != np.float32 or out.shape != g.shape or not out.flags.c_contiguous or not out.flags.writeable:
+            raise ValueError("map_confidence: out must be a writable C-contiguous float32 array of the grid's shape")
+        q = np.empty(g.shape, np.float64) if want_q else None
+        srt = np.empty(g.size, np.float32) if details else None
+        qs = np.empty(g.size, np.float64) if details else None
+        count, value, stats = np.zeros(max(len(lv), 1), np.int64), np.zeros(max(len(lv), 1), np.float32), np.zeros(3, np.float64)
+        d = np.array(g.shape, np.int32)
+        self._chk(self.dll.mad_map_confidence(self.ctx, _p(g), _p(d), C.c_int32(len(b)), _p(b), C.c_double(c), C.c_int32(len(lv)), _p(lv), _p(out),
+                                              _p(q), _p(srt), _p(qs), _p(count), _p(value), _p(stats)))
+        r = dict(confidence=out, q=q, mean=float(stats[0]), var=float(stats[1]), n=int(stats[2]), count=count[:len(lv)].copy(), value=value[:len(lv)].copy())
+        if details:
+            r.update(sorted=srt, q_sorted=qs)
+        return r
 
 
 _default = None

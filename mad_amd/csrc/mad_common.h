@@ -175,7 +175,7 @@ struct DevBuf {
 
 enum { MAD_T_ORIENT = 0, MAD_T_DESCRIBE, MAD_T_CORRELATE, MAD_T_PAIRS, MAD_T_POSE, MAD_T_TOPK, MAD_T_REFINE,
        MAD_T_DENSITY, MAD_T_CCC, MAD_T_SEG_PARENT, MAD_T_SEG_JUMP, MAD_T_SEG_SCAN, MAD_T_SEG_SMOOTH, MAD_T_FFT, MAD_T_FSC, MAD_T_FILTER, MAD_T_SCAN, MAD_T_SEARCH, MAD_T_LOCALRES, MAD_T_LOCALFILTER, MAD_T_LOCALSCALE,
-       MAD_T_ENV_Z, MAD_T_ENV_Y, MAD_T_ENV_X, MAD_T_ENV_WEIGHT, MAD_T_QSCORE, MAD_T_CC_TILE, MAD_T_CC_BORDER, MAD_T_CC_LABEL, MAD_T_CC_SELECT, MAD_T_COUNT };
+       MAD_T_ENV_Z, MAD_T_ENV_Y, MAD_T_ENV_X, MAD_T_ENV_WEIGHT, MAD_T_QSCORE, MAD_T_CF_SORT, MAD_T_CF_NOISE, MAD_T_CF_Q, MAD_T_CF_LOOKUP, MAD_T_CC_TILE, MAD_T_CC_BORDER, MAD_T_CC_LABEL, MAD_T_CC_SELECT, MAD_T_COUNT };
 
 #define MAD_T_RING 32
 #define MAD_LANES 8
