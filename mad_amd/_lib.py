@@ -12,42 +12,69 @@ import numpy as np
 _HERE = os.path.dirname(os.path.abspath(__file__))
 # MAD_LIB_PATH: another build of the same library (diagnostic builds with other compiler flags; tools/build_variant.sh)
 LIB_PATH = os.environ.get("MAD_LIB_PATH") or os.path.join(_HERE, "libmad_amd.so")
+# mirrors of include/mad_amd.h (tests/test_host.py compares each with the header's #define)
 RESULT_COLS = 23
-RANK_MAX_N, RANK_MAX_K, RANK_MAX_TOP, RANK_MAX_OUT = 96, 16, 512, 4096      # MAD_RANK_* of include/mad_amd.h
+RANK_MAX_N, RANK_MAX_K, RANK_MAX_TOP, RANK_MAX_OUT = 96, 16, 512, 4096      # MAD_RANK_*
 RANK_TOP, RANK_BELOW = 0, 1
 SHARD_MERGE_MAX = 8192      # MAD_SHARD_MERGE_MAX: records x k one workgroup of k_shard_merge sorts
 SHARD_FLAG_MISMATCH = 32    # MAD_SHARD_FLAG_MISMATCH
 DIST_ID_BYTES = 128         # MAD_DIST_ID_BYTES
 DIST_BUF_FLAGS, DIST_BUF_MINE, DIST_BUF_ALL, DIST_BUF_MERGED, DIST_BUF_WIRE, DIST_BUF_GATHER = range(6)      # MAD_DIST_BUF_*
-POSE_CLUSTER_MAX_N = 4096      # MAD_POSE_CLUSTER_MAX_N of include/mad_amd.h: rows of one match in pose_cluster_many
+POSE_CLUSTER_MAX_N = 4096      # MAD_POSE_CLUSTER_MAX_N: rows of one match in pose_cluster_many
+EINVAL, ENOMEM, ENOSPC, ENODEV, EDOM, EHIP = -22, -12, -28, -19, -33, -5      # MAD_E*
+ERRORS = {EINVAL: "EINVAL", ENOMEM: "ENOMEM", ENOSPC: "ENOSPC", ENODEV: "ENODEV", EDOM: "EDOM", EHIP: "EHIP"}
+# mirrors of headers under csrc/ (no test compares these)
 # wide sets (include/mad_amd.h; MAD_WIDE_* of csrc/mad_common.h): from this descriptor radius on a set's int8 rows hold count - WIDE_C
 WIDE_FROM_R = 11
 WIDE_C = 108
 WIDE_MAX = WIDE_C + 127
-
 QSCORE_CHUNK = 256          # QS_CHUNK of csrc/mad_qscore_plan.h: neighbours of one LDS chunk of k_qscore
 QSCORE_MAX_SHELLS, QSCORE_MAX_TRIES = 64, 64      # QS_MAX_R, QS_MAX_TRIES
+TAB_ZBINS, TAB_PBINS, TAB_BELTS = 2048, 2048, 4      # MAD_TAB_* of csrc/mad_common.h
 
-ERRORS = {-22: "EINVAL", -12: "ENOMEM", -28: "ENOSPC", -19: "ENODEV", -33: "EDOM", -5: "EHIP"}
-
-# every symbol include/mad_amd.h declares (tests check the library exports all of them)
-SYMBOLS = [
-    "mad_init", "mad_destroy", "mad_last_error", "mad_synchronize", "mad_stream", "mad_set_overlap",
-    "mad_timing_enable", "mad_timing_reset", "mad_timing_get", "mad_last_ms", "mad_probe_peaks",
-    "mad_set_eqsp", "mad_eqsp_tab_build", "mad_upload_field", "mad_upload_field_device", "mad_free_field", "mad_field_download",
-    "mad_set_orient_window", "mad_orient", "mad_describe", "mad_describe_sized", "mad_correlate", "mad_pose_score", "mad_topk",
-    "mad_set_create", "mad_set_destroy", "mad_set_build", "mad_set_build_many", "mad_set_load", "mad_set_mark_wide", "mad_set_is_wide", "mad_set_size", "mad_set_download",
-    "mad_match_topk", "mad_match_topk_many", "mad_match_topk_many_begin", "mad_match_topk_many_finish", "mad_match_topk_many_begin2", "mad_match_topk_many2", "mad_set_batching", "mad_set_option", "mad_last_pose_kernel", "mad_last_pose_selected", "mad_last_pose_plan", "mad_device_allocations", "mad_match_fetch", "mad_match_results", "mad_match_used",
-    "mad_match_shard_pairs", "mad_match_shard_topk", "mad_match_shard_begin", "mad_match_shard_score", "mad_match_shard_record_doubles", "mad_match_shard_collect", "mad_match_shard_wait", "mad_match_shard_merge",
-    "mad_dist_unique_id", "mad_dist_init", "mad_dist_destroy", "mad_dist_info", "mad_dist_rehearse_flags", "mad_dist_or_allreduce", "mad_dist_allgather",
-    "mad_dist_allgather_topk", "mad_dist_scratch", "mad_dist_copy",
-    "mad_set_wire_bytes", "mad_set_export", "mad_set_import", "mad_set_lane", "mad_set_stream", "mad_set_bind_lane",
-    "mad_upload_density", "mad_refine", "mad_last_refine_plan", "mad_last_density_chunks", "mad_structure_to_density", "mad_ccc", "mad_map_mask", "mad_map_multiply", "mad_map_ccc", "mad_map_resample", "mad_map_zone", "mad_map_envelope", "mad_map_group_fit", "mad_map_qscore", "mad_map_smooth", "mad_map_segment", "mad_map_components", "mad_map_dust", "mad_map_sort", "mad_map_kth", "mad_map_confidence", "mad_map_fsc", "mad_map_fsc_masked", "mad_map_phase_randomize", "mad_map_fft", "mad_map_filter", "mad_map_ifft", "mad_map_scan", "mad_map_search", "mad_map_rotate", "mad_map_local_fsc", "mad_map_local_scale", "mad_map_local_filter", "mad_density_ccc", "mad_dock_refine_score", "mad_grid_overlap", "mad_overlap_matrix",
-    "mad_space_create", "mad_space_destroy", "mad_space_build", "mad_space_info", "mad_space_download",
-    "mad_space_peaks", "mad_space_patches", "mad_space_localize", "mad_localize_volume",
-    "mad_pose_cluster_many",
-    "mad_rank_copies", "mad_rank_models", "mad_last_rank_plan",
-]
+# The C ABI, stated once: every function of include/mad_amd.h as name=return(arguments), one letter per type.  load_library() sets
+# restype and argtypes from it, so a call passes plain Python numbers and ctypes refuses a wrapper of another width.  A new function
+# of the header gets its entry here; tests/test_host.py parses the header and says where the two disagree.
+_CTYPE = {"p": C.c_void_p,      # any pointer: handles, arrays, byref results, ctypes arrays of pointers, None
+          "i": C.c_int,         # int, int32_t
+          "q": C.c_int64, "Q": C.c_uint64, "d": C.c_double, "f": C.c_float,
+          "s": C.c_char_p,      # const char *
+          "v": None}            # void (return only)
+PROTOTYPES = {entry[:entry.index("=")]: (entry[entry.index("=") + 1], tuple(entry[entry.index("(") + 1:-1])) for entry in """
+mad_init=i(ip) mad_destroy=v(p) mad_last_error=s(p) mad_synchronize=i(p) mad_stream=p(p) mad_set_overlap=i(pi)
+mad_timing_enable=i(pi) mad_timing_reset=i(p) mad_timing_get=i(pspp) mad_last_ms=d(ps) mad_probe_peaks=i(ppp)
+mad_set_eqsp=i(piippp) mad_eqsp_tab_build=i(pipp) mad_upload_field=i(pipppiii) mad_upload_field_device=i(pipiii)
+mad_free_field=i(pi) mad_field_download=i(pipp) mad_set_orient_window=i(pd) mad_orient=i(piipiiiippppppqp)
+mad_describe=i(piippqip) mad_describe_sized=i(piippqiip) mad_correlate=i(ppqpqidppppq) mad_pose_score=i(ppppqpppqpppqpqpqdpp)
+mad_topk=i(ppqqp) mad_set_create=i(pp) mad_set_destroy=v(pp) mad_set_build=i(pppppppiiii) mad_set_build_many=i(pipppppppiii)
+mad_set_mark_wide=i(ppi) mad_set_is_wide=i(pp) mad_set_load=i(ppqppppipppi) mad_set_size=i(pppp) mad_set_download=i(ppppppp)
+mad_match_topk=i(pppddqpppp) mad_match_topk_many=i(pippddqpppp) mad_match_topk_many_begin=i(pippddqpppp)
+mad_match_topk_many_finish=i(p) mad_match_topk_many_begin2=i(pippddqpppppp) mad_match_topk_many2=i(pippddqpppppp)
+mad_set_batching=i(pi) mad_set_option=i(psd) mad_last_pose_kernel=i(p) mad_last_pose_plan=i(pp) mad_last_pose_selected=q(p)
+mad_device_allocations=q(p) mad_match_fetch=i(pppppq) mad_match_results=i(ppppq) mad_match_used=i(ppipi)
+mad_upload_density=i(ppiiidddd) mad_refine=i(ppiqiddpp) mad_last_refine_plan=i(ppp) mad_last_density_chunks=i(p)
+mad_structure_to_density=i(pppqdddippp) mad_ccc=i(pppppppddp) mad_map_mask=i(pppppppd) mad_map_multiply=i(pppppppd)
+mad_map_ccc=i(ppppipppddp) mad_map_resample=i(ppppdppippdp) mad_map_zone=i(ppppdpqddip) mad_map_envelope=i(pppddddppp)
+mad_map_group_fit=i(pppppppdppiddpp) mad_map_qscore=i(ppppdpqpqppipippppp) mad_map_smooth=i(pppdp)
+mad_map_segment=i(pppdidqpppppqppp) mad_map_components=i(pppdipppqp) mad_map_dust=i(pppdiqqfpp) mad_map_sort=i(ppqp)
+mad_map_kth=i(ppqqpp) mad_map_confidence=i(pppipdipppppppp) mad_map_fsc=i(pppppppdpppq)
+mad_map_fsc_masked=i(pppppppdpppidQpppppp) mad_map_phase_randomize=i(ppiiQ) mad_map_fft=i(pppppppdpp)
+mad_map_filter=i(pppppipqppp) mad_map_ifft=i(ppip) mad_map_scan=i(pppippddidqpppppp) mad_map_search=i(ppppppipiddidqppppppp)
+mad_map_rotate=i(ppppipdpp) mad_map_local_fsc=i(pppppppdiidppppp) mad_map_local_scale=i(pppppppdiipppp)
+mad_map_local_filter=i(pppdppippp) mad_match_shard_pairs=i(pppqqdppp) mad_match_shard_topk=i(pppppdqppppp)
+mad_match_shard_record_doubles=q(q) mad_match_shard_begin=i(pppqqqdp) mad_match_shard_score=i(ppppdqp)
+mad_match_shard_collect=i(pppqp) mad_match_shard_wait=i(pipq) mad_match_shard_merge=i(pppiqp) mad_dist_unique_id=i(pp)
+mad_dist_init=i(piip) mad_dist_destroy=i(p) mad_dist_info=i(pppp) mad_dist_rehearse_flags=i(ppq) mad_dist_or_allreduce=i(pppq)
+mad_dist_allgather=i(ppppq) mad_dist_allgather_topk=i(ppppqp) mad_dist_scratch=i(piiqp) mad_dist_copy=i(pppqi)
+mad_set_wire_bytes=q(iq) mad_set_export=i(pppiq) mad_set_import=i(pppiiqppppi) mad_set_lane=i(pp) mad_set_stream=p(pp)
+mad_set_bind_lane=i(ppi) mad_density_ccc=i(pppiqdddp) mad_dock_refine_score=i(pipppippppidddddpppp)
+mad_grid_overlap=i(pppppppddpp) mad_overlap_matrix=i(ppppiddddp) mad_space_create=i(pp) mad_space_destroy=v(pp)
+mad_space_build=i(pppiiiiiippidpipppii) mad_space_info=i(pppppp) mad_space_download=i(ppiip) mad_space_peaks=i(ppidippqp)
+mad_space_patches=i(ppipiip) mad_space_localize=i(ppipippppp) mad_localize_volume=i(ppiiiipippppp)
+mad_pose_cluster_many=i(pippppdpppp) mad_rank_copies=i(ppiiidqqqpppppp) mad_rank_models=i(ppipiqqqqpppppp)
+mad_last_rank_plan=i(ppppp)
+""".split()}
+SYMBOLS = list(PROTOTYPES)      # every symbol include/mad_amd.h declares (tests check the library exports all of them)
 
 
 class MadBackendError(RuntimeError):
@@ -82,7 +109,7 @@ def _share_torch_hip_runtime():
 
 
 def load_library():
-    """dlopen the HIP library (works without a GPU; opening a device does not)."""
+    """dlopen the HIP library (works without a GPU; opening a device does not) and give every function of PROTOTYPES its types."""
     global _dll
     if _dll is None:
         if not os.path.exists(LIB_PATH):
@@ -91,28 +118,16 @@ def load_library():
                 "or `make -C mad_amd/csrc` (there is no CPU fallback)" % LIB_PATH)
         _share_torch_hip_runtime()
         try:
-            _dll = C.CDLL(LIB_PATH)
+            dll = C.CDLL(LIB_PATH)
         except OSError as e:
             raise MadBackendError("MaD> cannot load %s: %s" % (LIB_PATH, e))
-        _dll.mad_last_error.restype = C.c_char_p
-        _dll.mad_last_error.argtypes = [C.c_void_p]
-        _dll.mad_stream.restype = C.c_void_p
-        _dll.mad_stream.argtypes = [C.c_void_p]
-        _dll.mad_last_ms.restype = C.c_double
-        _dll.mad_last_ms.argtypes = [C.c_void_p, C.c_char_p]
-        _dll.mad_set_stream.restype = C.c_void_p
-        _dll.mad_set_stream.argtypes = [C.c_void_p, C.c_void_p]
-        _dll.mad_last_pose_selected.restype = C.c_int64
-        _dll.mad_last_pose_selected.argtypes = [C.c_void_p]
-        _dll.mad_device_allocations.restype = C.c_int64
-        _dll.mad_device_allocations.argtypes = [C.c_void_p]
-        _dll.mad_set_wire_bytes.restype = C.c_int64
-        _dll.mad_set_wire_bytes.argtypes = [C.c_int, C.c_int64]
-        _dll.mad_match_shard_record_doubles.restype = C.c_int64
-        _dll.mad_match_shard_record_doubles.argtypes = [C.c_int64]
-        _dll.mad_destroy.restype = None
-        _dll.mad_set_destroy.restype = None
-        _dll.mad_space_destroy.restype = None
+        for name, (ret, args) in PROTOTYPES.items():
+            try:
+                fn = getattr(dll, name)
+            except AttributeError:
+                raise MadBackendError("MaD> %s does not export %s, which include/mad_amd.h declares: rebuild it" % (LIB_PATH, name))
+            fn.restype, fn.argtypes = _CTYPE[ret], [_CTYPE[a] for a in args]
+        _dll = dll
     return _dll
 
 
@@ -124,9 +139,6 @@ class _PosePlanInfo(C.Structure):      # mad_pose_plan_info of include/mad_amd.h
                 ("bits_rad", C.c_double), ("bits_rad_in", C.c_double), ("lds64", C.c_int64), ("lds32", C.c_int64), ("lds32_hi", C.c_int64)]
 
 
-TAB_ZBINS, TAB_PBINS, TAB_BELTS = 2048, 2048, 4      # MAD_TAB_* of csrc/mad_common.h
-
-
 def eqsp_tab_build(bounds):
     """The table classifier of the 4-byte texels as the library builds it for the zone table `bounds` (Z x 4), on the host: no
     device is opened.  Returns (ok, zbelt[2048], ptab[4, 2048]) as uint8, 255 = undecided; ok is False when the zone table does
@@ -134,18 +146,84 @@ def eqsp_tab_build(bounds):
     dll = load_library()
     b = _c(bounds, np.float64).reshape(-1, 4)
     zbelt, ptab = np.empty(TAB_ZBINS, np.uint8), np.empty((TAB_BELTS, TAB_PBINS), np.uint8)
-    rc = dll.mad_eqsp_tab_build(_p(b), C.c_int(len(b)), _p(zbelt), _p(ptab))
+    rc = dll.mad_eqsp_tab_build(_p(b), len(b), _p(zbelt), _p(ptab))
     if rc < 0:
         raise ValueError("mad_eqsp_tab_build: %s" % ERRORS.get(rc, rc))
     return rc == 1, zbelt, ptab
 
 
+# -- arguments: what every wrapper checks and converts the same way ---------------------------------------------------------
 def _p(a):
+    """The address of an array, or NULL for None (the pointer keeps its array alive)."""
     return a.ctypes.data_as(C.c_void_p) if a is not None else None
 
 
 def _c(a, dt):
     return np.ascontiguousarray(a, dtype=dt)
+
+
+def _dims(g):
+    """The int32[3] shape argument of a grid."""
+    return np.array(g.shape, np.int32)
+
+
+def _vec(x, n):
+    """A contiguous float64[n]: origins, centres, R (9), T."""
+    return _c(np.asarray(x, np.float64).reshape(n), np.float64)
+
+
+def _grid(who, g, ndim=3, writable=False, what="grid"):
+    """`g` as the library reads it in place: a C-contiguous float32 array, `ndim`-dimensional (None: any), writable where the call
+    writes into it.  -> g"""
+    if not isinstance(g, np.ndarray) or g.dtype != np.float32 or not g.flags.c_contiguous or (writable and not g.flags.writeable):
+        raise ValueError("%s needs a %sC-contiguous float32 %s" % (who, "writable " if writable else "", what))
+    if ndim is not None and g.ndim != ndim:
+        raise ValueError("%s needs a %d-D %s" % (who, ndim, what))
+    return g
+
+
+def _placed(who, g, origin, writable=False, what="grid"):
+    """The three arguments (grid, dims[3], origin[3]) of a map with its place; three NULLs for a `g` of None."""
+    if g is None:
+        return None, None, None
+    return _p(_grid(who, g, writable=writable, what=what)), _p(_dims(g)), _p(_vec(origin, 3))
+
+
+def _countable(who, g):
+    if g.size < 1 or g.size >= 2 ** 31:
+        raise ValueError("%s: %d voxels (1 .. 2^31 - 1)" % (who, g.size))
+
+
+def _out(who, out, shape, dtype=np.float32, of="the grid's shape", new=np.empty, name="out"):
+    """The array a call fills: a fresh one, or the caller's `out` once it is a writable C-contiguous `dtype` array of `shape`."""
+    if out is None:
+        return new(shape, dtype)
+    if (not isinstance(out, np.ndarray) or out.dtype != dtype or out.shape != tuple(shape) or not out.flags.c_contiguous
+            or not out.flags.writeable):
+        raise ValueError("%s: %s must be a writable C-contiguous %s array of %s" % (who, name, np.dtype(dtype).name, of))
+    return out
+
+
+def _whole(who, name, v, lo=-2 ** 31, hi=2 ** 31):
+    """`v` as an int when it is a whole number in [lo, hi)."""
+    i = int(v)
+    if i != v or not lo <= i < hi:
+        raise ValueError("%s: %s %r" % (who, name, v))
+    return i
+
+
+def _retry_enospc(lib, call, cap, grow=True, slack=0):
+    """One C call whose tables may be too small: `call(cap)` makes it with tables of capacity `cap` and returns (rc, needed).  On
+    MAD_ENOSPC with needed > cap the call is made again at needed + slack; with grow=False (the caller fixed the capacity) it is
+    not, and the answer is False.  Any other failure raises.  -> True when the tables of the last call hold the result."""
+    while True:
+        rc, needed = call(cap)
+        if rc != ENOSPC or needed <= cap:
+            lib._chk(rc)
+            return True
+        if not grow:
+            return False
+        cap = needed + slack
 
 
 def _pad_rows(dsc, to=128):
@@ -190,9 +268,8 @@ class BuildBatch(object):
         self.lib.set_orient_window(self.gw_sig)      # the window is state of the context: every build states its own, as set_build does
         for s, n in zip(self.sets, self.counts):
             s.n_anchors = n
-        self.lib._chk(self.lib.dll.mad_set_build_many(self.lib.ctx, C.c_int(len(self.sets)), self._h, self._slots, self._coords, self._octave,
-                                                      self._subv, self._index, self._n, C.c_int(self.r), C.c_int(self.lim_main),
-                                                      C.c_int(self.lim_sec)))
+        self.lib._chk(self.lib.dll.mad_set_build_many(self.lib.ctx, len(self.sets), self._h, self._slots, self._coords, self._octave,
+                                                      self._subv, self._index, self._n, self.r, self.lim_main, self.lim_sec))
         return self.sets
 
 
@@ -216,7 +293,7 @@ class DeviceSet(object):
 
     def bind_lane(self, lane):
         """Put the set on lane `lane` (0..7): sets of one lane run in order on one stream.  Synchronises the context."""
-        self.lib._chk(self.lib.dll.mad_set_bind_lane(self.lib.ctx, self.h, C.c_int(int(lane))))
+        self.lib._chk(self.lib.dll.mad_set_bind_lane(self.lib.ctx, self.h, int(lane)))
 
     def stream(self):
         """The HIP stream (as an integer handle) the set's kernels are enqueued on."""
@@ -262,7 +339,7 @@ def _localize(lib, dtype, coords, call):
     status, coord = np.zeros(n, np.int32), np.zeros((n, 3), np.int32)
     H, G = np.zeros((n, 3, 3), dtype), np.zeros((n, 3), dtype)
     nu = C.c_int64(0)
-    lib._chk(call(_p(c), C.c_int(n), _p(status), _p(coord), _p(H), _p(G), C.byref(nu)))
+    lib._chk(call(_p(c), n, _p(status), _p(coord), _p(H), _p(G), C.byref(nu)))
     return status, coord, H, G, int(nu.value)
 
 
@@ -291,7 +368,7 @@ class DeviceSpace(object):
         g2 = np.ascontiguousarray(st.gaussian_kernel1d(sig_init, 2, R)[::-1])
         pre_R = st.kernel_radius(sig_presmooth) if (sig_presmooth and mode & 2) else 0
         pre = np.ascontiguousarray(st.gaussian_kernel1d(sig_presmooth, 0, pre_R)[::-1]) if pre_R else None
-        P3, I3 = C.c_void_p * 3, C.c_void_p * 3
+        P3 = C.c_void_p * 3
         lu = ev_w = ev_i = None
         keep = []
         if mode & 2 and min(g.shape) + 2 * pad >= 4:      # shorter lines: mad_space_build refuses them (MAD_EINVAL)
@@ -299,11 +376,10 @@ class DeviceSpace(object):
             keep = tabs
             lu = P3(*[t[0].ctypes.data for t in tabs])
             ev_w = P3(*[t[1].ctypes.data for t in tabs])
-            ev_i = I3(*[t[2].ctypes.data for t in tabs])
+            ev_i = P3(*[t[2].ctypes.data for t in tabs])
         self.lib._chk(self.lib.dll.mad_space_build(
-            self.lib.ctx, self.h, _p(g), C.c_int(1 if g.dtype == np.float64 else 0), C.c_int(g.shape[0]), C.c_int(g.shape[1]),
-            C.c_int(g.shape[2]), C.c_int(pad), C.c_int(mode), _p(g0), _p(g2), C.c_int(R), C.c_double(float(sig_init) ** 2),
-            _p(pre), C.c_int(pre_R), lu, ev_w, ev_i, C.c_int(slot_up), C.c_int(slot_base)))
+            self.lib.ctx, self.h, _p(g), 1 if g.dtype == np.float64 else 0, g.shape[0], g.shape[1], g.shape[2], pad, mode,
+            _p(g0), _p(g2), R, float(sig_init) ** 2, _p(pre), pre_R, lu, ev_w, ev_i, slot_up, slot_base))
         del keep
         n = C.c_int(0)
         dims, kind, f64 = np.zeros(6, np.int32), np.zeros(2, np.int32), np.zeros(2, np.int32)
@@ -319,23 +395,21 @@ class DeviceSpace(object):
 
     def download(self, entry, what):
         out = np.empty(self.shapes[entry], self.dtypes[entry])
-        self.lib._chk(self.lib.dll.mad_space_download(self.lib.ctx, self.h, C.c_int(entry), C.c_int(what), _p(out)))
+        self.lib._chk(self.lib.dll.mad_space_download(self.lib.ctx, self.h, entry, what, _p(out)))
         return out
 
     def peaks(self, entry, threshold=5e-2, border=12, cap0=1 << 16):
         """-> (coords int (n, 3), values float64 (n,)) in skimage's order: descending value, row-major among equals.
         A float32 entry compares with float32(threshold), as numpy does; cap0 is the first capacity tried (it grows on MAD_ENOSPC)."""
-        cap = int(cap0)
-        while True:
+        idx = val = None
+        n = C.c_int64(0)
+
+        def call(cap):
+            nonlocal idx, val
             idx, val = np.zeros(cap, np.int64), np.zeros(cap, np.float64)
-            n = C.c_int64(0)
-            rc = self.lib.dll.mad_space_peaks(self.lib.ctx, self.h, C.c_int(entry), C.c_double(threshold), C.c_int(border), _p(idx), _p(val),
-                                              C.c_int64(cap), C.byref(n))
-            if rc == -28 and n.value > cap:      # MAD_ENOSPC: n holds the required capacity
-                cap = int(n.value) + 1024
-                continue
-            self.lib._chk(rc)
-            break
+            return self.lib.dll.mad_space_peaks(self.lib.ctx, self.h, entry, threshold, border, _p(idx), _p(val), cap, C.byref(n)), n.value
+
+        _retry_enospc(self.lib, call, int(cap0), slack=1024)
         idx, val = idx[:n.value], val[:n.value]
         order = np.argsort(idx, kind="stable")              # row-major, like np.nonzero
         idx, val = idx[order], val[order]
@@ -349,7 +423,7 @@ class DeviceSpace(object):
         coords = _c(coords, np.int32).reshape(-1, 3)
         side = 2 * r + 1
         out = np.zeros((len(coords), side, side, side), self.dtypes[entry])
-        self.lib._chk(self.lib.dll.mad_space_patches(self.lib.ctx, self.h, C.c_int(entry), _p(coords), C.c_int(len(coords)), C.c_int(r), _p(out)))
+        self.lib._chk(self.lib.dll.mad_space_patches(self.lib.ctx, self.h, entry, _p(coords), len(coords), r, _p(out)))
         return out
 
     def localize(self, entry, coords):
@@ -359,8 +433,7 @@ class DeviceSpace(object):
         entry = int(entry)
         dtype = self.dtypes[entry] if 0 <= entry < len(self.dtypes) else np.float32      # a bad entry: MAD_EINVAL from the library
         return _localize(self.lib, dtype, coords,
-                         lambda c, n, st, co, H, G, nu: self.lib.dll.mad_space_localize(self.lib.ctx, self.h, C.c_int(entry), c, n,
-                                                                                       st, co, H, G, nu))
+                         lambda c, n, st, co, H, G, nu: self.lib.dll.mad_space_localize(self.lib.ctx, self.h, entry, c, n, st, co, H, G, nu))
 
     def close(self):
         if self.h and self.lib.ctx:
@@ -380,7 +453,7 @@ class Lib(object):
     def __init__(self, device=0):
         self.dll = load_library()
         self.ctx = C.c_void_p()
-        rc = self.dll.mad_init(C.c_int(device), C.byref(self.ctx))
+        rc = self.dll.mad_init(device, C.byref(self.ctx))
         if rc != 0:
             msg = self.dll.mad_last_error(None)
             self.ctx = None
@@ -412,21 +485,21 @@ class Lib(object):
 
     def set_overlap(self, on=True):
         """False: kernels of all lanes run one at a time (per-kernel timing); True (default): lanes overlap."""
-        self._chk(self.dll.mad_set_overlap(self.ctx, C.c_int(1 if on else 0)))
+        self._chk(self.dll.mad_set_overlap(self.ctx, 1 if on else 0))
 
     def timing_enable(self, on=True):
-        self._chk(self.dll.mad_timing_enable(self.ctx, C.c_int(1 if on else 0)))
+        self._chk(self.dll.mad_timing_enable(self.ctx, 1 if on else 0))
 
     def timing_reset(self):
         self._chk(self.dll.mad_timing_reset(self.ctx))
 
     def set_batching(self, on):
         """One GEMM launch for all matches of a `match_topk_many` bracket (True) or one per match (False, default)."""
-        self._chk(self.dll.mad_set_batching(self.ctx, C.c_int(1 if on else 0)))
+        self._chk(self.dll.mad_set_batching(self.ctx, 1 if on else 0))
 
     def set_option(self, name, value):
         """Tuning values that change speed, never results (`mad_set_option`)."""
-        self._chk(self.dll.mad_set_option(self.ctx, name.encode(), C.c_double(float(value))))
+        self._chk(self.dll.mad_set_option(self.ctx, name.encode(), float(value)))
 
     def probe_peaks(self):
         """(device copy GB/s, int8 MFMA TOP/s) measured now on this device (mad_probe_peaks)."""
@@ -445,14 +518,14 @@ class Lib(object):
         bounds = _c(bounds, np.float64)
         to_dom = None if to_dom is None else _c(to_dom, np.float64)
         adj_sec = None if adj_sec is None else _c(adj_sec, np.float64)
-        self._chk(self.dll.mad_set_eqsp(self.ctx, C.c_int(which), C.c_int(len(bounds)), _p(bounds), _p(to_dom), _p(adj_sec)))
+        self._chk(self.dll.mad_set_eqsp(self.ctx, which, len(bounds), _p(bounds), _p(to_dom), _p(adj_sec)))
 
     def set_orient_window(self, gw_sig=0.0):
         """Orientator(gw_sig): Gaussian window on the orientation histogram (0 = none) for the following `orient` calls.  The window is
         state of the context; `set_build`, `set_build_many` and `BuildBatch.run` set it themselves for every build (their `gw_sig`,
         default 0), so what is set here does not reach them.  A change of window waits for the device (mad_synchronize)."""
         if getattr(self, "_gw_sig", 0.0) != float(gw_sig):
-            self._chk(self.dll.mad_set_orient_window(self.ctx, C.c_double(float(gw_sig))))
+            self._chk(self.dll.mad_set_orient_window(self.ctx, float(gw_sig)))
             self._gw_sig = float(gw_sig)
 
     def new_slot(self):
@@ -473,8 +546,7 @@ class Lib(object):
         v = np.ascontiguousarray(v)
         return _localize(self, v.dtype.type, coords,
                          lambda c, n, st, co, H, G, nu: self.dll.mad_localize_volume(
-                             self.ctx, _p(v), C.c_int(1 if v.dtype == np.float64 else 0), C.c_int(v.shape[0]), C.c_int(v.shape[1]),
-                             C.c_int(v.shape[2]), c, n, st, co, H, G, nu))
+                             self.ctx, _p(v), 1 if v.dtype == np.float64 else 0, v.shape[0], v.shape[1], v.shape[2], c, n, st, co, H, G, nu))
 
     def upload_field(self, slot, grad):
         """grad: the reference's grad_list entry, shape (X, Y, Z, 3), any strides; or a (3, X, Y, Z) array."""
@@ -487,12 +559,11 @@ class Lib(object):
             raise ValueError("gradient field must be (X, Y, Z, 3) or (3, X, Y, Z)")
         planes = [_c(g[i], np.float32) for i in range(3)]
         nx, ny, nz = planes[0].shape
-        self._chk(self.dll.mad_upload_field(self.ctx, C.c_int(slot), _p(planes[0]), _p(planes[1]), _p(planes[2]),
-                                            C.c_int(nx), C.c_int(ny), C.c_int(nz)))
+        self._chk(self.dll.mad_upload_field(self.ctx, slot, _p(planes[0]), _p(planes[1]), _p(planes[2]), nx, ny, nz))
         self._field_dims[slot] = (nx, ny, nz)
 
     def upload_field_device(self, slot, dev_ptr, nx, ny, nz):
-        self._chk(self.dll.mad_upload_field_device(self.ctx, C.c_int(slot), C.c_void_p(dev_ptr), C.c_int(nx), C.c_int(ny), C.c_int(nz)))
+        self._chk(self.dll.mad_upload_field_device(self.ctx, slot, dev_ptr, nx, ny, nz))
         self._field_dims[slot] = (int(nx), int(ny), int(nz))
 
     def download_field(self, slot):
@@ -500,14 +571,14 @@ class Lib(object):
         -> (float32 (X, Y, Z, 4) {gx, gy, gz, |g|}, uint32 (X, Y, Z) packed 4-byte texels)."""
         dims = self._field_dims.get(slot)
         if dims is None:      # nothing known to be there: the library says so
-            self._chk(self.dll.mad_field_download(self.ctx, C.c_int(slot), None, None))
+            self._chk(self.dll.mad_field_download(self.ctx, slot, None, None))
             raise MadBackendError("MaD> download_field: the size of slot %d is unknown to this binding" % slot)
         tex, tex4 = np.empty(tuple(dims) + (4,), np.float32), np.empty(tuple(dims), np.uint32)
-        self._chk(self.dll.mad_field_download(self.ctx, C.c_int(slot), _p(tex), _p(tex4)))
+        self._chk(self.dll.mad_field_download(self.ctx, slot, _p(tex), _p(tex4)))
         return tex, tex4
 
     def free_field(self, slot):
-        self._chk(self.dll.mad_free_field(self.ctx, C.c_int(slot)))
+        self._chk(self.dll.mad_free_field(self.ctx, slot))
         self._field_dims.pop(slot, None)
         if slot not in self._free_slots:
             self._free_slots.append(slot)
@@ -522,9 +593,8 @@ class Lib(object):
         cnt = np.zeros((cap, Z), np.int32) if want_counts else None
         nrows = C.c_int64(0)
         nrej = C.c_int32(0)
-        self._chk(self.dll.mad_orient(self.ctx, C.c_int(slot), C.c_int(octave), _p(coords), C.c_int(n), C.c_int(r),
-                                      C.c_int(lim_main), C.c_int(lim_sec), _p(ra), _p(rm), _p(rs), _p(R), _p(cnt),
-                                      C.byref(nrows), C.c_int64(cap), C.byref(nrej)))
+        self._chk(self.dll.mad_orient(self.ctx, slot, octave, _p(coords), n, r, lim_main, lim_sec, _p(ra), _p(rm), _p(rs), _p(R), _p(cnt),
+                                      C.byref(nrows), cap, C.byref(nrej)))
         k = nrows.value
         return dict(anchor=ra[:k].copy(), main=rm[:k].copy(), sec=rs[:k].copy(), R=R[:k].reshape(k, 3, 3).copy(),
                     counts=None if cnt is None else cnt[:k].copy(), n_reject=nrej.value)
@@ -534,8 +604,7 @@ class Lib(object):
         R = _c(R, np.float64).reshape(-1, 9)
         n = len(coords)
         out = np.zeros((n, dsc_size * Zd), np.int16)
-        self._chk(self.dll.mad_describe_sized(self.ctx, C.c_int(slot), C.c_int(octave), _p(coords), _p(R), C.c_int64(n), C.c_int(r),
-                                              C.c_int(dsc_size), _p(out)))
+        self._chk(self.dll.mad_describe_sized(self.ctx, slot, octave, _p(coords), _p(R), n, r, dsc_size, _p(out)))
         return out
 
     def correlate(self, hi, lo, cc):
@@ -543,16 +612,14 @@ class Lib(object):
         n_hi, D = hi.shape
         n_lo = lo.shape[0]
         npairs = C.c_int64(0)
-        cap = 1 << 16
-        while True:
+        ph = pl = ps = None
+
+        def call(cap):
+            nonlocal ph, pl, ps
             ph, pl, ps = np.zeros(cap, np.int32), np.zeros(cap, np.int32), np.zeros(cap)
-            rc = self.dll.mad_correlate(self.ctx, _p(hi), C.c_int64(n_hi), _p(lo), C.c_int64(n_lo), C.c_int(D), C.c_double(cc),
-                                        _p(ph), _p(pl), _p(ps), C.byref(npairs), C.c_int64(cap))
-            if rc == -28:      # ENOSPC: the needed size came back in npairs
-                cap = npairs.value
-                continue
-            self._chk(rc)
-            break
+            return self.dll.mad_correlate(self.ctx, _p(hi), n_hi, _p(lo), n_lo, D, cc, _p(ph), _p(pl), _p(ps), C.byref(npairs), cap), npairs.value
+
+        _retry_enospc(self, call, 1 << 16)
         k = npairs.value
         return ph[:k].copy(), pl[:k].copy(), ps[:k].copy()
 
@@ -567,18 +634,16 @@ class Lib(object):
         n = len(pair_hi)
         res = np.zeros((n, RESULT_COLS)) if want_results else None
         cnt = np.zeros(n, np.int32)
-        self._chk(self.dll.mad_pose_score(self.ctx, _p(pair_hi), _p(pair_lo), _p(pair_score), C.c_int64(n),
-                                          _p(hi_p), _p(hi_R), _p(hi_meta), C.c_int64(len(hi_p)),
-                                          _p(lo_p), _p(lo_R), _p(lo_meta), C.c_int64(len(lo_p)),
-                                          _p(hi_cloud), C.c_int64(len(hi_cloud)), _p(lo_cloud), C.c_int64(len(lo_cloud)),
-                                          C.c_double(dist), _p(res), _p(cnt)))
+        self._chk(self.dll.mad_pose_score(self.ctx, _p(pair_hi), _p(pair_lo), _p(pair_score), n,
+                                          _p(hi_p), _p(hi_R), _p(hi_meta), len(hi_p), _p(lo_p), _p(lo_R), _p(lo_meta), len(lo_p),
+                                          _p(hi_cloud), len(hi_cloud), _p(lo_cloud), len(lo_cloud), dist, _p(res), _p(cnt)))
         return res, cnt
 
     def topk(self, counts, k):
         counts = _c(counts, np.int32)
         k = min(int(k), len(counts))
         order = np.zeros(max(k, 1), np.int64)
-        self._chk(self.dll.mad_topk(self.ctx, _p(counts), C.c_int64(len(counts)), C.c_int64(k), _p(order)))
+        self._chk(self.dll.mad_topk(self.ctx, _p(counts), len(counts), k, _p(order)))
         return order[:k]
 
     # -- device-resident pipeline -------------------------------------------------------
@@ -596,7 +661,7 @@ class Lib(object):
         anc_index = _c(anc_index, np.int32)
         s.n_anchors = len(anc_octave)
         self._chk(self.dll.mad_set_build(self.ctx, s.h, slots, _p(anc_coords), _p(anc_octave), _p(anc_subv), _p(anc_index),
-                                         C.c_int(len(anc_octave)), C.c_int(r), C.c_int(lim_main), C.c_int(lim_sec)))
+                                         len(anc_octave), r, lim_main, lim_sec))
         return s
 
     def prepare_build_many(self, jobs, r=8, lim_main=6, lim_sec=6, gw_sig=0.0):
@@ -613,7 +678,7 @@ class Lib(object):
         marked wide before the load (include/mad_amd.h, "Wide sets") and matches wide sets only."""
         s = DeviceSet(self)
         if wide:
-            self._chk(self.dll.mad_set_mark_wide(self.ctx, s.h, C.c_int(1)))
+            self._chk(self.dll.mad_set_mark_wide(self.ctx, s.h, 1))
         row_anchor, row_main = _c(row_anchor, np.int32), _c(row_main, np.int32)
         row_R = _c(row_R, np.float64).reshape(-1, 9)
         dsc = _c(dsc, np.int16)
@@ -623,9 +688,8 @@ class Lib(object):
         anc_subv = _c(anc_subv, np.float64).reshape(-1, 3)
         anc_index, anc_octave = _c(anc_index, np.int32), _c(anc_octave, np.int32)
         s.n_anchors = len(anc_index)
-        self._chk(self.dll.mad_set_load(self.ctx, s.h, C.c_int64(len(row_anchor)), _p(row_anchor), _p(row_main), _p(row_R),
-                                        _p(dsc), C.c_int(dsc.shape[1] if len(dsc) else 1024), _p(anc_subv), _p(anc_index),
-                                        _p(anc_octave), C.c_int(len(anc_index))))
+        self._chk(self.dll.mad_set_load(self.ctx, s.h, len(row_anchor), _p(row_anchor), _p(row_main), _p(row_R), _p(dsc),
+                                        dsc.shape[1] if len(dsc) else 1024, _p(anc_subv), _p(anc_index), _p(anc_octave), len(anc_index)))
         return s
 
     def match_topk(self, hi, lo, cc, dist, k):
@@ -634,24 +698,22 @@ class Lib(object):
         idx = np.zeros(max(k, 1), np.int64)
         n_out = C.c_int64(0)
         stats = np.zeros(4, np.int64)
-        self._chk(self.dll.mad_match_topk(self.ctx, hi.h, lo.h, C.c_double(cc), C.c_double(dist), C.c_int64(k), _p(res), _p(idx),
-                                          C.byref(n_out), _p(stats)))
+        self._chk(self.dll.mad_match_topk(self.ctx, hi.h, lo.h, cc, dist, k, _p(res), _p(idx), C.byref(n_out), _p(stats)))
         g = n_out.value
         return res[:g], idx[:g], dict(n_pairs=int(stats[0]), l_hi=int(stats[1]), l_lo=int(stats[2]), n_corr=int(stats[3]))
+
+    def _many_call(self, plain, with_used, his, lo, cc, dist, k, want_used):
+        """One bracket through `plain`, or with want_used through `with_used`, which also takes the two flag arrays -> its arrays."""
+        h = self._many_args(his, lo, k, want_used)
+        used = (_p(h["used_hi"]), _p(h["used_lo"])) if want_used else ()
+        self._chk((with_used if want_used else plain)(self.ctx, h["n"], h["arr"], lo.h, cc, dist, h["k"], _p(h["res"]), _p(h["idx"]),
+                                                      _p(h["n_out"]), _p(h["stats"]), *used))
+        return h
 
     def match_topk_many(self, his, lo, cc, dist, k, want_used=False):
         """[(rows, pair_index, stats)] for every subunit set of `his` against `lo`; see mad_match_topk_many.  want_used=True:
         [(rows, pair_index, stats, used_hi, used_lo)], each match's anchor-use flags as bool arrays (mad_match_topk_many2)."""
-        h = self._many_args(his, lo, k, want_used)
-        n = h["n"]
-        if want_used:
-            self._chk(self.dll.mad_match_topk_many2(self.ctx, C.c_int(n), h["arr"], lo.h, C.c_double(cc), C.c_double(dist), C.c_int64(h["k"]),
-                                                    _p(h["res"]), _p(h["idx"]), _p(h["n_out"]), _p(h["stats"]), _p(h["used_hi"]),
-                                                    _p(h["used_lo"])))
-        else:
-            self._chk(self.dll.mad_match_topk_many(self.ctx, C.c_int(n), h["arr"], lo.h, C.c_double(cc), C.c_double(dist), C.c_int64(h["k"]),
-                                                   _p(h["res"]), _p(h["idx"]), _p(h["n_out"]), _p(h["stats"])))
-        return self._many_unpack(h)
+        return self._many_unpack(self._many_call(self.dll.mad_match_topk_many, self.dll.mad_match_topk_many2, his, lo, cc, dist, k, want_used))
 
     @staticmethod
     def _many_args(his, lo, k, want_used):
@@ -710,15 +772,7 @@ class Lib(object):
         """Enqueue every match and return a handle; `match_topk_many_finish(handle)` waits and unpacks.  In between
         the caller may build the sets of its next batch (not the ones this bracket reads).  want_used=True: every match also
         hands back its anchor-use flags (mad_match_topk_many_begin2), and finish returns 5-tuples."""
-        h = self._many_args(his, lo, k, want_used)
-        n = h["n"]
-        if want_used:
-            self._chk(self.dll.mad_match_topk_many_begin2(self.ctx, C.c_int(n), h["arr"], lo.h, C.c_double(cc), C.c_double(dist),
-                                                          C.c_int64(h["k"]), _p(h["res"]), _p(h["idx"]), _p(h["n_out"]), _p(h["stats"]),
-                                                          _p(h["used_hi"]), _p(h["used_lo"])))
-        else:
-            self._chk(self.dll.mad_match_topk_many_begin(self.ctx, C.c_int(n), h["arr"], lo.h, C.c_double(cc), C.c_double(dist),
-                                                         C.c_int64(h["k"]), _p(h["res"]), _p(h["idx"]), _p(h["n_out"]), _p(h["stats"])))
+        h = self._many_call(self.dll.mad_match_topk_many_begin, self.dll.mad_match_topk_many_begin2, his, lo, cc, dist, k, want_used)
         self._open_brackets = getattr(self, "_open_brackets", []) + [h]      # at most three (MAD_BRACKETS); they finish in the order they began
         return h
 
@@ -734,8 +788,7 @@ class Lib(object):
         """Stage B of a sharded match -> (used_hi flags, used_lo flags, n_pairs) of the lo-row block [lo_begin, lo_end)."""
         used_hi, used_lo = np.zeros(max(hi.n_anchors, 1), np.uint8), np.zeros(max(lo.n_anchors, 1), np.uint8)
         n = C.c_int64(0)
-        self._chk(self.dll.mad_match_shard_pairs(self.ctx, hi.h, lo.h, C.c_int64(lo_begin), C.c_int64(lo_end), C.c_double(cc),
-                                                 _p(used_hi), _p(used_lo), C.byref(n)))
+        self._chk(self.dll.mad_match_shard_pairs(self.ctx, hi.h, lo.h, lo_begin, lo_end, cc, _p(used_hi), _p(used_lo), C.byref(n)))
         return used_hi[:hi.n_anchors], used_lo[:lo.n_anchors], n.value
 
     def match_shard_topk(self, hi, lo, used_hi_all, used_lo_all, dist, k):
@@ -745,40 +798,37 @@ class Lib(object):
         res = np.zeros((k, RESULT_COLS))
         rank, cnt = np.zeros(k, np.int64), np.zeros(k, np.int32)
         n, l_hi = C.c_int64(0), C.c_int64(0)
-        self._chk(self.dll.mad_match_shard_topk(self.ctx, hi.h, lo.h, _p(uh), _p(ul), C.c_double(dist), C.c_int64(k), _p(res), _p(rank),
-                                                _p(cnt), C.byref(n), C.byref(l_hi)))
+        self._chk(self.dll.mad_match_shard_topk(self.ctx, hi.h, lo.h, _p(uh), _p(ul), dist, k, _p(res), _p(rank), _p(cnt), C.byref(n),
+                                                C.byref(l_hi)))
         m = n.value
         return res[:m].copy(), cnt[:m].copy(), rank[:m].copy(), l_hi.value
 
     def match_shard_record_doubles(self, k):
-        return int(self.dll.mad_match_shard_record_doubles(C.c_int64(int(k))))
+        return int(self.dll.mad_match_shard_record_doubles(int(k)))
 
     def match_shard_begin(self, hi, lo, lo_begin, lo_end, n_lo, cc, flags_ptr):
         """Stage B, asynchronous on hi's lane: the shard's flags go to device memory at `flags_ptr` (hi.n_anchors + lo.n_anchors bytes)."""
-        self._chk(self.dll.mad_match_shard_begin(self.ctx, hi.h, lo.h, C.c_int64(int(lo_begin)), C.c_int64(int(lo_end)), C.c_int64(int(n_lo)),
-                                                 C.c_double(cc), C.c_void_p(int(flags_ptr))))
+        self._chk(self.dll.mad_match_shard_begin(self.ctx, hi.h, lo.h, int(lo_begin), int(lo_end), int(n_lo), cc, int(flags_ptr)))
 
     def match_shard_score(self, hi, lo, flags_all_ptr, dist, k, out_ptr):
         """Stage C, asynchronous: the shard's record (match_shard_record_doubles(k) float64) goes to device memory at `out_ptr`."""
-        self._chk(self.dll.mad_match_shard_score(self.ctx, hi.h, lo.h, C.c_void_p(int(flags_all_ptr)), C.c_double(dist), C.c_int64(int(k)),
-                                                 C.c_void_p(int(out_ptr))))
+        self._chk(self.dll.mad_match_shard_score(self.ctx, hi.h, lo.h, int(flags_all_ptr), dist, int(k), int(out_ptr)))
 
     def match_shard_collect(self, hi, all_ptr, n):
         """The n float64 at device address `all_ptr` on their way to the host, behind everything enqueued on hi's lane -> ticket."""
         t = C.c_int(0)
-        self._chk(self.dll.mad_match_shard_collect(self.ctx, hi.h, C.c_void_p(int(all_ptr)), C.c_int64(int(n)), C.byref(t)))
+        self._chk(self.dll.mad_match_shard_collect(self.ctx, hi.h, int(all_ptr), int(n), C.byref(t)))
         return t.value
 
     def match_shard_wait(self, ticket, n):
         out = np.zeros(int(n))
-        self._chk(self.dll.mad_match_shard_wait(self.ctx, C.c_int(int(ticket)), _p(out), C.c_int64(int(n))))
+        self._chk(self.dll.mad_match_shard_wait(self.ctx, int(ticket), _p(out), int(n)))
         return out
 
     def match_shard_merge(self, hi, all_ptr, nranks, k, merged_ptr):
         """k_shard_merge on hi's lane: the `nranks` records at device address `all_ptr` -> one record at `merged_ptr` (the order of
         dist.merge_topk).  nranks * k > SHARD_MERGE_MAX raises (EDOM)."""
-        self._chk(self.dll.mad_match_shard_merge(self.ctx, hi.h, C.c_void_p(int(all_ptr)), C.c_int(int(nranks)), C.c_int64(int(k)),
-                                                 C.c_void_p(int(merged_ptr))))
+        self._chk(self.dll.mad_match_shard_merge(self.ctx, hi.h, int(all_ptr), int(nranks), int(k), int(merged_ptr)))
 
     # -- the exchanges of a sharded step inside the library (mad_dist.hip; mad_amd/dist.py::LibComm drives them) ---------
     def dist_unique_id(self):
@@ -791,7 +841,7 @@ class Lib(object):
         """unique_id None: the rehearsal communicator (one rank of nranks alone on its GPU, RCCL not loaded)."""
         if unique_id is not None and len(unique_id) != DIST_ID_BYTES:
             raise ValueError("dist_init: a unique id has %d bytes" % DIST_ID_BYTES)
-        self._chk(self.dll.mad_dist_init(self.ctx, C.c_int(int(nranks)), C.c_int(int(rank)), C.c_char_p(unique_id) if unique_id is not None else None))
+        self._chk(self.dll.mad_dist_init(self.ctx, int(nranks), int(rank), unique_id))
 
     def dist_destroy(self):
         self._chk(self.dll.mad_dist_destroy(self.ctx))
@@ -803,37 +853,36 @@ class Lib(object):
         return n.value, r.value, bool(e.value)
 
     def dist_rehearse_flags(self, peer_ptr, n):
-        self._chk(self.dll.mad_dist_rehearse_flags(self.ctx, C.c_void_p(int(peer_ptr)) if peer_ptr else None, C.c_int64(int(n))))
+        self._chk(self.dll.mad_dist_rehearse_flags(self.ctx, int(peer_ptr) if peer_ptr else None, int(n)))
 
     def dist_or_allreduce(self, stream, flags_ptr, n):
-        self._chk(self.dll.mad_dist_or_allreduce(self.ctx, C.c_void_p(stream), C.c_void_p(int(flags_ptr)), C.c_int64(int(n))))
+        self._chk(self.dll.mad_dist_or_allreduce(self.ctx, stream, int(flags_ptr), int(n)))
 
     def dist_allgather(self, stream, send_ptr, recv_ptr, bytes_per_rank):
-        self._chk(self.dll.mad_dist_allgather(self.ctx, C.c_void_p(stream), C.c_void_p(int(send_ptr)), C.c_void_p(int(recv_ptr)), C.c_int64(int(bytes_per_rank))))
+        self._chk(self.dll.mad_dist_allgather(self.ctx, stream, int(send_ptr), int(recv_ptr), int(bytes_per_rank)))
 
     def dist_allgather_topk(self, hi, mine_ptr, all_ptr, k, merged_ptr):
-        self._chk(self.dll.mad_dist_allgather_topk(self.ctx, hi.h, C.c_void_p(int(mine_ptr)), C.c_void_p(int(all_ptr)), C.c_int64(int(k)),
-                                                   C.c_void_p(int(merged_ptr))))
+        self._chk(self.dll.mad_dist_allgather_topk(self.ctx, hi.h, int(mine_ptr), int(all_ptr), int(k), int(merged_ptr)))
 
     def dist_scratch(self, lane, which, nbytes):
         """Device address of the grow-only buffer `which` (DIST_BUF_*) of `lane`, at least nbytes long."""
         p = C.c_void_p()
-        self._chk(self.dll.mad_dist_scratch(self.ctx, C.c_int(int(lane)), C.c_int(int(which)), C.c_int64(int(nbytes)), C.byref(p)))
+        self._chk(self.dll.mad_dist_scratch(self.ctx, int(lane), int(which), int(nbytes), C.byref(p)))
         return int(p.value)
 
     def dist_upload(self, dev_ptr, array):
         """Host array -> device memory at `dev_ptr`, synchronous (set-up, rehearsals, tests)."""
         a = np.ascontiguousarray(array)
-        self._chk(self.dll.mad_dist_copy(self.ctx, C.c_void_p(int(dev_ptr)), _p(a), C.c_int64(a.nbytes), C.c_int(0)))
+        self._chk(self.dll.mad_dist_copy(self.ctx, int(dev_ptr), _p(a), a.nbytes, 0))
 
     def dist_download(self, dev_ptr, n, dtype=np.float64):
         out = np.zeros(int(n), dtype)
-        self._chk(self.dll.mad_dist_copy(self.ctx, _p(out), C.c_void_p(int(dev_ptr)), C.c_int64(out.nbytes), C.c_int(1)))
+        self._chk(self.dll.mad_dist_copy(self.ctx, _p(out), int(dev_ptr), out.nbytes, 1))
         return out
 
     # -- a structure's rows built in shares (SURVEY.md 8(e) stage A; the all-gather is mad_amd/dist.py's, or mad_dist_allgather) --------
     def set_wire_bytes(self, cap_rows, D=1024):
-        n = int(self.dll.mad_set_wire_bytes(C.c_int(int(D)), C.c_int64(int(cap_rows))))
+        n = int(self.dll.mad_set_wire_bytes(int(D), int(cap_rows)))
         if n < 0:
             raise ValueError("set_wire_bytes(%r, %r)" % (cap_rows, D))
         return n
@@ -842,14 +891,14 @@ class Lib(object):
         """Wire image of a built set.  device_ptr: address of device memory of set_wire_bytes(cap_rows) bytes (asynchronous
         on the set's stream); otherwise a host uint8 array is filled (and returned)."""
         if device_ptr is not None:
-            self._chk(self.dll.mad_set_export(self.ctx, share.h, C.c_void_p(int(device_ptr)), C.c_int(1), C.c_int64(int(cap_rows))))
+            self._chk(self.dll.mad_set_export(self.ctx, share.h, int(device_ptr), 1, int(cap_rows)))
             return None
         nbytes = self.set_wire_bytes(cap_rows)
         if wire is None:
             wire = np.zeros(nbytes, np.uint8)
         if wire.dtype != np.uint8 or wire.size != nbytes or not wire.flags.c_contiguous:
             raise ValueError("set_export: wire must be a contiguous uint8 array of %d bytes" % nbytes)
-        self._chk(self.dll.mad_set_export(self.ctx, share.h, _p(wire), C.c_int(0), C.c_int64(int(cap_rows))))
+        self._chk(self.dll.mad_set_export(self.ctx, share.h, _p(wire), 0, int(cap_rows)))
         return wire
 
     def set_import(self, n_shares, cap_rows, anc_coords, anc_octave, anc_subv, anc_index, wires=None, device_ptr=None, into=None):
@@ -864,31 +913,31 @@ class Lib(object):
         if len(anc_subv) != n or len(anc_index) != n or (anc_coords is not None and len(anc_coords) != n):
             raise ValueError("set_import: anchor arrays of different lengths")
         if device_ptr is not None:
-            src, on_dev = C.c_void_p(int(device_ptr)), 1
+            src, on_dev = int(device_ptr), 1
         else:
             wires = np.ascontiguousarray(wires, dtype=np.uint8)
             if wires.size != n_shares * self.set_wire_bytes(cap_rows):
                 raise ValueError("set_import: %d bytes for %d shares of %d" % (wires.size, n_shares, self.set_wire_bytes(cap_rows)))
             src, on_dev = _p(wires), 0
         s.n_anchors = n
-        self._chk(self.dll.mad_set_import(self.ctx, s.h, src, C.c_int(on_dev), C.c_int(int(n_shares)), C.c_int64(int(cap_rows)),
-                                          _p(anc_coords), _p(anc_octave), _p(anc_subv), _p(anc_index), C.c_int(n)))
+        self._chk(self.dll.mad_set_import(self.ctx, s.h, src, on_dev, int(n_shares), int(cap_rows), _p(anc_coords), _p(anc_octave),
+                                          _p(anc_subv), _p(anc_index), n))
         return s
 
     def match_fetch(self, n_pairs):
         ph, pl = np.zeros(n_pairs, np.int32), np.zeros(n_pairs, np.int32)
         ps, cn = np.zeros(n_pairs), np.zeros(n_pairs, np.int32)
-        self._chk(self.dll.mad_match_fetch(self.ctx, _p(ph), _p(pl), _p(ps), _p(cn), C.c_int64(n_pairs)))
+        self._chk(self.dll.mad_match_fetch(self.ctx, _p(ph), _p(pl), _p(ps), _p(cn), n_pairs))
         return ph, pl, ps, cn
 
     def match_results(self, hi, lo, n_pairs):
         res = np.zeros((max(n_pairs, 1), RESULT_COLS))
-        self._chk(self.dll.mad_match_results(self.ctx, hi.h, lo.h, _p(res), C.c_int64(n_pairs)))
+        self._chk(self.dll.mad_match_results(self.ctx, hi.h, lo.h, _p(res), n_pairs))
         return res[:n_pairs]
 
     def match_used(self, n_hi_anchors, n_lo_anchors):
         uh, ul = np.zeros(max(n_hi_anchors, 1), np.uint8), np.zeros(max(n_lo_anchors, 1), np.uint8)
-        self._chk(self.dll.mad_match_used(self.ctx, _p(uh), C.c_int32(n_hi_anchors), _p(ul), C.c_int32(n_lo_anchors)))
+        self._chk(self.dll.mad_match_used(self.ctx, _p(uh), n_hi_anchors, _p(ul), n_lo_anchors))
         return uh[:n_hi_anchors].astype(bool), ul[:n_lo_anchors].astype(bool)
 
     def pose_cluster_many(self, rows_list, clouds, n_samples_list, rmsd_thresh=10.0):
@@ -914,7 +963,7 @@ class Lib(object):
         n_done, status = np.zeros(max(nm, 1), np.int32), np.zeros(max(nm, 1), np.int32)
         PP = C.c_void_p * max(nm, 1)
         ptrs = [PP(*[a.ctypes.data if a.size else None for a in arrs]) for arrs in (rows, cl, owner, d2min)]
-        self._chk(self.dll.mad_pose_cluster_many(self.ctx, C.c_int(nm), ptrs[0], _p(n_rows), ptrs[1], _p(n_cloud), C.c_double(float(rmsd_thresh)),
+        self._chk(self.dll.mad_pose_cluster_many(self.ctx, nm, ptrs[0], _p(n_rows), ptrs[1], _p(n_cloud), float(rmsd_thresh),
                                                  ptrs[2], ptrs[3], _p(n_done), _p(status)))
         return [(owner[m], d2min[m], int(n_done[m]), int(status[m])) for m in range(nm)]
 
@@ -922,9 +971,9 @@ class Lib(object):
     def _rank_result(self, rc, width, idx, key, rank, n_out, n_total, status):
         """(status, entries, n_total) of a mad_rank_* call: status "ok" with entries = (idx [m][width], key [m], rank [m]), or
         "edom" / "enospc" / "budget" with entries None -- the three answers after which the caller runs the host loop."""
-        if rc == -33:
+        if rc == EDOM:
             return "edom", None, 0
-        if rc == -28:
+        if rc == ENOSPC:
             return "enospc", None, int(n_total.value)
         self._chk(rc)
         if status.value:
@@ -945,9 +994,9 @@ class Lib(object):
         idx, key, rank = np.zeros(room * max(c, 1), np.int32), np.zeros(room, np.float64), np.zeros(room, np.int64)
         n_out, n_total, status = C.c_int64(0), C.c_int64(0), C.c_int32(0)
         mode = RANK_TOP if max_overlap is None else RANK_BELOW
-        rc = self.dll.mad_rank_copies(self.ctx, _p(t), C.c_int(n), C.c_int(c), C.c_int(mode), C.c_double(0.0 if max_overlap is None else float(max_overlap)),
-                                      C.c_int64(min(cap, room)), C.c_int64(int(launch_items)), C.c_int64(int(budget)), _p(idx), _p(key), _p(rank),
-                                      C.byref(n_out), C.byref(n_total), C.byref(status))
+        rc = self.dll.mad_rank_copies(self.ctx, _p(t), n, c, mode, 0.0 if max_overlap is None else float(max_overlap), min(cap, room),
+                                      int(launch_items), int(budget), _p(idx), _p(key), _p(rank), C.byref(n_out), C.byref(n_total),
+                                      C.byref(status))
         return self._rank_result(rc, c, idx, key, rank, n_out, n_total, status)
 
     def rank_models(self, overlap, groups, cap, out_cap=None, launch_items=0, budget=0):
@@ -970,9 +1019,8 @@ class Lib(object):
         idx, key, rank = np.zeros(room * max(g, 1), np.int32), np.zeros(room, np.float64), np.zeros(room, np.int64)
         n_out, n_total, status = C.c_int64(0), C.c_int64(0), C.c_int32(0)
         first = np.array(first, np.int32)
-        rc = self.dll.mad_rank_models(self.ctx, _p(t), C.c_int(n), _p(first), C.c_int(g), C.c_int64(min(cap, room)), C.c_int64(room),
-                                      C.c_int64(int(launch_items)), C.c_int64(int(budget)), _p(idx), _p(key), _p(rank),
-                                      C.byref(n_out), C.byref(n_total), C.byref(status))
+        rc = self.dll.mad_rank_models(self.ctx, _p(t), n, _p(first), g, min(cap, room), room, int(launch_items), int(budget),
+                                      _p(idx), _p(key), _p(rank), C.byref(n_out), C.byref(n_total), C.byref(status))
         return self._rank_result(rc, g, idx, key, rank, n_out, n_total, status)
 
     def last_rank_plan(self):
@@ -991,8 +1039,7 @@ class Lib(object):
     def upload_density(self, grid, origin, voxsp):
         grid = _c(grid, np.float32)
         nx, ny, nz = grid.shape
-        self._chk(self.dll.mad_upload_density(self.ctx, _p(grid), C.c_int(nx), C.c_int(ny), C.c_int(nz),
-                                              C.c_double(origin[0]), C.c_double(origin[1]), C.c_double(origin[2]), C.c_double(voxsp)))
+        self._chk(self.dll.mad_upload_density(self.ctx, _p(grid), nx, ny, nz, origin[0], origin[1], origin[2], voxsp))
 
     def refine(self, coords, n_steps=500, max_step=0.5, min_step=0.01):
         """coords: (n_cand, n_atoms, 3) or (n_atoms, 3).  Returns (coords, converged[], last_step[])."""
@@ -1002,8 +1049,7 @@ class Lib(object):
             c = c[None]
         n_cand, n_atoms, _ = c.shape
         conv, last = np.zeros(n_cand, np.int32), np.zeros(n_cand, np.int32)
-        self._chk(self.dll.mad_refine(self.ctx, _p(c), C.c_int(n_cand), C.c_int64(n_atoms), C.c_int(n_steps),
-                                      C.c_double(max_step), C.c_double(min_step), _p(conv), _p(last)))
+        self._chk(self.dll.mad_refine(self.ctx, _p(c), n_cand, n_atoms, n_steps, max_step, min_step, _p(conv), _p(last)))
         if single:
             return c[0], bool(conv[0]), int(last[0])
         return c, conv.astype(bool), last
@@ -1023,8 +1069,7 @@ class Lib(object):
         atoms, mass = _c(atoms, np.float64), _c(mass, np.float64)
         dims = np.zeros(3, np.int32)
         org = np.zeros(3)
-        args = (self.ctx, _p(atoms), _p(mass), C.c_int64(len(atoms)), C.c_double(resolution), C.c_double(voxsp),
-                C.c_double(isovalue), C.c_int(pad), _p(dims), _p(org))
+        args = (self.ctx, _p(atoms), _p(mass), len(atoms), resolution, voxsp, isovalue, pad, _p(dims), _p(org))
         self._chk(self.dll.mad_structure_to_density(*args, None))
         grid = np.zeros(tuple(int(d) for d in dims), np.float32)
         self._chk(self.dll.mad_structure_to_density(*args, _p(grid)))
@@ -1039,8 +1084,7 @@ class Lib(object):
         n_cand, n_atoms, _ = c.shape
         mass = _c(mass, np.float64)
         out = np.zeros(n_cand, np.float64)
-        self._chk(self.dll.mad_density_ccc(self.ctx, _p(c), _p(mass), C.c_int(n_cand), C.c_int64(n_atoms), C.c_double(resolution),
-                                           C.c_double(density_isovalue), C.c_double(ccc_isovalue), _p(out)))
+        self._chk(self.dll.mad_density_ccc(self.ctx, _p(c), _p(mass), n_cand, n_atoms, resolution, density_isovalue, ccc_isovalue, _p(out)))
         return out
 
     def dock_refine_score(self, base_atoms, mass, hi_p, lo_p, rot, resolution, n_steps=500, max_step=0.5, min_step=0.01,
@@ -1065,10 +1109,9 @@ class Lib(object):
         flat = np.zeros((int(sizes.sum()), 3)) if want_coords else None
         conv, last = np.zeros(max(n_cand, 1), np.int32), np.zeros(max(n_cand, 1), np.int32)
         ccc = np.zeros(max(n_cand, 1))
-        self._chk(self.dll.mad_dock_refine_score(self.ctx, C.c_int(len(bases)), _p(base_all), _p(mass_all), _p(first), C.c_int(n_cand), _p(cs),
-                                                 _p(hi_p), _p(lo_p), _p(rot), C.c_int(int(n_steps)), C.c_double(max_step), C.c_double(min_step),
-                                                 C.c_double(resolution), C.c_double(density_isovalue), C.c_double(ccc_isovalue),
-                                                 _p(flat) if want_coords else None, _p(conv), _p(last), _p(ccc)))
+        self._chk(self.dll.mad_dock_refine_score(self.ctx, len(bases), _p(base_all), _p(mass_all), _p(first), n_cand, _p(cs),
+                                                 _p(hi_p), _p(lo_p), _p(rot), int(n_steps), max_step, min_step, resolution, density_isovalue,
+                                                 ccc_isovalue, _p(flat), _p(conv), _p(last), _p(ccc)))
         coords = None
         if want_coords:
             if many:
@@ -1080,14 +1123,9 @@ class Lib(object):
 
     def grid_overlap(self, g1, o1, g2, o2, voxsp, isovalue=1e-8):
         """-> (common, positives of g1); both grids (writable C-contiguous float32) are clamped in place."""
-        for g in (g1, g2):
-            if g.dtype != np.float32 or not g.flags.c_contiguous or not g.flags.writeable:
-                raise ValueError("grid_overlap needs writable C-contiguous float32 grids")
-        d1, d2 = np.array(g1.shape, np.int32), np.array(g2.shape, np.int32)
-        o1, o2 = _c(o1, np.float64), _c(o2, np.float64)
         common, npos = C.c_int64(0), C.c_int64(0)
-        self._chk(self.dll.mad_grid_overlap(self.ctx, _p(g1), _p(d1), _p(o1), _p(g2), _p(d2), _p(o2), C.c_double(voxsp),
-                                            C.c_double(isovalue), C.byref(common), C.byref(npos)))
+        self._chk(self.dll.mad_grid_overlap(self.ctx, *_placed("grid_overlap", g1, o1, True), *_placed("grid_overlap", g2, o2, True),
+                                            voxsp, isovalue, C.byref(common), C.byref(npos)))
         return common.value, npos.value
 
     def overlap_matrix(self, coords_list, mass_list, resolution=5.0, voxsp=2.0, density_isovalue=0.2, overlap_isovalue=1e-8):
@@ -1102,48 +1140,27 @@ class Lib(object):
         mass = _c(np.concatenate([np.asarray(m, np.float64).reshape(-1) for m in mass_list]), np.float64)
         if len(mass) != len(atoms):
             raise ValueError("overlap_matrix: %d masses for %d atoms" % (len(mass), len(atoms)))
-        self._chk(self.dll.mad_overlap_matrix(self.ctx, _p(atoms), _p(mass), _p(first), C.c_int(n), C.c_double(resolution),
-                                              C.c_double(voxsp), C.c_double(density_isovalue), C.c_double(overlap_isovalue), _p(out)))
+        self._chk(self.dll.mad_overlap_matrix(self.ctx, _p(atoms), _p(mass), _p(first), n, resolution, voxsp, density_isovalue,
+                                              overlap_isovalue, _p(out)))
         return out
 
     def ccc(self, g1, o1, g2, o2, voxsp, isovalue=0.0):
-        """Both grids must be C-contiguous float32; they are clamped in place like the reference."""
-        for g in (g1, g2):
-            if g.dtype != np.float32 or not g.flags.c_contiguous or not g.flags.writeable:
-                raise ValueError("ccc needs writable C-contiguous float32 grids")
-        d1, d2 = np.array(g1.shape, np.int32), np.array(g2.shape, np.int32)
-        o1, o2 = _c(o1, np.float64), _c(o2, np.float64)
+        """Both grids must be writable C-contiguous float32; they are clamped in place like the reference."""
         out = C.c_double(0)
-        self._chk(self.dll.mad_ccc(self.ctx, _p(g1), _p(d1), _p(o1), _p(g2), _p(d2), _p(o2), C.c_double(voxsp),
-                                   C.c_double(isovalue), C.byref(out)))
+        self._chk(self.dll.mad_ccc(self.ctx, *_placed("ccc", g1, o1, True), *_placed("ccc", g2, o2, True), voxsp, isovalue, C.byref(out)))
         return out.value
 
     def map_mask(self, g1, o1, mask, o2, voxsp):
         """Dmap.mask_with: g1 (writable C-contiguous float32) is zeroed in place outside `mask` and where `mask` is below 1e-8;
         the mask (C-contiguous float32) is only read."""
-        if g1.dtype != np.float32 or not g1.flags.c_contiguous or not g1.flags.writeable:
-            raise ValueError("map_mask needs a writable C-contiguous float32 grid")
-        if mask.dtype != np.float32 or not mask.flags.c_contiguous:
-            raise ValueError("map_mask needs a C-contiguous float32 mask")
-        if g1.ndim != 3 or mask.ndim != 3:
-            raise ValueError("map_mask needs 3-D grids")
-        d1, d2 = np.array(g1.shape, np.int32), np.array(mask.shape, np.int32)
-        o1, o2 = _c(o1, np.float64), _c(o2, np.float64)
-        self._chk(self.dll.mad_map_mask(self.ctx, _p(g1), _p(d1), _p(o1), _p(mask), _p(d2), _p(o2), C.c_double(voxsp)))
+        self._chk(self.dll.mad_map_mask(self.ctx, *_placed("map_mask", g1, o1, True), *_placed("map_mask", mask, o2, what="mask"), voxsp))
 
     def map_multiply(self, g1, o1, mask, o2, voxsp):
         """g1 (writable C-contiguous float32) times the soft mask (C-contiguous float32, only read) in place: the mask sits at the
         whole-voxel offset round(o2 / voxsp - o1 / voxsp), a voxel under a mask value of 1 keeps its bits, one outside the mask's
         box becomes +0 (mad_map_multiply)."""
-        if g1.dtype != np.float32 or not g1.flags.c_contiguous or not g1.flags.writeable:
-            raise ValueError("map_multiply needs a writable C-contiguous float32 grid")
-        if mask.dtype != np.float32 or not mask.flags.c_contiguous:
-            raise ValueError("map_multiply needs a C-contiguous float32 mask")
-        if g1.ndim != 3 or mask.ndim != 3:
-            raise ValueError("map_multiply needs 3-D grids")
-        d1, d2 = np.array(g1.shape, np.int32), np.array(mask.shape, np.int32)
-        o1, o2 = _c(np.asarray(o1, np.float64).reshape(3), np.float64), _c(np.asarray(o2, np.float64).reshape(3), np.float64)
-        self._chk(self.dll.mad_map_multiply(self.ctx, _p(g1), _p(d1), _p(o1), _p(mask), _p(d2), _p(o2), C.c_double(voxsp)))
+        self._chk(self.dll.mad_map_multiply(self.ctx, *_placed("map_multiply", g1, o1, True),
+                                            *_placed("map_multiply", mask, o2, what="mask"), voxsp))
 
     def map_envelope(self, g, voxsp, threshold, extend, soft, want_d2=False, out=None):
         """A soft mask from the map `g` (C-contiguous float32 [x, y, z], not modified) itself: 1 within `extend` Angstrom of a voxel
@@ -1151,19 +1168,11 @@ class Lib(object):
         core, edge)); d2, with `want_d2`, is the squared distance in voxels to the nearest seed, 2^31 - 1 beyond the window
         (mad_map_envelope).  `out`: a float32 array to take the mask instead of a new one; it stays as it is
         when the call is refused."""
-        if g.dtype != np.float32 or not g.flags.c_contiguous:
-            raise ValueError("map_envelope needs a C-contiguous float32 grid")
-        if g.ndim != 3:
-            raise ValueError("map_envelope needs a 3-D grid")
-        d = np.array(g.shape, np.int32)
-        if out is None:
-            out = np.empty(g.shape, np.float32)
-        elif out.dtype != np.float32 or out.shape != g.shape or not out.flags.c_contiguous or not out.flags.writeable:
-            raise ValueError("map_envelope: out must be a writable C-contiguous float32 array of the grid's shape")
+        _grid("map_envelope", g)
+        out = _out("map_envelope", out, g.shape)
         d2 = np.empty(g.shape, np.int32) if want_d2 else None
         counts = np.zeros(3, np.int64)
-        self._chk(self.dll.mad_map_envelope(self.ctx, _p(g), _p(d), C.c_double(voxsp), C.c_double(threshold), C.c_double(extend),
-                                            C.c_double(soft), _p(out), _p(d2), _p(counts)))
+        self._chk(self.dll.mad_map_envelope(self.ctx, _p(g), _p(_dims(g)), voxsp, threshold, extend, soft, _p(out), _p(d2), _p(counts)))
         return out, d2, (int(counts[0]), int(counts[1]), int(counts[2]))
 
     def map_ccc(self, g1, o1, seconds, voxsp, isovalue=0.0):
@@ -1171,67 +1180,42 @@ class Lib(object):
         All grids C-contiguous float32; none is modified."""
         seconds = list(seconds)
         for g in [g1] + [g for g, _ in seconds]:
-            if g.dtype != np.float32 or not g.flags.c_contiguous:
-                raise ValueError("map_ccc needs C-contiguous float32 grids")
-            if g.ndim != 3:
-                raise ValueError("map_ccc needs 3-D grids")
+            _grid("map_ccc", g)
         n = len(seconds)
         out = np.zeros(n, np.float64)
         if n == 0:
             return out
-        d1, o1 = np.array(g1.shape, np.int32), _c(o1, np.float64)
         d2 = np.array([g.shape for g, _ in seconds], np.int32).reshape(n, 3)
-        o2 = _c(np.array([np.asarray(o, np.float64).reshape(3) for _, o in seconds]), np.float64)
+        o2 = _c(np.array([_vec(o, 3) for _, o in seconds]), np.float64)
         ptrs = (C.c_void_p * n)(*[g.ctypes.data for g, _ in seconds])
-        self._chk(self.dll.mad_map_ccc(self.ctx, _p(g1), _p(d1), _p(o1), C.c_int(n), ptrs, _p(d2), _p(o2), C.c_double(voxsp),
-                                       C.c_double(isovalue), _p(out)))
+        self._chk(self.dll.mad_map_ccc(self.ctx, *_placed("map_ccc", g1, o1), n, ptrs, _p(d2), _p(o2), voxsp, isovalue, _p(out)))
         return out
 
     def map_resample(self, g, origin, voxsp, out_dims, out_origin, out_voxsp, R=None, T=None, order=3):
         """`g` (C-contiguous float32 [x, y, z] with `origin` and `voxsp`) sampled on the lattice (`out_dims`, `out_origin`,
         `out_voxsp`) -> a new float32 array.  `R`, `T` (both or neither) move the source first: a point x goes to x @ R + T.
         order 1 is trilinear, order 3 cubic B-spline interpolation; outside the source the result is 0 (mad_map_resample)."""
-        if g.dtype != np.float32 or not g.flags.c_contiguous:
-            raise ValueError("map_resample needs a C-contiguous float32 grid")
-        if g.ndim != 3:
-            raise ValueError("map_resample needs a 3-D grid")
-        d = np.array(g.shape, np.int32)
-        md = np.array([int(v) for v in out_dims], np.int64).reshape(3)
+        source = _placed("map_resample", g, origin)
+        md =np.array([int(v) for v in out_dims], np.int64).reshape(3)
         if np.any(md < -2 ** 31) or np.any(md >= 2 ** 31):
             raise ValueError("map_resample: out_dims %s" % (tuple(md),))
         md = md.astype(np.int32)
-        o, p = _c(np.asarray(origin, np.float64).reshape(3), np.float64), _c(np.asarray(out_origin, np.float64).reshape(3), np.float64)
-        Rp = None if R is None else _c(np.asarray(R, np.float64).reshape(9), np.float64)
-        Tp = None if T is None else _c(np.asarray(T, np.float64).reshape(3), np.float64)
+        Rp = None if R is None else _vec(R, 9)
+        Tp = None if T is None else _vec(T, 3)
         n_out = int(np.prod(np.maximum(md.astype(np.int64), 0)))
         out = np.empty(tuple(int(v) for v in md) if 0 < n_out < 2 ** 32 else (0,), np.float32)      # (a refused call writes nothing)
-        self._chk(self.dll.mad_map_resample(self.ctx, _p(g), _p(d), _p(o), C.c_double(voxsp), None if Rp is None else _p(Rp),
-                                            None if Tp is None else _p(Tp), C.c_int(order), _p(md), _p(p), C.c_double(out_voxsp), _p(out)))
+        self._chk(self.dll.mad_map_resample(self.ctx, *source, voxsp, _p(Rp), _p(Tp), order, _p(md),
+                                            _p(_vec(out_origin, 3)), out_voxsp, _p(out)))
         return out
-
-    @staticmethod
-    def _fourier_args(who, g1, o1, g2, o2):
-        for g in (g1, g2):
-            if g is None:
-                continue
-            if g.dtype != np.float32 or not g.flags.c_contiguous:
-                raise ValueError("%s needs C-contiguous float32 grids" % who)
-            if g.ndim != 3:
-                raise ValueError("%s needs 3-D grids" % who)
-        d1, o1 = np.array(g1.shape, np.int32), _c(np.asarray(o1, np.float64).reshape(3), np.float64)
-        d2 = None if g2 is None else np.array(g2.shape, np.int32)
-        o2 = None if g2 is None else _c(np.asarray(o2, np.float64).reshape(3), np.float64)
-        return d1, o1, d2, o2
 
     def map_fsc(self, g1, o1, g2, o2, voxsp):
         """Fourier shell correlation sums of two maps of one spacing -> (N, sums float64 [N / 2 + 1, 3] = P1, P2, C per shell,
         count int64 [N / 2 + 1]) (mad_map_fsc; `fourier.FSC(N, voxsp, sums, count)` makes the curve).
         Both grids C-contiguous float32 [x, y, z]; neither is modified."""
-        d1, o1, d2, o2 = self._fourier_args("map_fsc", g1, o1, g2, o2)
         cap = 1024 // 2 + 1
         n, sums, count = C.c_int32(0), np.zeros((cap, 3), np.float64), np.zeros(cap, np.int64)
-        self._chk(self.dll.mad_map_fsc(self.ctx, _p(g1), _p(d1), _p(o1), _p(g2), _p(d2), _p(o2), C.c_double(voxsp), C.byref(n),
-                                       _p(sums), _p(count), C.c_int64(cap)))
+        self._chk(self.dll.mad_map_fsc(self.ctx, *_placed("map_fsc", g1, o1), *_placed("map_fsc", g2, o2), voxsp, C.byref(n),
+                                       _p(sums), _p(count), cap))
         sh = n.value // 2 + 1
         return int(n.value), sums[:sh].copy(), count[:sh].copy()
 
@@ -1241,8 +1225,9 @@ class Lib(object):
         randomised from shell `shell_r` on, or with None from the lowest shell whose unmasked curve is below `t_r`
         (mad_map_fsc_masked; `fourier.fsc_masked_numpy` restates it, `fourier.MaskedFSC` makes the curves).
         All three grids C-contiguous float32 [x, y, z]; none is modified."""
-        d1, o1, d2, o2 = self._fourier_args("map_fsc_masked", g1, o1, g2, o2)
-        dm, om, _, _ = self._fourier_args("map_fsc_masked", mask, om, None, None)
+        who = "map_fsc_masked"
+        maps = _placed(who, g1, o1) + _placed(who, g2, o2) + (voxsp,)
+        masked = _placed(who, mask, om)
         seed = int(seed)
         if not 0 <= seed < 2 ** 64:
             raise ValueError("map_fsc_masked: seed %r (0 .. 2^64 - 1)" % (seed,))
@@ -1250,12 +1235,11 @@ class Lib(object):
         if shell_r is not None and not 0 <= sr < 2 ** 31:
             raise ValueError("map_fsc_masked: shell_r %r (0 or more, or None)" % (shell_r,))
         n = C.c_int32(0)
-        self._chk(self.dll.mad_map_fft(self.ctx, _p(g1), _p(d1), _p(o1), _p(g2), _p(d2), _p(o2), C.c_double(voxsp), C.byref(n), None))
+        self._chk(self.dll.mad_map_fft(self.ctx, *maps, C.byref(n), None))
         sh = n.value // 2 + 1
         su, sm, sr_sums, count = np.zeros((sh, 3)), np.zeros((sh, 3)), np.zeros((sh, 3)), np.zeros(sh, np.int64)
         got = C.c_int32(0)
-        self._chk(self.dll.mad_map_fsc_masked(self.ctx, _p(g1), _p(d1), _p(o1), _p(g2), _p(d2), _p(o2), C.c_double(voxsp), _p(mask), _p(dm), _p(om),
-                                              C.c_int32(sr), C.c_double(float(t_r)), C.c_uint64(seed), _p(su), _p(sm), _p(sr_sums), _p(count),
+        self._chk(self.dll.mad_map_fsc_masked(self.ctx, *maps, *masked, sr, float(t_r), seed, _p(su), _p(sm), _p(sr_sums), _p(count),
                                               C.byref(n), C.byref(got)))
         return int(n.value), su, sm, sr_sums, count, int(got.value)
 
@@ -1268,28 +1252,32 @@ class Lib(object):
         seed = int(seed)
         if not 0 <= seed < 2 ** 64:
             raise ValueError("map_phase_randomize: seed %r (0 .. 2^64 - 1)" % (seed,))
-        self._chk(self.dll.mad_map_phase_randomize(self.ctx, _p(s), C.c_int32(s.shape[0]), C.c_int32(int(shell_r)), C.c_uint64(seed)))
+        self._chk(self.dll.mad_map_phase_randomize(self.ctx, _p(s), s.shape[0], int(shell_r), seed))
         return s
+
+    @staticmethod
+    def _selection(who, select, shape):
+        """`select` over the sample lattice of `shape` as the uint8 flags the library reads, or None."""
+        if select is None:
+            return None
+        sel = np.ascontiguousarray(np.asarray(select) != 0, dtype=np.uint8)
+        if sel.shape != shape:
+            raise ValueError("%s: select of shape %r, the sample lattice is %r" % (who, sel.shape, shape))
+        return sel
 
     def map_local_fsc(self, g1, o1, g2, o2, voxsp, box=16, step=2, threshold=0.143, select=None, sums=False):
         """Local resolution by windowed Fourier shell correlation -> (resolution float64 [nx, ny, nz], shell int32 [nx, ny, nz],
         sums float64 [nx, ny, nz, box / 2 + 1, 3] or None) over the samples at every `step`-th voxel of `g1` (mad_map_local_fsc;
         DESIGN.md section 4p; `fourier.local_fsc_numpy` restates it).  `select`: an array over the sample lattice, a sample where it
         is 0 gets 0.0 / -1 and is not computed.  Both grids C-contiguous float32 [x, y, z]; neither is modified."""
-        d1, o1, d2, o2 = self._fourier_args("map_local_fsc", g1, o1, g2, o2)
         n = np.zeros(3, np.int32)
-        args = (self.ctx, _p(g1), _p(d1), _p(o1), _p(g2), _p(d2), _p(o2), C.c_double(voxsp), C.c_int32(int(box)), C.c_int32(int(step)),
-                C.c_double(float(threshold)))
+        args = (self.ctx,) + _placed("map_local_fsc", g1, o1) + _placed("map_local_fsc", g2, o2) + (voxsp, int(box), int(step), float(threshold))
         self._chk(self.dll.mad_map_local_fsc(*args, None, None, None, None, _p(n)))      # the size query
         shape = tuple(int(v) for v in n)
-        sel = None
-        if select is not None:
-            sel = np.ascontiguousarray(np.asarray(select) != 0, dtype=np.uint8)
-            if sel.shape != shape:
-                raise ValueError("map_local_fsc: select of shape %r, the sample lattice is %r" % (sel.shape, shape))
+        sel = self._selection("map_local_fsc", select, shape)
         res, shell = np.empty(shape, np.float64), np.empty(shape, np.int32)
         sm = np.empty(shape + (int(box) // 2 + 1, 3), np.float64) if sums else None
-        self._chk(self.dll.mad_map_local_fsc(*args, None if sel is None else _p(sel), _p(res), _p(shell), None if sm is None else _p(sm), _p(n)))
+        self._chk(self.dll.mad_map_local_fsc(*args, _p(sel), _p(res), _p(shell), _p(sm), _p(n)))
         return res, shell, sm
 
     def map_local_scale(self, g1, o1, g2, o2, voxsp, box=16, step=1, select=None, gains=False):
@@ -1297,19 +1285,14 @@ class Lib(object):
         gains float64 [nx, ny, nz, box / 2 + 1] or None) over the samples at every `step`-th voxel of `g1` (mad_map_local_scale;
         DESIGN.md section 4v; `fourier.local_scale_numpy` restates it).  `select`: an array over the sample lattice, a sample where
         it is 0 gets 0.0 and is not computed.  Both grids C-contiguous float32 [x, y, z]; neither is modified."""
-        d1, o1, d2, o2 = self._fourier_args("map_local_scale", g1, o1, g2, o2)
         n = np.zeros(3, np.int32)
-        args = (self.ctx, _p(g1), _p(d1), _p(o1), _p(g2), _p(d2), _p(o2), C.c_double(voxsp), C.c_int32(int(box)), C.c_int32(int(step)))
+        args = (self.ctx,) + _placed("map_local_scale", g1, o1) + _placed("map_local_scale", g2, o2) + (voxsp, int(box), int(step))
         self._chk(self.dll.mad_map_local_scale(*args, None, None, None, _p(n)))      # the size query
         shape = tuple(int(v) for v in n)
-        sel = None
-        if select is not None:
-            sel = np.ascontiguousarray(np.asarray(select) != 0, dtype=np.uint8)
-            if sel.shape != shape:
-                raise ValueError("map_local_scale: select of shape %r, the sample lattice is %r" % (sel.shape, shape))
+        sel = self._selection("map_local_scale", select, shape)
         value = np.empty(shape, np.float64)
         gn = np.empty(shape + (int(box) // 2 + 1,), np.float64) if gains else None
-        self._chk(self.dll.mad_map_local_scale(*args, None if sel is None else _p(sel), _p(value), None if gn is None else _p(gn), _p(n)))
+        self._chk(self.dll.mad_map_local_scale(*args, _p(sel), _p(value), _p(gn), _p(n)))
         return value, (np.ones(shape, bool) if sel is None else sel.astype(bool)), gn
 
     def map_local_filter(self, grid, res, step, voxsp, out=None, out64=False, sigma=False):
@@ -1319,32 +1302,22 @@ class Lib(object):
         `fourier.local_filter_numpy` restates it).  -> the float32 result (a new array, or `out`, which may be `grid` itself); with
         `out64` and / or `sigma` a tuple (out, out64 or None, sigma or None): the float64 result before rounding and the per-voxel
         sigma in voxels.  The results do not depend on which of the two were asked for."""
-        if not isinstance(grid, np.ndarray) or grid.dtype != np.float32 or not grid.flags.c_contiguous:
-            raise ValueError("map_local_filter needs a C-contiguous float32 grid")
-        if grid.ndim != 3:
-            raise ValueError("map_local_filter needs a 3-D grid")
+        _grid("map_local_filter", grid)
         r = _c(np.asarray(res), np.float64)
         if r.ndim != 3:
             raise ValueError("map_local_filter needs a 3-D field of resolutions")
-        step_i = int(step)
-        if step_i != step or not -2 ** 31 <= step_i < 2 ** 31:
-            raise ValueError("map_local_filter: step %r" % (step,))
-        if out is None:
-            out = np.empty(grid.shape, np.float32)
-        elif out.dtype != np.float32 or not out.flags.c_contiguous or not out.flags.writeable or out.shape != grid.shape:
-            raise ValueError("map_local_filter: out must be a writable C-contiguous float32 array of the grid's shape")
-        d, rd = np.array(grid.shape, np.int32), np.array(r.shape, np.int32)
+        step = _whole("map_local_filter", "step", step)
+        out = _out("map_local_filter", out, grid.shape)
         o64 = np.empty(grid.shape, np.float64) if out64 else None
         sg = np.empty(grid.shape, np.float64) if sigma else None
-        self._chk(self.dll.mad_map_local_filter(self.ctx, _p(grid), _p(d), C.c_double(float(voxsp)), _p(r), _p(rd), C.c_int32(step_i), _p(out),
-                                                None if o64 is None else _p(o64), None if sg is None else _p(sg)))
+        self._chk(self.dll.mad_map_local_filter(self.ctx, _p(grid), _p(_dims(grid)), float(voxsp), _p(r), _p(_dims(r)), step, _p(out),
+                                                _p(o64), _p(sg)))
         return (out, o64, sg) if (out64 or sigma) else out
 
     def map_fft(self, g1, o1, g2=None, o2=None, voxsp=1.0):
         """The transform `map_fsc` works on, for testing it alone -> complex128 [N, N, N]: the FFT of the lattice that holds `g1`
         in the real and `g2` (may be None) in the imaginary part (mad_map_fft)."""
-        d1, o1, d2, o2 = self._fourier_args("map_fft", g1, o1, g2, o2)
-        args = (self.ctx, _p(g1), _p(d1), _p(o1), _p(g2), _p(d2), _p(o2), C.c_double(voxsp))
+        args = (self.ctx,) + _placed("map_fft", g1, o1) + _placed("map_fft", g2, o2) + (voxsp,)
         n = C.c_int32(0)
         self._chk(self.dll.mad_map_fft(*args, C.byref(n), None))
         out = np.empty((n.value,) * 3, np.complex128)
@@ -1356,13 +1329,14 @@ class Lib(object):
         (mad_map_filter; `fourier.filter_numpy` restates it).  `gain`: float64 [3 (N / 2)^2 + 1] by
         r2 = i^2 + j^2 + k^2 (`fourier.radial_gain`), N = `fourier.filter_lattice(g1.shape, pad, g2.shape)`.  The grids
         (C-contiguous float32 [x, y, z]) need no common frame; neither is modified."""
-        d1, _, d2, _ = self._fourier_args("map_filter", g1, np.zeros(3), g2, np.zeros(3))
-        gain = _c(np.asarray(gain, np.float64).reshape(-1), np.float64)
+        _grid("map_filter", g1)
+        d2 = None if g2 is None else _dims(_grid("map_filter", g2))
+        gain = _vec(gain, -1)
         out1 = np.empty(g1.shape, np.float32)
         out2 = None if g2 is None else np.empty(g2.shape, np.float32)
         n = C.c_int32(0)
-        self._chk(self.dll.mad_map_filter(self.ctx, _p(g1), _p(d1), _p(g2), _p(d2), C.c_int32(int(pad)), _p(gain), C.c_int64(len(gain)),
-                                          C.byref(n), _p(out1), _p(out2)))
+        self._chk(self.dll.mad_map_filter(self.ctx, _p(g1), _p(_dims(g1)), _p(g2), _p(d2), int(pad), _p(gain), len(gain), C.byref(n),
+                                          _p(out1), _p(out2)))
         return out1 if g2 is None else (out1, out2)
 
     def map_ifft(self, spectrum):
@@ -1372,7 +1346,7 @@ class Lib(object):
         if s.ndim != 3 or s.shape[0] != s.shape[1] or s.shape[0] != s.shape[2]:
             raise ValueError("map_ifft needs a cubic 3-D spectrum, got %r" % (s.shape,))
         out = np.empty(s.shape, np.complex128)
-        self._chk(self.dll.mad_map_ifft(self.ctx, _p(s), C.c_int32(s.shape[0]), _p(out)))
+        self._chk(self.dll.mad_map_ifft(self.ctx, _p(s), s.shape[0], _p(out)))
         return out
 
     def map_scan_lattice(self, d1, d2):
@@ -1380,8 +1354,7 @@ class Lib(object):
         or launched; it refuses what `fourier.scan_lattice` refuses)."""
         d1, d2 = np.array(d1, np.int32).reshape(3), np.array(d2, np.int32).reshape(3)
         n = C.c_int32(0)
-        self._chk(self.dll.mad_map_scan(self.ctx, None, _p(d1), C.c_int32(1), None, _p(d2), C.c_double(0.0), C.c_double(0.0), C.c_int32(0),
-                                        C.c_double(0.0), C.c_int64(0), None, None, None, None, None, C.byref(n)))
+        self._chk(self.dll.mad_map_scan(self.ctx, None, _p(d1), 1, None, _p(d2), 0.0, 0.0, 0, 0.0, 0, None, None, None, None, None, C.byref(n)))
         return int(n.value)
 
     def _corr_outputs(self, who, k, shape, ext):
@@ -1401,28 +1374,24 @@ class Lib(object):
         templates = list(templates)
         if len(templates) < 1:
             raise ValueError("map_scan needs one template or more")
+        _grid("map_scan", m)
         for g in templates:
-            self._fourier_args("map_scan", m, np.zeros(3), g, np.zeros(3))
-            if g.shape != templates[0].shape:
+            if _grid("map_scan", g).shape != templates[0].shape:
                 raise ValueError("map_scan needs templates of one shape, got %r and %r" % (templates[0].shape, g.shape))
-        d1, d2 = np.array(m.shape, np.int32), np.array(templates[0].shape, np.int32)
         k, best, best_t, peaks, n_peaks, n_found, _, n = self._corr_outputs("map_scan", k, m.shape, templates[0].shape)
         ptrs = (C.c_void_p * len(templates))(*[g.ctypes.data for g in templates])
-        self._chk(self.dll.mad_map_scan(self.ctx, _p(m), _p(d1), C.c_int32(len(templates)), ptrs, _p(d2), C.c_double(float(iso)),
-                                        C.c_double(float(e_min)), C.c_int32(int(mode)), C.c_double(float(min_score)), C.c_int64(k), _p(best),
-                                        _p(best_t), _p(peaks), C.byref(n_peaks), C.byref(n_found), C.byref(n)))
+        self._chk(self.dll.mad_map_scan(self.ctx, _p(m), _p(_dims(m)), len(templates), ptrs, _p(_dims(templates[0])), float(iso), float(e_min),
+                                        int(mode), float(min_score), k, _p(best), _p(best_t), _p(peaks), C.byref(n_peaks), C.byref(n_found),
+                                        C.byref(n)))
         return best, best_t, peaks[:n_peaks.value].copy(), int(n_found.value), int(n.value)
 
     def map_rotate(self, base, c0, edge, R, iso=0.0):
         """One rotated template of `map_search` and its sums -> (g float32 [e, e, e], n_w, G, S) (mad_map_rotate; DESIGN.md section
         4o; `fourier.rotate_numpy` and `fourier.tree_sum` restate it bit for bit).  `base`: C-contiguous float32 [x, y, z]; `c0`: the
         centre of rotation in its voxel coordinates; `R`: 3 x 3."""
-        self._fourier_args("map_rotate", base, np.zeros(3), None, None)
-        d0, e = np.array(base.shape, np.int32), int(edge)
-        c0 = _c(np.asarray(c0, np.float64).reshape(3), np.float64)
-        R = _c(np.asarray(R, np.float64).reshape(9), np.float64)
+        e = int(edge)
         out, stats = np.zeros((max(e, 0),) * 3 if e <= 1024 else (0,), np.float32), np.zeros(3, np.float64)
-        self._chk(self.dll.mad_map_rotate(self.ctx, _p(base), _p(d0), _p(c0), C.c_int32(e), _p(R), C.c_double(float(iso)), _p(out), _p(stats)))
+        self._chk(self.dll.mad_map_rotate(self.ctx, *_placed("map_rotate", base, c0), e, _p(_vec(R, 9)), float(iso), _p(out), _p(stats)))
         return out, int(stats[0]), float(stats[1]), float(stats[2])
 
     def map_search(self, m, base, c0, edge, rotations, iso=0.0, e_fill=0.0, mode=0, min_score=0.0, k=20):
@@ -1432,18 +1401,16 @@ class Lib(object):
         float32 [x, y, z]; `c0`: the centre of rotation in `base`'s voxel coordinates; the rotated templates are cubes of `edge`
         voxels, D = m.shape - edge + 1; `rotations`: (n, 3, 3).  An offset is scored by a rotation where E (E') > e_fill n_w.  A
         rotation whose mask is empty (or, centred, flat) is skipped and counted in n_skipped.  Nothing is modified."""
-        self._fourier_args("map_search", m, np.zeros(3), base, np.zeros(3))
-        rot = _c(np.asarray(rotations, np.float64), np.float64)
+        _grid("map_search", m)
+        template = _placed("map_search", base, c0)
+        rot =_c(np.asarray(rotations, np.float64), np.float64)
         if rot.ndim != 3 or rot.shape[1:] != (3, 3) or len(rot) < 1:
             raise ValueError("map_search: rotations of shape %r, not (n, 3, 3) with n >= 1" % (rot.shape,))
         e = int(edge)
         k, best, best_r, peaks, n_peaks, n_found, n_skipped, n = self._corr_outputs("map_search", k, m.shape, (e, e, e))
-        d1, d0 = np.array(m.shape, np.int32), np.array(base.shape, np.int32)
-        c0 = _c(np.asarray(c0, np.float64).reshape(3), np.float64)
-        self._chk(self.dll.mad_map_search(self.ctx, _p(m), _p(d1), _p(base), _p(d0), _p(c0), C.c_int32(e), _p(rot), C.c_int32(len(rot)),
-                                          C.c_double(float(iso)), C.c_double(float(e_fill)), C.c_int32(int(mode)), C.c_double(float(min_score)),
-                                          C.c_int64(k), _p(best), _p(best_r), _p(peaks), C.byref(n_peaks), C.byref(n_found), C.byref(n_skipped),
-                                          C.byref(n)))
+        self._chk(self.dll.mad_map_search(self.ctx, _p(m), _p(_dims(m)), *template, e, _p(rot), len(rot), float(iso),
+                                          float(e_fill), int(mode), float(min_score), k, _p(best), _p(best_r), _p(peaks), C.byref(n_peaks),
+                                          C.byref(n_found), C.byref(n_skipped), C.byref(n)))
         return best, best_r, peaks[:n_peaks.value].copy(), int(n_found.value), int(n_skipped.value), int(n.value)
 
     def map_zone(self, g, origin, voxsp, atoms, radius, soft=0.0, erase=False):
@@ -1451,16 +1418,11 @@ class Lib(object):
         `radius` of an atom keeps its bits, one `radius + soft` away or farther becomes 0, a raised cosine in between;
         `erase=True` takes one minus that weight.  `atoms`: anything np.asarray(..., float64).reshape(-1, 3) accepts.
         -> (voxels within radius, voxels in the soft edge) (mad_map_zone)."""
-        if g.dtype != np.float32 or not g.flags.c_contiguous or not g.flags.writeable:
-            raise ValueError("map_zone needs a writable C-contiguous float32 grid")
-        if g.ndim != 3:
-            raise ValueError("map_zone needs a 3-D grid")
-        d = np.array(g.shape, np.int32)
-        o = _c(np.asarray(origin, np.float64).reshape(3), np.float64)
-        a = _c(np.asarray(atoms, np.float64).reshape(-1, 3), np.float64)
+        placed = _placed("map_zone", g, origin, True)
+        a = _vec(atoms, (-1, 3))
         counts = np.zeros(2, np.int64)
-        self._chk(self.dll.mad_map_zone(self.ctx, _p(g), _p(d), _p(o), C.c_double(voxsp), _p(a) if len(a) else None, C.c_int64(len(a)),
-                                        C.c_double(radius), C.c_double(soft), C.c_int(1 if erase else 0), _p(counts)))
+        self._chk(self.dll.mad_map_zone(self.ctx, *placed, voxsp, _p(a) if len(a) else None, len(a), radius, soft, 1 if erase else 0,
+                                        _p(counts)))
         return int(counts[0]), int(counts[1])
 
     def map_group_fit(self, g1, o1, g2, o2, voxsp, atoms, first_atom, radius, isovalue=0.0, out=None):
@@ -1469,15 +1431,9 @@ class Lib(object):
         -> (n_vox int64 [G], sums float64 [G, 5]): per group the voxels of g1 within `radius` of one of its atoms, and over them
         sum a*a, sum b*b, sum a*b, sum a, sum b with a, b the two densities clamped at `isovalue`, b = 0 beyond g2
         (mad_map_group_fit).  Nothing is modified.  `out`: a pair of arrays to fill instead of new ones."""
-        for g in (g1, g2):
-            if g.dtype != np.float32 or not g.flags.c_contiguous:
-                raise ValueError("map_group_fit needs C-contiguous float32 grids")
-            if g.ndim != 3:
-                raise ValueError("map_group_fit needs 3-D grids")
-        d1, d2 = np.array(g1.shape, np.int32), np.array(g2.shape, np.int32)
-        o1 = _c(np.asarray(o1, np.float64).reshape(3), np.float64)
-        o2 = _c(np.asarray(o2, np.float64).reshape(3), np.float64)
-        a = _c(np.asarray(atoms, np.float64).reshape(-1, 3), np.float64)
+        who = "map_group_fit"
+        maps = _placed(who, g1, o1) + _placed(who, g2, o2)
+        a = _vec(atoms, (-1, 3))
         first = _c(np.asarray(first_atom, np.int64).reshape(-1), np.int64)
         if len(first) < 1:
             raise ValueError("map_group_fit: first_atom needs n_groups + 1 entries")
@@ -1486,16 +1442,11 @@ class Lib(object):
             raise ValueError("map_group_fit: %d groups" % n_groups)
         if int(first[-1]) > len(a):
             raise ValueError("map_group_fit: first_atom ends at %d, there are %d atoms" % (int(first[-1]), len(a)))
-        if out is None:
-            n_vox, sums = np.zeros(n_groups, np.int64), np.zeros((n_groups, 5), np.float64)
-        else:
-            n_vox, sums = out
-            if (n_vox.dtype != np.int64 or sums.dtype != np.float64 or n_vox.shape != (n_groups,) or sums.shape != (n_groups, 5)
-                    or not n_vox.flags.c_contiguous or not sums.flags.c_contiguous or not n_vox.flags.writeable or not sums.flags.writeable):
-                raise ValueError("map_group_fit: out must be writable C-contiguous (int64 [G], float64 [G, 5])")
-        self._chk(self.dll.mad_map_group_fit(self.ctx, _p(g1), _p(d1), _p(o1), _p(g2), _p(d2), _p(o2), C.c_double(voxsp),
-                                             _p(a) if len(a) else None, _p(first), C.c_int32(n_groups), C.c_double(radius),
-                                             C.c_double(isovalue), _p(n_vox), _p(sums)))
+        n_vox, sums = (None, None) if out is None else out
+        n_vox = _out(who, n_vox, (n_groups,), np.int64, "[G] entries", np.zeros, "out[0]")
+        sums = _out(who, sums, (n_groups, 5), np.float64, "shape [G, 5]", np.zeros, "out[1]")
+        self._chk(self.dll.mad_map_group_fit(self.ctx, *maps, voxsp, _p(a) if len(a) else None, _p(first), n_groups, radius, isovalue,
+                                             _p(n_vox), _p(sums)))
         return n_vox, sums
 
     def map_qscore(self, g, origin, voxsp, atoms, radii, ref, dirs, tries, index=None, details=False):
@@ -1504,16 +1455,8 @@ class Lib(object):
         vectors (`localfit.qscore_tables` makes the three).  `index`: the atoms to score (int64; None: all).
         -> (q float64 [m], n_samples int32 [m]), with `details` also (tries_used int32 [m, n_r], picked int32 [m, n_r, 8], values
         float64 [m, n_r, 8]) (mad_map_qscore).  Nothing is modified."""
-        if g.dtype != np.float32 or not g.flags.c_contiguous:
-            raise ValueError("map_qscore needs a C-contiguous float32 grid")
-        if g.ndim != 3:
-            raise ValueError("map_qscore needs a 3-D grid")
-        d = np.array(g.shape, np.int32)
-        o = _c(np.asarray(origin, np.float64).reshape(3), np.float64)
-        a = _c(np.asarray(atoms, np.float64).reshape(-1, 3), np.float64)
-        radii = _c(np.asarray(radii, np.float64).reshape(-1), np.float64)
-        ref = _c(np.asarray(ref, np.float64).reshape(-1), np.float64)
-        dirs = _c(np.asarray(dirs, np.float64).reshape(-1, 3), np.float64)
+        placed = _placed("map_qscore", g, origin)
+        a, radii, ref, dirs = _vec(atoms, (-1, 3)), _vec(radii, -1), _vec(ref, -1), _vec(dirs, (-1, 3))
         tries, n_r = int(tries), len(radii)
         if len(ref) != n_r:
             raise ValueError("map_qscore: %d ref values for %d radii" % (len(ref), n_r))
@@ -1528,27 +1471,33 @@ class Lib(object):
         m = len(a) if index is None else len(index)
         q, n_samples = np.full(m, np.nan), np.zeros(m, np.int32)
         det = (np.zeros((m, n_r), np.int32), np.full((m, n_r, 8), -1, np.int32), np.zeros((m, n_r, 8), np.float64)) if details else (None, None, None)
-        self._chk(self.dll.mad_map_qscore(self.ctx, _p(g), _p(d), _p(o), C.c_double(voxsp), _p(a) if len(a) else None, C.c_int64(len(a)),
-                                          _p(index) if index is not None else None, C.c_int64(m if index is not None else 0), _p(radii), _p(ref),
-                                          C.c_int32(n_r), _p(dirs), C.c_int32(tries), _p(q), _p(n_samples), _p(det[0]), _p(det[1]), _p(det[2])))
+        self._chk(self.dll.mad_map_qscore(self.ctx, *placed, voxsp, _p(a) if len(a) else None, len(a), _p(index), m if index is not None else 0,
+                                          _p(radii), _p(ref), n_r, _p(dirs), tries, _p(q), _p(n_samples), _p(det[0]), _p(det[1]), _p(det[2])))
         return (q, n_samples) + (det if details else ())
 
     def map_smooth(self, g, sigma_vox, out=None):
         """`g` (C-contiguous float32 [x, y, z]) smoothed with a Gaussian of `sigma_vox` voxels, zero beyond the grid, float64 inside
         -> a new float32 array, or `out` (which may be `g` itself) (mad_map_smooth)."""
-        if g.dtype != np.float32 or not g.flags.c_contiguous:
-            raise ValueError("map_smooth needs a C-contiguous float32 grid")
-        if g.ndim != 3:
-            raise ValueError("map_smooth needs a 3-D grid")
-        if out is None:
-            out = np.empty(g.shape, np.float32)
-        elif out.dtype != np.float32 or not out.flags.c_contiguous or not out.flags.writeable or out.shape != g.shape:
-            raise ValueError("map_smooth: out must be a writable C-contiguous float32 array of the grid's shape")
-        d = np.array(g.shape, np.int32)
-        self._chk(self.dll.mad_map_smooth(self.ctx, _p(g), _p(d), C.c_double(sigma_vox), _p(out)))
+        _grid("map_smooth", g)
+        out = _out("map_smooth", out, g.shape)
+        self._chk(self.dll.mad_map_smooth(self.ctx, _p(g), _p(_dims(g)), sigma_vox, _p(out)))
         return out
 
     SEGMENT_CAP0 = 1 << 16      # regions the tables of map_segment hold at first (they grow on MAD_ENOSPC, at the price of a second call)
+
+    def _tables(self, g, cap, dtypes, call):
+        """The per-region tables of map_segment / map_components: `call(tabs, cap, n)` makes the C call that fills arrays of `dtypes`
+        and the count n.  By default they grow until they fit; a given `cap` that is too small -> (None, n needed)."""
+        tabs, n = None, C.c_int64(0)
+
+        def attempt(try_cap):
+            nonlocal tabs
+            tabs = tuple(np.zeros(max(try_cap, 0), dt) for dt in dtypes)
+            return call(tabs, try_cap, n), n.value
+
+        fits = _retry_enospc(self, attempt, int(cap) if cap is not None else max(1, min(g.size, self.SEGMENT_CAP0)), grow=cap is None)
+        n = int(n.value)
+        return (tuple(t[:n].copy() for t in tabs) if fits else None), n
 
     def map_segment(self, g, threshold=0.0, steps=4, step=1.0, stop_at=0, cap=None):
         """Watershed regions of `g` (C-contiguous float32 [x, y, z]; foreground: value > threshold), grouped by following their maxima
@@ -1557,40 +1506,21 @@ class Lib(object):
         background), per region `root` (int64 linear index), `peak` (float32), `size` (int64), `group` (int32), and `history` (groups
         after step 0 .. steps_done), `steps_done`, `n_regions`, `n_groups`.  `cap`: the capacity of the region tables; by default it
         grows until they fit, with a given one that is too small the four tables come back as None and `n_regions` says what is needed."""
-        if g.dtype != np.float32 or not g.flags.c_contiguous:
-            raise ValueError("map_segment needs a C-contiguous float32 grid")
-        if g.ndim != 3:
-            raise ValueError("map_segment needs a 3-D grid")
-        steps_i = int(steps)
-        if steps_i != steps or not -2 ** 31 <= steps_i < 2 ** 31:
-            raise ValueError("map_segment: steps %r" % (steps,))
-        stop_i = int(stop_at)
-        if stop_i != stop_at or not -2 ** 63 <= stop_i < 2 ** 63:
-            raise ValueError("map_segment: stop_at %r" % (stop_at,))
-        d = np.array(g.shape, np.int32)
+        _grid("map_segment", g)
+        steps = _whole("map_segment", "steps", steps)
+        stop_at = _whole("map_segment", "stop_at", stop_at, -2 ** 63, 2 ** 63)
+        d = _dims(g)
         labels = np.zeros(g.shape, np.int32)
-        history = np.zeros(max(steps_i, 0) + 1, np.int64)
-        try_cap = int(cap) if cap is not None else max(1, min(g.size, self.SEGMENT_CAP0))
-        while True:
-            tabs = (np.zeros(max(try_cap, 0), np.int64), np.zeros(max(try_cap, 0), np.float32), np.zeros(max(try_cap, 0), np.int64),
-                    np.zeros(max(try_cap, 0), np.int32))
-            n, done = C.c_int64(0), C.c_int32(0)
-            rc = self.dll.mad_map_segment(self.ctx, _p(g), _p(d), C.c_double(threshold), C.c_int32(steps_i), C.c_double(step), C.c_int64(stop_i),
-                                          _p(labels), _p(tabs[0]), _p(tabs[1]), _p(tabs[2]), _p(tabs[3]), C.c_int64(try_cap), C.byref(n),
-                                          _p(history), C.byref(done))
-            if rc == -28 and n.value > try_cap:      # MAD_ENOSPC: n holds the capacity needed; labels and history are valid
-                if cap is not None:
-                    tabs = None
-                    break
-                try_cap = n.value
-                continue
-            self._chk(rc)
-            break
-        n, done = int(n.value), int(done.value)
+        history = np.zeros(max(steps, 0) + 1, np.int64)
+        done = C.c_int32(0)      # on MAD_ENOSPC labels and history are valid all the same
+        tabs, n = self._tables(g, cap, (np.int64, np.float32, np.int64, np.int32), lambda t, try_cap, n: self.dll.mad_map_segment(
+            self.ctx, _p(g), _p(d), threshold, steps, step, stop_at, _p(labels), _p(t[0]), _p(t[1]), _p(t[2]), _p(t[3]), try_cap,
+            C.byref(n), _p(history), C.byref(done)))
+        done = int(done.value)
         hist = history[:done + 1].copy()
         out = dict(labels=labels, history=hist, steps_done=done, n_regions=n, n_groups=int(hist[-1]))
         for k, name in enumerate(("root", "peak", "size", "group")):
-            out[name] = None if tabs is None else tabs[k][:n].copy()
+            out[name] = None if tabs is None else tabs[k]
         return out
 
     def map_components(self, g, threshold, connectivity=26, cap=None):
@@ -1599,31 +1529,13 @@ class Lib(object):
         (the component of every voxel, 1 .. n by ascending smallest linear index, 0 for background), per component `root` (int64, that
         index) and `size` (int64, its voxels), and `n`.  `cap`: the capacity of the two tables; by default it grows until they fit,
         with a given one that is too small they come back as None and `n` says what is needed."""
-        if g.dtype != np.float32 or not g.flags.c_contiguous:
-            raise ValueError("map_components needs a C-contiguous float32 grid")
-        if g.ndim != 3:
-            raise ValueError("map_components needs a 3-D grid")
-        conn = int(connectivity)
-        if conn != connectivity or not -2 ** 31 <= conn < 2 ** 31:
-            raise ValueError("map_components: connectivity %r" % (connectivity,))
-        d = np.array(g.shape, np.int32)
-        labels = np.zeros(g.shape, np.int32)
-        try_cap = int(cap) if cap is not None else max(1, min(g.size, self.SEGMENT_CAP0))
-        while True:
-            tabs = (np.zeros(max(try_cap, 0), np.int64), np.zeros(max(try_cap, 0), np.int64))
-            n = C.c_int64(0)
-            rc = self.dll.mad_map_components(self.ctx, _p(g), _p(d), C.c_double(threshold), C.c_int32(conn), _p(labels), _p(tabs[0]),
-                                             _p(tabs[1]), C.c_int64(try_cap), C.byref(n))
-            if rc == -28 and n.value > try_cap:      # MAD_ENOSPC: n holds the capacity needed; labels are valid
-                if cap is not None:
-                    tabs = None
-                    break
-                try_cap = n.value
-                continue
-            self._chk(rc)
-            break
-        n = int(n.value)
-        return dict(labels=labels, n=n, root=None if tabs is None else tabs[0][:n].copy(), size=None if tabs is None else tabs[1][:n].copy())
+        _grid("map_components", g)
+        conn = _whole("map_components", "connectivity", connectivity)
+        d = _dims(g)
+        labels = np.zeros(g.shape, np.int32)      # on MAD_ENOSPC the labels are valid all the same
+        tabs, n = self._tables(g, cap, (np.int64, np.int64), lambda t, try_cap, n: self.dll.mad_map_components(
+            self.ctx, _p(g), _p(d), threshold, conn, _p(labels), _p(t[0]), _p(t[1]), try_cap, C.byref(n)))
+        return dict(labels=labels, n=n, root=None if tabs is None else tabs[0], size=None if tabs is None else tabs[1])
 
     def map_dust(self, g, threshold, connectivity=26, min_size=1, keep=0, fill=None, out=None):
         """`g` (C-contiguous float32 [x, y, z]) without its dust: the components of `map_components` are ranked by size descending,
@@ -1633,65 +1545,37 @@ class Lib(object):
         components, foreground voxels, kept voxels)).  `out`: a float32 array to take the result instead of a new one; it may be `g`,
         and stays as it is when the call is refused."""
         from .components import default_fill
-        if g.dtype != np.float32 or not g.flags.c_contiguous:
-            raise ValueError("map_dust needs a C-contiguous float32 grid")
-        if g.ndim != 3:
-            raise ValueError("map_dust needs a 3-D grid")
-        ints = []
-        for name, v in (("connectivity", connectivity), ("min_size", min_size), ("keep", keep)):
-            i = int(v)
-            if i != v or not -2 ** 31 <= i < 2 ** 63:
-                raise ValueError("map_dust: %s %r" % (name, v))
-            ints.append(i)
-        if not -2 ** 31 <= ints[0] < 2 ** 31:
-            raise ValueError("map_dust: connectivity %r" % (connectivity,))
-        if out is None:
-            out = np.empty(g.shape, np.float32)
-        elif out.dtype != np.float32 or out.shape != g.shape or not out.flags.c_contiguous or not out.flags.writeable:
-            raise ValueError("map_dust: out must be a writable C-contiguous float32 array of the grid's shape")
+        _grid("map_dust", g)
+        conn = _whole("map_dust", "connectivity", connectivity)
+        min_size = _whole("map_dust", "min_size", min_size, -2 ** 31, 2 ** 63)
+        keep = _whole("map_dust", "keep", keep, -2 ** 31, 2 ** 63)
+        out =_out("map_dust", out, g.shape)
         fill = default_fill(threshold) if fill is None else np.float32(fill)
-        d = np.array(g.shape, np.int32)
         counts = np.zeros(4, np.int64)
-        self._chk(self.dll.mad_map_dust(self.ctx, _p(g), _p(d), C.c_double(threshold), C.c_int32(ints[0]), C.c_int64(ints[1]),
-                                        C.c_int64(ints[2]), C.c_float(float(fill)), _p(out), _p(counts)))
+        self._chk(self.dll.mad_map_dust(self.ctx, _p(g), _p(_dims(g)), threshold, conn, min_size, keep, fill, _p(out), _p(counts)))
         return out, tuple(int(v) for v in counts)
-
-    @staticmethod
-    def _map_arg(who, g, ndim=None):
-        if not isinstance(g, np.ndarray) or g.dtype != np.float32 or not g.flags.c_contiguous:
-            raise ValueError("%s needs a C-contiguous float32 array" % who)
-        if ndim is not None and g.ndim != ndim:
-            raise ValueError("%s needs a %d-D grid" % (who, ndim))
-        if g.size < 1 or g.size >= 2 ** 31:
-            raise ValueError("%s: %d voxels (1 .. 2^31 - 1)" % (who, g.size))
 
     def map_sort(self, g, out=None):
         """The values of `g` (C-contiguous float32 of any shape, not modified) in descending order, -0.0 as +0.0 -> float32 [g.size]
         (mad_map_sort; DESIGN.md section 4w: a radix sort of the keys on the device).  A voxel that is not finite is refused, and `out`
         (a float32 array to take the result) then stays as it is."""
-        self._map_arg("map_sort", g)
-        if out is None:
-            out = np.empty(g.size, np.float32)
-        elif out.dtype != np.float32 or out.shape != (g.size,) or not out.flags.c_contiguous or not out.flags.writeable:
-            raise ValueError("map_sort: out must be a writable C-contiguous float32 array of g.size values")
-        self._chk(self.dll.mad_map_sort(self.ctx, _p(g), C.c_int64(g.size), _p(out)))
+        _countable("map_sort", _grid("map_sort", g, None, what="array"))
+        out = _out("map_sort", out, (g.size,), of="g.size values")
+        self._chk(self.dll.mad_map_sort(self.ctx, _p(g), g.size, _p(out)))
         return out
 
     def map_kth(self, g, k, out=None):
         """The `k`-th largest values of `g` (C-contiguous float32 of any shape), 1-based: k = 1 the maximum, k = g.size the minimum; `k`
         a whole number or several -> float32 [len(k)] (mad_map_kth)."""
-        self._map_arg("map_kth", g)
+        _countable("map_kth", _grid("map_kth", g, None, what="array"))
         ka = np.atleast_1d(np.asarray(k))
         if ka.ndim != 1 or len(ka) < 1 or not np.issubdtype(ka.dtype, np.integer):
             raise ValueError("map_kth: ranks must be whole numbers, got %s %s" % (ka.dtype, ka.shape))
         ka = _c(ka, np.int64)
         if ka.min() < 1 or ka.max() > g.size:
             raise ValueError("map_kth: ranks %d .. %d of %d voxels (1 is the largest)" % (ka.min(), ka.max(), g.size))
-        if out is None:
-            out = np.empty(len(ka), np.float32)
-        elif out.dtype != np.float32 or out.shape != (len(ka),) or not out.flags.c_contiguous or not out.flags.writeable:
-            raise ValueError("map_kth: out must be a writable C-contiguous float32 array of len(k) values")
-        self._chk(self.dll.mad_map_kth(self.ctx, _p(g), C.c_int64(g.size), C.c_int64(len(ka)), _p(ka), _p(out)))
+        out = _out("map_kth", out, (len(ka),), of="len(k) values")
+        self._chk(self.dll.mad_map_kth(self.ctx, _p(g), g.size, len(ka), _p(ka), _p(out)))
         return out
 
     def map_confidence(self, g, boxes, c, levels=(0.01,), want_q=True, details=False, out=None):
@@ -1703,7 +1587,7 @@ class Lib(object):
         float32 per level (NaN where count is 0), and with details=True `sorted` (float32, the densities descending) and `q_sorted`.
         `out`: a float32 array of the grid's shape to take the confidence; it stays as it is when the call is refused."""
         from .confidence import check_boxes
-        self._map_arg("map_confidence", g, 3)
+        _countable("map_confidence", _grid("map_confidence", g, what="array"))
         b = _c(check_boxes("map_confidence", g.shape, boxes), np.int32)
         c = float(c)
         if not (c >= 1.0) or not np.isfinite(c):
@@ -1711,17 +1595,13 @@ class Lib(object):
         lv = _c(np.atleast_1d(np.asarray(levels, np.float64)), np.float64)
         if lv.ndim != 1 or len(lv) > 256 or not ((lv >= 0) & (lv <= 1)).all():
             raise ValueError("map_confidence: levels %r (at most 256 false discovery rates, 0 .. 1)" % (levels,))
-        if out is None:
-            out = np.empty(g.shape, np.float32)
-        elif out.dtype != np.float32 or out.shape != g.shape or not out.flags.c_contiguous or not out.flags.writeable:
-            raise ValueError("map_confidence: out must be a writable C-contiguous float32 array of the grid's shape")
+        out = _out("map_confidence", out, g.shape)
         q = np.empty(g.shape, np.float64) if want_q else None
         srt = np.empty(g.size, np.float32) if details else None
         qs = np.empty(g.size, np.float64) if details else None
         count, value, stats = np.zeros(max(len(lv), 1), np.int64), np.zeros(max(len(lv), 1), np.float32), np.zeros(3, np.float64)
-        d = np.array(g.shape, np.int32)
-        self._chk(self.dll.mad_map_confidence(self.ctx, _p(g), _p(d), C.c_int32(len(b)), _p(b), C.c_double(c), C.c_int32(len(lv)), _p(lv), _p(out),
-                                              _p(q), _p(srt), _p(qs), _p(count), _p(value), _p(stats)))
+        self._chk(self.dll.mad_map_confidence(self.ctx, _p(g), _p(_dims(g)), len(b), _p(b), c, len(lv), _p(lv), _p(out), _p(q), _p(srt),
+                                              _p(qs), _p(count), _p(value), _p(stats)))
         r = dict(confidence=out, q=q, mean=float(stats[0]), var=float(stats[1]), n=int(stats[2]), count=count[:len(lv)].copy(), value=value[:len(lv)].copy())
         if details:
             r.update(sorted=srt, q_sorted=qs)

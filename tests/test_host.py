@@ -29,6 +29,103 @@ def test_library_exports_every_declared_symbol():
     assert not missing, missing
 
 
+_C_SCALARS = {"int": "i", "int32_t": "i", "int64_t": "q", "uint64_t": "Q", "double": "d", "float": "f"}      # the codes of _lib._CTYPE
+
+
+def _header_text():
+    """include/mad_amd.h without its comments."""
+    header = open(os.path.join(ROOT, "include", "mad_amd.h")).read()
+    return re.sub(r"//[^\n]*", " ", re.sub(r"/\*.*?\*/", " ", header, flags=re.S))
+
+
+def _header_defines(prefix):
+    """{name: value} of every `#define <prefix>... <integer>` of the header."""
+    return {name: int(value) for name, value in re.findall(r"^\s*#\s*define\s+(%s\w*)\s+(-?\d+)\s*$" % prefix, _header_text(), flags=re.M)}
+
+
+def _c_class(decl, parameter):
+    """The code of one C type as _lib.PROTOTYPES writes it: `decl` is a return type, or a parameter with its name."""
+    decl, arrays = re.subn(r"\[[^\]]*\]", "", decl)
+    words = decl.replace("*", " * ").split()
+    if parameter and words[-1] != "*" and len([w for w in words if w not in ("*", "const")]) > 1:
+        words = words[:-1]      # the parameter's name
+    if words == ["const", "char", "*"]:
+        return "s"
+    if "*" in words or arrays:
+        return "p"
+    words = [w for w in words if w != "const"]
+    assert len(words) == 1, decl
+    return "v" if words == ["void"] and not parameter else _C_SCALARS[words[0]]      # a type outside the vocabulary: KeyError
+
+
+def _header_prototypes():
+    """{name: (return code, (argument codes))} of every function include/mad_amd.h declares."""
+    text = re.sub(r"^\s*#.*$", " ", _header_text(), flags=re.M)
+    protos = {}
+    for ret, name, params in re.findall(r"([A-Za-z_][\w\s\*]*?)\b(mad_\w+)\s*\(([^()]*)\)\s*;", text):
+        assert name not in protos, name
+        params = [] if params.strip() in ("", "void") else params.split(",")
+        protos[name] = (_c_class(ret, False), tuple(_c_class(p, True) for p in params))
+    return protos
+
+
+def test_prototype_table_of_the_wrapper_is_the_headers():
+    """_lib.PROTOTYPES states the C ABI for ctypes: per function of the header the same return type and, argument by argument,
+    a pointer where the header has one and otherwise the scalar of the header's width and kind."""
+    declared = _header_prototypes()
+    assert len(declared) >= 122
+    assert sorted(declared) == sorted(set(re.findall(r"\b(mad_[a-z0-9_]+)\s*\(", _header_text())))      # the parser missed none
+    assert sorted(_lib.PROTOTYPES) == sorted(declared), sorted(set(_lib.PROTOTYPES) ^ set(declared))
+    wrong = {name: (_lib.PROTOTYPES[name], proto) for name, proto in declared.items() if _lib.PROTOTYPES[name] != proto}
+    assert not wrong, "mad_amd/_lib.py PROTOTYPES (first) and include/mad_amd.h (second) disagree: %r" % wrong
+    assert _lib.SYMBOLS == list(_lib.PROTOTYPES)
+
+
+def test_every_prototype_is_set_on_the_loaded_library():
+    import ctypes as C
+    dll = _lib.load_library()
+    ctype = {"p": C.c_void_p, "i": C.c_int, "q": C.c_int64, "Q": C.c_uint64, "d": C.c_double, "f": C.c_float, "s": C.c_char_p, "v": None}
+    assert C.sizeof(C.c_int) == 4 and _lib._CTYPE == ctype
+    for name, (ret, args) in _lib.PROTOTYPES.items():
+        fn = getattr(dll, name)
+        assert fn.restype is ctype[ret], name
+        assert fn.argtypes is not None and tuple(fn.argtypes) == tuple(ctype[a] for a in args), name
+    # a wrapper of another width is refused before the library is entered; the header's width reaches it (no context: MAD_EINVAL)
+    out = np.full(4, 7.0, np.float32)
+    p = out.ctypes.data_as(C.c_void_p)
+    assert dll.mad_map_sort(None, p, C.c_int64(4), p) == dll.mad_map_sort(None, p, 4, p) == _lib.EINVAL
+    for bad in (C.c_int(4), C.c_double(4.0), 4.0):
+        with pytest.raises(C.ArgumentError):
+            dll.mad_map_sort(None, p, bad, p)      # int64_t n
+    with pytest.raises(C.ArgumentError):
+        dll.mad_map_sort(None, C.c_int(0), 4, p)      # const float *grid
+    with pytest.raises(C.ArgumentError):
+        dll.mad_match_shard_merge(None, None, None, C.c_int64(2), 1, None)      # int nranks
+    with pytest.raises(TypeError):
+        dll.mad_map_sort(None, p, 4)      # an argument short
+    assert np.all(out == 7.0)
+
+
+def test_mirrored_constants_are_the_headers():
+    """Every constant of _lib.py that mirrors a #define of include/mad_amd.h has the header's value (those that mirror headers
+    under csrc/ -- WIDE_*, QSCORE_*, TAB_* -- are not compared: a test reads the public header only)."""
+    errors = _header_defines("MAD_E")
+    assert len(errors) >= 6
+    for name, value in errors.items():
+        assert getattr(_lib, name[len("MAD_"):]) == value and _lib.ERRORS[value] == name[len("MAD_"):], name
+    assert len(_lib.ERRORS) == len(errors)
+    mirrored = ["RESULT_COLS", "RANK_MAX_N", "RANK_MAX_K", "RANK_MAX_TOP", "RANK_MAX_OUT", "RANK_TOP", "RANK_BELOW", "POSE_CLUSTER_MAX_N",
+                "SHARD_MERGE_MAX", "SHARD_FLAG_MISMATCH", "DIST_ID_BYTES", "DIST_BUF_FLAGS", "DIST_BUF_MINE", "DIST_BUF_ALL",
+                "DIST_BUF_MERGED", "DIST_BUF_WIRE", "DIST_BUF_GATHER"]
+    defines = _header_defines("MAD_")
+    for name in mirrored:
+        assert getattr(_lib, name) == defines["MAD_" + name], name
+    # and none was forgotten: a #define of one of these families has its mirror
+    for name in defines:
+        if re.match(r"MAD_(RANK|SHARD|DIST|POSE_CLUSTER)_", name):
+            assert name[len("MAD_"):] in mirrored, name
+
+
 def test_pose_plan_record_of_the_wrapper_is_the_headers():
     """mad_last_pose_plan fills a struct: the ctypes mirror in _lib.py must list the header's fields, in order, with their types."""
     import ctypes as C
