@@ -72,6 +72,7 @@ int mad_set_overlap(mad_ctx *ctx, int on);
 /*
  * Per-kernel-group timing with HIP events recorded on the ctx stream around each launch.
  * Groups: "orient", "describe", "correlate", "pairs", "pose", "topk", "refine", "density", "ccc".
+ * mad_assembly_density / mad_assembly_refine: "jf_model" (splat and blur), "jf_field" (M, s, texels or residual), "jf_steps".
  * Off by default; mad_timing_get drains pending events (a sync) and returns the accumulated
  * device time and launch count since the last reset; mad_last_ms = total / launches (<0 if none).
  */
@@ -403,6 +404,44 @@ int mad_refine(mad_ctx *ctx, double *coords, int n_cand, int64_t n_atoms, int n_
 int mad_last_refine_plan(mad_ctx *ctx, int *G, int *in_registers);
 /* Into how many chunks (of at most 512 Mi float64 voxels) the most recent density simulation cut its batch; -1 before the first. */
 int mad_last_density_chunks(mad_ctx *ctx);
+
+/* ---- next to a13: the placed bodies of an assembly refined together (mad_jointfit.hip) ---- */
+
+/*
+ * The model of n_bodies placed bodies (1 .. 64) on the lattice of the map given to mad_upload_density, and what the map holds
+ * beyond it.  Body b's atoms are rows first_atom[b] .. first_atom[b + 1] - 1 of atoms (x 3, Angstrom) and mass; first_atom has
+ * n_bodies + 1 entries, the first 0.  rho_b: the atoms splatted trilinearly, mass-weighted, onto the lattice (voxel (i, j, k) at
+ * origin + vs (i, j, k); an atom counts when its cell index is 0 .. n - 2 on every axis) and blurred by the separable Gaussian of
+ * mad_structure_to_density (sig = resolution / (pi sqrt 2) / vs, r = ceil(3 sig), taps of sum 1, zero beyond the lattice), float64,
+ * neither normalised nor thresholded.  M = the sum of the rho_b in ascending b; *scale = s = <map, M> / <M, M> over the lattice (0
+ * when <M, M> is 0).  model (nullable): M, float64 [nx][ny][nz].  residual (nullable): map - s M as float32.
+ * MAD_EINVAL with a message for a NULL pointer, n_bodies outside 1 .. 64, an empty body, a coordinate or mass that is not finite,
+ * resolution <= 0 (or a blur of more than 64 voxels) and a ctx without a map.
+ */
+int mad_assembly_density(mad_ctx *ctx, int n_bodies, const double *atoms, const double *mass, const int64_t *first_atom,
+                         double resolution, double *model, double *scale, float *residual);
+/*
+ * The bodies refined together.  Every body carries the state of refine_pdb (structure_utils.py:58-161: start coordinates and
+ * their centre, the farthest atom, translation, rotation, step size, the coordinates at the last batch boundary).  A round is one
+ * batch of refine_pdb: 4 steps, fewer in the last round when n_steps is no multiple of 4.  Before a round M and s are formed as
+ * mad_assembly_density forms them from where the bodies stand; body b then takes the round's steps of refine_pdb against
+ * F_b = float32(map - s (M - rho_b)), unless fixed[b] (nullable: none is) or converged.  The run ends when no body moves or
+ * n_steps are taken.  With one body F is the map and the call is mad_refine.
+ * coords: all atoms x 3, the refined coordinates.  rot (n_bodies x 9) and trans (n_bodies x 3): coords = (start - centre) rot +
+ * centre + trans up to the rounding of the last step.  converged / last_step: refine_pdb's return values per body (a fixed body:
+ * 0 and -1).  scale_per_round (nullable, (n_steps + 3) / 4 entries): s of every round that ran, 0 behind them.  *n_rounds: rounds
+ * in which steps were taken.  Refusals as mad_assembly_density, and n_steps < 1 or steps that are not 0 < min_step <= max_step.
+ */
+int mad_assembly_refine(mad_ctx *ctx, int n_bodies, const double *atoms, const double *mass, const int64_t *first_atom,
+                        const uint8_t *fixed, double resolution, int n_steps, double max_step, double min_step, double *coords,
+                        double *rot, double *trans, int32_t *converged, int32_t *last_step, double *scale_per_round,
+                        int32_t *n_rounds);
+/*
+ * What the most recent mad_assembly_refine chose: *G = workgroups of body 0, *in_registers = the form of k_jf_steps (1: a thread
+ * keeps its atoms in registers for the round; 0: global memory), *workgroups = workgroups of all bodies.  -1 before the first.
+ * mad_set_option "jointfit_split" (1 .. 8: workgroups per body at most) and "jointfit_registers" (0: never) are the tests' hooks.
+ */
+int mad_last_assembly_plan(mad_ctx *ctx, int *G, int *in_registers, int *workgroups);
 
 /* ---- a14-a15: PDB.structure_to_density (PDB.py:131-292) ------------------------ */
 

@@ -194,6 +194,24 @@ class Dmap(object):
             self.grid3d = g
         return _lib.get_lib().map_zone(g, (self.xi, self.yi, self.zi), self.voxsp, atoms, radius, soft, erase)
 
+    def refine_together(self, structures, resolution, n_steps=500, max_step=0.5, min_step=0.01, fixed=None, masses=None):
+        """Refine placed bodies against this map TOGETHER -> `jointfit.JointFit` (coords, R, T, converged, last_step, scale,
+        `rmsd()`, `place(i, pdb)`, `write_pdb(prefix)`).  Every body takes `refine_pdb`'s steps, four to a round, not against the
+        map but against the map minus the scaled model of the OTHER bodies where they then stand, re-made before every round;
+        `fixed[b]` keeps body b where it is (it still explains its density).  `structures`: a `PDB`, an (n, 3) array, or a list /
+        tuple of those, one body each (at most 64); `masses`: one array per body for arrays (default carbon; a `PDB` brings its
+        own).  `resolution` is that of the model (Angstrom).  With one body this is `refine_pdb`.  Neither `self` nor the
+        structures are modified.  DESIGN.md section 4x has the exact contract."""
+        from . import jointfit
+        return jointfit.refine_together(self, structures, resolution, n_steps=n_steps, max_step=max_step, min_step=min_step, fixed=fixed, masses=masses)
+
+    def residual(self, structures, resolution, masses=None):
+        """What this map holds beyond the placed bodies, as a new `Dmap` on the same lattice: map - s M, M the sum of the bodies'
+        simulated densities at `resolution` (not normalised) and s = <map, M> / <M, M>, kept as `scale` on the result.
+        `structures` and `masses` as `refine_together`.  `self` is not modified.  DESIGN.md section 4x."""
+        from . import jointfit
+        return jointfit.residual(self, structures, resolution, masses=masses)
+
     def envelope(self, threshold, extend=3.0, soft=6.0, min_size=1, keep=0, connectivity=26):
         """A soft mask made from this map itself, as a new `Dmap` with the same dims, origin and spacing (`self` is untouched):
         1 on every voxel within `extend` Angstrom of a voxel above `threshold`, a raised-cosine edge over the next `soft`

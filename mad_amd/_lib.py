@@ -72,7 +72,8 @@ mad_grid_overlap=i(pppppppddpp) mad_overlap_matrix=i(ppppiddddp) mad_space_creat
 mad_space_build=i(pppiiiiiippidpipppii) mad_space_info=i(pppppp) mad_space_download=i(ppiip) mad_space_peaks=i(ppidippqp)
 mad_space_patches=i(ppipiip) mad_space_localize=i(ppipippppp) mad_localize_volume=i(ppiiiipippppp)
 mad_pose_cluster_many=i(pippppdpppp) mad_rank_copies=i(ppiiidqqqpppppp) mad_rank_models=i(ppipiqqqqpppppp)
-mad_last_rank_plan=i(ppppp)
+mad_last_rank_plan=i(ppppp) mad_assembly_density=i(pipppdppp) mad_assembly_refine=i(pippppdiddppppppp)
+mad_last_assembly_plan=i(pppp)
 """.split()}
 SYMBOLS = list(PROTOTYPES)      # every symbol include/mad_amd.h declares (tests check the library exports all of them)
 
@@ -1040,6 +1041,11 @@ class Lib(object):
         grid = _c(grid, np.float32)
         nx, ny, nz = grid.shape
         self._chk(self.dll.mad_upload_density(self.ctx, _p(grid), nx, ny, nz, origin[0], origin[1], origin[2], voxsp))
+        self._density_dims = (nx, ny, nz)
+
+    def density_dims(self):
+        """Shape of the map given to upload_density, or None."""
+        return getattr(self, "_density_dims", None)
 
     def refine(self, coords, n_steps=500, max_step=0.5, min_step=0.01):
         """coords: (n_cand, n_atoms, 3) or (n_atoms, 3).  Returns (coords, converged[], last_step[])."""
@@ -1060,6 +1066,59 @@ class Lib(object):
         g, reg = C.c_int(-1), C.c_int(-1)
         self._chk(self.dll.mad_last_refine_plan(self.ctx, C.byref(g), C.byref(reg)))
         return g.value, reg.value
+
+    @staticmethod
+    def _bodies(who, coords_list, mass_list):
+        """Bodies as the assembly calls take them: (atoms (N, 3), mass (N), first_atom (B + 1) int64)."""
+        if len(coords_list) != len(mass_list):
+            raise ValueError("%s: %d bodies, %d mass arrays" % (who, len(coords_list), len(mass_list)))
+        parts = [_c(c, np.float64).reshape(-1, 3) for c in coords_list]
+        ms = [_c(m, np.float64).reshape(-1) for m in mass_list]
+        for b, (c, m) in enumerate(zip(parts, ms)):
+            if len(c) != len(m):
+                raise ValueError("%s: mass: body %d has %d masses for %d atoms" % (who, b, len(m), len(c)))
+        first = np.zeros(len(parts) + 1, np.int64)
+        first[1:] = np.cumsum([len(c) for c in parts])
+        atoms = np.concatenate(parts, axis=0) if parts else np.zeros((0, 3))
+        mass = np.concatenate(ms) if ms else np.zeros(0)
+        return np.ascontiguousarray(atoms), np.ascontiguousarray(mass), first
+
+    def assembly_density(self, coords_list, mass_list, resolution, want_model=True, want_residual=True):
+        """The model of placed bodies on the lattice of the map given to upload_density (mad_assembly_density) -> (M float64 or
+        None, s, map - s M float32 or None)."""
+        atoms, mass, first = self._bodies("assembly_density", coords_list, mass_list)
+        dims = self.density_dims()
+        model = np.empty(dims, np.float64) if want_model and dims else None
+        res = np.empty(dims, np.float32) if want_residual and dims else None
+        s = C.c_double(0.0)
+        self._chk(self.dll.mad_assembly_density(self.ctx, len(first) - 1, _p(atoms), _p(mass), _p(first), resolution, _p(model), C.byref(s), _p(res)))
+        return model, s.value, res
+
+    def assembly_refine(self, coords_list, mass_list, resolution, n_steps=500, max_step=0.5, min_step=0.01, fixed=None):
+        """The bodies refined together against the map given to upload_density (mad_assembly_refine) -> ([coords (n_b, 3)],
+        R (B, 3, 3), T (B, 3), converged (B) bool, last_step (B), s of every round that ran)."""
+        atoms, mass, first = self._bodies("assembly_refine", coords_list, mass_list)
+        B = len(first) - 1
+        fx = None
+        if fixed is not None:
+            fx = _c(np.asarray(fixed, bool), np.uint8).reshape(-1)
+            if len(fx) != B:
+                raise ValueError("assembly_refine: fixed has %d entries for %d bodies" % (len(fx), B))
+        n_steps = _whole("assembly_refine", "n_steps", n_steps)
+        out = np.empty_like(atoms)
+        rot, trans = np.zeros((B, 3, 3)), np.zeros((B, 3))
+        conv, last = np.zeros(B, np.int32), np.zeros(B, np.int32)
+        scale = np.zeros(max((n_steps + 3) // 4, 1))
+        rounds = C.c_int32(0)
+        self._chk(self.dll.mad_assembly_refine(self.ctx, B, _p(atoms), _p(mass), _p(first), _p(fx), resolution, n_steps, max_step, min_step,
+                                               _p(out), _p(rot), _p(trans), _p(conv), _p(last), _p(scale), C.byref(rounds)))
+        return ([out[first[b]:first[b + 1]].copy() for b in range(B)], rot, trans, conv.astype(bool), last, scale[:rounds.value].copy())
+
+    def last_assembly_plan(self):
+        """(G of body 0, in_registers, workgroups) of the most recent assembly_refine (mad_last_assembly_plan); -1 before the first."""
+        g, reg, wgs = C.c_int(-1), C.c_int(-1), C.c_int(-1)
+        self._chk(self.dll.mad_last_assembly_plan(self.ctx, C.byref(g), C.byref(reg), C.byref(wgs)))
+        return g.value, reg.value, wgs.value
 
     def last_density_chunks(self):
         """Chunks the most recent density simulation cut its batch into (mad_last_density_chunks); -1 before the first."""

@@ -175,7 +175,7 @@ struct DevBuf {
 
 enum { MAD_T_ORIENT = 0, MAD_T_DESCRIBE, MAD_T_CORRELATE, MAD_T_PAIRS, MAD_T_POSE, MAD_T_TOPK, MAD_T_REFINE,
        MAD_T_DENSITY, MAD_T_CCC, MAD_T_SEG_PARENT, MAD_T_SEG_JUMP, MAD_T_SEG_SCAN, MAD_T_SEG_SMOOTH, MAD_T_FFT, MAD_T_FSC, MAD_T_FILTER, MAD_T_SCAN, MAD_T_SEARCH, MAD_T_LOCALRES, MAD_T_LOCALFILTER, MAD_T_LOCALSCALE,
-       MAD_T_ENV_Z, MAD_T_ENV_Y, MAD_T_ENV_X, MAD_T_ENV_WEIGHT, MAD_T_QSCORE, MAD_T_CF_SORT, MAD_T_CF_NOISE, MAD_T_CF_Q, MAD_T_CF_LOOKUP, MAD_T_CC_TILE, MAD_T_CC_BORDER, MAD_T_CC_LABEL, MAD_T_CC_SELECT, MAD_T_COUNT };
+       MAD_T_ENV_Z, MAD_T_ENV_Y, MAD_T_ENV_X, MAD_T_ENV_WEIGHT, MAD_T_QSCORE, MAD_T_CF_SORT, MAD_T_CF_NOISE, MAD_T_CF_Q, MAD_T_CF_LOOKUP, MAD_T_JF_MODEL, MAD_T_JF_FIELD, MAD_T_JF_STEPS, MAD_T_CC_TILE, MAD_T_CC_BORDER, MAD_T_CC_LABEL, MAD_T_CC_SELECT, MAD_T_COUNT };
 
 #define MAD_T_RING 32
 #define MAD_LANES 8
@@ -289,6 +289,8 @@ struct mad_ctx {
     int last_pose_kernel = -1;               // 0 k_pose_lds, 1 k_pose_lds32, 2 k_pose (mad_last_pose_kernel)
     mad_pose_plan_info last_pose_plan = mad_pose_plan_none();      // what pose_device / match_enqueue_tail chose last (mad_last_pose_plan)
     int last_refine_G = -1, last_refine_reg = -1;      // workgroups per candidate and kernel form (1 k_refine<8>, 0 k_refine<0>) of the last refine_device (mad_last_refine_plan)
+    int jf_split = 8, jf_no_reg = 0;      // test hooks (mad_set_option "jointfit_split" / "jointfit_registers"): workgroups per body at most, 1 = k_jf_steps<0> always
+    int last_jf_G = -1, last_jf_reg = -1, last_jf_wgs = -1;      // body 0's workgroups, the kernel form and all workgroups of the last mad_assembly_refine (mad_last_assembly_plan)
     int64_t last_rank_launches = 0, last_rank_evaluated = 0, last_rank_skipped = 0;      // the last mad_rank_* call (mad_last_rank_plan)
     int last_rank_band_extra = 0;
     int last_density_chunks = -1;            // chunks the last density_batch cut its jobs into (mad_last_density_chunks)

@@ -3665,6 +3665,16 @@ extern "C" int mad_set_option(mad_ctx *ctx, const char *name, double value) {
         (name[0] == 'o' ? ctx->ori_queue_cap : ctx->dsc_queue_cap) = (int)value;
         return MAD_OK;
     }
+    if (!strcmp(name, "jointfit_split")) {      // test hook: workgroups per body of mad_assembly_refine at most (the summation order, hence the last bits, depend on it)
+        if (!(value >= 1) || !(value <= 8)) return mad_fail(ctx, MAD_EINVAL, "mad_set_option: jointfit_split = %g (1 .. 8)", value);
+        ctx->jf_split = (int)value;
+        return MAD_OK;
+    }
+    if (!strcmp(name, "jointfit_registers")) {      // test hook: 0 = k_jf_steps walks global memory whatever the bodies' sizes
+        if (value != 0 && value != 1) return mad_fail(ctx, MAD_EINVAL, "mad_set_option: jointfit_registers = %g (0 or 1)", value);
+        ctx->jf_no_reg = value == 0;
+        return MAD_OK;
+    }
     if (!strcmp(name, "fft_bpt")) {      // test hook: the k_fft_lines form (butterflies per thread) for every N; 0 = chosen by N
         if (value != 0 && value != 1 && value != 2 && value != 4) return mad_fail(ctx, MAD_EINVAL, "mad_set_option: fft_bpt = %g (0, 1, 2 or 4)", value);
         ctx->fft_bpt = (int)value;
