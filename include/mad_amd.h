@@ -319,7 +319,8 @@ int mad_set_batching(mad_ctx *ctx, int on);
  * (0 default, 1, 2, 4): butterflies per thread of k_fft_lines, i.e. which of its three forms mad_map_fft / mad_map_fsc / mad_map_filter / mad_map_ifft / mad_map_scan launch (by
  * default 1 up to N = 256, 2 at 512, 4 at 1024; a value below that is raised to it) -- a test hook, the bits are the same.
  * "search_prune" (1 default, 0): 0 makes mad_map_search run full line passes instead of the pruned ones -- a test hook, it changes
- * speed, never numbers. */
+ * speed, never numbers.  "symmetry_scratch" (bytes, default 64 MiB): what the partial records of one chunk of operators of
+ * mad_map_symmetry_score may take -- it changes the chunks, never numbers. */
 int mad_set_option(mad_ctx *ctx, const char *name, double value);
 
 /*
@@ -525,6 +526,39 @@ int mad_map_ccc(mad_ctx *ctx, const float *grid1, const int32_t dims1[3], const 
 int mad_map_resample(mad_ctx *ctx, const float *grid, const int32_t dims[3], const double origin[3], double voxsp,
                      const double *R9, const double *T3,          /* NULL, NULL: no motion */
                      int order, const int32_t out_dims[3], const double out_origin[3], double out_voxsp, float *out);
+
+/*
+ * The self-correlation of a map under a batch of rigid motions, and the average of a map over a set of them (mad_symmetry.hip,
+ * mad_resample.hip; mad_amd/symmetry.py restates both with numpy).  Host pointers, synchronous, the grid is
+ * not modified.  An operator g is a pair (R, T) in mad_map_resample's convention: R9[9 g + 3 a + k] = R_g[a][k], T3[3 g + k], a
+ * point x (a row vector, Angstrom) moves to x @ R + T.
+ *
+ * mad_map_symmetry_score: out[6 g ..] = (n, sum a, sum b, sum a^2, sum b^2, sum a b) over the sample points j.  Candidates are the
+ * lattice indices j_a = stride k_a; with c = (ball_centre - origin) / voxsp and r = radius / voxsp the box holds per axis the k_a
+ * with |j_a - c_a| <= r and 0 <= j_a <= dims[a] - 1, and a point of the box counts when ((dx dx + dy dy) + dz dz) <= r r
+ * (d = j - c, float64).  a = (double)grid[j]; b = the float32 that mad_map_resample(order 1, R_g, T_g, onto the map's own
+ * lattice) writes at voxel j in its general form (the same fold into u = b + A j, the same expressions, 0 outside
+ * 0 <= u <= dims - 1).  The box is walked in linear [x][y][z] order in runs of 256, points that do not count enter every sum as
+ * +0.0, and every sum is paired as fourier.tree_sum pairs it (a run by halving, then level after level): the same call gives the
+ * same bits, whatever the chunking.  An empty box gives n = 0 and zero sums.  The operators are scored in chunks whose partial
+ * records fit mad_set_option "symmetry_scratch" bytes (default 64 MiB; one operator's records at least); all operators of a chunk
+ * are one grid.  MAD_EINVAL, with nothing launched and out untouched: NULL, n_ops < 1, stride < 1, radius < 0, a dimension < 2,
+ * 2^32 voxels or more, voxsp <= 0, a number that is not finite, an R that mad_map_resample refuses.
+ *
+ * mad_map_symmetrize: out[j] = (float)((sum over g of v_g) / n_ops) on the map's own lattice, v_g the float64 interpolated value
+ * of the map moved by operator g at voxel j before any rounding to float32 (0 outside the source), the sum from +0.0 in the order
+ * g = 0, 1, ...  order 1: trilinear; order 3: the cubic B-spline of mad_map_resample, prefiltered once per call.  n_ops = 1 gives
+ * mad_map_resample's bits (general form).  MAD_EINVAL as mad_map_resample, and for n_ops outside 1 .. 64.
+ *
+ * mad_last_symmetry_plan: operators per workgroup of the score kernel (a constant), and the chunks and the bytes of partial records
+ * of the most recent mad_map_symmetry_score (-1 before the first).  Any pointer may be NULL.
+ */
+int mad_map_symmetry_score(mad_ctx *ctx, const float *grid, const int32_t dims[3], const double origin[3], double voxsp,
+                           const double ball_centre[3], double radius, int32_t stride, int32_t n_ops, const double *R9,
+                           const double *T3, double *out);
+int mad_map_symmetrize(mad_ctx *ctx, const float *grid, const int32_t dims[3], const double origin[3], double voxsp, int32_t n_ops,
+                       const double *R9, const double *T3, int order, float *out);
+int mad_last_symmetry_plan(mad_ctx *ctx, int32_t *ops_per_workgroup, int32_t *n_chunks, int64_t *scratch_bytes);
 
 /*
  * A map cut around a structure, or with the structure erased (mad_zone.hip).  Host pointers, synchronous.

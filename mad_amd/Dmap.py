@@ -291,6 +291,63 @@ class Dmap(object):
         from . import localfit
         return localfit.qscore(self, structure, sigma=sigma, rmax=rmax, step=step, tries=tries, select=select, details=details)
 
+    def _symmetry_ball(self, centre, radius):
+        """The ball of `symmetry_score` where none is given: about the middle of the map, the largest that stays inside it."""
+        o, n = np.array([self.xi, self.yi, self.zi], np.float64), np.array(self.grid3d.shape, np.float64)
+        c = o + float(self.voxsp) * (n - 1.0) / 2.0 if centre is None else np.asarray(centre, np.float64).reshape(3)
+        if radius is None:
+            cv = (c - o) / float(self.voxsp)
+            radius = max(0.0, float(min(np.minimum(cv, n - 1.0 - cv)))) * float(self.voxsp)
+        return c, float(radius)
+
+    def symmetry_score(self, ops, centre=None, radius=None, stride=1):
+        """How well the map matches itself moved by every operator of `ops` -> `symmetry.Scores` (sums [n, 6] = n, sum a, sum b,
+        sum a^2, sum b^2, sum a b, and the centred correlation `cc` [n], nan where fewer than 2 points or no variance).  `ops`: a
+        `symmetry.Operators`, or a pair (R [n, 3, 3], T [n, 3]); a point x moves to x @ R + T.  The sums run over the lattice
+        points within `radius` Angstrom of `centre` (None: the middle of the map and the largest ball inside it) at every
+        `stride`-th index: a = the map there, b = the moved map there, trilinear, as `resample(R=, T=, order=1)` writes it.  All
+        operators go to the device in one call.  `self` is not modified.  DESIGN.md section 4y has the exact contract."""
+        from . import symmetry
+        R, T = (ops.R, ops.T) if hasattr(ops, "R") else ops
+        c, radius = self._symmetry_ball(centre, radius)
+        g = np.ascontiguousarray(self.grid3d, dtype=np.float32)
+        return symmetry.Scores(_lib.get_lib().map_symmetry_score(g, (self.xi, self.yi, self.zi), float(self.voxsp), c, radius, R, T, stride=stride))
+
+    def symmetrize(self, ops_or_symmetry, order=3):
+        """The map averaged over the elements of a group, as a new `Dmap` on the same lattice (`self` is untouched): voxel j becomes
+        the mean over the operators g of the map moved by g, interpolated at j (order 1 trilinear, 3 cubic B-spline as `resample`;
+        0 where a moved map has no value), summed in float64 in the operators' order.  `ops_or_symmetry`: a `symmetry.Symmetry` (what
+        `find_symmetry` returns), a `symmetry.Operators` (`symmetry.point_group(...)`), or a pair (R, T); 1 .. 64 operators."""
+        if order not in (1, 3):
+            raise ValueError("Dmap.symmetrize: order %r (1 or 3)" % (order,))
+        ops = ops_or_symmetry.operators() if hasattr(ops_or_symmetry, "operators") else ops_or_symmetry
+        R, T = (ops.R, ops.T) if hasattr(ops, "R") else ops
+        g = np.ascontiguousarray(self.grid3d, dtype=np.float32)
+        out = Dmap.__new__(Dmap)
+        out.grid3d = _lib.get_lib().map_symmetrize(g, (self.xi, self.yi, self.zi), float(self.voxsp), R, T, order=order)
+        out.voxsp = self.voxsp
+        out.xi, out.yi, out.zi = self.xi, self.yi, self.zi
+        out.xb, out.yb, out.zb = out.grid3d.shape
+        for k in ("map_name", "name"):
+            if hasattr(self, k):
+                setattr(out, k, getattr(self, k))
+        return out
+
+    def find_symmetry(self, threshold=0.0, angle=6.0, max_order=12, min_cc=0.9, tol=0.02, centre=None, radius=None, stride=None):
+        """The cyclic or dihedral point group of the map -> `symmetry.Symmetry` (name "C1" / "C<n>" / "D<n>", order, axis, axis2,
+        centre, score, the per-order `table`, radius, stride, `operators()`, `copies(structure)`, `write_csv(path)`).  The centre is
+        the centre of mass of the density above `threshold`; every direction of a spiral of spacing `angle` degrees is tried with
+        every order 2 .. `max_order` in one device call on a strided ball, the best direction per order is refined by a pattern
+        search over the axis' tilt and position, and the largest order whose worst non-identity element still correlates at
+        `min_cc` or more and within `tol` of the best order wins; a perpendicular two-fold that holds the same way makes it D<n>.
+        `centre`, `radius` (Angstrom) and `stride` override what the search derives.  T, O and I are not detected: such a map
+        reports its largest cyclic or dihedral subgroup.  `symmetry.find` has the steps, DESIGN.md section 4y the contract."""
+        from . import symmetry
+        g = np.ascontiguousarray(self.grid3d, dtype=np.float32)
+        lib, o, vs = _lib.get_lib(), (self.xi, self.yi, self.zi), float(self.voxsp)
+        return symmetry.find(lambda R, T, c, r, s: lib.map_symmetry_score(g, o, vs, c, r, R, T, stride=s), g, o, vs, threshold=threshold, angle=angle,
+                             max_order=max_order, min_cc=min_cc, tol=tol, centre=centre, radius=radius, stride=stride)
+
     def fsc(self, other, resolution=None, masses=None, mask=None, randomize_from=None, seed=0):
         """Fourier shell correlation of this map against `other` -> `fourier.FSC` (freq, fsc, n, power1, power2, `resolution()`,
         `write_csv()`).  `other`: a `Dmap` of the same spacing (half map against half map; `resample(like=...)` first where the

@@ -30,6 +30,7 @@ WIDE_C = 108
 WIDE_MAX = WIDE_C + 127
 QSCORE_CHUNK = 256          # QS_CHUNK of csrc/mad_qscore_plan.h: neighbours of one LDS chunk of k_qscore
 QSCORE_MAX_SHELLS, QSCORE_MAX_TRIES = 64, 64      # QS_MAX_R, QS_MAX_TRIES
+SYMMETRIZE_MAX_OPS = 64     # SYMZ_MAX_OPS of csrc/mad_resample.hip
 TAB_ZBINS, TAB_PBINS, TAB_BELTS = 2048, 2048, 4      # MAD_TAB_* of csrc/mad_common.h
 
 # The C ABI, stated once: every function of include/mad_amd.h as name=return(arguments), one letter per type.  load_library() sets
@@ -73,7 +74,8 @@ mad_space_build=i(pppiiiiiippidpipppii) mad_space_info=i(pppppp) mad_space_downl
 mad_space_patches=i(ppipiip) mad_space_localize=i(ppipippppp) mad_localize_volume=i(ppiiiipippppp)
 mad_pose_cluster_many=i(pippppdpppp) mad_rank_copies=i(ppiiidqqqpppppp) mad_rank_models=i(ppipiqqqqpppppp)
 mad_last_rank_plan=i(ppppp) mad_assembly_density=i(pipppdppp) mad_assembly_refine=i(pippppdiddppppppp)
-mad_last_assembly_plan=i(pppp)
+mad_last_assembly_plan=i(pppp) mad_map_symmetry_score=i(ppppdpdiippp) mad_map_symmetrize=i(ppppdippip)
+mad_last_symmetry_plan=i(pppp)
 """.split()}
 SYMBOLS = list(PROTOTYPES)      # every symbol include/mad_amd.h declares (tests check the library exports all of them)
 
@@ -1266,6 +1268,47 @@ class Lib(object):
         self._chk(self.dll.mad_map_resample(self.ctx, *source, voxsp, _p(Rp), _p(Tp), order, _p(md),
                                             _p(_vec(out_origin, 3)), out_voxsp, _p(out)))
         return out
+
+    @staticmethod
+    def _operators(who, R, T):
+        """The operator table of a call: R (n, 3, 3) and T (n, 3), or anything with fields `R` and `T` in the first place."""
+        if T is None and hasattr(R, "R") and hasattr(R, "T") and not isinstance(R, np.ndarray):
+            R, T = R.R, R.T
+        R, T = _c(np.asarray(R, np.float64), np.float64), _c(np.asarray(T, np.float64), np.float64)
+        if R.ndim != 3 or R.shape[1:] != (3, 3) or T.shape != (len(R), 3):
+            raise ValueError("%s: operators of shapes %r and %r, not (n, 3, 3) and (n, 3)" % (who, R.shape, T.shape))
+        if not 0 <= len(R) < 2 ** 31:
+            raise ValueError("%s: %d operators" % (who, len(R)))
+        return R, T
+
+    def map_symmetry_score(self, g, origin, voxsp, centre, radius, R, T=None, stride=1, out=None):
+        """The sums of `g` against itself moved by every operator (R[i], T[i]) over the lattice points of the ball (`centre`,
+        `radius`, Angstrom) at every `stride`-th index -> float64 [n, 6] = n, sum a, sum b, sum a^2, sum b^2, sum a b
+        (mad_map_symmetry_score; `symmetry.score_numpy` restates it bit for bit).  Nothing is modified."""
+        who = "map_symmetry_score"
+        placed = _placed(who, g, origin)
+        R, T = self._operators(who, R, T)
+        out = _out(who, out, (len(R), 6), np.float64, of="shape (n, 6)")
+        self._chk(self.dll.mad_map_symmetry_score(self.ctx, *placed, float(voxsp), _p(_vec(centre, 3)), float(radius), _whole(who, "stride", stride),
+                                                  len(R), _p(R), _p(T), _p(out)))
+        return out
+
+    def map_symmetrize(self, g, origin, voxsp, R, T=None, order=3, out=None):
+        """`g` averaged over the operators (R[i], T[i]) on its own lattice -> a new float32 array (mad_map_symmetrize; DESIGN.md
+        section 4y; `symmetry.symmetrize_numpy` restates it).  1 .. 64 operators; order 1 or 3 as `map_resample`."""
+        who = "map_symmetrize"
+        placed = _placed(who, g, origin)
+        R, T = self._operators(who, R, T)
+        out = _out(who, out, g.shape)
+        self._chk(self.dll.mad_map_symmetrize(self.ctx, *placed, float(voxsp), len(R), _p(R), _p(T), _whole(who, "order", order), _p(out)))
+        return out
+
+    def last_symmetry_plan(self):
+        """-> (operators per workgroup of the score kernel, chunks of operators, bytes of partial records) of the most recent
+        `map_symmetry_score` (mad_last_symmetry_plan; the last two -1 before the first call)."""
+        w, c, b = C.c_int32(0), C.c_int32(0), C.c_int64(0)
+        self._chk(self.dll.mad_last_symmetry_plan(self.ctx, C.byref(w), C.byref(c), C.byref(b)))
+        return int(w.value), int(c.value), int(b.value)
 
     def map_fsc(self, g1, o1, g2, o2, voxsp):
         """Fourier shell correlation sums of two maps of one spacing -> (N, sums float64 [N / 2 + 1, 3] = P1, P2, C per shell,

@@ -175,7 +175,7 @@ struct DevBuf {
 
 enum { MAD_T_ORIENT = 0, MAD_T_DESCRIBE, MAD_T_CORRELATE, MAD_T_PAIRS, MAD_T_POSE, MAD_T_TOPK, MAD_T_REFINE,
        MAD_T_DENSITY, MAD_T_CCC, MAD_T_SEG_PARENT, MAD_T_SEG_JUMP, MAD_T_SEG_SCAN, MAD_T_SEG_SMOOTH, MAD_T_FFT, MAD_T_FSC, MAD_T_FILTER, MAD_T_SCAN, MAD_T_SEARCH, MAD_T_LOCALRES, MAD_T_LOCALFILTER, MAD_T_LOCALSCALE,
-       MAD_T_ENV_Z, MAD_T_ENV_Y, MAD_T_ENV_X, MAD_T_ENV_WEIGHT, MAD_T_QSCORE, MAD_T_CF_SORT, MAD_T_CF_NOISE, MAD_T_CF_Q, MAD_T_CF_LOOKUP, MAD_T_JF_MODEL, MAD_T_JF_FIELD, MAD_T_JF_STEPS, MAD_T_CC_TILE, MAD_T_CC_BORDER, MAD_T_CC_LABEL, MAD_T_CC_SELECT, MAD_T_COUNT };
+       MAD_T_ENV_Z, MAD_T_ENV_Y, MAD_T_ENV_X, MAD_T_ENV_WEIGHT, MAD_T_QSCORE, MAD_T_CF_SORT, MAD_T_CF_NOISE, MAD_T_CF_Q, MAD_T_CF_LOOKUP, MAD_T_JF_MODEL, MAD_T_JF_FIELD, MAD_T_JF_STEPS, MAD_T_SYM_SCORE, MAD_T_SYM_AVERAGE, MAD_T_CC_TILE, MAD_T_CC_BORDER, MAD_T_CC_LABEL, MAD_T_CC_SELECT, MAD_T_COUNT };
 
 #define MAD_T_RING 32
 #define MAD_LANES 8
@@ -307,6 +307,9 @@ struct mad_ctx {
     DevBuf fft_tw;
     int fft_tw_n = 0;
     int fft_bpt = 0;      // test hook (mad_set_option "fft_bpt"): 1, 2 or 4 forces that k_fft_lines form, 0 = by N
+    int64_t sym_scratch = (int64_t)64 << 20;      // mad_set_option "symmetry_scratch": bytes of partial records one chunk of mad_map_symmetry_score's operators may take
+    int last_sym_chunks = -1;      // chunks of operators and bytes of partial records of the last mad_map_symmetry_score (mad_last_symmetry_plan)
+    int64_t last_sym_scratch = -1;
     int search_prune = 1; // test hook (mad_set_option "search_prune"): 0 = mad_map_search runs full line passes; the same numbers
     // mad_localres.hip: per box edge 8 / 16 / 32 the window, the twiddles and the box's lattice points in shell order (uploaded once
     // per edge); lr_n[i] = {chunks, points, points per chunk} of that list, 0 until built.  0 - 2: mad_map_local_fsc's lists; 3 - 5:

@@ -3685,6 +3685,11 @@ extern "C" int mad_set_option(mad_ctx *ctx, const char *name, double value) {
         ctx->search_prune = (int)value;
         return MAD_OK;
     }
+    if (!strcmp(name, "symmetry_scratch")) {      // bytes of partial records per chunk of operators of mad_map_symmetry_score: it changes the chunks, never numbers
+        if (!(value >= 1) || !(value <= 0x1p40)) return mad_fail(ctx, MAD_EINVAL, "mad_set_option: symmetry_scratch = %g (1 .. 2^40 bytes)", value);
+        ctx->sym_scratch = (int64_t)value;
+        return MAD_OK;
+    }
     return mad_fail(ctx, MAD_EINVAL, "mad_set_option: unknown option '%s'", name);
 }
 

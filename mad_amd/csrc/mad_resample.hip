@@ -8,12 +8,16 @@
 //   k_bspline_axis / k_bspline_axis_z   one pass of the recursive prefilter (pole sqrt(3) - 2) along x or y / along z
 //   k_resample<ORDER>                   the general form: 8 or 64 taps per output voxel, output in compact bricks
 //   k_resample_axis / k_resample_z      the axis-aligned form: three 1-D passes of 2 or 4 taps from per-axis tables
+//   k_symmetrize<ORDER>                 mad_map_symmetrize (section 4y): the general form's value under up to 64 motions, averaged
+//
+// The taps, the fold of a motion and the checks of a grid are in mad_resample_taps.h, which mad_symmetry.hip shares.
 //
 // Determinism: no atomics, and no sum depends on the launch geometry.
 #include <algorithm>
 #include <vector>
 
 #include "mad_common.h"
+#include "mad_resample_taps.h"
 
 #define RS_THREADS 256
 #define RS_K 40                 // terms of the causal start value: |pole|^40 = 1.3e-23
@@ -163,58 +167,7 @@ __global__ __launch_bounds__(RS_THREADS) void k_bspline_axis_z(double *c, size_t
 // interpolation
 // ---------------------------------------------------------------------------
 
-// index i in [-1, n + 1] of an axis of n >= 2 samples, mirrored about sample 0 and sample n - 1 (period 2 (n - 1))
-__host__ __device__ static inline int rs_mirror(int i, int n) {
-    i = i < 0 ? -i : i;
-    i = i >= n ? 2 * n - 2 - i : i;
-    return i < 0 ? -i : i;
-}
-
-// weights of the taps f - 1 .. f + 2 (ORDER 3) or f, f + 1 (ORDER 1) at t = u - f
-template <int ORDER> __host__ __device__ static inline void rs_weights(double t, double *w) {
-    if (ORDER == 1) { w[0] = 1.0 - t; w[1] = t; return; }
-    const double r = 1.0 - t, t2 = t * t, t3 = t2 * t;
-    w[0] = r * r * r / 6.0;
-    w[1] = (3.0 * t3 - 6.0 * t2 + 4.0) / 6.0;
-    w[2] = (-3.0 * t3 + 3.0 * t2 + 3.0 * t + 1.0) / 6.0;
-    w[3] = t3 / 6.0;
-}
-
-struct RsGeo {
-    int n[3], m[3];             // source and output dims
-    double A[9], b[3];          // u = b + A j
-};
-
-template <int ORDER, typename SRC>
-__device__ __forceinline__ float rs_sample(const SRC *__restrict__ src, const RsGeo &G, int jx, int jy, int jz) {
-    constexpr int NT = ORDER == 1 ? 2 : 4, LO = ORDER == 1 ? 0 : -1;
-    double w[3][NT];
-    int idx[3][NT];
-#pragma unroll
-    for (int a = 0; a < 3; a++) {
-        const double u = ((G.b[a] + G.A[3 * a] * (double)jx) + G.A[3 * a + 1] * (double)jy) + G.A[3 * a + 2] * (double)jz;
-        if (!(u >= 0.0 && u <= (double)(G.n[a] - 1))) return 0.0f;
-        const double f = floor(u);
-        rs_weights<ORDER>(u - f, w[a]);
-#pragma unroll
-        for (int k = 0; k < NT; k++) idx[a][k] = rs_mirror((int)f + LO + k, G.n[a]);
-    }
-    double acc = 0.0;
-#pragma unroll
-    for (int a = 0; a < NT; a++) {
-        double sy = 0.0;
-#pragma unroll
-        for (int b = 0; b < NT; b++) {
-            const SRC *row = src + ((size_t)idx[0][a] * G.n[1] + idx[1][b]) * (size_t)G.n[2];
-            double sz = 0.0;
-#pragma unroll
-            for (int k = 0; k < NT; k++) sz += w[2][k] * (double)row[idx[2][k]];
-            sy += w[1][b] * sz;
-        }
-        acc += w[0][a] * sy;
-    }
-    return (float)acc;
-}
+// rs_mirror, rs_weights, RsGeo, rs_value / rs_sample: mad_resample_taps.h (shared with mad_symmetry.hip)
 
 // The general form.  ORDER 1 reads the float32 source, ORDER 3 the float64 coefficients.  Workgroup blockIdx.x takes brick
 // (blockIdx.x & 7) * per_xcd + (blockIdx.x >> 3) of the bricks counted z fastest: workgroups b and b + 8 share an XCD, so every XCD
@@ -327,19 +280,6 @@ __global__ __launch_bounds__(RS_THREADS) void k_resample_z(const SRC *__restrict
 // host
 // ---------------------------------------------------------------------------
 
-static bool rs_finite(const double *v, int n) {
-    for (int k = 0; k < n; k++)
-        if (!std::isfinite(v[k])) return false;
-    return true;
-}
-
-static bool rs_voxels(const int32_t d[3], size_t *n) {
-    const unsigned long long v = (unsigned long long)d[0] * (unsigned long long)d[1];
-    if (v >= (1ull << 32) || v * (unsigned long long)d[2] >= (1ull << 32)) return false;
-    *n = (size_t)(v * (unsigned long long)d[2]);
-    return true;
-}
-
 static int rs_blocks(mad_ctx *ctx, size_t items) {
     return (int)std::max<int64_t>(1, std::min<int64_t>(mad_ceil_div((int64_t)items, RS_THREADS), (int64_t)ctx->n_cu * 16));
 }
@@ -380,6 +320,33 @@ template <int ORDER, typename SRC> static void rs_general(mad_ctx *ctx, const SR
     hipLaunchKernelGGL((k_resample<ORDER, SRC>), dim3(per_xcd * 8), dim3(RS_THREADS), 0, ctx->stream, src, out, G, by, bz, n_bricks, per_xcd);
 }
 
+// The prefilter of the float32 source d_src into the float64 coefficients d_coef, three passes; d_small takes the three axes' tables
+// (3 * 2 * RS_K doubles), staged in the caller's h_pref, which lives until the caller has synchronised.
+static int rs_prefilter(mad_ctx *ctx, const int32_t dims[3], const float *d_src, double *d_coef, char *d_small, double (*h_pref)[2 * RS_K]) {
+    const size_t bytes_pref = 2 * RS_K * sizeof(double);
+    const double z = sqrt(3.0) - 2.0;
+    PrefArgs P[3];
+    for (int a = 0; a < 3; a++) {
+        const int n = dims[a];
+        for (int i = 0; i < RS_K; i++) {
+            h_pref[a][i] = i == 0 ? 1.0 : (i == n - 1 ? pow(z, (double)i) : (i < n ? pow(z, (double)i) + pow(z, (double)(2 * n - 2 - i)) : 0.0));
+            h_pref[a][RS_K + i] = pow(z, (double)i);
+        }
+        P[a].z = z; P[a].gain = (1.0 - z) * (1.0 - 1.0 / z); P[a].zfac = z / (z * z - 1.0);
+        P[a].den = 1.0 - pow(z, (double)(2 * n - 2));
+        P[a].tab = (const double *)(d_small + a * bytes_pref);
+    }
+    MAD_HIP(hipMemcpyAsync(d_small, h_pref, 3 * bytes_pref, hipMemcpyHostToDevice, ctx->stream));
+    const size_t nyz = (size_t)dims[1] * dims[2], nxz = (size_t)dims[0] * dims[2], nxy = (size_t)dims[0] * dims[1];
+    hipLaunchKernelGGL((k_bspline_axis<float>), dim3((unsigned)mad_ceil_div((int64_t)nyz, RS_THREADS)), dim3(RS_THREADS), 0, ctx->stream,
+                       (const float *)d_src, d_coef, nyz, nyz, (size_t)0, nyz, dims[0], P[0]);
+    hipLaunchKernelGGL((k_bspline_axis<double>), dim3((unsigned)mad_ceil_div((int64_t)nxz, RS_THREADS)), dim3(RS_THREADS), 0, ctx->stream,
+                       (const double *)d_coef, d_coef, nxz, (size_t)dims[2], nyz, (size_t)dims[2], dims[1], P[1]);
+    hipLaunchKernelGGL(k_bspline_axis_z, dim3((unsigned)mad_ceil_div((int64_t)nxy, RS_ZB)), dim3(RS_THREADS), 0, ctx->stream, d_coef, nxy,
+                       dims[2], P[2]);
+    return MAD_OK;
+}
+
 extern "C" int mad_map_resample(mad_ctx *ctx, const float *grid, const int32_t dims[3], const double origin[3], double voxsp,
                                 const double *R9, const double *T3, int order, const int32_t out_dims[3], const double out_origin[3],
                                 double out_voxsp, float *out) {
@@ -403,22 +370,12 @@ extern "C" int mad_map_resample(mad_ctx *ctx, const float *grid, const int32_t d
     static const double eye[9] = {1, 0, 0, 0, 1, 0, 0, 0, 1}, zero3[3] = {0, 0, 0};
     const double *R = R9 ? R9 : eye, *T = T3 ? T3 : zero3;
     if (R9) {
-        double dev = 0.0;
-        for (int i = 0; i < 3; i++)
-            for (int j = 0; j < 3; j++) {
-                const double d = (R[3 * i] * R[3 * j] + R[3 * i + 1] * R[3 * j + 1]) + R[3 * i + 2] * R[3 * j + 2] - (i == j ? 1.0 : 0.0);
-                dev = std::max(dev, fabs(d));
-            }
-        const double det = R[0] * (R[4] * R[8] - R[5] * R[7]) - R[1] * (R[3] * R[8] - R[5] * R[6]) + R[2] * (R[3] * R[7] - R[4] * R[6]);
-        if (dev > 1e-9 || det < 0) return mad_fail(ctx, MAD_EINVAL, "%s: R is no rotation (max|R R^T - I| = %g, det %g)", who, dev, det);
+        double dev = 0.0, det = 0.0;
+        if (!rs_rotation_ok(R, &dev, &det)) return mad_fail(ctx, MAD_EINVAL, "%s: R is no rotation (max|R R^T - I| = %g, det %g)", who, dev, det);
     }
-    // u = ((p + w j - T) @ R^T - o) / v as u = b + A j (mad_amd/resample.py::affine, the same expressions)
     RsGeo G;
-    for (int a = 0; a < 3; a++) {
-        G.n[a] = dims[a]; G.m[a] = out_dims[a];
-        for (int k = 0; k < 3; k++) G.A[3 * a + k] = (R[3 * a + k] * out_voxsp) / voxsp;
-        G.b[a] = ((((out_origin[0] - T[0]) * R[3 * a] + (out_origin[1] - T[1]) * R[3 * a + 1]) + (out_origin[2] - T[2]) * R[3 * a + 2]) - origin[a]) / voxsp;
-    }
+    for (int a = 0; a < 3; a++) { G.n[a] = dims[a]; G.m[a] = out_dims[a]; }
+    rs_fold(R, T, origin, voxsp, out_origin, out_voxsp, G.A, G.b);
     if (!rs_finite(G.A, 9) || !rs_finite(G.b, 3)) return mad_fail(ctx, MAD_EINVAL, "%s: the lattices are too far apart for float64", who);
     const char *env = getenv("MAD_RESAMPLE_GENERAL");      // read per call: both forms can run in one process
     const bool general = memcmp(R, eye, sizeof(eye)) != 0 || (env && env[0] && strcmp(env, "0") != 0);
@@ -470,29 +427,8 @@ extern "C" int mad_map_resample(mad_ctx *ctx, const float *grid, const int32_t d
     AxisTap *d_tab = (AxisTap *)(d_small + 3 * bytes_pref);
     MAD_HIP(hipMemcpyAsync(d_src, grid, n_src * 4, hipMemcpyHostToDevice, ctx->stream));
     if (!general) MAD_HIP(hipMemcpyAsync(d_tab, tab.data(), n_tab * sizeof(AxisTap), hipMemcpyHostToDevice, ctx->stream));
-    if (order == 3) {
-        const double z = sqrt(3.0) - 2.0;
-        double h_pref[3][2 * RS_K];
-        PrefArgs P[3];
-        for (int a = 0; a < 3; a++) {
-            const int n = dims[a];
-            for (int i = 0; i < RS_K; i++) {
-                h_pref[a][i] = i == 0 ? 1.0 : (i == n - 1 ? pow(z, (double)i) : (i < n ? pow(z, (double)i) + pow(z, (double)(2 * n - 2 - i)) : 0.0));
-                h_pref[a][RS_K + i] = pow(z, (double)i);
-            }
-            P[a].z = z; P[a].gain = (1.0 - z) * (1.0 - 1.0 / z); P[a].zfac = z / (z * z - 1.0);
-            P[a].den = 1.0 - pow(z, (double)(2 * n - 2));
-            P[a].tab = (const double *)(d_small + a * bytes_pref);
-        }
-        MAD_HIP(hipMemcpyAsync(d_small, h_pref, 3 * bytes_pref, hipMemcpyHostToDevice, ctx->stream));
-        const size_t nyz = (size_t)dims[1] * dims[2], nxz = (size_t)dims[0] * dims[2], nxy = (size_t)dims[0] * dims[1];
-        hipLaunchKernelGGL((k_bspline_axis<float>), dim3((unsigned)mad_ceil_div((int64_t)nyz, RS_THREADS)), dim3(RS_THREADS), 0, ctx->stream,
-                           (const float *)d_src, d_coef, nyz, nyz, (size_t)0, nyz, dims[0], P[0]);
-        hipLaunchKernelGGL((k_bspline_axis<double>), dim3((unsigned)mad_ceil_div((int64_t)nxz, RS_THREADS)), dim3(RS_THREADS), 0, ctx->stream,
-                           (const double *)d_coef, d_coef, nxz, (size_t)dims[2], nyz, (size_t)dims[2], dims[1], P[1]);
-        hipLaunchKernelGGL(k_bspline_axis_z, dim3((unsigned)mad_ceil_div((int64_t)nxy, RS_ZB)), dim3(RS_THREADS), 0, ctx->stream, d_coef, nxy,
-                           dims[2], P[2]);
-    }
+    double h_pref[3][2 * RS_K];
+    if (order == 3) MAD_TRY(rs_prefilter(ctx, dims, d_src, d_coef, d_small, h_pref));
     if (general) {
         if (order == 1) rs_general<1, float>(ctx, d_src, d_out, G);
         else rs_general<3, double>(ctx, d_coef, d_out, G);
@@ -502,6 +438,98 @@ extern "C" int mad_map_resample(mad_ctx *ctx, const float *grid, const int32_t d
     }
     MAD_HIP(hipGetLastError());
     MAD_HIP(hipMemcpyAsync(out, d_out, n_out * 4, hipMemcpyDeviceToHost, ctx->stream));
+    MAD_HIP(hipStreamSynchronize(ctx->stream));
+    return MAD_OK;
+}
+
+// ---------------------------------------------------------------------------
+// the average over a set of motions
+// ---------------------------------------------------------------------------
+
+#define SYMZ_MAX_OPS 64
+
+// out[j] = (float)((sum over g of v_g) / n_ops), v_g = rs_value of the source moved by operator g at voxel j of the source's own
+// lattice, the sum from +0.0 in the order g = 0, 1, ...; ops[g] = A[9] then b[3].  The bricks and their order over the XCDs are
+// k_resample's; the operators are uniform over the launch, so their coefficients are scalar loads.
+template <int ORDER, typename SRC>
+__global__ __launch_bounds__(RS_THREADS) void k_symmetrize(const SRC *__restrict__ src, float *__restrict__ out, const double *__restrict__ ops, int n_ops,
+                                                           int nx, int ny, int nz, unsigned bricks_y, unsigned bricks_z, unsigned n_bricks,
+                                                           unsigned per_xcd) {
+    const unsigned brick = (blockIdx.x & 7u) * per_xcd + (blockIdx.x >> 3);
+    if (brick >= n_bricks) return;
+    const unsigned bz = brick % bricks_z, t = brick / bricks_z, by = t % bricks_y, bx = t / bricks_y;
+    const int jx = (int)(bx * RS_BX + (threadIdx.x >> 6)), jy = (int)(by * RS_BY + ((threadIdx.x >> 3) & 7)),
+              jz = (int)(bz * RS_BZ + (threadIdx.x & 7) * 4);
+    if (jx >= nx || jy >= ny || jz >= nz) return;
+    const int nv = nz - jz < 4 ? nz - jz : 4;
+    const size_t o = ((size_t)jx * ny + jy) * (size_t)nz + jz;
+    double acc[4] = {0.0, 0.0, 0.0, 0.0};
+    RsGeo G;
+    G.n[0] = G.m[0] = nx; G.n[1] = G.m[1] = ny; G.n[2] = G.m[2] = nz;
+    for (int g = 0; g < n_ops; g++) {
+        const double *q = ops + (size_t)12 * g;
+#pragma unroll
+        for (int k = 0; k < 9; k++) G.A[k] = q[k];
+#pragma unroll
+        for (int k = 0; k < 3; k++) G.b[k] = q[9 + k];
+#pragma unroll
+        for (int k = 0; k < 4; k++)
+            if (k < nv) acc[k] += rs_value<ORDER, SRC>(src, G, jx, jy, jz + k);
+    }
+    const double n = (double)n_ops;
+#pragma unroll
+    for (int k = 0; k < 4; k++)
+        if (k < nv) out[o + k] = (float)(acc[k] / n);
+}
+
+extern "C" int mad_map_symmetrize(mad_ctx *ctx, const float *grid, const int32_t dims[3], const double origin[3], double voxsp, int32_t n_ops,
+                                  const double *R9, const double *T3, int order, float *out) {
+    const char *who = "mad_map_symmetrize";
+    if (ctx) mad_use_lane(ctx, 0);
+    if (!ctx || !grid || !dims || !origin || !R9 || !T3 || !out) return ctx ? mad_fail(ctx, MAD_EINVAL, "%s: NULL argument", who) : MAD_EINVAL;
+    if (order != 1 && order != 3) return mad_fail(ctx, MAD_EINVAL, "%s: order %d (1 or 3)", who, order);
+    if (n_ops < 1 || n_ops > SYMZ_MAX_OPS) return mad_fail(ctx, MAD_EINVAL, "%s: %d operators (1 .. %d)", who, n_ops, SYMZ_MAX_OPS);
+    for (int k = 0; k < 3; k++)
+        if (dims[k] < 2) return mad_fail(ctx, MAD_EINVAL, "%s: source of %d x %d x %d voxels: every axis needs 2", who, dims[0], dims[1], dims[2]);
+    if (!rs_finite(origin, 3) || !std::isfinite(voxsp) || !rs_finite(R9, 9 * n_ops) || !rs_finite(T3, 3 * n_ops))
+        return mad_fail(ctx, MAD_EINVAL, "%s: a number that is not finite", who);
+    if (!(voxsp > 0)) return mad_fail(ctx, MAD_EINVAL, "%s: voxsp %g", who, voxsp);
+    size_t n_src = 0;
+    if (!rs_voxels(dims, &n_src))
+        return mad_fail(ctx, MAD_EINVAL, "%s: %d x %d x %d voxels: grids of 2^32 voxels or more are not supported", who, dims[0], dims[1], dims[2]);
+    std::vector<double> ops((size_t)12 * n_ops);
+    for (int g = 0; g < n_ops; g++) {
+        double dev = 0.0, det = 0.0;
+        if (!rs_rotation_ok(R9 + 9 * g, &dev, &det))
+            return mad_fail(ctx, MAD_EINVAL, "%s: R of operator %d is no rotation (max|R R^T - I| = %g, det %g)", who, g, dev, det);
+        rs_fold(R9 + 9 * g, T3 + 3 * g, origin, voxsp, origin, voxsp, &ops[(size_t)12 * g], &ops[(size_t)12 * g + 9]);
+        if (!rs_finite(&ops[(size_t)12 * g], 12)) return mad_fail(ctx, MAD_EINVAL, "%s: operator %d moves the map too far for float64", who, g);
+    }
+    const size_t bytes_pref = 2 * RS_K * sizeof(double), bytes_ops = ops.size() * sizeof(double);
+    MAD_TRY(mad_reserve(ctx, mad_sb(ctx, S_TMP_H), (n_src + 4) * 4));
+    MAD_TRY(mad_reserve(ctx, mad_sb(ctx, S_TMP_I), (n_src + 4) * 4));
+    if (order == 3) MAD_TRY(mad_reserve(ctx, mad_sb(ctx, S_TMP_A), (n_src + 4) * 8));
+    MAD_TRY(mad_reserve(ctx, mad_sb(ctx, S_TMP_G), 3 * bytes_pref + bytes_ops + 64));
+    float *d_src = scratch<float>(ctx, S_TMP_H), *d_out = scratch<float>(ctx, S_TMP_I);
+    double *d_coef = scratch<double>(ctx, S_TMP_A);
+    char *d_small = scratch<char>(ctx, S_TMP_G);
+    double *d_ops = (double *)(d_small + 3 * bytes_pref);
+    MAD_HIP(hipMemcpyAsync(d_src, grid, n_src * 4, hipMemcpyHostToDevice, ctx->stream));
+    MAD_HIP(hipMemcpyAsync(d_ops, ops.data(), bytes_ops, hipMemcpyHostToDevice, ctx->stream));
+    double h_pref[3][2 * RS_K];
+    if (order == 3) MAD_TRY(rs_prefilter(ctx, dims, d_src, d_coef, d_small, h_pref));      // once per call, whatever n_ops
+    const unsigned bx = (unsigned)mad_ceil_div(dims[0], RS_BX), by = (unsigned)mad_ceil_div(dims[1], RS_BY), bz = (unsigned)mad_ceil_div(dims[2], RS_BZ);
+    const unsigned n_bricks = bx * by * bz, per_xcd = (n_bricks + 7) / 8;
+    mad_timer_begin(ctx, MAD_T_SYM_AVERAGE);
+    if (order == 1)
+        hipLaunchKernelGGL((k_symmetrize<1, float>), dim3(per_xcd * 8), dim3(RS_THREADS), 0, ctx->stream, (const float *)d_src, d_out, (const double *)d_ops,
+                           (int)n_ops, dims[0], dims[1], dims[2], by, bz, n_bricks, per_xcd);
+    else
+        hipLaunchKernelGGL((k_symmetrize<3, double>), dim3(per_xcd * 8), dim3(RS_THREADS), 0, ctx->stream, (const double *)d_coef, d_out,
+                           (const double *)d_ops, (int)n_ops, dims[0], dims[1], dims[2], by, bz, n_bricks, per_xcd);
+    mad_timer_end(ctx, MAD_T_SYM_AVERAGE);
+    MAD_HIP(hipGetLastError());
+    MAD_HIP(hipMemcpyAsync(out, d_out, n_src * 4, hipMemcpyDeviceToHost, ctx->stream));
     MAD_HIP(hipStreamSynchronize(ctx->stream));
     return MAD_OK;
 }
