@@ -96,6 +96,29 @@ int main() {
     CHECK(jf_groups(256, 4, 26000, 8) == 8 && jf_groups(256, 1, 4097, 1) == 1 && jf_groups(8, 64, 100000, 8) == 1);
     CHECK(jf_fits_registers(4096, 1) && !jf_fits_registers(4097, 1) && jf_fits_registers(4097, 2) && jf_fits_registers(26000, 8));
     for (int B = 1; B <= JF_MAX_BODIES; B++) CHECK(B * jf_groups(256, B, 1 << 20, 8) <= 256);      // all workgroups resident at one per compute unit
+    // ... and with bodies of mixed sizes, as jf_setup adds them up: every B, every cap, sizes of 30, 4097 and 2^20 atoms in turn from
+    // every starting size, in runs of 1 to 3 bodies, and drawn at random.  A body's G never exceeds that of the largest size.
+    {
+        const int64_t sizes[3] = {30, 4097, 1 << 20};
+        for (int B = 1; B <= JF_MAX_BODIES; B++)
+            for (int cap = 1; cap <= 8; cap++) {
+                const int32_t g_max = jf_groups(256, B, sizes[2], cap);
+                CHECK(jf_groups(256, B, sizes[0], cap) == 1 && jf_groups(256, B, sizes[1], cap) == (cap >= 2 ? 2 : 1) && g_max <= cap);
+                for (int pattern = 0; pattern < 12; pattern++) {
+                    int total = 0;
+                    bool mixed[3] = {false, false, false};
+                    for (int b = 0; b < B; b++) {
+                        const int pick = pattern < 9 ? (b / (1 + pattern / 3) + pattern % 3) % 3 : (int)(uniform() * 3.0);
+                        const int32_t G = jf_groups(256, B, sizes[pick], cap);
+                        CHECK(G >= 1 && G <= g_max && G <= JF_MAX_G);
+                        total += G;
+                        mixed[pick] = true;
+                    }
+                    CHECK(total <= 256 && total >= B);
+                    if (B >= 9 && pattern < 9) CHECK(mixed[0] && mixed[1] && mixed[2]);
+                }
+            }
+    }
 
     // the plan of three bodies
     {

@@ -113,6 +113,72 @@ def test_fixed_bodies_and_step_counts():
     assert frozen["n_rounds"] == 0 and len(frozen["scale"]) == 0 and np.array_equal(frozen["coords"][1], s["start"][1])
 
 
+@pytest.mark.parametrize("name", jc.PLAN_SCENES)
+def test_plan_scenes_meet_their_conditions(name):
+    """The scenes of tests/test_gpu_jointfit_plans.py (jointfit_cases.plan_scene): the restatement decides every batch by 1e-4 A or
+    more, every free body moves by 0.5 A or more and, where the scene runs to convergence, converges; each scene shows what it is
+    there for."""
+    s, r = jc.plan_scene(name), jc.restated_plan(name)
+    n, shape = len(s["start"]), s["grid"].shape
+    free = [b for b in range(n) if not (s["fixed"] and s["fixed"][b])]
+    moved = [np.abs(r["coords"][b] - s["start"][b]).max() for b in range(n)]
+    rounds = [(r["last_step"][b] + 4) // 4 for b in free]
+    print("%s: %d bodies of %d - %d atoms, margin %.3g A, %d rounds, bodies stop in rounds %d - %d, %d converged, moved %.2f - %.2f A" % (
+        name, n, min(map(len, s["start"])), max(map(len, s["start"])), r["margin"], r["n_rounds"], min(rounds), max(rounds),
+        sum(r["converged"]), min(moved[b] for b in free), max(moved[b] for b in free)))
+    assert r["margin"] >= 1e-4
+    assert all(moved[b] >= 0.5 for b in free)
+    assert r["n_rounds"] == max(rounds)
+    if name in ("pair", "mixed", "mixed_swapped", "many16", "slab"):
+        assert all(r["converged"])
+    if name in ("pair", "mixed", "mixed_swapped"):
+        assert sorted(jc.jf_groups(256, 2, len(c), 8) for c in s["start"]) == ([2, 2] if name == "pair" else [1, 2])
+    if name == "mixed_swapped":      # two bodies add up to the same M in either order: the same bits, body for body
+        other = jc.restated_plan("mixed")
+        assert [c.tobytes() for c in r["coords"]] == [c.tobytes() for c in other["coords"][::-1]] and r["last_step"] == other["last_step"][::-1]
+        assert r["scale"].tobytes() == other["scale"].tobytes()
+    if name == "g8":
+        assert [jc.jf_groups(256, 2, len(c), 8) for c in s["start"]] == [8, 2] and r["n_rounds"] == 6 and r["last_step"] == [23, 23]
+    if name == "many64":
+        assert n == jointfit.MAX_BODIES and r["n_rounds"] == 10 and sum(s["fixed"]) == len(jc.MANY_FIXED)
+        for b in jc.MANY_FIXED:
+            assert r["last_step"][b] == -1 and np.array_equal(r["coords"][b], s["start"][b])
+        assert 0 < sum(r["converged"]) < len(free)      # some bodies stop before the host's first poll, most run all 40 steps
+    if name == "many16":      # the bodies stop in different windows of the host's poll, and rounds run with a single body left
+        assert max(rounds) - min(rounds) > 8 and len(set(v // 8 for v in rounds)) >= 3 and sorted(rounds)[-1] - sorted(rounds)[-2] > 8
+    if name == "slab":
+        r_blur = jointfit.blur_taps(s["resolution"], jc.VS)[0]
+        edges = [jc.jf_box_edge(np.linalg.norm(c - c.mean(axis=0), axis=1).max(), r_blur, jc.VS, 0.5) for c in s["start"]]
+        assert all(shape[2] < e < shape[0] for e in edges)      # a body's cube is cut to the map's 14 voxels on z, and only there
+        out0, out1 = jc.outside_the_map(s["start"][1], shape), jc.outside_the_map(r["coords"][1], shape)
+        print("slab: atoms of the body at the face outside the map: %d at the start, %d at the end" % (out0, out1))
+        assert 0 < out0 < out1 < len(s["start"][1]) // 2      # the body moves towards the face
+        assert jc.outside_the_map(s["start"][0], shape) == 0 == jc.outside_the_map(r["coords"][0], shape)
+        assert abs(r["coords"][1][:, 0].mean() - jc.ORIGIN[0] - 3.0) < 1.0      # centred about 3 A inside the x = 0 face
+        for c in (s["start"][1], r["coords"][1]):      # centred, its cube would begin before the face: it is shifted against it
+            assert np.floor((c[:, 0].mean() - jc.ORIGIN[0]) / jc.VS + 0.5) - edges[1] // 2 < 0
+
+
+def test_the_plan_restated():
+    """jointfit_cases.jf_groups, jf_fits_registers and expected_plan against the figures check_jointfit_plan.cpp asserts of
+    mad_jointfit_plan.h, and the constants against the header's."""
+    text = open(os.path.join(ROOT, "mad_amd", "csrc", "mad_jointfit_plan.h")).read()
+    for name in ("JF_THREADS", "JF_THREADS_REG", "JF_MAXA", "JF_MAX_G"):
+        assert int(re.search(r"^#define %s (\d+)" % name, text, re.M).group(1)) == getattr(jc, name)
+    assert int(re.search(r"^#define JF_MAX_BODIES (\d+)", text, re.M).group(1)) == jointfit.MAX_BODIES
+    g = jc.jf_groups
+    assert (g(256, 1, 4097, 8), g(256, 1, 4095, 8), g(256, 1, 26000, 8), g(256, 64, 26000, 8)) == (2, 1, 8, 4)
+    assert (g(256, 4, 26000, 8), g(256, 1, 4097, 1), g(8, 64, 100000, 8), g(256, 1, 16384, 8), g(256, 1, 16383, 8)) == (8, 1, 1, 8, 7)
+    f = jc.jf_fits_registers
+    assert f(4096, 1) and not f(4097, 1) and f(4097, 2) and f(26000, 8) and f(16400, 5) and not f(16400, 3)
+    assert jc.jf_box_edge(0.0, 3, 1.5, 0.5) == 13 and jc.jf_box_edge(0.0, 3, 1.5, 0.0) == 10 and jc.jf_box_edge(0.0, 0, 1.0, 0.0) == 4
+    p = jc.expected_plan
+    assert p([4100, 4112], 256) == (2, 1, 4) and p([4100, 4112], 256, registers=0) == (2, 0, 4) and p([4100, 4112], 256, split=1) == (1, 0, 2)
+    assert p([4100, 90], 256) == (2, 1, 3) and p([90, 4100], 256) == (1, 1, 3) and p([90, 4100], 256, split=1) == (1, 0, 2)
+    assert p([16400, 4100], 256) == (8, 1, 10) and p([16400, 4100], 256, split=5) == (5, 1, 7) and p([16400, 4100], 256, split=3) == (3, 0, 5)
+    assert p([30] * 64, 256) == (1, 1, 64) and p([16400], 256, split=3) == (3, 0, 3) and p([16400] * 64, 304) == (4, 0, 256)
+
+
 def test_arguments_of_the_python_side():
     a, b = np.zeros((4, 3)), np.ones((2, 3))
     coords, ms, src = jointfit.bodies_of("t", [a, b])
