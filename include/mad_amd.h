@@ -438,8 +438,25 @@ int mad_assembly_refine(mad_ctx *ctx, int n_bodies, const double *atoms, const d
                         double *rot, double *trans, int32_t *converged, int32_t *last_step, double *scale_per_round,
                         int32_t *n_rounds);
 /*
- * What the most recent mad_assembly_refine chose: *G = workgroups of body 0, *in_registers = the form of k_jf_steps (1: a thread
- * keeps its atoms in registers for the round; 0: global memory), *workgroups = workgroups of all bodies.  -1 before the first.
+ * n_units asymmetric units refined under a point group.  The units are given as mad_assembly_refine's bodies
+ * (atoms, mass, first_atom, fixed: per unit).  The n_ops operators are op_rot (n_ops x 9, row-major, for row vectors) and op_trans
+ * (n_ops x 3): image (u, g) of unit u is x -> x op_rot[g] + op_trans[g], each component ((x R[0][j] + y R[1][j]) + z R[2][j]) + T[j],
+ * and it is body u n_ops + g of the model; image 0 is the unit itself.  Operator 0 must be the identity bit for bit, every op_rot[g]
+ * orthonormal (|R R^T - I| <= 1e-6 in every entry) with a positive determinant, and n_units n_ops at most 64.  A round is
+ * mad_assembly_refine's over the images as bodies, except that the images of a unit take ONE common step: the force is the sum over
+ * images and atoms of the gathered gradients pulled back into the unit's frame (h = g R^T), the torque that of cross(h, x - centre)
+ * over the unit's own coordinates x, and the batch decision is taken on the unit's coordinates.  With n_ops = 1 every output is
+ * mad_assembly_refine's, bit for bit.  coords (all unit atoms x 3), rot, trans, converged, last_step: per UNIT, as
+ * mad_assembly_refine gives them per body.  Refusals as mad_assembly_refine, and the operator conditions above, each by name.
+ */
+int mad_assembly_refine_symmetric(mad_ctx *ctx, int n_units, const double *atoms, const double *mass, const int64_t *first_atom,
+                                  const uint8_t *fixed, int n_ops, const double *op_rot, const double *op_trans, double resolution,
+                                  int n_steps, double max_step, double min_step, double *coords, double *rot, double *trans,
+                                  int32_t *converged, int32_t *last_step, double *scale_per_round, int32_t *n_rounds);
+/*
+ * What the most recent mad_assembly_refine or mad_assembly_refine_symmetric chose: *G = workgroups of body 0 (per image of unit 0),
+ * *in_registers = the form of k_jf_steps / k_jf_steps_sym (1: a thread keeps its atoms in registers for the round; 0: global
+ * memory), *workgroups = workgroups of all bodies (of all images).  -1 before the first.
  * mad_set_option "jointfit_split" (1 .. 8: workgroups per body at most) and "jointfit_registers" (0: never) are the tests' hooks.
  */
 int mad_last_assembly_plan(mad_ctx *ctx, int *G, int *in_registers, int *workgroups);

@@ -205,6 +205,16 @@ class Dmap(object):
         from . import jointfit
         return jointfit.refine_together(self, structures, resolution, n_steps=n_steps, max_step=max_step, min_step=min_step, fixed=fixed, masses=masses)
 
+    def refine_symmetric(self, structures, resolution, symmetry, n_steps=500, max_step=0.5, min_step=0.01, fixed=None, masses=None):
+        """Refine asymmetric units against this map under a point group -> `jointfit.SymmetricFit`, a `JointFit` over the UNITS
+        with `operators`, `images(u)`, `assembly()` and `write_pdb(prefix)` (`<prefix>_<u>_<g>.pdb`).  `symmetry`: what
+        `find_symmetry` returned, `symmetry.point_group(...)`, or a pair (R (K, 3, 3), T (K, 3)) with operator 0 the identity.  The
+        model holds every image x @ R_g + T_g of every unit (at most 64 in all); the images of a unit take ONE common step, from
+        the gradients all of them gather, so the assembly stays exactly symmetric.  `structures`, `masses`, `fixed` (per unit)
+        and the steps as `refine_together`.  Neither `self` nor the structures are modified.  DESIGN.md section 4z."""
+        from . import jointfit
+        return jointfit.refine_symmetric(self, structures, resolution, symmetry, n_steps=n_steps, max_step=max_step, min_step=min_step, fixed=fixed, masses=masses)
+
     def residual(self, structures, resolution, masses=None):
         """What this map holds beyond the placed bodies, as a new `Dmap` on the same lattice: map - s M, M the sum of the bodies'
         simulated densities at `resolution` (not normalised) and s = <map, M> / <M, M>, kept as `scale` on the result.

@@ -74,6 +74,7 @@ mad_space_build=i(pppiiiiiippidpipppii) mad_space_info=i(pppppp) mad_space_downl
 mad_space_patches=i(ppipiip) mad_space_localize=i(ppipippppp) mad_localize_volume=i(ppiiiipippppp)
 mad_pose_cluster_many=i(pippppdpppp) mad_rank_copies=i(ppiiidqqqpppppp) mad_rank_models=i(ppipiqqqqpppppp)
 mad_last_rank_plan=i(ppppp) mad_assembly_density=i(pipppdppp) mad_assembly_refine=i(pippppdiddppppppp)
+mad_assembly_refine_symmetric=i(pippppippdiddppppppp)
 mad_last_assembly_plan=i(pppp) mad_map_symmetry_score=i(ppppdpdiippp) mad_map_symmetrize=i(ppppdippip)
 mad_last_symmetry_plan=i(pppp)
 """.split()}
@@ -1116,8 +1117,34 @@ class Lib(object):
                                                _p(out), _p(rot), _p(trans), _p(conv), _p(last), _p(scale), C.byref(rounds)))
         return ([out[first[b]:first[b + 1]].copy() for b in range(B)], rot, trans, conv.astype(bool), last, scale[:rounds.value].copy())
 
+    def assembly_refine_symmetric(self, coords_list, mass_list, R, T, resolution, n_steps=500, max_step=0.5, min_step=0.01, fixed=None):
+        """The units refined under the operators x -> x @ R[g] + T[g] (R (K, 3, 3), T (K, 3), operator 0 the identity) against the
+        map given to upload_density (mad_assembly_refine_symmetric) -> per UNIT what assembly_refine returns per body."""
+        who = "assembly_refine_symmetric"
+        atoms, mass, first = self._bodies(who, coords_list, mass_list)
+        U = len(first) - 1
+        rot_in, tr_in = _c(R, np.float64), _c(T, np.float64)
+        if rot_in.ndim != 3 or rot_in.shape[1:] != (3, 3) or tr_in.shape != (len(rot_in), 3):
+            raise ValueError("%s: R of shape %s and T of shape %s, not (K, 3, 3) and (K, 3)" % (who, rot_in.shape, tr_in.shape))
+        fx = None
+        if fixed is not None:
+            fx = _c(np.asarray(fixed, bool), np.uint8).reshape(-1)
+            if len(fx) != U:
+                raise ValueError("%s: fixed has %d entries for %d units" % (who, len(fx), U))
+        n_steps = _whole(who, "n_steps", n_steps)
+        out = np.empty_like(atoms)
+        rot, trans = np.zeros((U, 3, 3)), np.zeros((U, 3))
+        conv, last = np.zeros(U, np.int32), np.zeros(U, np.int32)
+        scale = np.zeros(max((n_steps + 3) // 4, 1))
+        rounds = C.c_int32(0)
+        self._chk(self.dll.mad_assembly_refine_symmetric(self.ctx, U, _p(atoms), _p(mass), _p(first), _p(fx), len(rot_in), _p(rot_in), _p(tr_in),
+                                                         resolution, n_steps, max_step, min_step, _p(out), _p(rot), _p(trans), _p(conv),
+                                                         _p(last), _p(scale), C.byref(rounds)))
+        return ([out[first[b]:first[b + 1]].copy() for b in range(U)], rot, trans, conv.astype(bool), last, scale[:rounds.value].copy())
+
     def last_assembly_plan(self):
-        """(G of body 0, in_registers, workgroups) of the most recent assembly_refine (mad_last_assembly_plan); -1 before the first."""
+        """(G of body 0, in_registers, workgroups) of the most recent assembly_refine or assembly_refine_symmetric
+        (mad_last_assembly_plan); -1 before the first."""
         g, reg, wgs = C.c_int(-1), C.c_int(-1), C.c_int(-1)
         self._chk(self.dll.mad_last_assembly_plan(self.ctx, C.byref(g), C.byref(reg), C.byref(wgs)))
         return g.value, reg.value, wgs.value

@@ -199,6 +199,116 @@ int main() {
     }
     CHECK(jf_box_edge(1e9, 3, 1.0, 0.5) == -1 && jf_box_edge(NAN, 3, 1.0, 0.5) == -1 && jf_box_edge(0.0, 0, 1.0, 0.0) == 4);
 
+    // ---- units under operators (mad_assembly_refine_symmetric) ----
+    // the operators: the quarter turn about z through (10, 2, 0) and its powers, on heap buffers of exactly n_ops x 9 and n_ops x 3
+    {
+        const double c[3] = {10.0, 2.0, 0.0};
+        std::vector<double> rot, tr;
+        for (int g = 0; g < 4; g++) {
+            const double co[4] = {1, 0, -1, 0}, si[4] = {0, 1, 0, -1};
+            const double R[9] = {co[g], si[g], 0, -si[g], co[g], 0, 0, 0, 1};      // row vectors: x -> x R
+            rot.insert(rot.end(), R, R + 9);
+            for (int j = 0; j < 3; j++) tr.push_back(g == 0 ? 0.0 : c[j] - ((c[0] * R[j] + c[1] * R[3 + j]) + c[2] * R[6 + j]));
+        }
+        auto ops_refused = [&](int32_t U, int32_t K, const std::vector<double> &r, const std::vector<double> &t, const char *word) {
+            std::vector<double> rr(r), tt(t);      // exact sizes
+            char m[256] = "";
+            const bool ok = jf_ops_check("check", U, K, rr.empty() ? nullptr : rr.data(), tt.empty() ? nullptr : tt.data(), m, sizeof m);
+            if (ok || !strstr(m, word)) fprintf(stderr, "  wanted a refusal naming '%s', got %s '%s'\n", word, ok ? "a pass," : "", m);
+            return !ok && strstr(m, word) != nullptr;
+        };
+        CHECK(jf_ops_check("check", 16, 4, rot.data(), tr.data(), msg, sizeof msg));
+        CHECK(jf_ops_check("check", 64, 1, rot.data(), tr.data(), msg, sizeof msg));
+        CHECK(ops_refused(17, 4, rot, tr, "n_units x n_ops = 68"));
+        CHECK(ops_refused(0, 4, rot, tr, "n_units") && ops_refused(65, 1, rot, tr, "n_units"));
+        CHECK(ops_refused(1, 0, rot, tr, "n_ops") && ops_refused(1, 65, rot, tr, "n_ops") && ops_refused(1, -1, rot, tr, "n_ops"));
+        CHECK(ops_refused(1, 4, {}, tr, "op_rot") && ops_refused(1, 4, rot, {}, "op_trans"));
+        std::vector<double> r2(rot), t2(tr);
+        r2[0] = 1.0 + 1e-15; CHECK(ops_refused(1, 4, r2, tr, "identity"));
+        r2 = rot; r2[1] = 1e-300; CHECK(ops_refused(1, 4, r2, tr, "identity"));
+        t2[2] = -1e-300; CHECK(ops_refused(1, 4, rot, t2, "identity"));
+        r2 = rot; std::swap_ranges(r2.begin(), r2.begin() + 9, r2.begin() + 9); CHECK(ops_refused(1, 4, r2, tr, "identity"));
+        r2 = rot; for (int i = 0; i < 9; i++) r2[9 + i] *= 1.0 + 1e-6; CHECK(ops_refused(1, 4, r2, tr, "orthonormal"));      // R R^T - I = 2e-6
+        r2 = rot; for (int i = 0; i < 9; i++) r2[9 + i] *= 1.0 + 1e-7; CHECK(jf_ops_check("check", 1, 4, r2.data(), tr.data(), msg, sizeof msg));
+        r2 = rot; r2[18 + 5] = 2e-6; CHECK(ops_refused(1, 4, r2, tr, "operator 2 is not orthonormal"));      // a shear
+        r2 = rot; r2[27 + 8] = -1.0; CHECK(ops_refused(1, 4, r2, tr, "operator 3 is a reflection"));
+        r2 = rot; r2[9 + 4] = NAN; CHECK(ops_refused(1, 4, r2, tr, "op_rot"));
+        t2 = tr; t2[4] = INFINITY; CHECK(ops_refused(1, 4, rot, t2, "op_trans"));
+        t2 = tr; t2[4] = 1e13; CHECK(ops_refused(1, 4, rot, t2, "op_trans"));
+        // image and pull-back: a point and its images keep their distance to the centre; h = g R^T undoes x R on a vector
+        const double p[3] = {13.0, 3.0, 5.0};
+        for (int g = 1; g < 4; g++) {
+            double q[3], h[3], back[3];
+            jf_image(&rot[9 * g], &tr[3 * g], p, q);
+            CHECK(fabs(hypot(q[0] - c[0], q[1] - c[1]) - hypot(3.0, 1.0)) < 1e-12 && q[2] == 5.0);
+            const double zero[3] = {0, 0, 0}, v[3] = {0.3, -1.1, 2.0};
+            jf_image(&rot[9 * g], zero, v, h);
+            jf_pull_back(&rot[9 * g], h, back);
+            CHECK(fabs(back[0] - v[0]) < 1e-15 && fabs(back[1] - v[1]) < 1e-15 && back[2] == v[2]);
+        }
+        double q4[3];
+        jf_image(&rot[9], &tr[3], p, q4);
+        CHECK(q4[0] == 10.0 - 1.0 && q4[1] == 2.0 + 3.0);      // (3, 1) about the centre turns to (-1, 3)
+
+        // the plan of the images: two units under the four operators in the map of base_call
+        Call cl;
+        cl.body(40, 24.0, 6.0, 20.0, 3.0);
+        cl.body(7, 18.0, -2.0, 30.0, 2.0);
+        std::vector<double> a(cl.atoms), ms(cl.mass);
+        std::vector<int64_t> f(cl.first);
+        static JfPlan U;
+        CHECK(jf_plan("check", cl.dims, cl.origin, cl.vs, 2, a.data(), ms.data(), f.data(), 6.0, true, 500, 0.5, 0.01, U, msg, sizeof msg));
+        CHECK(jf_plan_sym("check", cl.dims, cl.origin, cl.vs, 2, a.data(), ms.data(), f.data(), 4, rot.data(), tr.data(), 6.0, 500, 0.5, 0.01, P, msg, sizeof msg));
+        CHECK(P.n_bodies == 8 && P.n_atoms == 4 * 47 && P.max_atoms == 40 && P.r == U.r && P.max_box == U.max_box);
+        int64_t sum = 0;
+        for (int b = 0; b < 8; b++) {
+            const int u = b / 4, g = b % 4;
+            CHECK(P.edge[b] == U.edge[u] && P.max_dist[b] == U.max_dist[u] && P.vox0[b] == sum);
+            double q[3];
+            jf_image(&rot[9 * g], &tr[3 * g], U.cen[u], q);
+            int64_t v = 1;
+            for (int d = 0; d < 3; d++) {
+                CHECK(g == 0 ? P.cen[b][d] == U.cen[u][d] : P.cen[b][d] == q[d]);
+                CHECK(P.e[b][d] == U.e[u][d] && P.lo[b][d] == jf_box_lo(P.cen[b][d], cl.origin[d], cl.vs, P.edge[b], cl.dims[d]));
+                CHECK(P.lo[b][d] >= 0 && P.lo[b][d] + P.e[b][d] <= cl.dims[d]);
+                if (g == 0) CHECK(P.lo[b][d] == U.lo[u][d]);
+                v *= P.e[b][d];
+            }
+            sum += v;
+        }
+        CHECK(P.vox0[8] == sum);
+        // the refusals of the units are jf_plan's, those of the operators come first, no map before either
+        char m2[256];
+        CHECK(!jf_plan_sym("check", nullptr, cl.origin, cl.vs, 2, a.data(), ms.data(), f.data(), 0, nullptr, nullptr, 6.0, 500, 0.5, 0.01, P, m2, sizeof m2) && strstr(m2, "mad_upload_density"));
+        CHECK(!jf_plan_sym("check", cl.dims, cl.origin, cl.vs, 2, nullptr, ms.data(), f.data(), 0, rot.data(), tr.data(), 6.0, 500, 0.5, 0.01, P, m2, sizeof m2) && strstr(m2, "n_ops"));
+        CHECK(!jf_plan_sym("check", cl.dims, cl.origin, cl.vs, 2, nullptr, ms.data(), f.data(), 4, rot.data(), tr.data(), 6.0, 500, 0.5, 0.01, P, m2, sizeof m2) && strstr(m2, "atoms"));
+        CHECK(!jf_plan_sym("check", cl.dims, cl.origin, cl.vs, 2, a.data(), ms.data(), f.data(), 4, rot.data(), tr.data(), 6.0, 0, 0.5, 0.01, P, m2, sizeof m2) && strstr(m2, "n_steps"));
+        a[5] = NAN;
+        CHECK(!jf_plan_sym("check", cl.dims, cl.origin, cl.vs, 2, a.data(), ms.data(), f.data(), 4, rot.data(), tr.data(), 6.0, 500, 0.5, 0.01, P, m2, sizeof m2) && strstr(m2, "atoms"));
+        // 64 images: the last body's entries are the arrays' last
+        Call one;
+        one.body(5, 20.0, 4.0, 25.0, 1.0);
+        std::vector<double> r64, t64;
+        for (int g = 0; g < 64; g++) { r64.insert(r64.end(), rot.begin() + 9 * (g % 4), rot.begin() + 9 * (g % 4) + 9); t64.insert(t64.end(), tr.begin() + 3 * (g % 4), tr.begin() + 3 * (g % 4) + 3); }
+        CHECK(jf_plan_sym("check", one.dims, one.origin, one.vs, 1, one.atoms.data(), one.mass.data(), one.first.data(), 64, r64.data(), t64.data(), 6.0, 500, 0.5, 0.01, P, m2, sizeof m2));
+        CHECK(P.n_bodies == 64 && P.n_atoms == 320 && P.vox0[64] == 64 * P.vox0[1] && P.edge[63] == P.edge[0]);
+    }
+    // residency: the image count in the place of the body count.  Every U x K <= 64, every cap, units of 30, 4097 and 2^20 atoms: all
+    // images' workgroups are at most the compute units, and a unit's reduction group is at most JF_SYM_MAX_MEMBERS
+    for (int U = 1; U <= JF_MAX_BODIES; U++)
+        for (int K = 1; U * K <= JF_MAX_BODIES; K++)
+            for (int cap = 1; cap <= 8; cap++) {
+                const int64_t sizes[3] = {30, 4097, 1 << 20};
+                int total = 0;
+                for (int u = 0; u < U; u++) {
+                    const int32_t G = jf_groups(256, U * K, sizes[(u + cap) % 3], cap);
+                    CHECK(G >= 1 && K * G <= JF_SYM_MAX_MEMBERS && K * G <= 256 / U);
+                    total += K * G;
+                }
+                CHECK(total <= 256 && total >= U * K);
+            }
+    CHECK(jf_groups(256, 2, 4100, 8) == 2 && jf_groups(256, 60, 30, 8) == 1 && jf_groups(256, 4, 26000, 8) == 8 && jf_groups(256, 60, 1 << 20, 8) == 4);
+
     if (failures) {
         fprintf(stderr, "check_jointfit_plan: %d check(s) failed\n", failures);
         return 1;

@@ -1,7 +1,8 @@
 // mad_jointfit_plan.h -- the host side of mad_assembly_density and mad_assembly_refine: the argument checks,
-// the blur taps, a body's box (edge and clipped placement), the round count and the workgroups per body.  Plain C++ without a HIP
-// type, so that it also compiles into a stand-alone host program (check_jointfit_plan.cpp); the functions the kernels share with
-// that program carry JF_HD.
+// the blur taps, a body's box (edge and clipped placement), the round count and the workgroups per body; and of
+// mad_assembly_refine_symmetric (section 4z): the operator checks, an image and a pulled-back gradient, the plan of the images.
+// Plain C++ without a HIP type, so that it also compiles into a stand-alone host program (check_jointfit_plan.cpp); the functions
+// the kernels share with that program carry JF_HD.
 #pragma once
 
 #include <cmath>
@@ -159,5 +160,87 @@ static inline bool jf_plan(const char *who, const int32_t *dims, const double *o
         if (vox > P.max_box) P.max_box = vox;
         if (n > P.max_atoms) P.max_atoms = n;
     }
+    return true;
+}
+
+// ---------------------------------------------------------------------------
+// mad_assembly_refine_symmetric: units under the operators of a point group
+// ---------------------------------------------------------------------------
+#define JF_SYM_MAX_MEMBERS (JF_MAX_BODIES * JF_MAX_G)      // workgroups of a unit's reduction group at most (K G; a launch has n_cu at most)
+#define JF_SYM_ORTHO_TOL 1e-6                              // |R R^T - I| in every entry
+
+// q = p R + T for row vectors, R row-major: ((x R[0][j] + y R[1][j]) + z R[2][j]) + T[j]
+JF_HD static inline void jf_image(const double *R, const double *T, const double p[3], double q[3]) {
+    for (int j = 0; j < 3; j++) q[j] = ((p[0] * R[j] + p[1] * R[3 + j]) + p[2] * R[6 + j]) + T[j];
+}
+// h = g R^T: a gradient gathered at the image, in the unit's frame
+JF_HD static inline void jf_pull_back(const double *R, const double g[3], double h[3]) {
+    for (int i = 0; i < 3; i++) h[i] = (g[0] * R[3 * i] + g[1] * R[3 * i + 1]) + g[2] * R[3 * i + 2];
+}
+
+// false with a message: n_units, n_ops, their product, or an operator is refused
+static inline bool jf_ops_check(const char *who, int32_t n_units, int32_t n_ops, const double *op_rot, const double *op_trans, char *msg,
+                                size_t msg_len) {
+    if (n_units < 1 || n_units > JF_MAX_BODIES) { snprintf(msg, msg_len, "%s: n_units = %d (1 .. %d)", who, n_units, JF_MAX_BODIES); return false; }
+    if (n_ops < 1 || n_ops > JF_MAX_BODIES) { snprintf(msg, msg_len, "%s: n_ops = %d (1 .. %d)", who, n_ops, JF_MAX_BODIES); return false; }
+    if (n_units * n_ops > JF_MAX_BODIES) {
+        snprintf(msg, msg_len, "%s: n_units x n_ops = %d images (%d at most)", who, n_units * n_ops, JF_MAX_BODIES);
+        return false;
+    }
+    if (!op_rot) { snprintf(msg, msg_len, "%s: NULL op_rot", who); return false; }
+    if (!op_trans) { snprintf(msg, msg_len, "%s: NULL op_trans", who); return false; }
+    for (int i = 0; i < 9; i++)
+        if (op_rot[i] != ((i % 4 == 0) ? 1.0 : 0.0)) { snprintf(msg, msg_len, "%s: op_rot: operator 0 is not the identity", who); return false; }
+    for (int i = 0; i < 3; i++)
+        if (op_trans[i] != 0.0) { snprintf(msg, msg_len, "%s: op_trans: operator 0 is not the identity", who); return false; }
+    for (int g = 0; g < n_ops; g++) {
+        const double *R = op_rot + 9 * g, *T = op_trans + 3 * g;
+        for (int i = 0; i < 9; i++)
+            if (!std::isfinite(R[i])) { snprintf(msg, msg_len, "%s: op_rot: operator %d is not finite", who, g); return false; }
+        for (int i = 0; i < 3; i++)
+            if (!std::isfinite(T[i]) || !(fabs(T[i]) < 1e12)) { snprintf(msg, msg_len, "%s: op_trans: operator %d is not finite", who, g); return false; }
+        for (int i = 0; i < 3; i++)
+            for (int k = 0; k < 3; k++) {
+                const double d = (R[3 * i] * R[3 * k] + R[3 * i + 1] * R[3 * k + 1]) + R[3 * i + 2] * R[3 * k + 2];
+                if (!(fabs(d - (i == k ? 1.0 : 0.0)) <= JF_SYM_ORTHO_TOL)) {
+                    snprintf(msg, msg_len, "%s: op_rot: operator %d is not orthonormal (|R R^T - I| above %g)", who, g, JF_SYM_ORTHO_TOL);
+                    return false;
+                }
+            }
+        const double det = R[0] * (R[4] * R[8] - R[5] * R[7]) - R[1] * (R[3] * R[8] - R[5] * R[6]) + R[2] * (R[3] * R[7] - R[4] * R[6]);
+        if (!(det > 0.0)) { snprintf(msg, msg_len, "%s: op_rot: operator %d is a reflection (determinant %g)", who, g, det); return false; }
+    }
+    return true;
+}
+
+// The plan of the n_units x n_ops images as bodies: image (u, g) is body u n_ops + g.  The units are checked as jf_plan checks
+// bodies; an image's box has its unit's edge and is placed around the image of the unit's centre.  P.n_atoms counts the atoms of
+// all images, P.max_atoms those of the largest unit.
+static inline bool jf_plan_sym(const char *who, const int32_t *dims, const double *origin, double vs, int32_t n_units, const double *atoms,
+                               const double *mass, const int64_t *first_atom, int32_t n_ops, const double *op_rot, const double *op_trans,
+                               double resolution, int32_t n_steps, double max_step, double min_step, JfPlan &P, char *msg, size_t msg_len) {
+    if (!dims) { snprintf(msg, msg_len, "%s: no map: call mad_upload_density first", who); return false; }
+    if (!jf_ops_check(who, n_units, n_ops, op_rot, op_trans, msg, msg_len)) return false;
+    if (!jf_plan(who, dims, origin, vs, n_units, atoms, mass, first_atom, resolution, true, n_steps, max_step, min_step, P, msg, msg_len)) return false;
+    const int32_t K = n_ops;
+    for (int u = n_units - 1; u >= 0; u--)      // descending: body u K + g >= u is written after unit u was read
+        for (int g = K - 1; g >= 0; g--) {
+            const int b = u * K + g;
+            const double c[3] = {P.cen[u][0], P.cen[u][1], P.cen[u][2]};
+            const double md = P.max_dist[u];
+            const int32_t edge = P.edge[u];
+            double q[3] = {c[0], c[1], c[2]};
+            if (g > 0) jf_image(op_rot + 9 * g, op_trans + 3 * g, c, q);
+            P.max_dist[b] = md; P.edge[b] = edge;
+            for (int d = 0; d < 3; d++) {
+                P.cen[b][d] = q[d];
+                P.e[b][d] = jf_box_extent(edge, dims[d]);
+                P.lo[b][d] = jf_box_lo(q[d], origin[d], vs, edge, dims[d]);
+            }
+        }
+    P.n_bodies = n_units * K;
+    P.n_atoms *= K;
+    P.vox0[0] = 0;
+    for (int b = 0; b < P.n_bodies; b++) P.vox0[b + 1] = P.vox0[b] + (int64_t)P.e[b][0] * P.e[b][1] * P.e[b][2];
     return true;
 }

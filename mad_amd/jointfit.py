@@ -233,6 +233,150 @@ def joint_refine_numpy(grid, origin, vs, bodies, masses, resolution, n_steps=500
                 last_step=[b.last for b in B], scale=np.array(scales), n_rounds=n_rounds, margin=float(margin))
 
 
+# -- units under a point group ---------------------------------------------------------------------------
+ORTHO_TOL = 1e-6      # JF_SYM_ORTHO_TOL of csrc/mad_jointfit_plan.h
+
+
+def operators_of(who, symmetry):
+    """`symmetry` -- a `symmetry.Symmetry` (its `operators()`), a `symmetry.Operators`, or a pair (R (K, 3, 3), T (K, 3)) -- as a
+    checked `symmetry.Operators`: operator 0 the identity bit for bit, every R orthonormal within ORTHO_TOL and no reflection."""
+    from . import symmetry as sym
+    if hasattr(symmetry, "operators"):
+        ops = symmetry.operators()
+    elif hasattr(symmetry, "R") and hasattr(symmetry, "T"):
+        ops = symmetry
+    elif isinstance(symmetry, (list, tuple)) and len(symmetry) == 2:
+        R, T = np.asarray(symmetry[0], np.float64), np.asarray(symmetry[1], np.float64)
+        if R.ndim != 3 or R.shape[1:] != (3, 3) or T.shape != (len(R), 3):
+            raise ValueError("%s: symmetry: R of shape %s and T of shape %s, not (K, 3, 3) and (K, 3)" % (who, R.shape, T.shape))
+        ops = sym.Operators(R, T)
+    else:
+        raise ValueError("%s: symmetry must be a Symmetry, an Operators or a pair (R, T)" % who)
+    R, T = ops.R, ops.T
+    if len(R) < 1:
+        raise ValueError("%s: symmetry: no operator" % who)
+    if not (np.array_equal(R[0], np.identity(3)) and not T[0].any()):
+        raise ValueError("%s: symmetry: operator 0 is not the identity" % who)
+    if not (np.isfinite(R).all() and np.isfinite(T).all()):
+        raise ValueError("%s: symmetry: an operator is not finite" % who)
+    for g in range(len(R)):
+        if not np.abs(R[g] @ R[g].T - np.identity(3)).max() <= ORTHO_TOL:
+            raise ValueError("%s: symmetry: operator %d is not orthonormal" % (who, g))
+        if not np.linalg.det(R[g]) > 0.0:
+            raise ValueError("%s: symmetry: operator %d is a reflection" % (who, g))
+    return ops
+
+
+def image_numpy(x, R, T, g):
+    """Image g of the rows of x: x itself for g = 0, else ((x R[0][j] + y R[1][j]) + z R[2][j]) + T[j] per component."""
+    if g == 0:
+        return x
+    return np.stack([((x[:, 0] * R[g][0, j] + x[:, 1] * R[g][1, j]) + x[:, 2] * R[g][2, j]) + T[g][j] for j in range(3)], axis=1)
+
+
+def _pull_back(grads, R, g):
+    """h = grads @ R[g]^T, h_i = (g_0 R[i][0] + g_1 R[i][1]) + g_2 R[i][2]; grads itself for g = 0."""
+    if g == 0:
+        return grads
+    return np.stack([(grads[:, 0] * R[g][i, 0] + grads[:, 1] * R[g][i, 1]) + grads[:, 2] * R[g][i, 2] for i in range(3)], axis=1)
+
+
+def symmetric_refine_numpy(grid, origin, vs, units, masses, R, T, resolution, n_steps=500, max_step=0.5, min_step=0.01, fixed=None):
+    """The contract of `mad_assembly_refine_symmetric`, restated: `joint_refine_numpy` with the K images of every unit as the bodies
+    of the model (image (u, g) is body u K + g), one common step per unit from the pulled-back gradients of all its images, and
+    the batch decision on the unit's own coordinates.  -> joint_refine_numpy's dict, per UNIT."""
+    grid = np.asarray(grid, np.float32)
+    origin = np.asarray(origin, np.float64)
+    R, T = np.asarray(R, np.float64).reshape(-1, 3, 3), np.asarray(T, np.float64).reshape(-1, 3)
+    K = len(R)
+    if K < 1 or len(units) * K > MAX_BODIES:
+        raise ValueError("symmetric_refine_numpy: %d units x %d operators" % (len(units), K))
+    operators_of("symmetric_refine_numpy", (R, T))
+    fixed = [False] * len(units) if fixed is None else [bool(f) for f in fixed]
+    B = [_Body(np.asarray(a, np.float64).reshape(-1, 3), max_step, f) for a, f in zip(units, fixed)]
+    masses = [np.asarray(m, np.float64).reshape(-1) for m in masses]
+    nx, ny, nz = grid.shape
+    hi = origin + np.array([nx, ny, nz]) * vs - vs
+    scales, margin = [], np.inf
+    n_rounds = 0
+    rhos = [[None] * K for _ in B]
+    moved = [True] * len(B)      # the unit moved in the round before (or nothing has been made yet)
+    for rnd in range((n_steps + BATCH - 1) // BATCH):
+        if not any(b.moving for b in B):
+            break
+        n_rounds += 1
+        # 1: the model of all images, a unit's images re-made only when it moved; M in ascending body index; s
+        for u, (b, m) in enumerate(zip(B, masses)):
+            if moved[u]:
+                rhos[u] = [body_density_numpy(grid.shape, origin, vs, image_numpy(b.cur, R, T, g), m, resolution) for g in range(K)]
+            moved[u] = False
+        M = np.zeros(grid.shape, np.float64)
+        for per_unit in rhos:
+            for rho in per_unit:
+                M = M + rho
+        s = _scale(grid, M)
+        scales.append(s)
+        steps = range(BATCH * rnd, min(BATCH * (rnd + 1), n_steps))
+        for u, b in enumerate(B):
+            if not b.moving:
+                continue
+            moved[u] = True
+            # 2: every image's field and its np.gradient texels, float32
+            texs = []
+            for g in range(K):
+                F = (grid.astype(np.float64) - s * (M - rhos[u][g])).astype(np.float32)
+                texs.append(np.moveaxis(np.array(np.gradient(F)), 0, -1))
+            # 3: the round's steps
+            batch = 0
+            for step in steps:
+                b.last = step
+                b.cur = np.dot(b.init - b.cen, b.rot) + (b.cen + b.trans)
+                if np.any(np.isnan(b.cur)):
+                    b.moving = False
+                    break
+                c = b.cur
+                force, torque = [], []
+                for g in range(K):
+                    q = image_numpy(c, R, T, g)
+                    inside = ((q[:, 0] > origin[0]) & (q[:, 0] < hi[0]) & (q[:, 1] > origin[1]) & (q[:, 1] < hi[1])
+                              & (q[:, 2] > origin[2]) & (q[:, 2] < hi[2]))
+                    h = _pull_back(_gather(texs[g], origin, vs, q[inside]), R, g)
+                    if step % 2 == 0:
+                        force.append(np.sum(h, axis=0))
+                    else:
+                        torque.append(np.sum(np.cross(h, (c - b.cen)[inside]), axis=0))
+                if step % 2 == 0:
+                    total = force[0]
+                    for f in force[1:]:
+                        total = total + f
+                    uvec = _unit(total) * b.step
+                    b.trans = b.trans + uvec
+                    b.cur = b.cur + uvec
+                else:
+                    total = torque[0]
+                    for t in torque[1:]:
+                        total = total + t
+                    sm = euler_rod_mat(_unit(total), b.step / b.maxd)
+                    b.cur = np.dot(b.cur + (-1 * b.cen - b.trans), sm) + (b.cen + b.trans)
+                    b.rot = b.rot.dot(sm)
+                batch += 1
+                if batch == BATCH:
+                    mx = np.amax(np.linalg.norm(b.prev - b.cur, axis=1))
+                    margin = min(margin, abs(mx - b.step))
+                    if mx < b.step:
+                        b.step *= 0.5
+                    batch = 0
+                    b.prev = b.cur.copy()
+                if b.step < min_step:
+                    b.converged = True
+                    b.moving = False
+                    break
+            if b.last == n_steps - 1:
+                b.moving = False
+    return dict(coords=[b.cur for b in B], R=[b.rot for b in B], T=[b.trans for b in B], converged=[b.converged for b in B],
+                last_step=[b.last for b in B], scale=np.array(scales), n_rounds=n_rounds, margin=float(margin))
+
+
 # -- the result --------------------------------------------------------------------------------------------------------------
 class JointFit(object):
     """What `Dmap.refine_together` returns.  Per body b: `coords[b]` (n_b, 3), `R[b]` (3, 3) and `T[b]` (3) with
@@ -271,6 +415,35 @@ class JointFit(object):
         return names
 
 
+class SymmetricFit(JointFit):
+    """What `Dmap.refine_symmetric` returns: a `JointFit` over the units, and `operators` (a `symmetry.Operators`)."""
+
+    def __init__(self, operators, *args):
+        JointFit.__init__(self, *args)
+        self.operators = operators
+
+    def images(self, u):
+        """Unit u under every operator -> float64 [K, n_u, 3]; image 0 is `coords[u]`."""
+        return np.stack([image_numpy(self.coords[u], self.operators.R, self.operators.T, g) for g in range(len(self.operators))])
+
+    def assembly(self):
+        """All U K coordinate sets, image (u, g) at u K + g: the bodies of the model, as `Dmap.residual` takes them."""
+        return [im for u in range(len(self.coords)) for im in self.images(u)]
+
+    def write_pdb(self, prefix):
+        """`<prefix>_<u>_<g>.pdb` for every image of every unit that came from a PDB -> the names written."""
+        names = []
+        for u, src in enumerate(self._sources):
+            if src is None:
+                continue
+            for g, im in enumerate(self.images(u)):
+                out = copy.copy(src)
+                out.set_coords(im)
+                names.append("%s_%d_%d.pdb" % (prefix, u, g))
+                out.write_pdb(names[-1])
+        return names
+
+
 def _map_args(who, dmap):
     g = np.ascontiguousarray(dmap.grid3d, dtype=np.float32)
     if g.ndim != 3:
@@ -292,6 +465,26 @@ def refine_together(dmap, structures, resolution, n_steps=500, max_step=0.5, min
     structure_utils.invalidate_density()
     out, R, T, conv, last, scale = lib.assembly_refine(coords, ms, resolution, n_steps=n_steps, max_step=max_step, min_step=min_step, fixed=fixed)
     return JointFit(coords, out, R, T, conv, last, scale, src)
+
+
+def refine_symmetric(dmap, structures, resolution, symmetry, n_steps=500, max_step=0.5, min_step=0.01, fixed=None, masses=None):
+    from . import _lib, structure_utils
+    who = "Dmap.refine_symmetric"
+    coords, ms, src = bodies_of(who, structures, masses)
+    ops = operators_of(who, symmetry)
+    if len(coords) * len(ops) > MAX_BODIES:
+        raise ValueError("%s: %d units under %d operators are %d images (%d at most)" % (who, len(coords), len(ops), len(coords) * len(ops), MAX_BODIES))
+    if fixed is not None:
+        fixed = [bool(f) for f in fixed]
+        if len(fixed) != len(coords):
+            raise ValueError("%s: fixed has %d entries for %d units" % (who, len(fixed), len(coords)))
+    g, origin, vs = _map_args(who, dmap)
+    lib = _lib.get_lib()
+    lib.upload_density(g, origin, vs)
+    structure_utils.invalidate_density()
+    out, R, T, conv, last, scale = lib.assembly_refine_symmetric(coords, ms, ops.R, ops.T, resolution, n_steps=n_steps, max_step=max_step,
+                                                                 min_step=min_step, fixed=fixed)
+    return SymmetricFit(ops, coords, out, R, T, conv, last, scale, src)
 
 
 def residual(dmap, structures, resolution, masses=None):
