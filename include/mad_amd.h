@@ -578,6 +578,42 @@ int mad_map_symmetrize(mad_ctx *ctx, const float *grid, const int32_t dims[3], c
 int mad_last_symmetry_plan(mad_ctx *ctx, int32_t *ops_per_workgroup, int32_t *n_chunks, int64_t *scratch_bytes);
 
 /*
+ * Flexible fitting: the atoms of a model moved one by one up the gradient of the map given to mad_upload_density, held together
+ * by an elastic network (mad_flexfit.hip; DESIGN.md section 4za, restated in mad_amd/flexfit.py).  Host pointers, synchronous.
+ *
+ * mad_flex_network: every pair of the n_atoms coordinates (n x 3 float64) with (dx dx + dy dy) + dz dz <= cutoff cutoff in float64,
+ * dx = x_j - x_i, is a spring, stored for both atoms: first[n_atoms + 1] (a row per atom), nbr[] (a row's neighbours in ascending
+ * atom index) and rest[] (the square root of that sum), bit for bit flexfit.network_numpy's.  *n_springs receives first[n_atoms];
+ * MAD_ENOSPC when it exceeds cap_springs, the capacity of nbr and rest (then only *n_springs is written).  MAD_EDOM when an atom
+ * has more than MAD_FLEX_MAX_DEGREE neighbours (a convention: all-atom protein has 45 - 80 within 6 A); the message names the atom,
+ * its degree and the cutoff.  MAD_EINVAL: NULL, n_atoms outside 1 .. 2^24 - 1, a coordinate that is not finite, cutoff <= 0.
+ *
+ * mad_flex_fit: n_steps steps at most of x_i += F_i step / max_j |F_j|, F_i = (w_i g_i) / g0 + sum over the row of atom i of
+ * ((stiffness (d - d0)) / d) (x_j - x_i): g_i k_refine's gather of the gradient texels (0 unless the atom lies strictly inside
+ * the map), g0 = sqrt(sum |w_i g_i|^2 / n) at the start, d the length of x_j - x_i now and d0 the rest length.  weights (n, NULL:
+ * all 1) and fixed (n bytes, NULL: none; a fixed atom keeps its bits) are optional.  The network is the caller's: mad_flex_network's,
+ * or any with first[0] = 0, ascending first, rows that may be empty and need not be symmetric, neighbours in range and strictly
+ * ascending within a row, no atom its own neighbour, finite positive rest lengths.  After every 4 steps the step size halves
+ * when no atom moved as far as one step size since the last look; a step size below min_step is convergence, and so is a step in
+ * which no atom feels a force.  *last_step: the step that ended the run (refine_pdb's meaning); *step: the final step size; a NaN
+ * in a coordinate or a force ends the run with *converged = 0.  The same bits on every plan and in every call.
+ * MAD_EDOM when g0 is 0 (no atom feels the map).  MAD_EINVAL: NULL, n_atoms < 1, a coordinate or weight that is not finite,
+ * stiffness < 0, n_steps < 1, not 0 < min_step <= max_step, no map, a malformed network.
+ *
+ * mad_last_flex_plan: the workgroups, the threads of each, the atoms a thread owns at most and the springs of the most recent
+ * mad_flex_fit (-1 before the first).  Any pointer may be NULL.  mad_set_option "flex_groups" (0: by the atom count; never more than
+ * the compute units) and "flex_threads" (0: the default; a multiple of 64 up to 1024) are the tests' hooks.
+ * Timing groups: "flex_network", "flex_steps".
+ */
+#define MAD_FLEX_MAX_DEGREE 128
+int mad_flex_network(mad_ctx *ctx, int64_t n_atoms, const double *coords, double cutoff, int32_t *first, int64_t cap_springs,
+                     int32_t *nbr, double *rest, int64_t *n_springs);
+int mad_flex_fit(mad_ctx *ctx, int64_t n_atoms, const double *coords, const double *weights, const uint8_t *fixed, const int32_t *first,
+                 const int32_t *nbr, const double *rest, double stiffness, int n_steps, double max_step, double min_step,
+                 double *coords_out, int32_t *converged, int32_t *last_step, double *step, double *g0);
+int mad_last_flex_plan(mad_ctx *ctx, int32_t *workgroups, int32_t *threads, int32_t *atoms_per_thread, int64_t *springs);
+
+/*
  * A map cut around a structure, or with the structure erased (mad_zone.hip).  Host pointers, synchronous.
  * grid: float32 [x][y][z] with dims, origin (Angstrom, centre of voxel (0,0,0)) and spacing voxsp, updated IN PLACE; atoms:
  * n_atoms x 3 float64 (Angstrom), read only, NULL allowed when n_atoms == 0.  Voxel j sits at p_a = origin_a + voxsp * j_a

@@ -215,6 +215,21 @@ class Dmap(object):
         from . import jointfit
         return jointfit.refine_symmetric(self, structures, resolution, symmetry, n_steps=n_steps, max_step=max_step, min_step=min_step, fixed=fixed, masses=masses)
 
+    def flex_fit(self, structure, cutoff=6.0, stiffness=1.0, n_steps=2000, max_step=0.5, min_step=0.01, weights=None, fixed=None, network=None):
+        """Fit a model FLEXIBLY into this map -> `flexfit.FlexFit` (coords, converged, last_step, step, g0, network, `strain()`,
+        `displacement()`, `rmsd(other)`, `place(pdb)`, `write_pdb(prefix)`).  Every atom climbs the map's gradient on its own,
+        held to the atoms that started within `cutoff` Angstrom of it by springs of `stiffness` at their starting lengths: a
+        step moves atom i along (w_i g_i) / g0 + the pull of its springs, scaled so that the fastest atom moves one step size,
+        and the step size halves as in `refine_pdb`.  `structure`: a `PDB`, an (n, 3) array, or a list of those -- a list becomes
+        ONE network over all atoms, so interfaces are restrained too.  `weights` (per atom, default 1) scale the map's pull,
+        `fixed` (per atom) keeps atoms where they are, `network` = (first, nbr, rest) replaces the one built from `cutoff`
+        (C-alpha only, extra restraints, empty rows).  The defaults are conventions; stiffness of about 10 and above stalls
+        (steepest descent across stiff springs).  The map's resolution is no input.  Neither `self` nor the structure is
+        modified.  DESIGN.md section 4za has the exact contract."""
+        from . import flexfit
+        return flexfit.flex_fit(self, structure, cutoff=cutoff, stiffness=stiffness, n_steps=n_steps, max_step=max_step, min_step=min_step,
+                                weights=weights, fixed=fixed, network=network)
+
     def residual(self, structures, resolution, masses=None):
         """What this map holds beyond the placed bodies, as a new `Dmap` on the same lattice: map - s M, M the sum of the bodies'
         simulated densities at `resolution` (not normalised) and s = <map, M> / <M, M>, kept as `scale` on the result.

@@ -32,6 +32,7 @@ QSCORE_CHUNK = 256          # QS_CHUNK of csrc/mad_qscore_plan.h: neighbours of 
 QSCORE_MAX_SHELLS, QSCORE_MAX_TRIES = 64, 64      # QS_MAX_R, QS_MAX_TRIES
 SYMMETRIZE_MAX_OPS = 64     # SYMZ_MAX_OPS of csrc/mad_resample.hip
 TAB_ZBINS, TAB_PBINS, TAB_BELTS = 2048, 2048, 4      # MAD_TAB_* of csrc/mad_common.h
+FLEX_MAX_DEGREE = 128       # MAD_FLEX_MAX_DEGREE of include/mad_amd.h: springs of one atom that flex_network builds at most
 
 # The C ABI, stated once: every function of include/mad_amd.h as name=return(arguments), one letter per type.  load_library() sets
 # restype and argtypes from it, so a call passes plain Python numbers and ctypes refuses a wrapper of another width.  A new function
@@ -76,7 +77,7 @@ mad_pose_cluster_many=i(pippppdpppp) mad_rank_copies=i(ppiiidqqqpppppp) mad_rank
 mad_last_rank_plan=i(ppppp) mad_assembly_density=i(pipppdppp) mad_assembly_refine=i(pippppdiddppppppp)
 mad_assembly_refine_symmetric=i(pippppippdiddppppppp)
 mad_last_assembly_plan=i(pppp) mad_map_symmetry_score=i(ppppdpdiippp) mad_map_symmetrize=i(ppppdippip)
-mad_last_symmetry_plan=i(pppp)
+mad_last_symmetry_plan=i(pppp) mad_flex_network=i(pqpdpqppp) mad_flex_fit=i(pqppppppdiddppppp) mad_last_flex_plan=i(ppppp)
 """.split()}
 SYMBOLS = list(PROTOTYPES)      # every symbol include/mad_amd.h declares (tests check the library exports all of them)
 
@@ -1148,6 +1149,58 @@ class Lib(object):
         g, reg, wgs = C.c_int(-1), C.c_int(-1), C.c_int(-1)
         self._chk(self.dll.mad_last_assembly_plan(self.ctx, C.byref(g), C.byref(reg), C.byref(wgs)))
         return g.value, reg.value, wgs.value
+
+    def flex_network(self, coords, cutoff):
+        """The elastic network of (n, 3) coordinates (mad_flex_network) -> (first int32 [n + 1], nbr int32, rest float64): every pair
+        within `cutoff`, a row per atom, ascending; bit for bit flexfit.network_numpy's."""
+        x = _c(coords, np.float64).reshape(-1, 3)
+        n = len(x)
+        first = np.zeros(n + 1, np.int32)
+        held = {}
+
+        def call(cap):
+            held["nbr"], held["rest"] = np.zeros(max(cap, 1), np.int32), np.zeros(max(cap, 1), np.float64)
+            total = C.c_int64(0)
+            rc = self.dll.mad_flex_network(self.ctx, n, _p(x), float(cutoff), _p(first), cap, _p(held["nbr"]), _p(held["rest"]), C.byref(total))
+            held["total"] = total.value
+            return rc, total.value
+
+        _retry_enospc(self, call, 64 * max(n, 1))
+        return first, held["nbr"][:held["total"]].copy(), held["rest"][:held["total"]].copy()
+
+    def flex_fit(self, coords, network, stiffness=1.0, n_steps=2000, max_step=0.5, min_step=0.01, weights=None, fixed=None):
+        """The atoms moved on their elastic network against the map given to upload_density (mad_flex_fit) -> (coords (n, 3),
+        converged, last_step, step, g0).  network: (first, nbr, rest)."""
+        x = _c(coords, np.float64).reshape(-1, 3)
+        n = len(x)
+        first, nbr, rest = (_c(network[0], np.int32).reshape(-1), _c(network[1], np.int32).reshape(-1), _c(network[2], np.float64).reshape(-1))
+        if len(first) != n + 1:
+            raise ValueError("flex_fit: network: first has %d entries for %d atoms" % (len(first), n))
+        if len(nbr) != len(rest) or (len(first) and int(first[-1]) != len(nbr)):
+            raise ValueError("flex_fit: network: first ends at %d, nbr has %d and rest %d entries" % (int(first[-1]), len(nbr), len(rest)))
+        w = fx = None
+        if weights is not None:
+            w = _c(weights, np.float64).reshape(-1)
+            if len(w) != n:
+                raise ValueError("flex_fit: weights has %d entries for %d atoms" % (len(w), n))
+        if fixed is not None:
+            fx = _c(np.asarray(fixed, bool), np.uint8).reshape(-1)
+            if len(fx) != n:
+                raise ValueError("flex_fit: fixed has %d entries for %d atoms" % (len(fx), n))
+        n_steps = _whole("flex_fit", "n_steps", n_steps)
+        out = np.empty_like(x)
+        conv, last = C.c_int32(0), C.c_int32(-1)
+        step, g0 = C.c_double(0.0), C.c_double(0.0)
+        self._chk(self.dll.mad_flex_fit(self.ctx, n, _p(x), _p(w), _p(fx), _p(first), _p(nbr) if len(nbr) else None, _p(rest) if len(rest) else None,
+                                        float(stiffness), n_steps, float(max_step), float(min_step), _p(out), C.byref(conv), C.byref(last),
+                                        C.byref(step), C.byref(g0)))
+        return out, bool(conv.value), int(last.value), step.value, g0.value
+
+    def last_flex_plan(self):
+        """(workgroups, threads, atoms per thread, springs) of the most recent flex_fit (mad_last_flex_plan); -1 before the first."""
+        g, t, a, s = C.c_int32(-1), C.c_int32(-1), C.c_int32(-1), C.c_int64(-1)
+        self._chk(self.dll.mad_last_flex_plan(self.ctx, C.byref(g), C.byref(t), C.byref(a), C.byref(s)))
+        return g.value, t.value, a.value, s.value
 
     def last_density_chunks(self):
         """Chunks the most recent density simulation cut its batch into (mad_last_density_chunks); -1 before the first."""

@@ -3675,6 +3675,16 @@ extern "C" int mad_set_option(mad_ctx *ctx, const char *name, double value) {
         ctx->jf_no_reg = value == 0;
         return MAD_OK;
     }
+    if (!strcmp(name, "flex_groups")) {      // test hook: workgroups of mad_flex_fit's launch (cut to the compute units); 0 = by the atom count.  It changes speed, never numbers
+        if (!(value >= 0) || !(value <= 65536) || value != (int)value) return mad_fail(ctx, MAD_EINVAL, "mad_set_option: flex_groups = %g (0 .. 65536)", value);
+        ctx->flex_groups = (int)value;
+        return MAD_OK;
+    }
+    if (!strcmp(name, "flex_threads")) {      // test hook: threads of a workgroup of mad_flex_fit's launch; 0 = the default
+        if (!(value >= 0) || !(value <= 1024) || value != (int)value || (int)value % 64 != 0) return mad_fail(ctx, MAD_EINVAL, "mad_set_option: flex_threads = %g (0, or a multiple of 64 up to 1024)", value);
+        ctx->flex_threads = (int)value;
+        return MAD_OK;
+    }
     if (!strcmp(name, "fft_bpt")) {      // test hook: the k_fft_lines form (butterflies per thread) for every N; 0 = chosen by N
         if (value != 0 && value != 1 && value != 2 && value != 4) return mad_fail(ctx, MAD_EINVAL, "mad_set_option: fft_bpt = %g (0, 1, 2 or 4)", value);
         ctx->fft_bpt = (int)value;
