@@ -614,6 +614,46 @@ int mad_flex_fit(mad_ctx *ctx, int64_t n_atoms, const double *coords, const doub
 int mad_last_flex_plan(mad_ctx *ctx, int32_t *workgroups, int32_t *threads, int32_t *atoms_per_thread, int64_t *springs);
 
 /*
+ * A model's density with a Gaussian width per atom, and the B-factors of a placed model refined against a map (mad_bfactor.hip;
+ * DESIGN.md section 4zb, restated in mad_amd/bfactor.py).  Host pointers, synchronous, nothing modified.
+ *
+ * The contract: K = 8 pi^2, v0 = (resolution / (pi sqrt 2))^2, an atom of B-factor B has the variance v = v0 + B / K.  Voxel j sits at
+ * origin + voxsp j, d2 = (dx dx + dy dy) + dz dz in float64 without fused multiply-add.  The atom reaches the voxel iff d2 <= 9 v and
+ * adds e = (m / ((2 pi v) sqrt(2 pi v))) exp(-(d2 / (2 v))) to it.  The box is the union, over the atoms that reach the lattice, of
+ * floor((x - rmax - o) / voxsp) .. ceil((x + rmax - o) / voxsp) per axis, rmax = 3 sqrt(v0 + b_max / K), clipped to the lattice.
+ *
+ * mad_model_density_b: rho (float64 [x][y][z] of dims, zero outside the box) for n_atoms coordinates (n x 3 float64), masses and
+ * B-factors b_atom (0 <= b <= b_max).  A voxel's sum runs over the cells of a grid over the atoms in ascending order, atoms ascending
+ * within a cell, in float64: the same bits whatever "bf_chunk" and "bf_threads" are.  box (nullable) receives lo[3], dim[3].
+ *
+ * mad_bfactor_refine: the atoms come sorted by group, group g = first_atom[g] .. first_atom[g + 1] - 1 (first_atom[0] = 0,
+ * first_atom[n_groups] = n_atoms, a group may be empty), one B per group starting from b0 (within [b_min, b_max]); fixed (n_groups
+ * bytes, NULL: none) keeps a group's B.  A cycle: rho at the present B, s = <D, rho> / <rho, rho> over the box in fourier.tree_sum's
+ * pairing (D the map), r = s rho - D, g_a = (s sum_p (r e_a)(d2 / (2 v v) - 1.5 / v)) / K, a group's gradient the sum of its atoms'
+ * in ascending order, mx the largest |g| of the free groups (0: converged), B <- clip(B - step (g / mx), b_min, b_max).  Every
+ * fourth cycle the step halves when no B moved as far as one step since the last look; a step below min_step is convergence; a NaN
+ * ends the run with *converged = 0.  All cycles are queued at once and a flag on the device empties those after the end.
+ * b_out: n_groups.  stats[7]: the scale s, the loss <r, r> at b0 and at the end, the un-centred correlation at b0 and at the end, the
+ * final step, the scale at b0.  *last_cycle: the cycle that ended the run.  rho (nullable): as mad_model_density_b, at the final B,
+ * not scaled.
+ * MAD_EINVAL: NULL, resolution <= 0, a coordinate or mass that is not finite, b0 outside [b_min, b_max], a group table that does not
+ * cover the atoms, n_cycles < 1, not 0 < min_step <= max_step.  MAD_EDOM: no atom reaches the lattice, or <rho, rho> == 0.
+ *
+ * mad_last_bfactor_plan: the box (lo[3], dim[3]), the bricks and the cells per axis, the atoms per LDS chunk, the threads of a gather
+ * workgroup, the cycles queued (0 for mad_model_density_b) and the atoms that reach the lattice, of the most recent call of either
+ * (-1 before the first).  Any pointer may be NULL.  mad_set_option "bf_chunk" (0, or 64 .. 1024) and "bf_threads" (0, or a multiple of
+ * 64 up to 512) are the tests' hooks.  Timing groups: "bf_gather", "bf_sums", "bf_grad", "bf_step".
+ */
+int mad_model_density_b(mad_ctx *ctx, const int32_t dims[3], const double origin[3], double voxsp, int64_t n_atoms, const double *coords,
+                        const double *masses, const double *b_atom, double resolution, double b_max, double *rho, int32_t box[6]);
+int mad_bfactor_refine(mad_ctx *ctx, const float *grid, const int32_t dims[3], const double origin[3], double voxsp, int64_t n_atoms,
+                       const double *coords, const double *masses, int64_t n_groups, const int64_t *first_atom, const double *b0,
+                       const uint8_t *fixed, double resolution, double b_min, double b_max, int n_cycles, double max_step, double min_step,
+                       double *b_out, double *stats, int32_t *converged, int32_t *last_cycle, double *rho);
+int mad_last_bfactor_plan(mad_ctx *ctx, int32_t box[6], int32_t bricks[3], int32_t cells[3], int32_t *chunk, int32_t *threads, int32_t *cycles,
+                          int64_t *kept);
+
+/*
  * A map cut around a structure, or with the structure erased (mad_zone.hip).  Host pointers, synchronous.
  * grid: float32 [x][y][z] with dims, origin (Angstrom, centre of voxel (0,0,0)) and spacing voxsp, updated IN PLACE; atoms:
  * n_atoms x 3 float64 (Angstrom), read only, NULL allowed when n_atoms == 0.  Voxel j sits at p_a = origin_a + voxsp * j_a

@@ -230,6 +230,28 @@ class Dmap(object):
         return flexfit.flex_fit(self, structure, cutoff=cutoff, stiffness=stiffness, n_steps=n_steps, max_step=max_step, min_step=min_step,
                                 weights=weights, fixed=fixed, network=network)
 
+    def refine_bfactors(self, structure, resolution, by="residue", b0=None, b_min=0.0, b_max=400.0, n_cycles=400, max_step=32.0, min_step=0.25,
+                        fixed=None, masses=None):
+        """Refine the B-factors of a placed model against this map -> `bfactor.BFactorFit` (b, b_atom, labels, scale, loss0, loss,
+        cc0, cc, converged, last_cycle, step, `density()`, `write_pdb(outname)`, `write_csv(path)`).  An atom of B-factor B is a
+        Gaussian of variance (resolution / (pi sqrt 2))^2 + B / (8 pi^2); one B per group of atoms (`by` as `fit_by_group`:
+        "residue", "chain", "atom", "all" or an integer array) descends the squared residual of the scaled model density against
+        the map, the fastest group one step per cycle, and the step halves as in `refine_pdb`.  `b0`: a scalar, an array per
+        group, or None -- the PDB's own B-factors averaged per group where any is non-zero, 60 otherwise (a convention).
+        `fixed` (per group) keeps groups as they are.  `density()` is what `scale_local`, `fsc`, `local_resolution` and
+        `get_CCC_with_dmap` take as the model.  Neither `self` nor the structure is modified.  DESIGN.md section 4zb has the
+        exact contract."""
+        from . import bfactor
+        return bfactor.refine_bfactors(self, structure, resolution, by=by, b0=b0, b_min=b_min, b_max=b_max, n_cycles=n_cycles, max_step=max_step,
+                                       min_step=min_step, fixed=fixed, masses=masses)
+
+    def simulate(self, structure, resolution, bfactors=None, masses=None):
+        """The density of a model on this map's lattice as a new `Dmap` (not scaled, not normalised): every atom a Gaussian of
+        variance (resolution / (pi sqrt 2))^2 + B / (8 pi^2), cut at three sigma.  `bfactors`: per atom, a scalar, or None -- the
+        PDB's own (0 for an array).  `self` is not modified.  DESIGN.md section 4zb."""
+        from . import bfactor
+        return bfactor.simulate(self, structure, resolution, bfactors=bfactors, masses=masses)
+
     def residual(self, structures, resolution, masses=None):
         """What this map holds beyond the placed bodies, as a new `Dmap` on the same lattice: map - s M, M the sum of the bodies'
         simulated densities at `resolution` (not normalised) and s = <map, M> / <M, M>, kept as `scale` on the result.

@@ -26,7 +26,7 @@ class PDB(object):
         if not os.path.exists(pdb_file):
             print("PDB> File not found: %s" % pdb_file)
             sys.exit(1)
-        coords, info, ca, bb = [], [], [], []
+        coords, info, ca, bb, bfac = [], [], [], [], []
         # Column layout of PDB v3.3 coordinate records; a field that fails to parse keeps the
         # previous atom's value, as in the reference (PDB.py:45-57).
         serial = resnum = 0
@@ -47,6 +47,10 @@ class PDB(object):
                     elem = line[76:78].strip()
                 except Exception:
                     pass
+                try:      # columns 61-66; 0 where the field does not parse (not in the reference: it never reads the column)
+                    bfac.append(float(line[60:66]))
+                except Exception:
+                    bfac.append(0.0)
                 idx = len(coords)
                 info.append([serial, name, resname, chain, resnum, elem, rec])
                 coords.append([x, y, z])
@@ -56,6 +60,7 @@ class PDB(object):
                     bb.append(idx)
         self.info = info
         self.coords = np.array(coords)
+        self.bfactors = np.array(bfac, dtype=np.float64)
         self.CA_idx = tuple(ca)
         self.BB_idx = bb
         self.n_atoms = len(self.coords)

@@ -78,6 +78,7 @@ mad_last_rank_plan=i(ppppp) mad_assembly_density=i(pipppdppp) mad_assembly_refin
 mad_assembly_refine_symmetric=i(pippppippdiddppppppp)
 mad_last_assembly_plan=i(pppp) mad_map_symmetry_score=i(ppppdpdiippp) mad_map_symmetrize=i(ppppdippip)
 mad_last_symmetry_plan=i(pppp) mad_flex_network=i(pqpdpqppp) mad_flex_fit=i(pqppppppdiddppppp) mad_last_flex_plan=i(ppppp)
+mad_model_density_b=i(pppdqpppddpp) mad_bfactor_refine=i(ppppdqppqpppdddiddppppp) mad_last_bfactor_plan=i(pppppppp)
 """.split()}
 SYMBOLS = list(PROTOTYPES)      # every symbol include/mad_amd.h declares (tests check the library exports all of them)
 
@@ -1201,6 +1202,69 @@ class Lib(object):
         g, t, a, s = C.c_int32(-1), C.c_int32(-1), C.c_int32(-1), C.c_int64(-1)
         self._chk(self.dll.mad_last_flex_plan(self.ctx, C.byref(g), C.byref(t), C.byref(a), C.byref(s)))
         return g.value, t.value, a.value, s.value
+
+    def model_density_b(self, dims, origin, voxsp, coords, masses, b_atom, resolution, b_max=None):
+        """The density of a model whose atom a has the variance (resolution / (pi sqrt 2))^2 + b_atom[a] / (8 pi^2), on the lattice
+        (dims, origin, voxsp) (mad_model_density_b) -> (rho float64 [x][y][z], zero outside the box; box = (lo[3], dim[3])).
+        b_max (default: the largest of b_atom) sets the box and the cell grid."""
+        x = _c(coords, np.float64).reshape(-1, 3)
+        n = len(x)
+        m, b = _c(masses, np.float64).reshape(-1), _c(b_atom, np.float64).reshape(-1)
+        if len(m) != n or len(b) != n:
+            raise ValueError("model_density_b: %d masses and %d B-factors for %d atoms" % (len(m), len(b), n))
+        d = np.array([_whole("model_density_b", "dims", v) for v in dims], np.int32)
+        if d.shape != (3,) or np.any(d < 1):
+            raise ValueError("model_density_b: dims %r" % (dims,))
+        b_max = float(b.max()) if b_max is None and n else float(b_max if b_max is not None else 0.0)
+        rho = np.empty(tuple(int(v) for v in d), np.float64)
+        box = np.zeros(6, np.int32)
+        self._chk(self.dll.mad_model_density_b(self.ctx, _p(d), _p(_vec(origin, 3)), float(voxsp), n, _p(x), _p(m), _p(b), float(resolution), b_max,
+                                               _p(rho), _p(box)))
+        return rho, (tuple(int(v) for v in box[:3]), tuple(int(v) for v in box[3:]))
+
+    def bfactor_refine(self, grid, origin, voxsp, coords, masses, first_atom, b0, resolution, b_min=0.0, b_max=400.0, n_cycles=400, max_step=32.0,
+                       min_step=0.25, fixed=None, want_density=False):
+        """One B-factor per group of atoms refined against the map `grid` (mad_bfactor_refine) -> dict(b, scale, scale0, loss0, loss,
+        cc0, cc, step, converged, last_cycle, rho).  The atoms come sorted by group, group g = first_atom[g] .. first_atom[g + 1] - 1;
+        b0 one value per group; fixed one flag per group; rho (want_density) the unscaled float64 density at the final B."""
+        g = _c(grid, np.float32)
+        if g.ndim != 3:
+            raise ValueError("bfactor_refine: the grid has shape %r" % (g.shape,))
+        x = _c(coords, np.float64).reshape(-1, 3)
+        n = len(x)
+        m = _c(masses, np.float64).reshape(-1)
+        if len(m) != n:
+            raise ValueError("bfactor_refine: masses has %d entries for %d atoms" % (len(m), n))
+        first = _c(first_atom, np.int64).reshape(-1)
+        ng = len(first) - 1
+        if ng < 1:
+            raise ValueError("bfactor_refine: first_atom has %d entries" % len(first))
+        b = _c(b0, np.float64).reshape(-1)
+        if len(b) != ng:
+            raise ValueError("bfactor_refine: b0 has %d entries for %d groups" % (len(b), ng))
+        fx = None
+        if fixed is not None:
+            fx = _c(np.asarray(fixed, bool), np.uint8).reshape(-1)
+            if len(fx) != ng:
+                raise ValueError("bfactor_refine: fixed has %d entries for %d groups" % (len(fx), ng))
+        n_cycles = _whole("bfactor_refine", "n_cycles", n_cycles)
+        out, stats = np.empty(ng, np.float64), np.zeros(7, np.float64)
+        conv, last = C.c_int32(0), C.c_int32(-1)
+        rho = np.empty(g.shape, np.float64) if want_density else None
+        self._chk(self.dll.mad_bfactor_refine(self.ctx, _p(g), _p(_dims(g)), _p(_vec(origin, 3)), float(voxsp), n, _p(x), _p(m), ng, _p(first), _p(b),
+                                              _p(fx), float(resolution), float(b_min), float(b_max), n_cycles, float(max_step), float(min_step),
+                                              _p(out), _p(stats), C.byref(conv), C.byref(last), _p(rho)))
+        return dict(b=out, scale=stats[0], loss0=stats[1], loss=stats[2], cc0=stats[3], cc=stats[4], step=stats[5], scale0=stats[6],
+                    converged=bool(conv.value), last_cycle=int(last.value), rho=rho)
+
+    def last_bfactor_plan(self):
+        """dict(box_lo, box_dim, bricks, cells, chunk, threads, cycles, kept) of the most recent model_density_b / bfactor_refine
+        (mad_last_bfactor_plan); -1 before the first."""
+        box, bricks, cells = np.zeros(6, np.int32), np.zeros(3, np.int32), np.zeros(3, np.int32)
+        chunk, threads, cycles, kept = C.c_int32(-1), C.c_int32(-1), C.c_int32(-1), C.c_int64(-1)
+        self._chk(self.dll.mad_last_bfactor_plan(self.ctx, _p(box), _p(bricks), _p(cells), C.byref(chunk), C.byref(threads), C.byref(cycles), C.byref(kept)))
+        return dict(box_lo=tuple(int(v) for v in box[:3]), box_dim=tuple(int(v) for v in box[3:]), bricks=tuple(int(v) for v in bricks),
+                    cells=tuple(int(v) for v in cells), chunk=chunk.value, threads=threads.value, cycles=cycles.value, kept=kept.value)
 
     def last_density_chunks(self):
         """Chunks the most recent density simulation cut its batch into (mad_last_density_chunks); -1 before the first."""

@@ -175,7 +175,7 @@ struct DevBuf {
 
 enum { MAD_T_ORIENT = 0, MAD_T_DESCRIBE, MAD_T_CORRELATE, MAD_T_PAIRS, MAD_T_POSE, MAD_T_TOPK, MAD_T_REFINE,
        MAD_T_DENSITY, MAD_T_CCC, MAD_T_SEG_PARENT, MAD_T_SEG_JUMP, MAD_T_SEG_SCAN, MAD_T_SEG_SMOOTH, MAD_T_FFT, MAD_T_FSC, MAD_T_FILTER, MAD_T_SCAN, MAD_T_SEARCH, MAD_T_LOCALRES, MAD_T_LOCALFILTER, MAD_T_LOCALSCALE,
-       MAD_T_ENV_Z, MAD_T_ENV_Y, MAD_T_ENV_X, MAD_T_ENV_WEIGHT, MAD_T_QSCORE, MAD_T_CF_SORT, MAD_T_CF_NOISE, MAD_T_CF_Q, MAD_T_CF_LOOKUP, MAD_T_JF_MODEL, MAD_T_JF_FIELD, MAD_T_JF_STEPS, MAD_T_FLEX_NETWORK, MAD_T_FLEX_STEPS, MAD_T_SYM_SCORE, MAD_T_SYM_AVERAGE, MAD_T_CC_TILE, MAD_T_CC_BORDER, MAD_T_CC_LABEL, MAD_T_CC_SELECT, MAD_T_COUNT };
+       MAD_T_ENV_Z, MAD_T_ENV_Y, MAD_T_ENV_X, MAD_T_ENV_WEIGHT, MAD_T_QSCORE, MAD_T_CF_SORT, MAD_T_CF_NOISE, MAD_T_CF_Q, MAD_T_CF_LOOKUP, MAD_T_JF_MODEL, MAD_T_JF_FIELD, MAD_T_JF_STEPS, MAD_T_FLEX_NETWORK, MAD_T_FLEX_STEPS, MAD_T_BF_GATHER, MAD_T_BF_SUMS, MAD_T_BF_GRAD, MAD_T_BF_STEP, MAD_T_SYM_SCORE, MAD_T_SYM_AVERAGE, MAD_T_CC_TILE, MAD_T_CC_BORDER, MAD_T_CC_LABEL, MAD_T_CC_SELECT, MAD_T_COUNT };
 
 #define MAD_T_RING 32
 #define MAD_LANES 8
@@ -294,6 +294,9 @@ struct mad_ctx {
     int flex_groups = 0, flex_threads = 0;      // test hooks (mad_set_option "flex_groups" / "flex_threads"): workgroups and threads per workgroup of k_fx_fit, 0 = by fx_plan
     int last_flex_groups = -1, last_flex_threads = -1, last_flex_apt = -1;      // workgroups, threads, atoms per thread and springs of the last mad_flex_fit (mad_last_flex_plan)
     int64_t last_flex_springs = -1;
+    int bf_chunk = 0, bf_threads = 0;      // test hooks (mad_set_option "bf_chunk" / "bf_threads"): atoms per LDS chunk and threads per workgroup of k_bf_gather, 0 = by bf_plan
+    int last_bf[15] = {-1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1};      // box lo and dim, bricks, cells, chunk, threads, cycles queued of the last mad_model_density_b / mad_bfactor_refine (mad_last_bfactor_plan)
+    int64_t last_bf_kept = -1;             // atoms that reached the lattice in that call
     int64_t last_rank_launches = 0, last_rank_evaluated = 0, last_rank_skipped = 0;      // the last mad_rank_* call (mad_last_rank_plan)
     int last_rank_band_extra = 0;
     int last_density_chunks = -1;            // chunks the last density_batch cut its jobs into (mad_last_density_chunks)

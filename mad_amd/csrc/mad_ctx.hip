@@ -188,7 +188,7 @@ void mad_timer_end(mad_ctx *ctx, int group) {
 static const char *k_timer_names[MAD_T_COUNT] = {"orient", "describe", "correlate", "pairs", "pose",
                                                  "topk",   "refine",   "density",   "ccc",
                                                  "seg_parent", "seg_jump", "seg_scan", "seg_smooth", "fft", "fsc", "filter", "scan", "search", "localres", "localfilter", "localscale",
-                                                 "env_z", "env_y", "env_x", "env_weight", "qscore", "cf_sort", "cf_noise", "cf_q", "cf_lookup", "jf_model", "jf_field", "jf_steps", "flex_network", "flex_steps", "sym_score", "sym_average", "cc_tile", "cc_border", "cc_label", "cc_select"};
+                                                 "env_z", "env_y", "env_x", "env_weight", "qscore", "cf_sort", "cf_noise", "cf_q", "cf_lookup", "jf_model", "jf_field", "jf_steps", "flex_network", "flex_steps", "bf_gather", "bf_sums", "bf_grad", "bf_step", "sym_score", "sym_average", "cc_tile", "cc_border", "cc_label", "cc_select"};
 
 extern "C" int mad_timing_enable(mad_ctx *ctx, int on) {
     if (!ctx) return MAD_EINVAL;

@@ -3685,6 +3685,16 @@ extern "C" int mad_set_option(mad_ctx *ctx, const char *name, double value) {
         ctx->flex_threads = (int)value;
         return MAD_OK;
     }
+    if (!strcmp(name, "bf_chunk")) {      // test hook: atoms of one LDS chunk of k_bf_gather; 0 = the default.  It changes speed, never numbers
+        if (value != 0 && (!(value >= 64) || !(value <= 1024) || value != (int)value)) return mad_fail(ctx, MAD_EINVAL, "mad_set_option: bf_chunk = %g (0, or 64 .. 1024)", value);
+        ctx->bf_chunk = (int)value;
+        return MAD_OK;
+    }
+    if (!strcmp(name, "bf_threads")) {      // test hook: threads of a workgroup of k_bf_gather; 0 = the default
+        if (!(value >= 0) || !(value <= 512) || value != (int)value || (int)value % 64 != 0) return mad_fail(ctx, MAD_EINVAL, "mad_set_option: bf_threads = %g (0, or a multiple of 64 up to 512)", value);
+        ctx->bf_threads = (int)value;
+        return MAD_OK;
+    }
     if (!strcmp(name, "fft_bpt")) {      // test hook: the k_fft_lines form (butterflies per thread) for every N; 0 = chosen by N
         if (value != 0 && value != 1 && value != 2 && value != 4) return mad_fail(ctx, MAD_EINVAL, "mad_set_option: fft_bpt = %g (0, 1, 2 or 4)", value);
         ctx->fft_bpt = (int)value;
