@@ -253,7 +253,10 @@ int mad_set_load(mad_ctx *ctx, mad_set *set, int64_t n_rows, const int32_t *row_
                  const int32_t *row_main, const double *row_R, const int16_t *dsc, int D,
                  const double *anc_subv, const int32_t *anc_index, const int32_t *anc_octave, int n_anchors);
 int mad_set_size(mad_ctx *ctx, const mad_set *set, int64_t *n_rows, int32_t *n_anchors);
-/* Any of the output pointers may be NULL. */
+/* Any of the output pointers may be NULL.  A set built on the device keeps its rows as int8 only (what a match reads): its int16
+ * rows are materialised here, by one small kernel, the first time `dsc` is asked for after a build -- the count is the int8 value
+ * (narrow sets) or the int8 value + 108 (wide sets), a row that left the grid is all zero.  A loaded or imported set hands out the
+ * int16 rows it was given. */
 int mad_set_download(mad_ctx *ctx, const mad_set *set, int32_t *row_anchor, int32_t *row_main,
                      int32_t *row_sec, double *row_R, int16_t *dsc);
 

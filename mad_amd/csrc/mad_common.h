@@ -357,6 +357,7 @@ struct mad_set {
     hipEvent_t built = nullptr;         // recorded behind the last kernel of a build / load: consumers on other lanes wait for it
     // per row
     DevBuf row_anchor, row_main, row_sec, row_R, row_Rinv, row_meta, dsc, dsc8, norm;
+    bool dsc16_current = false;  // `dsc` holds the rows (loaded and imported sets); a build writes dsc8 only and mad_set_download fills dsc from it
     DevBuf rsum;                 // wide sets only: MAD_WIDE_BIAS per row (int32), padded like norm
     bool wide = false;           // the int8 rows are centred (built at r >= MAD_WIDE_FROM_R, or loaded under the mark)
     bool wide_mark = false;      // mad_set_mark_wide: what the next mad_set_load takes the rows for
@@ -430,8 +431,11 @@ int mad_scan_i32(mad_ctx *ctx, const int32_t *in, int32_t *out, int64_t n);
 // single-launch exclusive scan for n <= 65536 with the length read on the device; out[*n] = total, also to *total_out
 void mad_scan_small(mad_ctx *ctx, const int32_t *in, int32_t *out, const int32_t *d_n, int32_t *total_out, int n_host = 0);
 
-// What k_describe starts a row from, as one 128-byte record in WORKING order (the k-th record belongs to the k-th row the kernel
-// takes): written with the rows by k_orient_rows*, fetched with one vector load.
+// What k_describe starts a row from, as one 256-byte record in WORKING order (the k-th record belongs to the k-th row the kernel
+// takes): written with the rows by k_orient_rows*, fetched with one vector load of a wave.
+// The second half holds the float32 values every thread of the row works with, rounded ONCE by the record's writer (mad_rowrec_floats)
+// instead of by each of the row's 256 threads: the same conversions and the same product, so the same bits.  The doubles stay for the
+// exact paths.
 struct alignas(16) DscRowRec {
     int32_t row;           // the row (where its descriptor goes)
     int32_t c[3];          // voxel coordinates of its anchor
@@ -439,9 +443,19 @@ struct alignas(16) DscRowRec {
     int32_t pad0[3];
     double inv[9];         // inv(Rfinal) (np.linalg.inv of Descriptor.py:132, by cofactors)
     int32_t pad1[6];
+    // [0, 9): (float)inv[i]   [9, 18): (float)Rfinal[i]   [18, 21): (float)Rfinal[6 + i] * (1 / 511), the third row on the scale of the
+    // 4-byte texels' components (table form)   [21, 32): padding
+    float f32[32];
 };
 #define MAD_ROWREC_WORDS ((int)(sizeof(DscRowRec) / 4))
-static_assert(sizeof(DscRowRec) == 128, "DscRowRec is read as 32 dwords");
+#define MAD_ROWREC_F32 32      // word at which the float32 half begins
+static_assert(sizeof(DscRowRec) == 256 && offsetof(DscRowRec, f32) == 4 * MAD_ROWREC_F32, "DscRowRec is read as 64 dwords");
+// the float32 half of a record (f = DscRowRec::f32) from the doubles
+__device__ __forceinline__ void mad_rowrec_floats(float *f, const double *inv, const double *R) {
+    for (int i = 0; i < 9; i++) f[i] = (float)inv[i];
+    for (int i = 0; i < 9; i++) f[9 + i] = (float)R[i];
+    for (int i = 0; i < 3; i++) f[18 + i] = (float)R[6 + i] * (1.0f / 511.0f);
+}
 
 // implemented in mad_orient.hip; used by the set API in mad_match.hip.  Both are fully asynchronous.
 struct OrientOut {

@@ -2838,7 +2838,7 @@ static int set_rows(mad_ctx *ctx, const mad_set *cs, int64_t *n_rows) {
             J.d_row_perm = s->last_perm ? (const int32_t *)s->row_perm.p : nullptr;
             J.d_row_rec = s->last_rec ? (const DscRowRec *)s->row_rec.p : nullptr;
             J.d_n_rows = (const int32_t *)s->dev_n.p; J.grid_rows = s->cap_rows; J.d_overflow = (int32_t *)s->dev_n.p + 3;
-            J.d_dsc = (int16_t *)s->dsc.p; J.d_dsc8 = (int8_t *)s->dsc8.p; J.d_norm = (double *)s->norm.p;
+            J.d_dsc = nullptr; J.d_dsc8 = (int8_t *)s->dsc8.p; J.d_norm = (double *)s->norm.p;      // (int16 rows: on download, as after mad_set_build)
             J.d_rsum = s->wide ? (int32_t *)s->rsum.p : nullptr;
             MAD_TRY(mad_describe_device_many(ctx, 1, &J, s->last_r));
             MAD_HIP(hipEventRecord(s->built, ctx->stream));
@@ -3134,7 +3134,10 @@ extern "C" int mad_set_build_many(mad_ctx *ctx, int n_sets, mad_set *const *sets
         // the describe launch is sized from the row count of this set's previous build when there is one
         Q.grid_rows = n <= 0 ? 0 : (s->rows_hint > 0 ? std::min<int64_t>(s->cap_rows, s->rows_hint + s->rows_hint / 8 + 64) : s->cap_rows);
         Q.d_overflow = (int32_t *)s->dev_n.p + 3;
-        Q.d_dsc = (int16_t *)s->dsc.p; Q.d_dsc8 = (int8_t *)s->dsc8.p; Q.d_norm = (double *)s->norm.p;      // int8 copy + norms included: counts are <= 64 by construction
+        // The int8 rows and their norms are what a match reads: counts are <= 64 by construction.  The int16 rows nothing on the device
+        // reads: they are made from the int8 rows when somebody downloads them (set_rows16), not written here build after build.
+        Q.d_dsc = nullptr; Q.d_dsc8 = (int8_t *)s->dsc8.p; Q.d_norm = (double *)s->norm.p;
+        s->dsc16_current = false;
         Q.d_rsum = s->wide ? (int32_t *)s->rsum.p : nullptr;                                                // (wide: <= 216, centred, with the rows' biases)
         s->last_f[0] = J.f[0]; s->last_f[1] = J.f[1]; s->last_r = r;
         s->n_rows_host = -1;
@@ -3175,6 +3178,7 @@ extern "C" int mad_set_load(mad_ctx *ctx, mad_set *s, int64_t n_rows, const int3
         MAD_HIP(hipMemcpyAsync(s->row_R.p, row_R, n_rows * 72, hipMemcpyHostToDevice, ctx->stream));
         MAD_HIP(hipMemcpyAsync(s->dsc.p, dsc, (size_t)n_rows * D * 2, hipMemcpyHostToDevice, ctx->stream));
     }
+    s->dsc16_current = true;      // the rows as they were given
     MAD_TRY(set_finish_rows(ctx, s));
     MAD_HIP(hipEventRecord(s->built, ctx->stream));
     int64_t n_dev = 0;
@@ -3203,6 +3207,28 @@ extern "C" int mad_set_size(mad_ctx *ctx, const mad_set *s, int64_t *n_rows, int
     return MAD_OK;
 }
 
+// The int16 rows of a set built on the device, from its int8 rows: count = dsc8 (narrow), dsc8 + MAD_WIDE_C (wide).  A dead row is all 0
+// in a narrow set and all -MAD_WIDE_C in a wide one: zero counts either way.  Four counts per thread and step.
+__global__ __launch_bounds__(256) void k_unpack_rows(const unsigned *__restrict__ src, int64_t n_words, int add, uint2 *__restrict__ dst) {
+    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n_words; i += (int64_t)gridDim.x * 256) {
+        const unsigned q = src[i];
+        const int a = (int)(int8_t)(q & 255u) + add, b = (int)(int8_t)((q >> 8) & 255u) + add, c = (int)(int8_t)((q >> 16) & 255u) + add,
+                  d = (int)(int8_t)(q >> 24) + add;
+        dst[i] = make_uint2(((unsigned)a & 0xffffu) | ((unsigned)b << 16), ((unsigned)c & 0xffffu) | ((unsigned)d << 16));
+    }
+}
+
+// makes s->dsc current: mad_set_build leaves the int16 rows unwritten (nothing in a build or a match reads them); n = the set's rows
+static int set_rows16(mad_ctx *ctx, mad_set *s, int64_t n) {
+    if (s->dsc16_current || n <= 0) return MAD_OK;
+    const int64_t n_words = n * s->D / 4;      // D is a multiple of 64
+    hipLaunchKernelGGL(k_unpack_rows, dim3((unsigned)std::min<int64_t>(mad_ceil_div(n_words, 256), (int64_t)ctx->n_cu * 8)), dim3(256), 0, ctx->stream,
+                       (const unsigned *)s->dsc8.p, n_words, s->wide ? MAD_WIDE_C : 0, (uint2 *)s->dsc.p);
+    MAD_HIP(hipGetLastError());
+    s->dsc16_current = true;
+    return MAD_OK;
+}
+
 extern "C" int mad_set_download(mad_ctx *ctx, const mad_set *s, int32_t *row_anchor, int32_t *row_main, int32_t *row_sec,
                                 double *row_R, int16_t *dsc) {
     if (!ctx || !s) return MAD_EINVAL;
@@ -3210,6 +3236,7 @@ extern "C" int mad_set_download(mad_ctx *ctx, const mad_set *s, int32_t *row_anc
     int64_t n = 0;
     MAD_TRY(set_rows(ctx, s, &n));      // waits for the build, on whichever lane it ran
     if (n <= 0) return MAD_OK;
+    if (dsc) MAD_TRY(set_rows16(ctx, const_cast<mad_set *>(s), n));
     if (row_anchor) MAD_HIP(hipMemcpyAsync(row_anchor, s->row_anchor.p, n * 4, hipMemcpyDeviceToHost, ctx->stream));
     if (row_main) MAD_HIP(hipMemcpyAsync(row_main, s->row_main.p, n * 4, hipMemcpyDeviceToHost, ctx->stream));
     if (row_sec) MAD_HIP(hipMemcpyAsync(row_sec, s->row_sec.p, n * 4, hipMemcpyDeviceToHost, ctx->stream));
@@ -4393,6 +4420,7 @@ extern "C" int mad_set_import(mad_ctx *ctx, mad_set *s, const void *wires, int w
     MAD_HIP(hipGetLastError());
     s->last_r = 0;      // nothing to repeat locally: an incomplete import is the caller's to redo with larger images
     s->wide = false;
+    s->dsc16_current = true;      // k_import_rows wrote them
     s->n_rows_host = -1;
     MAD_HIP(hipEventRecord(s->built, ctx->stream));
     if (!wires_on_device) MAD_HIP(hipStreamSynchronize(ctx->stream));      // the host images may go away

@@ -485,13 +485,14 @@ struct RowsArgs {
     int uniform_octave;            // ... and their octave when anc_octave is null
 };
 
-// the record of one row (k_describe reads it with one 128-byte load); inv = inv(Rfinal), still in the thread's registers
-__device__ __forceinline__ void put_row_rec(const RowsArgs &A, int64_t pos, int row, int a, const double *inv) {
+// the record of one row (k_describe reads it with one 256-byte load); inv = inv(Rfinal) and R = Rfinal, still in the thread's registers
+__device__ __forceinline__ void put_row_rec(const RowsArgs &A, int64_t pos, int row, int a, const double *inv, const double *R) {
     DscRowRec &q = A.row_rec[pos];
     q.row = row;
     q.c[0] = A.coords[3 * a]; q.c[1] = A.coords[3 * a + 1]; q.c[2] = A.coords[3 * a + 2];
     q.octave = A.anc_octave ? A.anc_octave[a] : A.uniform_octave;
     for (int i = 0; i < 9; i++) q.inv[i] = inv[i];
+    mad_rowrec_floats(q.f32, inv, R);
 }
 
 // row offsets of every job: exclusive scan of its anchors' row counts, one workgroup per job
@@ -561,7 +562,7 @@ __global__ __launch_bounds__(256) void k_orient_rows(Batch<RowsArgs> B, int fan,
     if (A.row_Rinv)
         for (int i = 0; i < 9; i++) A.row_Rinv[9 * row + i] = inv9[i];
     if (A.row_meta) { A.row_meta[3 * row] = A.anc_index[a]; A.row_meta[3 * row + 1] = A.anc_octave[a]; A.row_meta[3 * row + 2] = mb; }
-    if (A.row_rec) put_row_rec(A, A.order ? A.perm_off[p] + s : row, (int)row, a, inv9);
+    if (A.row_rec) put_row_rec(A, A.order ? A.perm_off[p] + s : row, (int)row, a, inv9, R9);
 }
 
 // k_orient_scan + k_orient_rows in ONE launch (round 3): every workgroup forms the exclusive scan of its job's
@@ -625,7 +626,7 @@ __global__ __launch_bounds__(ORS_THREADS, 8) void k_orient_rows_scan(Batch<RowsA
     if (A.row_Rinv)
         for (int i = 0; i < 9; i++) A.row_Rinv[9 * row + i] = inv9[i];
     if (A.row_meta) { A.row_meta[3 * row] = A.anc_index[a]; A.row_meta[3 * row + 1] = A.anc_octave[a]; A.row_meta[3 * row + 2] = mb; }
-    if (A.row_rec) put_row_rec(A, A.order ? s_perm[pl] + sl : row, (int)row, a, inv9);
+    if (A.row_rec) put_row_rec(A, A.order ? s_perm[pl] + sl : row, (int)row, a, inv9, R9);
 }
 
 // Runs a1-a8 for the anchor lists of n_jobs structures (coordinates and octaves already on the device) in one k_orient
@@ -931,11 +932,9 @@ template <int S, int NSUB> __device__ __forceinline__ int sub_of_i(int i) {
 // where in the linear order nearly every sample had a 1 x 1 x 32 stick of its own: 4.04 M requests from the L1 to the L2 per launch
 // on C3 against 7.41 M, 61.7 us against 75.0, for 12 instructions of address per sample instead of 2.  The queue
 // holds tex4 indices; the queue phase, which reads the 16-byte texels in their linear order, decodes them with mad_tex4_voxel.
-// The 4-byte texels lie in bricks of 4 x 4 x 2 voxels, one 128-byte line each (FieldDev, mad_tex4_index): a wave-instruction's 64
-// samples -- one i, four j, sixteen k: a rotated planar patch of 8 x 32 voxels in octave 0, 4 x 16 in octave 1 -- then share lines
-// where in the linear order nearly every sample had a 1 x 1 x 32 stick of its own: 4.04 M requests from the L1 to the L2 per launch
-// on C3 against 7.41 M, 61.7 us against 75.0, for 12 instructions of address per sample instead of 2.  The queue
-// holds tex4 indices; the queue phase, which reads the 16-byte texels in their linear order, decodes them with mad_tex4_voxel.
+// Outside its samples: a row's float32 matrices come with its record, rounded once by the record's writer; the
+// epilogue of the table form takes four bins per thread -- one 16-byte LDS read, one 4-byte store of the int8 counts; and the int16
+// row is written only where the caller hands a buffer for it (mad_describe): a set build passes none.
 #define DSC_QUEUE_TAB 768
 #ifdef MAD_PROBE_STAMPS      // diagnostic build: s_memtime at the phases of every row's workgroup (tools/probe_describe.py)
 __device__ long long dsc_stamps[16384 * 8];
@@ -967,11 +966,11 @@ __global__ __launch_bounds__(DSC_NT(S), TAB ? DSC_OCC_TAB : DSC_OCC) void k_desc
     const int job = batch_job(B, (int)blockIdx.x);
     const DescribeArgs &A = B.job[job];
     const int bid = (int)blockIdx.x - B.first[job], gdim = B.first[job + 1] - B.first[job];      // this job's part of the grid (multiples of 8)
-    __shared__ int hist[NSUB * ZMAX];
+    __shared__ __align__(16) int hist[NSUB * ZMAX];
     __shared__ int s_oob, s_nq;
     __shared__ int s_part[NT / MAD_WAVE];
     __shared__ int s_sum[WIDE ? NT / MAD_WAVE : 1];
-    __shared__ __align__(16) int s_rec[32];      // the row's DscRowRec
+    __shared__ __align__(16) int s_rec[MAD_ROWREC_WORDS];      // the row's DscRowRec
     // TAB: the float32 / float64 tiers see 3-4 % of the samples, at the end, in full lanes: they read their tables from global
     // memory (cache-resident, shared by every workgroup) and the 12 KB image is not staged per row
     // (TAB: only what eqsp_fast32 reads -- the head of the image: g32, zlut, belt_f, belt_i -- is staged; the float64 tier, a few
@@ -1016,8 +1015,9 @@ __global__ __launch_bounds__(DSC_NT(S), TAB ? DSC_OCC_TAB : DSC_OCC) void k_desc
     const int Z = TAB ? 16 : A.eq->Z;
     const int D = NSUB * Z;            // S = 2 r samples per axis (16), NSUB sub-regions of Z zones each
     for (int i = tid; i < D; i += NT) hist[i] = 0;
-    // What a row starts from -- its index, its anchor's coordinates and octave, inv(Rfinal) -- is one 128-byte record (DscRowRec,
-    // written with the rows by k_orient_rows* in WORKING order) that 32 lanes fetch with one vector load and park in LDS, next
+    // What a row starts from -- its index, its anchor's coordinates and octave, inv(Rfinal), and both matrices as the float32 values
+    // the threads work with -- is one 256-byte record (DscRowRec,
+    // written with the rows by k_orient_rows* in WORKING order) that one wave fetches with one vector load and parks in LDS, next
     // to the staging of the tables.  Before (round 2) it was a chain of dependent scalar loads, row_perm -> row_anchor -> octave,
     // coordinates, inv(R): with the staging 7 700 of a row's 35 600 cycles (MAD_PROBE_STAMPS).  Without records (mad_describe
     // on rows of the caller) thread 0 walks that chain and forms the record itself.
@@ -1045,10 +1045,11 @@ __global__ __launch_bounds__(DSC_NT(S), TAB ? DSC_OCC_TAB : DSC_OCC) void k_desc
             mad_mat3_inv(p_R + 9 * (int64_t)r, m);
             for (int i = 0; i < 9; i++) inv[i] = m[i];
         }
+        mad_rowrec_floats((float *)(rec + MAD_ROWREC_F32), inv, p_R + 9 * (int64_t)r);
     };
     const int *const recs = (const int *)A.row_rec;
     if (recs) {
-        if (tid < 32) s_rec[tid] = recs[work * MAD_ROWREC_WORDS + tid];
+        if (tid < MAD_ROWREC_WORDS) s_rec[tid] = recs[work * MAD_ROWREC_WORDS + tid];      // (one wave)
     } else if (tid == 0) chain_record(work, s_rec);
     if (tid == 0) { s_oob = 0; s_nq = 0; }
     __syncthreads();      // the histogram is zero, the flags are reset, the record is there
@@ -1069,8 +1070,9 @@ __global__ __launch_bounds__(DSC_NT(S), TAB ? DSC_OCC_TAB : DSC_OCC) void k_desc
 
     const int ic0 = __builtin_amdgcn_readfirstlane(s_rec[1]), ic1 = __builtin_amdgcn_readfirstlane(s_rec[2]),
               ic2 = __builtin_amdgcn_readfirstlane(s_rec[3]);
-    const float h0 = (float)sInv[0], h1 = (float)sInv[1], h2 = (float)sInv[2], h3 = (float)sInv[3], h4 = (float)sInv[4], h5 = (float)sInv[5],
-                h6 = (float)sInv[6], h7 = (float)sInv[7], h8 = (float)sInv[8];
+    // (the record's float32 half: what (float)sInv[i] and (float)Rrow[i] give, converted once by the record's writer)
+    const float *const sF = (const float *)&s_rec[MAD_ROWREC_F32];
+    const float h0 = sF[0], h1 = sF[1], h2 = sF[2], h3 = sF[3], h4 = sF[4], h5 = sF[5], h6 = sF[6], h7 = sF[7], h8 = sF[8];
     // this thread's (j, k) column of the S^3 lattice; threads beyond S*S idle (NT >= S * S)
     const int j = tid / S, k = tid % S;
     const bool active = tid < S * S;
@@ -1160,11 +1162,10 @@ __global__ __launch_bounds__(DSC_NT(S), TAB ? DSC_OCC_TAB : DSC_OCC) void k_desc
             // a bit mask and handed to the exact path afterwards.  (A sample that left the grid zeroes the whole row below:
             // what its pass counted in the meantime is never written.)
             unsigned undecided = 0;
-            // (the rotation is converted here, behind the requests: nine registers fewer while the texels are in flight)
+            // (the rotation is read here, behind the requests: nine registers fewer while the texels are in flight)
             // (TAB: the third row carries the 1 / 511 of the texel's components: z on the unit scale, x and y on any common one)
-            const float zs = TAB ? (1.0f / 511.0f) : 1.0f;
-            const float f0 = (float)Rrow[0], f1 = (float)Rrow[1], f2 = (float)Rrow[2], f3 = (float)Rrow[3], f4 = (float)Rrow[4], f5 = (float)Rrow[5],
-                        f6 = (float)Rrow[6] * zs, f7 = (float)Rrow[7] * zs, f8 = (float)Rrow[8] * zs;
+            const float f0 = sF[9], f1 = sF[10], f2 = sF[11], f3 = sF[12], f4 = sF[13], f5 = sF[14],
+                        f6 = sF[TAB ? 18 : 15], f7 = sF[TAB ? 19 : 16], f8 = sF[TAB ? 20 : 17];
 #pragma unroll
             for (int i0 = 0; i0 < PS; i0 += DSC_CHUNK) {
                 int zone[DSC_CHUNK];
@@ -1246,7 +1247,8 @@ __global__ __launch_bounds__(DSC_NT(S), TAB ? DSC_OCC_TAB : DSC_OCC) void k_desc
     DSC_NOTE_OPEN(s_nq);
     const bool dead = s_oob != 0;      // Descriptor.py:142-149: a sample left the grid -> the whole descriptor is zero
     if (dead) {
-        for (int i = tid; i < D; i += NT) A.dsc[row * D + i] = 0;
+        if (A.dsc)
+            for (int i = tid; i < D; i += NT) A.dsc[row * D + i] = 0;
         if (A.dsc8) {
             for (int i = tid; i < D; i += NT) A.dsc8[row * D + i] = WIDE ? (int8_t)-MAD_WIDE_C : 0;
             if (tid == 0) A.norm[row] = 0.0;
@@ -1267,8 +1269,7 @@ __global__ __launch_bounds__(DSC_NT(S), TAB ? DSC_OCC_TAB : DSC_OCC) void k_desc
     } else if (TAB) {
         // the samples the table left open: their 16-byte texels, the float32 tier with its 1e-4 guard, the float64 tier behind it
         const int nq = s_nq;
-        const float f0 = (float)Rrow[0], f1 = (float)Rrow[1], f2 = (float)Rrow[2], f3 = (float)Rrow[3], f4 = (float)Rrow[4], f5 = (float)Rrow[5],
-                    f6 = (float)Rrow[6], f7 = (float)Rrow[7], f8 = (float)Rrow[8];
+        const float f0 = sF[9], f1 = sF[10], f2 = sF[11], f3 = sF[12], f4 = sF[13], f5 = sF[14], f6 = sF[15], f7 = sF[16], f8 = sF[17];
         for (int e = tid; e < nq; e += NT) {
             const float4 tx = F.tex[mad_tex4_voxel(F, qidx[e])];      // the queue holds tex4 (brick) indices; tex is linear
             if (tx.w < 1e-5f) continue;      // (cannot happen for a queued sample: such texels carry flag 3; kept for symmetry with the slow path)
@@ -1286,13 +1287,26 @@ __global__ __launch_bounds__(DSC_NT(S), TAB ? DSC_OCC_TAB : DSC_OCC) void k_desc
     DSC_STAMP(6);
     int ss = 0;      // counts <= 64 (S = 24: <= 216), 1024 of them: the sum of squares is exact in int32
     int sv = 0;      // WIDE: the sum of the counts (not a constant: samples below the magnitude cut are not counted)
-    for (int i = tid; i < D; i += NT) {
-        const int v = hist[i];
-        if (dead) continue;
-        A.dsc[row * D + i] = (int16_t)v;
-        if (A.dsc8) A.dsc8[row * D + i] = (int8_t)(WIDE ? v - MAD_WIDE_C : v);
-        ss += v * v;
-        if (WIDE) sv += v;
+    // (the int16 row only where somebody asked for it: a set keeps the int8 rows and makes the others from them on download)
+    if constexpr (TAB) {
+        // four consecutive bins per thread (D = 4 NT): one 16-byte read, one 4-byte store of the packed int8 counts (0 .. 64, so the
+        // bytes do not run into each other) and, for a caller's int16 rows, one 8-byte store
+        static_assert(!TAB || (NSUB * 16 == 4 * NT && !WIDE), "the table form's epilogue: four bins per thread, narrow counts");
+        const int4 v = *(const int4 *)&hist[4 * tid];
+        if (!dead) {
+            if (A.dsc) *(uint2 *)(A.dsc + row * D + 4 * tid) = make_uint2((unsigned)v.x | ((unsigned)v.y << 16), (unsigned)v.z | ((unsigned)v.w << 16));
+            if (A.dsc8) *(unsigned *)(A.dsc8 + row * D + 4 * tid) = (unsigned)v.x | ((unsigned)v.y << 8) | ((unsigned)v.z << 16) | ((unsigned)v.w << 24);
+            ss = v.x * v.x + v.y * v.y + v.z * v.z + v.w * v.w;
+        }
+    } else {
+        for (int i = tid; i < D; i += NT) {
+            const int v = hist[i];
+            if (dead) continue;
+            if (A.dsc) A.dsc[row * D + i] = (int16_t)v;
+            if (A.dsc8) A.dsc8[row * D + i] = (int8_t)(WIDE ? v - MAD_WIDE_C : v);
+            ss += v * v;
+            if (WIDE) sv += v;
+        }
     }
     if (A.dsc8 && !dead) {
         ss = wave_sum_i32(ss);
