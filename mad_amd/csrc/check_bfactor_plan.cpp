@@ -86,15 +86,17 @@ static void check_groups() {
 }
 
 // The box, the cells and the bricks of one scene; then, voxel by voxel of the box, that the atoms within rmax are exactly those the
-// voxel's brick finds in its cell range, each once and in ascending (cell, atom) order.
+// voxel's brick finds in its cell range, each once and in ascending (cell, atom) order.  *partial (where asked for) counts the bricks
+// whose cell range leaves out a cell that holds an atom; cell_dim gets the cells per axis.
 static void check_scene(const int32_t dims[3], const double origin[3], double vs, const std::vector<double> &coords, double resolution, double b_max,
-                        int64_t want_kept) {
+                        int64_t want_kept, int64_t *partial = nullptr, int32_t *cell_dim = nullptr) {
     std::vector<double> x(coords);
     const int64_t n = (int64_t)(x.size() / 3);
     BfBox box;
     std::vector<uint8_t> keep;
     bf_box(dims, origin, vs, n, x.data(), resolution, b_max, box, keep);
     CHECK((int64_t)keep.size() == n && box.kept == want_kept);
+    if (partial) *partial = 0;
     if (box.kept == 0) { CHECK(box.voxels == 0 && box.dim[0] == 0 && box.dim[1] == 0 && box.dim[2] == 0); return; }
     for (int d = 0; d < 3; d++) CHECK(box.lo[d] >= 0 && box.dim[d] >= 1 && box.lo[d] + box.dim[d] <= dims[d]);
     CHECK(box.voxels == (int64_t)box.dim[0] * box.dim[1] * box.dim[2]);
@@ -118,6 +120,7 @@ static void check_scene(const int32_t dims[3], const double origin[3], double vs
     CHECK((double)cells.g.cells <= 4.0 * (double)box.kept + 64.0 && cells.g.edge > box.rmax);
     for (int64_t c = 0; c < cells.g.cells; c++)
         for (int32_t k = cells.start[(size_t)c]; k + 1 < cells.start[(size_t)c + 1]; k++) CHECK(cells.order[(size_t)k] < cells.order[(size_t)k + 1]);
+    for (int d = 0; d < 3 && cell_dim; d++) cell_dim[d] = cells.g.dim[d];
     const BfPlan plan = bf_plan(box, 0, 0);
     CHECK(plan.chunk == BF_CHUNK && plan.threads == BF_THREADS && plan.runs[plan.levels - 1] == 1);
     for (int d = 0; d < 3; d++) CHECK(plan.bricks[d] * BF_BRICK >= box.dim[d] && (plan.bricks[d] - 1) * BF_BRICK < box.dim[d]);
@@ -149,7 +152,12 @@ static void check_scene(const int32_t dims[3], const double origin[3], double vs
                                 const double dx = origin[0] + vs * jx - x[3 * i], dy = origin[1] + vs * jy - x[3 * i + 1], dz = origin[2] + vs * jz - x[3 * i + 2];
                                 if ((dx * dx + dy * dy) + dz * dz <= r2) CHECK(keep[(size_t)i] && seen[(size_t)i] == 1);
                             }
-                for (int64_t i = 0; i < n; i++) CHECK(seen[(size_t)i] <= 1);
+                bool skipped = false;
+                for (int64_t i = 0; i < n; i++) {
+                    CHECK(seen[(size_t)i] <= 1);
+                    skipped = skipped || (keep[(size_t)i] && seen[(size_t)i] == 0);
+                }
+                if (partial && skipped) (*partial)++;
             }
 }
 
@@ -196,6 +204,64 @@ static void check_scenes() {
     // a lattice of one voxel
     const int32_t one[3] = {1, 1, 1};
     check_scene(one, origin, vs, {-7.5, 3.5, 10.0}, 4.0, 10.0, 1);
+    // a coarse lattice: voxels of 3.1 A at resolution 8, a reach of under 3 voxels
+    {
+        const int32_t coarse[3] = {12, 11, 13};
+        const double o[3] = {-7.3, 3.1, 11.7};
+        std::vector<double> x;
+        for (int i = 0; i < 24; i++) x.insert(x.end(), {o[0] + 3.1 * (1.0 + 9.0 * uniform()), o[1] + 3.1 * (1.0 + 8.0 * uniform()), o[2] + 3.1 * (1.0 + 10.0 * uniform())});
+        BfBox box;
+        std::vector<uint8_t> keep;
+        bf_box(coarse, o, 3.1, 24, x.data(), 8.0, 400.0, box, keep);
+        CHECK(box.rmax < 3.0 * 3.1);
+        check_scene(coarse, o, 3.1, x, 8.0, 400.0, 24);
+    }
+    // a fine lattice: voxels of 0.5 A at resolution 2 and b_max 120, a reach of about 8 voxels; the bricks of one axis see other cells
+    {
+        const int32_t fine[3] = {40, 38, 42};
+        std::vector<double> x;
+        for (int i = 0; i < 8; i++) x.insert(x.end(), {origin[0] + 0.5 * (4.0 + 31.0 * uniform()), origin[1] + 0.5 * (4.0 + 29.0 * uniform()), origin[2] + 0.5 * (4.0 + 33.0 * uniform())});
+        BfBox box;
+        std::vector<uint8_t> keep;
+        bf_box(fine, origin, 0.5, 8, x.data(), 2.0, 120.0, box, keep);
+        CHECK(box.rmax > 7.0 * 0.5 && box.rmax < 9.0 * 0.5);
+        check_scene(fine, origin, 0.5, x, 2.0, 120.0, 8);
+    }
+    // 40 atoms along the body diagonal of 44^3: a box of three sum levels, four cells an axis at least, and bricks that walk a part of
+    // the cells that hold atoms
+    {
+        const int32_t deep[3] = {44, 44, 44};
+        std::vector<double> x;
+        for (int i = 0; i < 40; i++) {
+            const double t = 0.5 * vs * 43.0 - 17.0 + 34.0 * i / 39.0;
+            x.insert(x.end(), {origin[0] + t + 1.2 * (uniform() - 0.5), origin[1] + t + 1.2 * (uniform() - 0.5), origin[2] + t + 1.2 * (uniform() - 0.5)});
+        }
+        int64_t partial = 0;
+        int32_t cell_dim[3] = {0, 0, 0};
+        check_scene(deep, origin, vs, x, 4.0, 400.0, 40, &partial, cell_dim);
+        CHECK(partial > 0 && cell_dim[0] >= 4 && cell_dim[1] >= 4 && cell_dim[2] >= 4);
+        BfBox box;
+        std::vector<uint8_t> keep;
+        bf_box(deep, origin, vs, 40, x.data(), 4.0, 400.0, box, keep);
+        const BfPlan p = bf_plan(box, 0, 0);
+        CHECK(box.voxels > 65536 && p.levels == 3 && p.runs[1] > 1 && p.runs[1] <= BF_RUN);
+    }
+    // kept atoms 3 to 5 A beyond a low and a high face of each axis, and beyond an edge: the clipped ranges begin or end at the face
+    {
+        const int32_t cube[3] = {16, 16, 16};
+        const double hi[3] = {origin[0] + vs * 15.0, origin[1] + vs * 15.0, origin[2] + vs * 15.0};
+        const std::vector<double> x = {origin[0] - 4.0, 12.0, 20.0,  hi[0] + 3.0, 13.0, 19.0,  -1.0, origin[1] - 5.0, 21.0,  1.0, hi[1] + 3.5, 18.0,
+                                       0.5, 11.0, origin[2] - 4.5,  -0.5, 12.5, hi[2] + 4.0,  origin[0] - 3.0, hi[1] + 3.0, 20.0,  2.0, 12.0, 20.0};
+        check_scene(cube, origin, vs, x, 4.0, 400.0, 8);
+        BfBox box;
+        std::vector<uint8_t> keep;
+        bf_box(cube, origin, vs, 8, x.data(), 4.0, 400.0, box, keep);
+        for (int d = 0; d < 3; d++) CHECK(box.lo[d] == 0 && box.dim[d] == 16);
+        // an atom whose range ends a voxel before the low face is not kept; one whose range, a voxel wider than its reach, begins at the
+        // last voxel of the high face is
+        const std::vector<double> near = {origin[0] - box.rmax - 1.3, 12.0, 20.0,  hi[0] + box.rmax + 1.1, 12.0, 20.0,  2.0, 12.0, 20.0};
+        check_scene(cube, origin, vs, near, 4.0, 400.0, 2);
+    }
 }
 
 static void check_plan() {

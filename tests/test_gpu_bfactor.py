@@ -43,14 +43,14 @@ def hooks(lib):
 
 def density(lib, name):
     c = bc.case(name)
-    return lib.model_density_b(c["shape"], bc.ORIGIN, bc.VS, c["coords"], c["masses"], c["b_atom"], bc.RESOLUTION, b_max=400.0)
+    return lib.model_density_b(c["shape"], c["origin"], c["vs"], c["coords"], c["masses"], c["b_atom"], c["resolution"], b_max=400.0)
 
 
 def fit(lib, name, **more):
     c = bc.case(name)
     kw = dict(c["kw"])
     kw.update(more)
-    return lib.bfactor_refine(c["grid"], bc.ORIGIN, bc.VS, c["coords"], c["masses"], c["first_atom"], c["b0"], bc.RESOLUTION, **kw)
+    return lib.bfactor_refine(c["grid"], c["origin"], c["vs"], c["coords"], c["masses"], c["first_atom"], c["b0"], c["resolution"], **kw)
 
 
 def bits(a):
